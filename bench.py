@@ -7,9 +7,14 @@ forward + backward + TF-form Adam) on synthetic B=32, N=1024, C=4 frustum batche
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` for the dominant kernel
-(per-launch HIP-event timing on the launch stream) and `cpu_baseline` (the oracle's torch-CPU restatement of
-the same step timed on this host's cores; baseline, not target).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps and
+prints the line; `roofline`, `cpu_baseline` and `other_configs` are null there.  `--full` adds everything else the benchmark
+measures: `roofline` for the dominant kernel (per-launch HIP-event timing on the launch stream), `cpu_baseline` (the oracle's
+torch-CPU restatement of the same step timed on this host's cores; baseline, not target), `other_configs` (child runs of the
+other configurations) and, with several ranks, the second data-parallel form and the exposed all-reduce time.
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR      # + what the last timed step computed, DIR/<name>.npy
 """
 import argparse
 import json
@@ -57,6 +62,12 @@ def parse():
     ap.add_argument('--profile_steps', type=int, default=5)
     ap.add_argument('--gemm_detail', action='store_true', help='per-shape GEMM timings on stderr')
     ap.add_argument('--call_detail', action='store_true', help='every launch of the step in order with its time, on stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='also the roofline pass, the CPU baseline, the other configurations and (several ranks) the second data-parallel '
+                         'form; a plain run times the headline step only')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (end points, weights, gradients, moving statistics) '
+                         'as DIR/<name>.npy (float32; integers float64), at most 64 MB in all')
     return ap.parse_args()
 
 
@@ -402,7 +413,7 @@ def other_configs(args):
     out = []
     for wl, dt, extra, env_over in runs:
         cmd = [sys.executable, os.path.abspath(__file__), '--workload', wl, '--dtype', dt, '--steps', '20', '--warmup', '5',
-               '--profile_steps', '2', '--no_cpu_baseline', '--no_other_configs'] + extra
+               '--full', '--profile_steps', '2', '--no_cpu_baseline', '--no_other_configs'] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240,
                                env=dict(os.environ, WORLD_SIZE='1', RANK='0', LOCAL_RANK='0', **env_over))
@@ -417,6 +428,58 @@ def other_configs(args):
         except Exception as e:      # a failed side run must not cost the headline line
             out.append({'workload': wl, 'dtype': dt, 'error': repr(e)[:200]})
     return out
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(model, vs):
+    """{name: ndarray} of what a caller of the step receives after it: the model's end points (outputs, loss and its terms) and the
+    variables the step updated -- trainable weights after the optimiser (`weights`), their gradients (`grads`), the moving statistics
+    (`moving_stats`), each the used part of its flat buffer.  Floating arrays as float32, integer ones as float64."""
+    out = {}
+
+    def put(name, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                put('%s.%s' % (name, k), x)
+            return
+        if v is None:
+            return
+        if isinstance(v, torch.Tensor):
+            v = v.detach().float().cpu().numpy() if v.is_floating_point() else v.detach().cpu().numpy()
+        a = np.asarray(v)
+        out[name] = a.astype(np.float32 if a.dtype.kind in 'fb' else np.float64)
+
+    for k, v in model.end_points().items():
+        put(k, v)
+    put('weights', vs.params[:vs.used])
+    put('grads', vs.grads[:vs.used])
+    put('moving_stats', vs.state[:vs.state_used])
+    return out
+
+
+def fit_budget(arrays, budget=DUMP_BUDGET_BYTES):
+    """Largest arrays first, each replaced by a fixed seeded sample of its flattened elements (sorted indices) until the total fits
+    `budget`.  The sample depends only on the arrays' sizes, so two builds run with the same arguments keep the same elements."""
+    total = sum(a.nbytes for a in arrays.values())
+    for name in sorted(arrays, key=lambda k: (-arrays[k].nbytes, k)):
+        if total <= budget:
+            break
+        a = arrays[name].ravel()
+        keep = max(1, a.size - -(-(total - budget) // a.itemsize))
+        idx = np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))
+        total -= a.nbytes - keep * a.itemsize
+        arrays[name] = a[idx]
+    return arrays
+
+
+def dump_outputs(path, model, vs):
+    arrays = fit_budget(step_outputs(model, vs))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return arrays
 
 
 def main():
@@ -549,7 +612,10 @@ def main():
         elapsed, median_step = float(t[0].item()), float(t[1].item())
     if run_guard is not None:
         run_guard.__exit__(None, None, None)
-    if trainstep.dist:          # five more steps (every rank) with events around the bucket waits: the exposed all-reduce time
+    if args.dump_outputs and rank == 0:      # before anything else runs on the step's state (the passes below run more launches)
+        dump_model = ctxs[(trainstep.n_runs - 1) % 2]['model'] if pipelined else model
+        dump_outputs(args.dump_outputs, dump_model, g.vars)
+    if trainstep.dist and args.full:          # five more steps (every rank) with events around the bucket waits: the exposed all-reduce time
         trainstep.time_waits = True
         for _ in range(5):
             step()
@@ -563,7 +629,7 @@ def main():
 
     roofline = None
     cpu = None
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and args.profile_steps > 0 and (args.full or args.call_detail or args.gemm_detail):
         # per-kernel timing for the roofline object (eager, per-launch events on the launch stream)
         # the launches of the program that was timed (the scheduled one: step.TrainStep._overlap), not of the plans it was made from
         if pipelined:
@@ -650,9 +716,9 @@ def main():
                                     b_ / (t_ / n_) / 1e9 / (HBM_PEAK_TBS * 1e3), b_ / 6.3e6))
     others = None
     default_workload = args.workload == 'A' and args.dtype == 'f32' and (B, N, C) == (32, 1024, 4)
-    if rank == 0 and world == 1 and default_workload and not args.no_other_configs:
+    if rank == 0 and world == 1 and default_workload and args.full and not args.no_other_configs:
         others = other_configs(args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == 'A':
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload == 'A':
         cpu = cpu_baseline(args, batch)
 
     if rank == 0:
@@ -691,7 +757,7 @@ def main():
         return code
 
     flat_default = os.environ.get('T3D_DP_FLAT', '1') == '1'
-    if (trainstep.dist and not pipelined and os.environ.get('T3D_DP_BOTH_MODES', '1') == '1'):      # (world 1: T3D_FORCE_DIST=1)
+    if (trainstep.dist and args.full and not pipelined and os.environ.get('T3D_DP_BOTH_MODES', '1') == '1'):      # (world 1: T3D_FORCE_DIST=1)
         # One driver run compares two forms of the data-parallel step: <= 20 timed steps of a second form on a second step object,
         # reported beside the default's.  RCCL default = the step and its one flat all-reduce captured in ONE graph; second form = the
         # same collective issued by the host between graph segments (the default of rounds 2-4).  gloo (no capture): flat vs bucketed.

@@ -12,12 +12,12 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-python3 $root/bench.py $flags > $out/bench.json 2> $out/bench.err
+python3 $root/bench.py --full $flags > $out/bench.json 2> $out/bench.err
 # (--no_other_configs in every profiler pass: the side runs of configs[2..4] are child processes that inherit the profiler and would
 # write their own counter / stats files into the same directories)
 # --profile_steps 0: no per-launch timing leg (bench.py's un-hosted eager launches of every kernel, which round 5's stats mixed with the
 # hosted graph replays: 994 calls of the dominant kernel, min 10.6 / max 58.3 us).  What the stats file then holds is one eager step and
-# W + K hipGraph replays of the step: its per-kernel averages ARE the hosted durations, and `roofline.avg_launch_us` of a plain bench
+# W + K hipGraph replays of the step: its per-kernel averages ARE the hosted durations, and `roofline.avg_launch_us` of a `--full` bench
 # run (events around the hosted replays of the dominant family) can be checked against it without the bench line.
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 $root/bench.py $flags --no_cpu_baseline --no_other_configs --profile_steps 0 > $out/trace_bench.json 2> $out/trace.log
 small="--steps 4 --warmup 2 --no_cpu_baseline --no_other_configs --no_graph --profile_steps 0"
