@@ -656,6 +656,28 @@ typedef struct {
 } t3d_boxpc_rep_args;
 int t3d_boxpc_rep(const t3d_boxpc_rep_args* args, t3d_stream_t stream);
 
+/* Representation B (independent_box_pc_mask_features_model, semisup_models.py:400-470) reads the box as a 7-vector and the RAW point
+ * cloud, so this writes only that:
+ *   box_out[B,7] = (cx,cy,cz,l,w,h,theta) of the box in either form of t3d_boxpc_rep (label form when y_dims_cls != NULL), when
+ *                  box_out != NULL (center / dims / theta then required);
+ *   pc_out[m, 0:C] = pc[m, 0:C] * rowmask[m] (--mask_pc_for_boxpc, test_semisup.py:103-105; columns C .. ld_out-1 zeroed), when
+ *                  rowmask != NULL (pc, pc_out, ld_out >= C required).  Without a row mask the net reads pc in place.
+ * At least one of the two; M = B * rows_per_frustum.  (An entry point of its own rather than a field appended to t3d_boxpc_rep_args:
+ * that struct keeps its version-2 size, below which a caller's struct is refused.)  Frozen struct. */
+typedef struct {
+  const float* center;            /* [B,3] */
+  const float* dims;              /* [B,3] */
+  const float* theta;             /* [B]   */
+  const int32_t* y_dims_cls;      /* [B] or NULL */
+  const int32_t* y_orient_cls;    /* [B] or NULL */
+  float* box_out;                 /* [B,7] or NULL */
+  const float* pc; int ld_pc; int C;
+  const float* rowmask;           /* [M] 0/1 or NULL */
+  float* pc_out; int ld_out;      /* [M, ld_out] */
+  int B, rows_per_frustum;
+} t3d_boxpc_rep_b_args;
+int t3d_boxpc_rep_b(const t3d_boxpc_rep_b_args* args, t3d_stream_t stream);
+
 /* Gradient of the representation w.r.t. the box: dbox[B,7] = d(cx,cy,cz,l,w,h,theta), reduced over the points,
  * from drep[m, coff .. coff+5] = gradient w.r.t. the six distance channels (stage c: train_semisup_adv.py:331-411). */
 typedef struct {

@@ -254,6 +254,11 @@ class BoxPcRepArgs(Sized):
                 ('y_orient_cls', I), ('rep', F), ('ld_rep', i32), ('box_out', F), ('M', i32), ('rows_per_frustum', i32), ('rowmask', F)]
 
 
+class BoxPcRepBArgs(C.Structure):
+    _fields_ = [('center', F), ('dims', F), ('theta', F), ('y_dims_cls', I), ('y_orient_cls', I), ('box_out', F), ('pc', F), ('ld_pc', i32),
+                ('C', i32), ('rowmask', F), ('pc_out', F), ('ld_out', i32), ('B', i32), ('rows_per_frustum', i32)]
+
+
 class BoxPcRepBwdArgs(C.Structure):
     _fields_ = [('pc', F), ('ld_pc', i32), ('box', F), ('drep', F), ('ld_drep', i32), ('coff', i32), ('dbox', F),
                 ('B', i32), ('rows_per_frustum', i32)]
@@ -368,6 +373,7 @@ ENTRY_POINTS = {
     't3d_act_dropout': [C.POINTER(ActDropoutArgs), VP],
     't3d_strong_loss': [C.POINTER(StrongLossArgs), VP],
     't3d_boxpc_rep': [C.POINTER(BoxPcRepArgs), VP],
+    't3d_boxpc_rep_b': [C.POINTER(BoxPcRepBArgs), VP],
     't3d_boxpc_rep_bwd': [C.POINTER(BoxPcRepBwdArgs), VP],
     't3d_boxpc_loss': [C.POINTER(BoxPcLossArgs), VP],
     't3d_pointmlp_dgrad_narrow': [C.POINTER(DgradNarrowArgs), VP],

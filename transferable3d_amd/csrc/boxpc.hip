@@ -64,6 +64,34 @@ __global__ __launch_bounds__(256) void k_boxpc_rep(const t3d_boxpc_rep_args p) {
   for (int i = p.C + 6; i < p.ld_rep; ++i) dst[i] = 0.f;
 }
 
+// Representation B: thread m < M writes the masked point row m (rowmask given), thread b < B the box 7-vector of frustum b, in the
+// arithmetic of load_box.
+__global__ __launch_bounds__(256) void k_boxpc_rep_b(const t3d_boxpc_rep_b_args p) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int M = p.B * p.rows_per_frustum;
+  if (p.rowmask != nullptr && i < M) {
+    const float km = p.rowmask[i];
+    const float* src = p.pc + (size_t)i * p.ld_pc;
+    float* dst = p.pc_out + (size_t)i * p.ld_out;
+    for (int c = 0; c < p.C; ++c) dst[c] = src[c] * km;
+    for (int c = p.C; c < p.ld_out; ++c) dst[c] = 0.f;
+  }
+  if (p.box_out != nullptr && i < p.B) {
+    float* o = p.box_out + i * 7;
+    o[0] = p.center[i * 3]; o[1] = p.center[i * 3 + 1]; o[2] = p.center[i * 3 + 2];
+    if (p.y_dims_cls != nullptr) {      // label form: convert_raw_y_box_to_reg_format (boxpc_sunrgbd.py:206-230)
+      const int k = p.y_dims_cls[i], j = p.y_orient_cls[i];
+      o[3] = fmaxf(kMean[k][0] + p.dims[i * 3], 1e-5f);
+      o[4] = fmaxf(kMean[k][1] + p.dims[i * 3 + 1], 1e-5f);
+      o[5] = fmaxf(kMean[k][2] + p.dims[i * 3 + 2], 1e-5f);
+      o[6] = (float)((double)j * (2.0 * 3.14159265358979323846 / 12.0)) + p.theta[i];
+    } else {
+      o[3] = p.dims[i * 3]; o[4] = p.dims[i * 3 + 1]; o[5] = p.dims[i * 3 + 2];
+      o[6] = p.theta[i];
+    }
+  }
+}
+
 // d(rep distances)/d(box): one workgroup per frustum reduces over its points.
 //   g = drep[m, C..C+5];  du = g1 - g0, dv = g3 - g2, dq = g5 - g4
 //   d centre = -(du*ex + dv*ey + dq*ez) ; d l = (g0+g1)/2, d h = (g2+g3)/2, d w = (g4+g5)/2
@@ -386,6 +414,18 @@ extern "C" int t3d_boxpc_rep(const t3d_boxpc_rep_args* a, t3d_stream_t stream) {
   if (a->y_dims_cls && !a->y_orient_cls) return T3D_ERR_ARG;
   if (a->M <= 0 || a->C < 3 || a->ld_rep < a->C + 6 || a->rows_per_frustum % 256) return T3D_ERR_SHAPE;
   T3D_LAUNCH(k_boxpc_rep, dim3((a->M + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+extern "C" int t3d_boxpc_rep_b(const t3d_boxpc_rep_b_args* a, t3d_stream_t stream) {
+  if (!a || (!a->box_out && !a->rowmask)) return T3D_ERR_ARG;
+  if (a->box_out && (!a->center || !a->dims || !a->theta || (a->y_dims_cls && !a->y_orient_cls))) return T3D_ERR_ARG;
+  if (a->rowmask && (!a->pc || !a->pc_out)) return T3D_ERR_ARG;
+  if (a->B <= 0 || a->rows_per_frustum <= 0 || (long)a->B * a->rows_per_frustum > (1L << 30)) return T3D_ERR_SHAPE;
+  if (a->rowmask && (a->C <= 0 || a->ld_pc < a->C || a->ld_out < a->C)) return T3D_ERR_SHAPE;
+  const int n = a->rowmask ? a->B * a->rows_per_frustum : a->B;
+  T3D_LAUNCH(k_boxpc_rep_b, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }

@@ -348,7 +348,10 @@ class VarStore:
                 if strict:
                     raise KeyError(k)
                 continue
-            self.get(k).copy_(torch.as_tensor(np.asarray(v, dtype=np.float32)).reshape(self.index[k][1]))
+            v = np.asarray(v, dtype=np.float32)
+            if v.size != int(np.prod(self.index[k][1])):
+                raise ValueError('variable %s: the state holds shape %s, the graph declares %s' % (k, v.shape, self.index[k][1]))
+            self.get(k).copy_(torch.as_tensor(v).reshape(self.index[k][1]))
 
     def trainable_ranges(self, prefixes=None):
         """Contiguous [offset, n) ranges of the trainable variables whose name starts with one of
@@ -435,10 +438,12 @@ class PointLayer:
     """tf_util.conv2d 1x1 (+ batch_norm + ReLU) over M = B*N point rows (tf_util.py:1258-1323)."""
 
     def __init__(self, g, scope, K, N, w=None, bias=None, kernel_1xD=False, w_name=None, w_row0=0, pool=False, gram=None, bn=True,
-                 n_alloc=None):
+                 n_alloc=None, pooled_out=None):
         """bn=False: tf_util.conv2d(bn=False) -- no batch-norm variables, the forward emits the GEMM only (forward-only surface:
         the hot path has no such layer except conv10, which lives in the segmentation head).  n_alloc: padded column count of the
-        GEMM (N < 64 outputs: the weights are copied into a zero-padded [K, n_alloc] matrix in front of the launch)."""
+        GEMM (N < 64 outputs: the weights are copied into a zero-padded [K, n_alloc] matrix in front of the launch).
+        pooled_out: (tensor, ld) -- a pooled layer writes its [B, N] max-pool into the first N columns of this [B, ld] view (a column
+        slice of a wider per-frustum buffer: the concat of representation B's feats_lv1 without a copy)."""
         self.g, self.scope, self.K, self.N = g, scope, K, N
         self.bn = bn
         # pooled layers: Gram-form backward (t3d.h K11e) -- the [M,N] output is never stored
@@ -484,6 +489,9 @@ class PointLayer:
             self.pmax, self.pmin = rt.zeros(T, N), rt.zeros(T, N)
             self.pamax, self.pamin = rt.zeros(T, N, dtype=torch.int32), rt.zeros(T, N, dtype=torch.int32)
             self.pooled, self.argidx, self.ysel = rt.zeros(B, N), rt.zeros(B, N, dtype=torch.int32), rt.zeros(B, N)
+        self.ld_pooled = N
+        if pool and pooled_out is not None:
+            self.pooled, self.ld_pooled = pooled_out
         self.src = None
         self.dz = None
         self.coef = None
@@ -522,7 +530,7 @@ class PointLayer:
         if pool:                      # the max-pool pick of the same channels rides in the finalize launch (K3)
             f.pool_pmax, f.pool_pmin, f.pool_pamax, f.pool_pamin = fptr(self.pmax), fptr(self.pmin), iptr(self.pamax), iptr(self.pamin)
             f.pool_B, f.pool_tiles_per_frustum = g.B, g.rpf // TILE
-            f.pooled, f.ld_pooled, f.argidx, f.ysel = fptr(self.pooled), self.N, iptr(self.argidx), fptr(self.ysel)
+            f.pooled, f.ld_pooled, f.argidx, f.ysel = fptr(self.pooled), self.ld_pooled, iptr(self.argidx), fptr(self.ysel)
         plan.add('t3d_bn_fwd_finalize', f)
         self._fin_args = f
         self.out = None if self.gram else ActSpec(self.y, self.N, self.N, 0, self.scale, self.shift, True, producer=self)
@@ -541,6 +549,7 @@ class PointLayer:
             self.pmax, self.pmin = rt.zeros(T, N), rt.zeros(T, N)
             self.pamax, self.pamin = rt.zeros(T, N, dtype=torch.int32), rt.zeros(T, N, dtype=torch.int32)
             self.pooled, self.argidx, self.ysel = rt.zeros(B, N), rt.zeros(B, N, dtype=torch.int32), rt.zeros(B, N)
+            self.ld_pooled = N
             self.pool = True
         a, f = self._fwd_args, self._fin_args
         self.rowmask = rowmask
@@ -606,7 +615,7 @@ class PointLayer:
         a = abi.BnBwdFinalizeArgs()
         if self.pool:
             a.dpool_in, a.ld_dpool_in = fptr(dpool_in), ld_dpool_in
-            a.pooled, a.ld_pooled, a.ysel, a.dpool, a.B = fptr(self.pooled), self.N, fptr(self.ysel), fptr(self.dpool), g.B
+            a.pooled, a.ld_pooled, a.ysel, a.dpool, a.B = fptr(self.pooled), self.ld_pooled, fptr(self.ysel), fptr(self.dpool), g.B
         else:
             a.psum_dz, a.psum_dzy, a.n_tiles = fptr(self.psum_dz), fptr(self.psum_dzy), self.T
         a.count, a.N = self.M, self.N
@@ -842,7 +851,10 @@ class FcLayer:
 
     IDENTITY = 'identity'      # w=IDENTITY: no matmul (a standalone batch_norm_for_fc / dropout node on a [B,N] tensor)
 
-    def __init__(self, g, scope, K, N, bn=True, act='relu', K2=0, w=None, bias='own', keep_prob=None, drop_scope=None, bn_scope=None):
+    def __init__(self, g, scope, K, N, bn=True, act='relu', K2=0, w=None, bias='own', keep_prob=None, drop_scope=None, bn_scope=None,
+                 out=None, ld_out=None):
+        """out, ld_out: the activated output goes to the first N columns of this [B, ld_out] view (a column slice of a wider
+        buffer) instead of a [B, N] tensor of its own."""
         self.g, self.scope, self.K, self.K2, self.N, self.bn, self.act = g, scope, K, K2, N, bn, act
         rt, vs = g.rt, g.vars
         B = g.B
@@ -868,7 +880,8 @@ class FcLayer:
             self.mv = vs.const(bn_scope + '/moving_variance', (N,), 1.0, trainable=False)
             self.mean, self.invstd = rt.zeros(N), rt.zeros(N)
         self.y = rt.zeros(B, N)
-        self.out = rt.zeros(B, N)
+        self.out = rt.zeros(B, N) if out is None else out
+        self.ld_out = N if out is None else ld_out
         self.dy = None
         self.keep_prob = keep_prob
         self.drop_scope = drop_scope
@@ -891,7 +904,7 @@ class FcLayer:
         if self.use_drop:
             a.drop_mask, a.keep_prob = fptr(self.drop_mask), self.keep_prob
         a.add_in, a.ld_add, a.add_n = fptr(add_in), ld_add, add_n
-        a.y, a.out, a.ld_out, a.B, a.N = fptr(self.y), fptr(self.out), self.N, g.B, self.N
+        a.y, a.out, a.ld_out, a.B, a.N = fptr(self.y), fptr(self.out), self.ld_out, g.B, self.N
         plan.add('t3d_fc_fwd', a)
         return self.out
 
@@ -905,7 +918,7 @@ class FcLayer:
         else:
             a.dy_next, a.w_next, a.N_next = fptr(nxt.dy), fptr(nxt.w), nxt.N
         a.in_, a.ld_in, a.K, a.in2, a.ld_in2, a.K2 = fptr(self.x), self.ld_in, self.K, fptr(self.in2), self.ld_in2, self.K2
-        a.y, a.out, a.ld_out = fptr(self.y), fptr(self.out), self.N
+        a.y, a.out, a.ld_out = fptr(self.y), fptr(self.out), self.ld_out
         if self.bn:
             a.gamma, a.beta, a.mean, a.invstd = fptr(self.gamma), fptr(self.beta), fptr(self.mean), fptr(self.invstd)
         a.bn_training = int(self.is_training)
@@ -921,22 +934,24 @@ class FcLayer:
         a.B, a.N = g.B, self.N
         plan.add('t3d_fc_bwd', a)
 
-    def dinput(self, plan, K=None, alpha=1.0, add_in=None, ld_add=0, bn_bwd_of=None, param_grads=True):
-        """[B,K] gradient w.r.t. the first K input columns.  `bn_bwd_of`: the max-pooled PointLayer whose pooled feature
-        these columns are -- its batch-norm-backward finalize (pooled form) then runs inside this launch and the layer's
-        later bn_bwd(plan, dpool_in=<this result>) call is a no-op."""
+    def dinput(self, plan, K=None, alpha=1.0, add_in=None, ld_add=0, bn_bwd_of=None, param_grads=True, row0=0, out=None):
+        """[B,K] gradient w.r.t. the K input columns row0 .. row0+K-1 (weight rows; default: the first K).  `bn_bwd_of`: the
+        max-pooled PointLayer whose pooled feature these columns are -- its batch-norm-backward finalize (pooled form) then runs inside
+        this launch and the layer's later bn_bwd(plan, dpool_in=<this result>) call is a no-op.  `out`: a [B,K] buffer to write
+        (default: a new one)."""
         g = self.g
         K = K or self.K
-        out = g.rt.zeros(g.B, K)
+        out = g.rt.zeros(g.B, K) if out is None else out
+        w = self.w if row0 == 0 else self.w[row0:row0 + K]
         a = abi.FcDinputArgs()
-        a.dy, a.N, a.w, a.add_in, a.ld_add, a.alpha, a.din, a.ld_din, a.B, a.K = fptr(self.dy), self.N, fptr(self.w), fptr(add_in), \
+        a.dy, a.N, a.w, a.add_in, a.ld_add, a.alpha, a.din, a.ld_din, a.B, a.K = fptr(self.dy), self.N, fptr(w), fptr(add_in), \
             ld_add, alpha, fptr(out), K, g.B, K
         L = bn_bwd_of
         if L is not None and FUSE_BWD:
             assert L.pool and L.N == K
             L._ensure_bwd_buffers()
             vs = g.vars
-            a.bn_pooled, a.bn_ld_pooled, a.bn_ysel, a.bn_dpool, a.bn_count = fptr(L.pooled), L.N, fptr(L.ysel), fptr(L.dpool), L.M
+            a.bn_pooled, a.bn_ld_pooled, a.bn_ysel, a.bn_dpool, a.bn_count = fptr(L.pooled), L.ld_pooled, fptr(L.ysel), fptr(L.dpool), L.M
             a.bn_gamma, a.bn_mean, a.bn_invstd, a.bn_scale = fptr(L.gamma), fptr(L.mean), fptr(L.invstd), fptr(L.scale)
             a.bn_frozen = int(not L.is_training)
             if param_grads and L.is_training:

@@ -825,6 +825,7 @@ class BoxPCNet:
         self.F1 = FcLayer(g, s + 'fc1', 512, 512, K2=oh, keep_prob=0.7, drop_scope=s + 'dp1')
         self.F2 = FcLayer(g, s + 'fc2', 512, 256, keep_prob=0.7, drop_scope=s + 'dp2')
         self.F3 = FcLayer(g, s + 'fc3', 256, 9, bn=False, act=None)
+        self.out9 = self.F3.out
 
     def fwd(self, plan, pc, center, dims, theta, one_hot, is_training, y_dims_cls=None, y_orient_cls=None, rowmask=None):
         """`rowmask` ([M] 0/1): the net sees pc * mask (--mask_pc_for_boxpc, test_semisup.py:103-105)."""
@@ -863,6 +864,143 @@ class BoxPCNet:
             self.P1.wgrad(plan)
 
 
+class BoxPCNetB:
+    """Box-PC Fit network, representation 'B' (independent_box_pc_mask_features_model, semisup_models.py:400-470, under the literal
+    scope `box_pc_mask_model`): the box 7-vector through the MLP `extract_box_feats` (mlps, semisup_models.py:30-42: 7 -> 128 -> 128
+    -> 256 with batch-norm + ReLU, -> 512 linear), the RAW point cloud through conv-reg1..4 + max-pool, feats_lv1 = [box_feat |
+    pooled] (B, 1024), then fc1 1024(+one_hot) -> 512, fc2 -> 512, dropout 0.7, fc3 -> 256, dropout 0.7, fc4 -> 9.
+
+    feats_lv1 is one [B, 1024] buffer: the box MLP's fc3 writes columns 0..511, conv-reg4's pool columns 512..1023 (no concat).
+    The box reaches the net only through the box MLP, so the input gradient of a frozen net (bwd(param_grads=False), stage c) is
+    fc0's (K = 7) and no per-point launch is part of it.
+
+    points: another BoxPCNetB of the same variables whose conv-reg1..4 this one reads instead of emitting its own (the frozen net of
+    stage c: its point branch sees the same point cloud in every evaluation -- eval-mode batch-norm, no dropout -- and is emitted once).
+    split_fc1: fc1 reads [box_feat] as its first input and the pooled columns as its second (`in2`), wherever they live; the
+    form of every stage-c evaluation (no one-hot there, nets.SemiModelF), shared point branch or not."""
+
+    def __init__(self, g, scope_prefix='', use_one_hot=False, points=None, split_fc1=False):
+        self.g = g
+        s = scope_prefix + 'box_pc_mask_model/'
+        self.scope = s
+        B = g.B
+        oh = NUM_CLASS if use_one_hot else 0
+        self.oh, self.split_fc1 = oh, bool(split_fc1)
+        assert not (self.split_fc1 and oh), 'split fc1 input: no one-hot column block'
+        self.box7 = g.rt.zeros(B, 7)
+        self.feats = g.rt.zeros(B, 1024)                         # feats_lv1 = [box_feat | pooled]
+        self.pc_masked = None
+        e = s + 'extract_box_feats/'                              # creation order of the reference: box MLP, conv-reg1..4, fc1..fc4
+        self.E0 = FcLayer(g, e + 'fc0', 7, 128)
+        self.E1 = FcLayer(g, e + 'fc1', 128, 128)
+        self.E2 = FcLayer(g, e + 'fc2', 128, 256)
+        self.E3 = FcLayer(g, e + 'fc3', 256, 512, bn=False, act=None, out=self.feats[:, :512], ld_out=1024)
+        if points is None:
+            C_ = g.C
+            self.P1 = PointLayer(g, s + 'conv-reg1', C_, 128, kernel_1xD=True)
+            self.P2 = PointLayer(g, s + 'conv-reg2', 128, 128)
+            self.P3 = PointLayer(g, s + 'conv-reg3', 128, 256)
+            self.P4 = PointLayer(g, s + 'conv-reg4', 256, 512, pool=True, pooled_out=(self.feats[:, 512:], 1024))
+            self.owns_points = True
+        else:
+            self.P1, self.P2, self.P3, self.P4 = points.P1, points.P2, points.P3, points.P4
+            self.owns_points = False
+        self.F1 = FcLayer(g, s + 'fc1', 512 if self.split_fc1 else 1024, 512, K2=512 if self.split_fc1 else oh)
+        self.F2 = FcLayer(g, s + 'fc2', 512, 512, keep_prob=0.7, drop_scope=s + 'dp2')
+        self.F3 = FcLayer(g, s + 'fc3', 512, 256, keep_prob=0.7, drop_scope=s + 'dp3')
+        self.F4 = FcLayer(g, s + 'fc4', 256, 9, bn=False, act=None)
+        self.out9 = self.F4.out
+
+    def layers(self):
+        return (self.E0, self.E1, self.E2, self.E3, self.P1, self.P2, self.P3, self.P4, self.F1, self.F2, self.F3, self.F4)
+
+    def fwd_points(self, plan, pc, is_training, rowmask=None):
+        """conv-reg1..4 + max-pool on the raw point cloud, read in place; `rowmask` ([M] 0/1): on pc * mask (--mask_pc_for_boxpc,
+        test_semisup.py:103-105), written once by t3d_boxpc_rep_b."""
+        assert self.owns_points
+        g = self.g
+        src = pc
+        if rowmask is not None:
+            if self.pc_masked is None:
+                self.pc_masked = g.rt.zeros(g.M, g.ldpc)
+            a = abi.BoxPcRepBArgs(None, None, None, None, None, None, fptr(pc), g.ldpc, g.C, fptr(rowmask), fptr(self.pc_masked), g.ldpc,
+                                  g.B, g.rpf)
+            plan.add('t3d_boxpc_rep_b', a)
+            src = self.pc_masked
+        x = ActSpec(src, g.ldpc, g.C)
+        x = self.P1.fwd(plan, x, is_training)
+        x = self.P2.fwd(plan, x, is_training)
+        x = self.P3.fwd(plan, x, is_training)
+        self.P4.fwd(plan, x, is_training)
+
+    def fwd_box(self, plan, center, dims, theta, is_training, y_dims_cls=None, y_orient_cls=None):
+        """box_out[B,7] (either box form) and the box MLP into feats_lv1[:, 0:512]."""
+        g = self.g
+        a = abi.BoxPcRepBArgs(fptr(center), fptr(dims), fptr(theta), iptr(y_dims_cls), iptr(y_orient_cls), fptr(self.box7), None, 0, g.C,
+                              None, None, 0, g.B, g.rpf)
+        plan.add('t3d_boxpc_rep_b', a)
+        f = self.E0.fwd(plan, self.box7, 7, is_training)
+        f = self.E1.fwd(plan, f, 128, is_training)
+        f = self.E2.fwd(plan, f, 128, is_training)
+        self.E3.fwd(plan, f, 256, is_training)
+
+    def fwd_head(self, plan, one_hot, is_training):
+        if self.split_fc1:
+            f = self.F1.fwd(plan, self.feats, 1024, is_training, in2=self.P4.pooled, ld_in2=self.P4.ld_pooled)
+        else:
+            f = self.F1.fwd(plan, self.feats, 1024, is_training, in2=one_hot if self.oh else None, ld_in2=NUM_CLASS)
+        f = self.F2.fwd(plan, f, 512, is_training)
+        f = self.F3.fwd(plan, f, 512, is_training)
+        self.out = self.F4.fwd(plan, f, 256, is_training)
+        return self.out
+
+    def fwd(self, plan, pc, center, dims, theta, one_hot, is_training, y_dims_cls=None, y_orient_cls=None, rowmask=None):
+        """The whole net, in the reference's order (box MLP, point branch, head)."""
+        self.fwd_box(plan, center, dims, theta, is_training, y_dims_cls=y_dims_cls, y_orient_cls=y_orient_cls)
+        self.fwd_points(plan, pc, is_training, rowmask=rowmask)
+        return self.fwd_head(plan, one_hot, is_training)
+
+    def bwd(self, plan, dout, param_grads=True, dbox7=None):
+        """param_grads=False (the frozen net of stage c): the data gradient only, down to d box7 (fc0's input gradient, into
+        `dbox7`); nothing per point.  param_grads=True (stage b): every variable's gradient; fc1's input gradient split by weight
+        rows -- rows 512..1023 (pooled) with conv-reg4's pooled batch-norm backward in the same launch, rows 0..511 (box_feat) into
+        the box MLP's backward."""
+        self.F4.bwd(plan, dout=dout, ld_dout=9, param_grads=param_grads)
+        self.F3.bwd(plan, nxt=self.F4, param_grads=param_grads)
+        self.F2.bwd(plan, nxt=self.F3, param_grads=param_grads)
+        self.F1.bwd(plan, nxt=self.F2, param_grads=param_grads)
+        dfeat = self.F1.dinput(plan, K=512, param_grads=param_grads)
+        if param_grads and self.F1.is_training:
+            # fc3's bias shifts every row of fc1's input by the same vector, which fc1's training-mode batch-norm removes: its gradient is
+            # exactly 0 (as computed, a sum of rounding noise); not written, the buffer keeps its 0
+            self.E3.bias_grad = None
+        self.E3.bwd(plan, dout=dfeat, ld_dout=512, param_grads=param_grads)
+        self.E2.bwd(plan, nxt=self.E3, param_grads=param_grads)
+        self.E1.bwd(plan, nxt=self.E2, param_grads=param_grads)
+        self.E0.bwd(plan, nxt=self.E1, param_grads=param_grads)
+        if not param_grads:
+            return self.E0.dinput(plan, K=7, param_grads=False, out=dbox7)
+        assert self.owns_points and not self.split_fc1
+        dpool = self.F1.dinput(plan, K=512, row0=512, bn_bwd_of=self.P4)
+        self.P4.bn_bwd(plan, dpool_in=dpool, ld_dpool_in=512)
+        self.P4.bwd_pair(plan)
+        for lay in (self.P3, self.P2):
+            lay.bn_bwd(plan)
+            lay.bwd_pair(plan)
+        self.P1.bn_bwd(plan)
+        self.P1.wgrad(plan)
+
+
+def make_boxpc_net(c, g, scope_prefix='', use_one_hot=False, **kw):
+    """The Box-PC Fit net of c.BOX_PC_MASK_REPRESENTATION (semisup_models.py:297-324): 'A' (and '', the parser's default) or 'B'."""
+    rep = getattr(c, 'BOX_PC_MASK_REPRESENTATION', 'A')
+    if rep in ('A', ''):
+        return BoxPCNet(g, scope_prefix, use_one_hot)
+    if rep == 'B':
+        return BoxPCNetB(g, scope_prefix, use_one_hot, **kw)
+    raise Exception('Box pc mask representation not implemented: %s' % rep)
+
+
 class BoxPCLoss:
     def __init__(self, g):
         self.g = g
@@ -884,12 +1022,11 @@ class BoxPCModel:
     """Stage-b training graph (train_boxpc.py:219-261): GT box (label form) + point cloud -> Box-PC net -> loss."""
 
     def __init__(self, g, c, use_one_hot=False, inputs=None):
-        assert c.BOX_PC_MASK_REPRESENTATION in ('A', ''), 'representation B is in no published recipe (out of scope)'
         assert c.BOXPC_DELTA_LOSS_TYPE in ('huber', 'mse'), c.BOXPC_DELTA_LOSS_TYPE
         assert not (c.BOXPC_WEIGH_DELTA_LOSS_BY_CLS_CONF and c.BOXPC_WEIGH_DELTA_LOSS_BY_CLS_GT)       # boxpc_sunrgbd.py:166
         self.g, self.c = g, c
         self.inputs = inputs or Inputs(g)
-        self.net = BoxPCNet(g, '', use_one_hot)
+        self.net = make_boxpc_net(c, g, '', use_one_hot)
         self.loss_op = BoxPCLoss(g)
 
     def emit_forward(self, plan, is_training, with_loss):
@@ -906,9 +1043,13 @@ class BoxPCModel:
 
     def end_points(self):
         n = self.net
-        return {'boxpc_out': n.out, 'box_pc_rep': n.rep, 'loss': self.loss_op.loss, 'terms': self.loss_op.terms,
-                'boxpc_fit_logits': n.out[:, 7:9], 'boxpc_delta_center': n.out[:, 0:3], 'boxpc_delta_size': n.out[:, 3:6],
-                'boxpc_delta_angle': n.out[:, 6], 'feats_lv1': n.P4.pooled}
+        if isinstance(n, BoxPCNetB):
+            rep = {'box7': n.box7, 'feats_lv1': n.feats}
+        else:
+            rep = {'box_pc_rep': n.rep, 'feats_lv1': n.P4.pooled}
+        return dict({'boxpc_out': n.out, 'loss': self.loss_op.loss, 'terms': self.loss_op.terms,
+                     'boxpc_fit_logits': n.out[:, 7:9], 'boxpc_delta_center': n.out[:, 0:3], 'boxpc_delta_size': n.out[:, 3:6],
+                     'boxpc_delta_angle': n.out[:, 6]}, **rep)
 
 
 class SemiModelF:
@@ -919,9 +1060,11 @@ class SemiModelF:
     Backward follows the var_list of train_semisup_adv.py:415-422: nothing for the seg net, box_est/fc1-3 receive no
     gradient (the loss never reads the class-agnostic heads); the Box-PC net back-propagates data gradients only."""
 
-    def __init__(self, g, c, use_one_hot=True, train_classes=None, inputs=None, oracle_mask=False, mask_pc_for_boxpc=False):
+    def __init__(self, g, c, use_one_hot=True, train_classes=None, inputs=None, oracle_mask=False, mask_pc_for_boxpc=False,
+                 share_boxpc_points=True):
         """oracle_mask: the seg logits are replaced by stack([1 - y_seg, y_seg]) (semisup_v1_sunrgbd.py:161-162; test_semisup.py:75);
-        mask_pc_for_boxpc: the Box-PC net of the inference graph sees pc * mask (test_semisup.py:103-105)."""
+        mask_pc_for_boxpc: the Box-PC net of the inference graph sees pc * mask (test_semisup.py:103-105).
+        share_boxpc_points (representation B): one emission of the frozen net's point branch per step for every evaluation."""
         self.g, self.c = g, c
         self.inputs = inputs or Inputs(g)
         self.oracle_mask, self.mask_pc_for_boxpc = bool(oracle_mask), bool(mask_pc_for_boxpc)
@@ -941,14 +1084,23 @@ class SemiModelF:
         self.R1 = FcLayer(g, q + 'fc1', 512, 256, act=last, keep_prob=dp, drop_scope=q + 'dp1')
         self.R2 = FcLayer(g, q + 'fc2', 256, BOX_OUT_DIMS, bn=False, act=None)
         self.loss_op = StrongLoss(g)
-        self.boxpc = BoxPCNet(g, 'D_boxpc_branch/', False)
+        # the frozen Box-PC net of c.BOX_PC_MASK_REPRESENTATION.  Representation B: its point branch (conv-reg1..4 + pool) does not
+        # depend on the box, so ONE emission of it serves every evaluation of a step (share_boxpc_points; False: one per evaluation,
+        # the same values -- kept for the test that says so)
+        self.rep_b = getattr(c, 'BOX_PC_MASK_REPRESENTATION', 'A') == 'B'
+        self.boxpc = make_boxpc_net(c, g, 'D_boxpc_branch/', False, split_fc1=True)
         # SEMI_REFINE_USING_BOXPC_DELTA_NUM > 1 in the TRAINING graph (train_semisup_adv.py:362-386): one evaluation of the frozen
         # Box-PC net per refinement step -- the same variables (reuse=True), own activations, because with
         # SEMI_BOXPC_MIN_FIT_LOSS_AFT_REFINE the fit loss reads the LAST evaluation and its gradient runs back through every step
         self.refine_train = max(1, int(c.SEMI_REFINE_USING_BOXPC_DELTA_NUM))
-        self.boxpc_nets = [self.boxpc] + [BoxPCNet(g, 'D_boxpc_branch/', False) for _ in range(self.refine_train - 1)]
+        pts = dict(points=self.boxpc if share_boxpc_points else None) if self.rep_b else {}
+        self.boxpc_nets = [self.boxpc] + [make_boxpc_net(c, g, 'D_boxpc_branch/', False, split_fc1=True, **pts)
+                                          for _ in range(self.refine_train - 1)]
         for i, net in enumerate(self.boxpc_nets[1:], 1):      # names under which tests read the decisions of the i-th further evaluation
-            for lay in (net.P1, net.P2, net.P3, net.P4, net.F1, net.F2, net.F3):
+            lays = net.layers() if self.rep_b else (net.P1, net.P2, net.P3, net.P4, net.F1, net.F2, net.F3)
+            for lay in lays:
+                if self.rep_b and not net.owns_points and lay in (net.P1, net.P2, net.P3, net.P4):
+                    continue                                  # (the shared point branch is evaluation 0's)
                 lay.decision_scope = lay.scope.replace('D_boxpc_branch/', 'D_boxpc_branch@%d/' % i, 1)
         self.loss_eval = self.refine_train - 1 if c.SEMI_BOXPC_MIN_FIT_LOSS_AFT_REFINE else 0
         self.refine_w = int(bool(c.SEMI_WEIGH_BOXPC_DELTA_DURING_TEST)) + int(bool(c.BOXPC_WEIGH_DELTA_PRED_BY_CLS_CONF))
@@ -957,7 +1109,7 @@ class SemiModelF:
         self.d_dims, self.dout9, self.fit_prob = rt.zeros(B, 3), rt.zeros(B, 9), rt.zeros(B)
         self.terms, self.loss = rt.zeros(2), rt.zeros(1)
         self.W_iou2d, self.W_iou3d = rt.zeros(B), rt.zeros(B)      # get_iou_summary(W_pred_box, ..., 'W_') (semisup_v1_sunrgbd.py:414)
-        self.drep, self.dbox7 = rt.zeros(g.M, 8), rt.zeros(B, 7)
+        self.drep, self.dbox7 = (None if self.rep_b else rt.zeros(g.M, 8)), rt.zeros(B, 7)
         self.carry, self.dout9_chain = rt.zeros(B, 7), rt.zeros(B, 9)
         self.weak = None
         # inference graph (test_semisup.py:95-149): iterated Box-PC refinement of the F_ box
@@ -997,7 +1149,13 @@ class SemiModelF:
         cur = (self.cur_center, self.cur_dims, self.cur_theta)
         self.outs9 = []
         for i, net in enumerate(self.boxpc_nets):
-            self.outs9.append(net.fwd(plan, x.pc, src[0], src[1], src[2], x.one_hot_vec, False))
+            if not self.rep_b:
+                self.outs9.append(net.fwd(plan, x.pc, src[0], src[1], src[2], x.one_hot_vec, False))
+            else:
+                if net.owns_points:
+                    net.fwd_points(plan, x.pc, False)
+                net.fwd_box(plan, src[0], src[1], src[2], False)
+                self.outs9.append(net.fwd_head(plan, None, False))
             if self.refine_train > 1:      # box <- box - w * delta(box, pc); the totals give the F2_ heads (train_semisup_adv.py:376-399)
                 r = abi.BoxRefineStepArgs(fptr(self.outs9[i]), fptr(src[0]), fptr(src[1]), fptr(src[2]), fptr(cur[0]), fptr(cur[1]),
                                           fptr(cur[2]), fptr(self.total_delta), None, self.refine_w, int(i == 0), g.B)
@@ -1039,10 +1197,15 @@ class SemiModelF:
         lo.emit(plan, self.F_out, s1, self.seg.seg_loss, lab, c, normalize_by_3d_count=True)
         src = (lo.center, lo.reg_dims, lo.reg_theta)
         cur = (self.cur_center, self.cur_dims, self.cur_theta)
+        rowmask = self.seg.mask if self.mask_pc_for_boxpc else None      # (mask = argmax(logits) = the head's hard mask: both are 0 on a tie)
+        if self.rep_b and refine_num:
+            self.boxpc.fwd_points(plan, x.pc, False, rowmask=rowmask)      # the same for every refinement step: once
         for i in range(int(refine_num)):
-            # (mask = argmax(logits) = the head's hard mask: both are 0 on a tie)
-            out9 = self.boxpc.fwd(plan, x.pc, src[0], src[1], src[2], x.one_hot_vec, False,
-                                  rowmask=self.seg.mask if self.mask_pc_for_boxpc else None)
+            if self.rep_b:
+                self.boxpc.fwd_box(plan, src[0], src[1], src[2], False)
+                out9 = self.boxpc.fwd_head(plan, None, False)
+            else:
+                out9 = self.boxpc.fwd(plan, x.pc, src[0], src[1], src[2], x.one_hot_vec, False, rowmask=rowmask)
             a = abi.BoxRefineStepArgs(fptr(out9), fptr(src[0]), fptr(src[1]), fptr(src[2]), fptr(cur[0]), fptr(cur[1]), fptr(cur[2]),
                                       fptr(self.total_delta), fptr(self.fit_prob),
                                       int(bool(c.SEMI_WEIGH_BOXPC_DELTA_DURING_TEST)) + int(bool(c.BOXPC_WEIGH_DELTA_PRED_BY_CLS_CONF)),
@@ -1055,11 +1218,14 @@ class SemiModelF:
         dout, carry = self.dout9, None
         for i in range(self.loss_eval, -1, -1):       # the evaluation the fit loss read, then back through the refinement steps before it
             bp = self.boxpc_nets[i]
-            bp.bwd(plan, dout, param_grads=False)
-            n = abi.DgradNarrowArgs(bp.P1.dy_struct(), fptr(bp.P1.w), g.C, 6, fptr(self.drep), 8, g.M, 128)
-            plan.add('t3d_pointmlp_dgrad_narrow', n)
-            r = abi.BoxPcRepBwdArgs(fptr(x.pc), g.ldpc, fptr(bp.box7), fptr(self.drep), 8, 0, fptr(self.dbox7), g.B, g.rpf)
-            plan.add('t3d_boxpc_rep_bwd', r)
+            if self.rep_b:       # the box reaches the net only through its box MLP: fc4 .. fc1, box MLP, fc0's input gradient
+                bp.bwd(plan, dout, param_grads=False, dbox7=self.dbox7)
+            else:
+                bp.bwd(plan, dout, param_grads=False)
+                n = abi.DgradNarrowArgs(bp.P1.dy_struct(), fptr(bp.P1.w), g.C, 6, fptr(self.drep), 8, g.M, 128)
+                plan.add('t3d_pointmlp_dgrad_narrow', n)
+                r = abi.BoxPcRepBwdArgs(fptr(x.pc), g.ldpc, fptr(bp.box7), fptr(self.drep), 8, 0, fptr(self.dbox7), g.B, g.rpf)
+                plan.add('t3d_boxpc_rep_bwd', r)
             if i > 0:        # box_i = box_{i-1} - w * delta_{i-1}: gradient into evaluation i-1's deltas, and past it (carry)
                 q = abi.BoxRefineStepBwdArgs(fptr(self.outs9[i - 1]), fptr(self.dbox7), fptr(carry), fptr(self.carry),
                                              fptr(self.dout9_chain), self.refine_w, int(not self.c.BOXPC_STOP_GRAD_OF_CLS_VIA_DELTA), g.B)
@@ -1101,7 +1267,7 @@ class SemiModelF:
         return {'logits': self.seg.logits.view(B, N, 2), 'stage1_center': self.tnet.stage1_center,
                 'feats_lv1': self.box.feats_lv1, 'box_params': self.box.box_params, 'F_box_params': self.F_out,
                 'F_center': lo.center, 'F_dims': lo.reg_dims, 'F_theta': lo.reg_theta, 'boxpc_fit_prob': self.fit_prob,
-                'boxpc_out': self.boxpc.F3.out, 'boxpc_out_last': self.boxpc_nets[-1].F3.out, 'loss': self.loss, 'strong_loss': lo.loss, 'terms': self.terms,
+                'boxpc_out': self.boxpc.out9, 'boxpc_out_last': self.boxpc_nets[-1].out9, 'loss': self.loss, 'strong_loss': lo.loss, 'terms': self.terms,
                 'loss_terms': lo.terms, 'iou2ds': lo.iou2d, 'iou3ds': lo.iou3d, 'W_iou2ds': self.W_iou2d, 'W_iou3ds': self.W_iou3d,
                 'total_delta': self.total_delta, 'refined_center': self.cur_center,
                 'refined_dims': self.cur_dims, 'refined_theta': self.cur_theta}

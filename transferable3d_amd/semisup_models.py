@@ -147,14 +147,14 @@ def mlps_with_dropout(input_feat, layers, activation_fns, keep_probs, is_trainin
 def box_pc_mask_features_model(box, pc, logits, num_outputs, is_training, end_points, reuse, bn_for_output, normalize_pc=False,
                                normalize_method='SD', one_hot_vec=None, norm_box2D=None, bn_decay=None, c=None, scope=None):
     """The Box-PC Fit net on a (box, point cloud) pair -> ((B, num_outputs) output, {feature level: tensor})
-    (semisup_models.py:297-324 -> combined_box_pc_mask_features_model 326-398).  Representation 'A' (the only one in a
-    published recipe): the 6 signed face distances per point appended to the raw channels, conv D->128->128->256->512,
-    max-pool, FC 512 -> 256 -> num_outputs with dropout 0.7.  Variables live under the literal scope box_pc_mask_model/."""
+    (semisup_models.py:297-324).  Representation 'A' (combined_box_pc_mask_features_model 326-398): the 6 signed face distances per
+    point appended to the raw channels, conv D->128->128->256->512, max-pool, FC 512 -> 256 -> num_outputs with dropout 0.7.
+    Representation 'B' (independent_box_pc_mask_features_model 400-470): the box 7-vector through an MLP 7 -> 128 -> 128 -> 256 -> 512,
+    the raw point cloud through conv C->128->128->256->512 + max-pool, [box_feat | pooled] (B, 1024) -> FC 512 -> 512 -> 256 ->
+    num_outputs with dropout 0.7 after the second and third.  Variables live under the literal scope box_pc_mask_model/."""
     from .boxpc_sunrgbd import BoxRegHandle
     from .nets import BoxPCModel
-    if c.BOX_PC_MASK_REPRESENTATION == 'B':
-        raise NotImplementedError('BOX_PC_MASK_REPRESENTATION B (independent_box_pc_mask_features_model) is in no published recipe')
-    if c.BOX_PC_MASK_REPRESENTATION != 'A':
+    if c.BOX_PC_MASK_REPRESENTATION not in ('A', 'B'):
         raise Exception('Box pc mask representation not implemented: %s' % c.BOX_PC_MASK_REPRESENTATION)
     if logits is not None or normalize_pc or norm_box2D is not None or bn_for_output:
         raise NotImplementedError('mask / normalize_pc / norm_box2D / bn_for_output are off at every call site of the reference')
@@ -172,6 +172,11 @@ def box_pc_mask_features_model(box, pc, logits, num_outputs, is_training, end_po
     net = ctx.assembly.net
     B = e.B
     T = lambda buf, shape, name: api.Tensor(ctx, buf, shape, name)
+    if c.BOX_PC_MASK_REPRESENTATION == 'B':
+        feats = {'box_pc_mask_model_feats_lv1': T(net.feats, (B, 1024), 'feats_lv1'),
+                 'box_pc_mask_model_feats_lv2': T(net.F2.out, (B, 512), 'feats_lv2'),
+                 'box_pc_mask_model_feats_lv3': T(net.F3.out, (B, 256), 'feats_lv3')}
+        return T(net.F4.out, (B, 9), 'box_pc_mask_model/output'), feats
     feats = {'box_pc_mask_model_feats_lv1': T(net.P4.pooled, (B, 512), 'feats_lv1'),
              'box_pc_mask_model_feats_lv2': T(net.F1.out, (B, 512), 'feats_lv2'),
              'box_pc_mask_model_feats_lv3': T(net.F2.out, (B, 256), 'feats_lv3')}

@@ -73,7 +73,7 @@ def get_semi_model_final(pc, bg_pc, img, one_hot_vec, is_training, use_one_hot, 
     end_points['F_pred_box_reg'] = (T(lo.center, (B, 3), 'F_center_reg'), T(lo.reg_dims, (B, 3), 'F_dims_reg'),
                                     T(lo.reg_theta, (B,), 'F_orient_reg'))
     # Box-PC branch outputs and the refined F2_ heads (train_semisup_adv.py:376-411), evaluated on the host at fetch time
-    out9 = T(m.boxpc.F3.out, (B, 9), 'boxpc_out')
+    out9 = T(m.boxpc.out9, (B, 9), 'boxpc_out')
     end_points['boxpc_fit_prob'] = T(m.fit_prob, (B,), 'boxpc_fit_prob')
     ST = semisup_models.SlicedTensor
 
@@ -91,7 +91,7 @@ def get_semi_model_final(pc, bg_pc, img, one_hot_vec, is_training, use_one_hot, 
         return (ST(full, lambda: full.numpy()[:, 0:3] * wd()[:, None], (B, 3), 'boxpc_delta_center'),
                 ST(full, lambda: full.numpy()[:, 3:6] * wd()[:, None], (B, 3), 'boxpc_delta_size'),
                 ST(full, lambda: full.numpy()[:, 6] * wd(), (B,), 'boxpc_delta_angle'))
-    end_points['boxpc_delta_center'], end_points['boxpc_delta_size'], end_points['boxpc_delta_angle'] = delta_heads(m.boxpc.F3.out)
+    end_points['boxpc_delta_center'], end_points['boxpc_delta_size'], end_points['boxpc_delta_angle'] = delta_heads(m.boxpc.out9)
     if not ctx.is_training:
         # inference graph (test_semisup.py:95-149): SEMI_REFINE_USING_BOXPC_DELTA_NUM refinement steps on the device,
         # F2_ = F_ - accumulated deltas
@@ -113,7 +113,7 @@ def get_semi_model_final(pc, bg_pc, img, one_hot_vec, is_training, use_one_hot, 
         # one evaluation per step on the device (nets.SemiModelF.boxpc_nets); the fit probability is the first evaluation's, or the
         # last one's with SEMI_BOXPC_MIN_FIT_LOSS_AFT_REFINE (train_semisup_adv.py:388-389); delta heads = the last evaluation's
         end_points['boxpc_delta_center'], end_points['boxpc_delta_size'], end_points['boxpc_delta_angle'] = \
-            delta_heads(m.boxpc_nets[-1].F3.out)
+            delta_heads(m.boxpc_nets[-1].out9)
         tot = T(m.total_delta, (B, 7), 'total_delta')
         end_points['F2_center'] = ST(tot, lambda: end_points['F_center'].numpy() - tot.numpy()[:, 0:3], (B, 3), 'F2_center')
         end_points['F2_heading_scores'] = end_points['F_heading_scores']
