@@ -1637,10 +1637,10 @@ def test_x3_weight_gradient_rounding_bias_is_bounded(hip_lib, sign):
 
 @pytest.mark.parametrize('K,N', [(128, 256), (64, 64), (96, 512)])
 def test_x3_forward_variants_are_bit_identical_to_the_default(hip_lib, monkeypatch, K, N):
-    """Two opt-in forms of the x3 forward kernel reproduce the default bit for bit -- every output, statistics and pool partials
+    """Other forms of the x3 forward kernel reproduce the default bit for bit -- every output, statistics and pool partials
     included: the weights pre-split into three bf16 planes (t3d_split_x3 + w_x3, 16-byte copies instead of the in-kernel split) and
-    the producer / consumer workgroups of round 5's experiment (T3D_X3_PC=1: eight waves, three LDS stages), and the eight-wave
-    128 x 256 tiles that launches of two or more rounds take by default (T3D_X3_W8; forced here at a small M, N % 256 == 0 only)."""
+    the eight-wave 128 x 256 tiles that launches of two or more rounds take by default (T3D_X3_W8; forced here at a small M,
+    N % 256 == 0 only)."""
     dev = 'cuda'
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     torch.manual_seed(7)
@@ -1652,9 +1652,8 @@ def test_x3_forward_variants_are_bit_identical_to_the_default(hip_lib, monkeypat
     bias = torch.randn(N, device=dev) * 0.1
     pf, _, fstride = _x3_frag_planes(hip_lib, w, st)
     res = {}
-    modes = ('default', 'presplit', 'producer_consumer') + (('eight_waves', 'presplit_eight_waves') if N % 256 == 0 else ())
+    modes = ('default', 'presplit') + (('eight_waves', 'presplit_eight_waves') if N % 256 == 0 else ())
     for mode in modes:
-        monkeypatch.setenv('T3D_X3_PC', '2' if mode == 'producer_consumer' else '0')
         monkeypatch.setenv('T3D_X3_W8', '2' if mode in ('eight_waves', 'presplit_eight_waves') else '0')
         o = [torch.zeros(M, N, device=dev)] + [torch.zeros(T, N, device=dev) for _ in range(4)] + \
             [torch.zeros(T, N, dtype=torch.int32, device=dev) for _ in range(2)]

@@ -1,7 +1,5 @@
 #!/usr/bin/env python3
-"""Times t3d_pool_sparse_rows (row-gated) on the arg-max patterns of the bench workload's three pooled layers, for the library in
-$T3D_LIB (default: the in-tree one; ablation builds: tools/build_variant.sh noscan "-DT3D_ABL_SR_NOSCAN" noadd "-DT3D_ABL_SR_NOADD").
-The patterns come from one forward + backward of SEMI_MODEL A at B=32, N=1024 with the in-tree library."""
+"""Times t3d_pool_sparse_rows (row-gated) on the arg-max patterns of the bench workload's three pooled layers.  The patterns come from one forward + backward of SEMI_MODEL A at B=32, N=1024 with the in-tree library."""
 import ctypes as C
 import os
 import sys
@@ -25,24 +23,23 @@ def main():
     m.emit_forward(g.fwd, True, True); m.emit_backward(g.bwd); g.finalize()
     m.inputs.load(make_batch(B, N, Cc, seed=1234))
     g.fwd.run(); g.bwd.run(); torch.cuda.synchronize()
-    libs = [('in-tree', g.rt.lib)] + [(os.path.basename(p), abi.load(p)) for p in sys.argv[1:]]
+    lib = g.rt.lib
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     R = 50
     for name, L in (('seg conv5', m.seg.L5), ('tnet conv3', m.tnet.T3), ('box conv4', m.box.B4)):
         S, live = torch.zeros_like(L.S), torch.zeros(L.M, dtype=torch.int32, device='cuda')
         a = abi.PoolSparseRowsArgs(iptr(L.argidx), fptr(L.dpool), fptr(L.wc), B, L.N, L.K, g.rpf, fptr(S), iptr(live))
         line = '%-11s K%-4d N%-5d' % (name, L.K, L.N)
-        for lname, lib in libs:
-            for _ in range(3):
-                assert lib.t3d_pool_sparse_rows(C.byref(a), s) == 0
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(R):
-                lib.t3d_pool_sparse_rows(C.byref(a), s)
-            e1.record()
-            torch.cuda.synchronize()
-            line += '  %s %6.1f us' % (lname, e0.elapsed_time(e1) / R * 1e3)
+        for _ in range(3):
+            assert lib.t3d_pool_sparse_rows(C.byref(a), s) == 0
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(R):
+            lib.t3d_pool_sparse_rows(C.byref(a), s)
+        e1.record()
+        torch.cuda.synchronize()
+        line += '  %6.1f us' % (e0.elapsed_time(e1) / R * 1e3)
         print(line)
 
 

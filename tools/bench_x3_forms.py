@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Variants of the x3 GEMM kernels against the default form: bit-identity of every output and time per launch on the layer shapes of
-the hot path (M = 32768).  T3D_PC_MODES: comma list of 0 (default), 1 / 2 (producer / consumer waves, T3D_X3_PC), p (the weights
-pre-split into three bf16 planes in fragment order, t3d_split_x3_frag + w_x3), w (eight-wave 128 x 256 forward tiles, T3D_X3_W8=2).  T3D_LIB: alternative library; T3D_ONLY=fwd:512x256 one case."""
+the hot path (M = 32768).  T3D_X3_MODES: comma list of 0 (default), p (the weights pre-split into three bf16 planes in fragment order, t3d_split_x3_frag + w_x3), w (eight-wave 128 x 256 forward tiles, T3D_X3_W8=2).  T3D_LIB: alternative library; T3D_ONLY=fwd:512x256 one case."""
 import ctypes as C
 import os
 import sys
@@ -14,7 +13,7 @@ from transferable3d_amd.abi import fptr, iptr
 
 FWD = [(512, 256, False), (256, 128, False), (128, 256, False), (256, 512, True), (128, 128, False), (128, 1024, True), (64, 128, False), (64, 64, False)]
 BWD = [(512, 256), (256, 128), (128, 256), (128, 128), (64, 128), (64, 64)]
-MODES = os.environ.get('T3D_PC_MODES', '0,1').split(',')
+MODES = os.environ.get('T3D_X3_MODES', '0,p,w').split(',')
 
 
 def timed(fn, R=30):
@@ -61,7 +60,6 @@ def main():
         from bench_x3 import frag_planes      # (round 6: `w_x3` = fragment-order planes, t3d_split_x3_frag)
         pf, pd, fstride = frag_planes(lib, w, s) if K % 32 == 0 else (None, None, 0)
         for mode in MODES:
-            os.environ['T3D_X3_PC'] = mode if mode in '012' else '0'
             os.environ['T3D_X3_W8'] = '2' if mode == 'w' else '0'
             a.w_x3, a.w_x3_stride = (C.c_void_p(pf.data_ptr()), fstride) if (mode == 'p' and pf is not None) else (None, 0)
             for t_ in [y, p1, p2] + pm:
@@ -74,7 +72,7 @@ def main():
         same = {m: all(torch.equal(u, v) for u, v in zip(outs[MODES[0]], outs[m])) for m in MODES[1:]}
         fl = 2.0 * M * K * N
         print('fwd %4d -> %4d %s ' % (K, N, 'pool' if pooled else '    ') +
-              '  '.join('pc=%s %7.1f us (%5.1f TF/s)' % (m, us[m], fl / us[m] / 1e6) for m in MODES) + '   identical: %s' % same, flush=True)
+              '  '.join('%s %7.1f us (%5.1f TF/s)' % (m, us[m], fl / us[m] / 1e6) for m in MODES) + '   identical: %s' % same, flush=True)
     for K, N in BWD:
         if only and only != 'bwd:%dx%d' % (K, N):
             continue
@@ -102,7 +100,6 @@ def main():
         from bench_x3 import frag_planes
         pf, pd, fstride = frag_planes(lib, w, s) if K % 32 == 0 else (None, None, 0)
         for mode in MODES:
-            os.environ['T3D_X3_PC'] = mode if mode in '012' else '0'
             d.w_x3, d.w_x3_stride = (C.c_void_p(pd.data_ptr()), fstride) if (mode == 'p' and pd is not None) else (None, 0)
             for t_ in (out, slabs, p1, p2):
                 t_.zero_()
@@ -114,8 +111,7 @@ def main():
         same = {m: all(torch.equal(u, v) for u, v in zip(outs[MODES[0]], outs[m])) for m in MODES[1:]}
         fl = 4.0 * M * K * N
         print('bwd %4d -> %4d (one_pass %d) ' % (K, N, one.value) +
-              '  '.join('pc=%s %7.1f us (%5.1f TF/s)' % (m, us[m], fl / us[m] / 1e6) for m in MODES) + '   identical: %s' % same, flush=True)
-    os.environ.pop('T3D_X3_PC', None)
+              '  '.join('%s %7.1f us (%5.1f TF/s)' % (m, us[m], fl / us[m] / 1e6) for m in MODES) + '   identical: %s' % same, flush=True)
     os.environ.pop('T3D_X3_W8', None)
     os.environ.pop('T3D_X3', None)
 

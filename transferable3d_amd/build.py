@@ -64,7 +64,7 @@ def _object_key(src, extra_flags):
 # main loop is a silent 10-30 % (round-2 review: five bf16 kernels spilled 10-49 VGPRs unnoticed).  build() parses hipcc's
 # -Rpass-analysis=kernel-resource-usage remarks and fails on any other kernel with `VGPRs Spill` > 0.
 SPILL_ALLOWED = {      # substring of the mangled name -> (most VGPRs it may spill, why)
-    'k_pointmlp_bwdILi128ELi128ELi128ENS_7PathX3PE': (2, 'opt-in pre-split-weights form (T3D_X3_PRESPLIT=1, off by default) of the fused x3 backward: 1 VGPR beside the hand-placed iteration'),
+    'k_pointmlp_bwdILi128ELi128ELi128ENS_7PathX3PE': (2, 'pre-split-weights form (the default; T3D_X3_PRESPLIT=0 turns it off) of the fused x3 backward: 1 VGPR beside the hand-placed iteration'),
     'k_pointmlp_bwdILi128ELi128ELi64ENS_7PathX3PE': (2, 'same'),
     'k_pointmlp_bwdILi128ELi64ELi128ENS_7PathX3PE': (2, 'same'),
     'k_pointmlp_bwdILi128ELi64ELi64ENS_7PathX3PE': (2, 'same'),
@@ -130,7 +130,7 @@ ISA_MAX_BURST = 2
 # instructions per MFMA by construction (half or a quarter of the MFMAs per staged element) and two micro-steps share a gap: 20.
 ISA_MAX_VALU_RUN = 20
 ISA_MAX_VALU_RUN_WIDE = 14
-ISA_GATED = ('PathX3E', 'PathX3WE', 'PathX3PE', 'PathX3WPE')      # mangled-name substrings: the x3 kernels of the default program (not the PathX3PC experiment)
+ISA_GATED = ('PathX3E', 'PathX3WE', 'PathX3PE', 'PathX3WPE')      # mangled-name substrings: the x3 kernels of the default program
 
 
 def check_x3_isa(asm_path, out_path=None):

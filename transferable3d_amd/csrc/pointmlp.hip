@@ -23,31 +23,10 @@
 
 namespace {
 
-#ifndef T3D_BK
-#define T3D_BK 32
-#endif
-constexpr int BK = T3D_BK;      // reduction depth of one LDS stage
-#ifndef T3D_WAVES
-#define T3D_WAVES 2
-#endif
-#ifndef T3D_FORCE_TILE
-#define T3D_FORCE_TILE 0       // diagnostic: 64 / 128 forces the column tile of fwd and dgrad
-#endif
+constexpr int BK = 32;          // reduction depth of one LDS stage
+constexpr int MIN_WAVES_PER_EU = 2;      // second __launch_bounds__ argument of the 256-thread kernels
 constexpr int LDR = BK + 4;
 constexpr int NT = 256;
-// prefetch distance (register slots) per kernel family.  Distance 2 was measured on MI355X (64-column kernels and
-// dgrad_gram<128>, B=32 N=1024 step): no gain (1.843 ms vs 1.822 ms per step) at 30-90 more VGPRs -- the narrow kernels
-// are bound by their fixed per-workgroup latency (first load, epilogue), not by the per-tile load latency -- so the
-// default stays 1; the variant is kept for other shapes.
-#ifndef T3D_PF_NARROW
-#define T3D_PF_NARROW 1      // 64-column tiles
-#endif
-#ifndef T3D_PF_WIDE
-#define T3D_PF_WIDE 1        // 128-column tiles of fwd / dgrad / wgrad (213-233 VGPRs already)
-#endif
-#ifndef T3D_PF_GRAM128
-#define T3D_PF_GRAM128 1     // dgrad_gram<128>
-#endif
 
 __device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
@@ -204,7 +183,7 @@ struct DyLoader {      // N % 32 == 0: every tile column is valid
     c.c2 = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.coef + 2 * N + ucol) + lbytes);
     return c;
   }
-  // The per-channel coefficients of the WHOLE reduction range as a table in LDS (T3D_X3_COEF_LDS, gemm_mainloop_x3): a k-tile's
+  // The per-channel coefficients of the WHOLE reduction range as a table in LDS (gemm_mainloop_x3): a k-tile's
   // coefficients then cost two or three ds_read_b128 instead of as many global loads -- each of which holds the wave ~50-60 cycles
   // beside MFMAs for 128 bytes of data every lane group shares (round 6: the memory INSTRUCTIONS bound these loops).
   static constexpr bool HAS_CTAB = !POOLED;
@@ -370,17 +349,16 @@ template <class WT, bool E> struct PassBf16<WLoaderT<WT, E>> { static constexpr 
 // ---------------------------------------------------------------------------------------------
 // staging of one [DIM x BK] operand tile through registers into LDS
 // ---------------------------------------------------------------------------------------------
-// PF = prefetch distance in k-tiles = number of register slots: with PF = 2 the loads of tile t+2 are already in flight
-// while tile t+1 is transformed into LDS, so a load has about two k-tile MFMA phases to land instead of one.  The narrow
-// (64-column) kernels need that: their k-tile is only 32 MFMAs per wave, shorter than the memory latency under load.
-template <int DIM, bool TYPE_R, class L, int PF_ = 1>
+// One register slot: the loads of tile t+1 are in flight while tile t is multiplied.  Two slots (tile t+2 in flight as well) were
+// measured on MI355X (64-column kernels and dgrad_gram<128>, B=32 N=1024 step): no gain at 30-90 more VGPRs -- the narrow kernels
+// are bound by their fixed per-workgroup latency (first load, epilogue), not by the per-tile load latency.
+template <int DIM, bool TYPE_R, class L>
 struct Stager {
-  static constexpr int PF = PF_;
   static constexpr int NV = DIM * (BK / 4) / NT;
   static constexpr int LDS_FLOATS = TYPE_R ? DIM * LDR : BK * DIM;
-  typename L::Raw raw[PF][NV];
-  typename L::Coef coef[PF];      // TYPE_C uses coef[0] only (the thread's column chunk never changes)
-  int lane0, red0[PF];
+  typename L::Raw raw[NV];
+  typename L::Coef coef;          // TYPE_C: set once (the thread's column chunk never changes)
+  int lane0, red0;
 
   __device__ __forceinline__ static void coords(int tid, int q, int& lane_i, int& red_i) {
     const int f = tid + NT * q;
@@ -389,32 +367,29 @@ struct Stager {
   }
   __device__ __forceinline__ void init(const L& l, int lane0_, int tid) {
     lane0 = lane0_;
-    if (!TYPE_R) { int li, ri; coords(tid, 0, li, ri); coef[0] = l.fetch_coef(lane0 + li); }
+    if (!TYPE_R) { int li, ri; coords(tid, 0, li, ri); coef = l.fetch_coef(lane0 + li); }
   }
-  template <int S = 0>
   __device__ __forceinline__ void fetch(const L& l, int red0_, int tid) {
-    red0[S] = red0_;
-    if (TYPE_R) { int li, ri; coords(tid, 0, li, ri); coef[S] = l.fetch_coef(red0_ + ri); }
+    red0 = red0_;
+    if (TYPE_R) { int li, ri; coords(tid, 0, li, ri); coef = l.fetch_coef(red0_ + ri); }
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
       int li, ri; coords(tid, q, li, ri);
-      raw[S][q] = TYPE_R ? l.fetch(lane0 + li, red0_ + ri) : l.fetch(red0_ + ri, lane0 + li);
+      raw[q] = TYPE_R ? l.fetch(lane0 + li, red0_ + ri) : l.fetch(red0_ + ri, lane0 + li);
     }
   }
-  template <int S = 0>
   __device__ __forceinline__ void store(const L& l, float* tile, int tid) {
 #pragma unroll
-    for (int q = 0; q < NV; ++q) store_piece<S>(l, tile, tid, q);
+    for (int q = 0; q < NV; ++q) store_piece(l, tile, tid, q);
   }
-  template <int S = 0>
   __device__ __forceinline__ void store_piece(const L& l, float* tile, int tid, int q) {
     int li, ri; coords(tid, q, li, ri);
-    const typename L::Coef& c = coef[TYPE_R ? S : 0];
+    const typename L::Coef& c = coef;
     if (TYPE_R) {
-      const float4 v = l.xform(raw[S][q], c, lane0 + li, red0[S] + ri);
+      const float4 v = l.xform(raw[q], c, lane0 + li, red0 + ri);
       *reinterpret_cast<float4*>(tile + li * LDR + ri) = v;
     } else {
-      const float4 v = l.xform(raw[S][q], c, red0[S] + ri, lane0 + li);
+      const float4 v = l.xform(raw[q], c, red0 + ri, lane0 + li);
       *reinterpret_cast<float4*>(tile + ri * DIM + li) = v;
     }
   }
@@ -462,9 +437,6 @@ __device__ __forceinline__ void mma_groups(const float* As, const float* Bs, int
 #pragma unroll
   for (int g = G0; g < G1; ++g) {
     if (g + 1 < G1) f[(g + 1) & 1].load(As, Bs, a0, b0, g + 1, l31, h);
-#ifdef T3D_PIN_FRAGS
-    __builtin_amdgcn_sched_barrier(0);   // keep the next group's ds_reads ahead of this group's 16 MFMAs
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -493,77 +465,9 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
 // and the loads of tile t+2 are issued.  The last tile is peeled so that the steady-state body is branch-free.
 //   RAW: stage (t+1)&1 is written during iteration t and read after the barrier that ends it.
 //   WAR: stage t&1 is overwritten (tile t+2) during iteration t+1, after the same barrier.
-// Prefetch-distance-2 variant (SA::PF == 2).  Register slot (t+1)&1 holds tile t+1 (landed), slot t&1 holds tile t+2
-// (in flight).  Iteration t: MFMAs of tile t from LDS stage t&1; tile t+1 goes from its slot into the other stage
-// between the MFMAs of the second half; the freed slot is refilled with tile t+3.  Unrolled by two so that the slot
-// index is a compile-time constant (register arrays).
-template <int S, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
-__device__ __forceinline__ void pf2_body(SA& sa, SB& sb, const LA& la, const LB& lb, float* smem, int cur, int red_fetch,
-                                         bool do_fetch, int a0, int b0, f32x16 (&acc)[TM][TN], int tid) {
-  constexpr int STAGE = SA::LDS_FLOATS + SB::LDS_FLOATS;
-  constexpr int GH = BK / 16, GT = BK / 8;
-  const int lane = tid & 63;
-  const float* As = smem + cur * STAGE;
-  const float* Bs = As + SA::LDS_FLOATS;
-  float* An = smem + (cur ^ 1) * STAGE;
-  float* Bn = An + SA::LDS_FLOATS;
-  mma_groups<TM, TN, AR, DIMA, BR, DIMB, 0, GH>(As, Bs, a0, b0, acc, lane, [](int) {});
-  __builtin_amdgcn_sched_barrier(0);
-  mma_groups<TM, TN, AR, DIMA, BR, DIMB, GH, GT>(As, Bs, a0, b0, acc, lane, [&](int step) {
-    if (step < SA::NV) sa.template store_piece<S>(la, An, tid, step);
-    else if (step - SA::NV < SB::NV) sb.template store_piece<S>(lb, Bn, tid, step - SA::NV);
-  });
-  __builtin_amdgcn_sched_barrier(0);
-  if (do_fetch) {                        // workgroup-uniform; short reductions would otherwise re-read their last tile
-    sa.template fetch<S>(la, red_fetch, tid);
-    sb.template fetch<S>(lb, red_fetch, tid);
-  }
-  __syncthreads();
-}
-
-template <int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
-__device__ __forceinline__ void gemm_mainloop_pf2(SA& sa, SB& sb, const LA& la, const LB& lb, float* smem, int red_begin,
-                                                  int red_end, int a0, int b0, f32x16 (&acc)[TM][TN], int tid) {
-  constexpr int STAGE = SA::LDS_FLOATS + SB::LDS_FLOATS;
-  constexpr int GT = BK / 8;
-  static_assert(SA::NV + SB::NV <= (GT - BK / 16) * 4, "staging pieces must fit the MFMA clusters of the second half");
-  const int nt = (red_end - red_begin) / BK;
-  sa.template fetch<0>(la, red_begin, tid);
-  sb.template fetch<0>(lb, red_begin, tid);
-  if (nt > 1) { sa.template fetch<1>(la, red_begin + BK, tid); sb.template fetch<1>(lb, red_begin + BK, tid); }
-  sa.template store<0>(la, smem, tid);
-  sb.template store<0>(lb, smem + SA::LDS_FLOATS, tid);
-  if (nt > 2) { sa.template fetch<0>(la, red_begin + 2 * BK, tid); sb.template fetch<0>(lb, red_begin + 2 * BK, tid); }
-  __syncthreads();
-  int cur = 0, t = 0;
-  for (; t + 2 < nt; t += 2) {
-    pf2_body<1, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, red_begin + (t + 3) * BK, t + 3 < nt, a0, b0,
-                                                           acc, tid);
-    cur ^= 1;
-    pf2_body<0, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, red_begin + (t + 4) * BK, t + 4 < nt, a0, b0,
-                                                           acc, tid);
-    cur ^= 1;
-  }
-  if (t + 1 < nt) {                      // two tiles left: t is even here, tile t+1 sits in slot 1
-    pf2_body<1, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, red_begin, false, a0, b0, acc, tid);
-    cur ^= 1;
-  }
-  {
-    const float* As = smem + cur * STAGE;
-    const float* Bs = As + SA::LDS_FLOATS;
-    mma_groups<TM, TN, AR, DIMA, BR, DIMB, 0, GT>(As, Bs, a0, b0, acc, tid & 63, [](int) {});
-  }
-  __syncthreads();
-}
-
 template <int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
 __device__ __forceinline__ void gemm_mainloop(SA& sa, SB& sb, const LA& la, const LB& lb, float* smem, int red_begin,
                                               int red_end, int a0, int b0, f32x16 (&acc)[TM][TN], int tid) {
-  static_assert(SA::PF == SB::PF, "both operands use the same prefetch distance");
-  if constexpr (SA::PF == 2) {
-    gemm_mainloop_pf2<TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, red_begin, red_end, a0, b0, acc, tid);
-    return;
-  }
   constexpr int STAGE = SA::LDS_FLOATS + SB::LDS_FLOATS;
   constexpr int GH = BK / 16, GT = BK / 8;     // k-groups in the first half / in the whole tile
   static_assert(SA::NV + SB::NV <= (GT - GH) * 4, "staging pieces must fit the MFMA clusters of the second half");
@@ -586,28 +490,17 @@ __device__ __forceinline__ void gemm_mainloop(SA& sa, SB& sb, const LA& la, cons
     // nothing of the staging work may be hoisted into the first half: the next tile's global loads were
     // issued only one barrier ago and get the first half's MFMAs (>= 2048 cycles) to land
     __builtin_amdgcn_sched_barrier(0);
-#ifndef T3D_ABL_NOSTAGE
     mma_groups<TM, TN, AR, DIMA, BR, DIMB, GH, GT>(As, Bs, a0, b0, acc, lane, [&](int step) {
       if (step < SA::NV) sa.store_piece(la, An, tid, step);
       else if (step - SA::NV < SB::NV) sb.store_piece(lb, Bn, tid, step - SA::NV);
     });
-#else
-    (void)An; (void)Bn;
-    mma_groups<TM, TN, AR, DIMA, BR, DIMB, GH, GT>(As, Bs, a0, b0, acc, lane, nofill);
-#endif
     // keep the new loads BEHIND every wait on the previous batch (vmcnt counts in issue order)
     __builtin_amdgcn_sched_barrier(0);
     // clamp instead of branching: the (unused) tile past the end re-reads the last one
     const int nxt = min(red + 2 * BK, red_end - BK);
-#ifndef T3D_ABL_NOSTAGE
     sa.fetch(la, nxt, tid);
     sb.fetch(lb, nxt, tid);
-#else
-    (void)nxt;
-#endif
-#ifndef T3D_ABL_NOBAR
     __syncthreads();
-#endif
     cur ^= 1;
   }
   {
@@ -769,11 +662,8 @@ struct StagerH8 {
 };
 template <class L, class = void> struct Has8 { static constexpr bool value = false; };
 template <class L> struct Has8<L, typename std::enable_if<L::HAS8>::type> { static constexpr bool value = true; };
-#ifndef T3D_STAGE8
-#define T3D_STAGE8 1       // 0: the 8-byte granules everywhere (A/B of the 16-byte stager)
-#endif
 template <int DIM, bool TYPE_R, class L, int PF>
-using StagerHSel = typename std::conditional<(T3D_STAGE8 != 0) && Has8<L>::value, StagerH8<DIM, TYPE_R, L, PF>, StagerH<DIM, TYPE_R, L, PF>>::type;
+using StagerHSel = typename std::conditional<Has8<L>::value, StagerH8<DIM, TYPE_R, L, PF>, StagerH<DIM, TYPE_R, L, PF>>::type;
 
 // fragment of MFMA step `st` (16 reduction indices) for the 32 operand rows / columns starting at `c0`
 template <bool TYPE_R, int DIM>
@@ -917,61 +807,19 @@ __device__ __forceinline__ void gemm_mainloop_h(SA& sa, SB& sb, const LA& la, co
 // layouts of the bf16 path) and the main loop differ.  Results agree with the fp32 MFMA kernels to the last bits, not bit for bit
 // (another summation order): the launchers take this path only when asked (T3D_X3, see t3d_pointmlp_fwd_r).
 constexpr int BKX = 16;             // reduction depth of an LDS stage = ONE step of v_mfma_f32_32x32x16_bf16
-// Where the accumulators live (an experiment of round 5; T3D_X3_AGPR=1 builds it, the default is 0).  hipcc keeps the C / D matrix of
-// an MFMA builtin in ordinary VGPRs whenever a kernel fits 256 of them ("AGPRs: 0" for every kernel of this file), and in a bare loop a
-// v_mfma whose accumulator is a VGPR block does not let vector instructions run beside it: tools/micro/mfma_valu_overlap.hip (MI355X,
-// two waves per SIMD, [one MFMA, six v_fma_f32] x 4 per iteration) takes 356 cycles per iteration with VGPR accumulators -- the 256
-// cycles of the matrix pipe PLUS the vector instructions -- against 284 with the accumulators in AGPRs, and a wave that only multiplies
-// starves its SIMD partner's vector stream almost completely (which is why the producer / consumer kernels below lose).  The compiler
-// takes the AGPR form of the builtins as soon as the function may use AGPRs at all -- which one (empty) inline-asm statement with an
-// "a" operand tells it.  In THESE kernels it buys nothing: per launch at M = 32768, AGPR vs VGPR form, forward 512 -> 256 55.7 vs
-// 56.1 us, 256 -> 128 26.2 vs 22.5, 128 -> 1024 63.6 vs 61.5, fused backward 512 -> 256 124.7 vs 112.1; the rider kernels, whose
-// small-op bodies need ~240 VGPRs of their own, spill 56-60 registers beside 128 AGPRs and the step goes from 1.205 to 1.257 ms
-// (tools/agpr_ab.sh, same box).  hipcc does interleave the staging pass between the MFMAs in the AGPR build (one MFMA : ~7 vector
-// instructions); what the waves wait for there is their fragment reads (s_waitcnt lgkmcnt in front of every other MFMA), not the
-// vector ports.
-#ifndef T3D_X3_W8_DEFAULT
-#define T3D_X3_W8_DEFAULT 1         // eight-wave 128 x 256 forward tiles (PathX3W): the default of T3D_X3_W8
-#endif
-#ifndef T3D_X3_AGPR
-#define T3D_X3_AGPR 0
-#endif
-#if T3D_X3_AGPR
-#define T3D_MFMA_IN_AGPRS() do { float agpr_hint_ = 0.f; asm volatile("; accumulators in AGPRs" : "+a"(agpr_hint_)); } while (0)
-#else
-#define T3D_MFMA_IN_AGPRS() do {} while (0)
-#endif
 // LDS budget: three planes per operand.  With the bf16 path's padded images (R rows of 16 + 8, C rows of DIM + 32) a 128 x 128 forward
-// tile needs 67.6 KB for its two stages: two workgroups per CU.  Alternative: the R image UNPADDED -- rows of 16 bf16 = 32 B, the two
-// 16-byte halves of row r swapped when bit 3 of r is set, so that the 16 lanes a ds_read_b128 serves together (16 consecutive rows,
-// one half) hit 16 different 16-byte slots -- and the C image is padded by 16 (two-way conflicts on its transposing reads, 12 per
-// k-tile): 52.2 KB, THREE workgroups per CU (T3D_X3_LDS=1).
-#ifndef T3D_X3_LDS
-#define T3D_X3_LDS 0                // 1: that layout.  Measured (B=32 N=1024 step, same box): 1.246 vs 1.241 ms -- most launches have
-                                    // exactly two tiles per CU, a third slot stays empty; the conflict-free images stay the default
-#endif
-constexpr int LDRX = T3D_X3_LDS ? BKX : BKX + 8;
-constexpr int LDCX_PAD = T3D_X3_LDS ? 16 : 32;
-__device__ __forceinline__ int x3_r_off(int row, int red) {      // bf16 element offset of (row, reduction index red) in an R image plane
-  if constexpr (T3D_X3_LDS != 0) return row * LDRX + ((((red >> 3) ^ (row >> 3)) & 1) << 3) + (red & 7);
-  else return row * LDRX + red;
-}
+// tile needs 67.6 KB for its two stages: two workgroups per CU.
+constexpr int LDRX = BKX + 8;
+constexpr int LDCX_PAD = 32;
+__device__ __forceinline__ int x3_r_off(int row, int red) { return row * LDRX + red; }      // bf16 element offset of (row, red) in an R image plane
 
-#ifndef T3D_X3_SPLIT_ASM
-#define T3D_X3_SPLIT_ASM 1
-#endif
 __device__ __forceinline__ void split3(const float4& v, bf16x4& h, bf16x4& m, bf16x4& l) {
   const float x[4] = {v.x, v.y, v.z, v.w};
-#ifdef T3D_ABL_X3_FAKESPLIT      // timing ablation (wrong results): one conversion, no residuals
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { h[e] = (bf16_t)x[e]; m[e] = h[e]; l[e] = h[e]; }
-  return;
-#endif
-#if T3D_X3_SPLIT_ASM
   // Two elements at a time, twelve vector instructions per pair: one packed conversion per term, the two halves widened with a shift
-  // and a mask, scalar subtractions.  Written out because from the per-element casts below hipcc (a) converts every other element
-  // twice -- once alone for the residual, once packed for the store -- and (b) SLP-packs the subtractions into v_pk_add_f32, which
-  // holds the issue port of a SIMD several times as long as two v_sub_f32 beside MFMAs.  Same roundings (v_cvt_pk_bf16_f32: nearest even) and exact subtractions: bit-identical to the form below.
+  // and a mask, scalar subtractions.  Written out because from per-element casts hipcc (a) converts every other element twice -- once
+  // alone for the residual, once packed for the store -- and (b) SLP-packs the subtractions into v_pk_add_f32, which holds the issue
+  // port of a SIMD several times as long as two v_sub_f32 beside MFMAs.  Roundings: v_cvt_pk_bf16_f32, nearest even; both subtractions
+  // are exact.
   unsigned hp[2], mp[2], lp[2];
   typedef float f32x2_ __attribute__((ext_vector_type(2)));
   auto pk = [](float a, float b) { const f32x2_ v = {a, b}; return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); };
@@ -979,14 +827,7 @@ __device__ __forceinline__ void split3(const float4& v, bf16x4& h, bf16x4& m, bf
   for (int e = 0; e < 2; ++e) {
     const float x0 = x[2 * e], x1 = x[2 * e + 1];
     hp[e] = pk(x0, x1);
-#if T3D_X3_SPLIT_ASM == 2      // the subtractions as instructions (hipcc then pads the hazards it cannot see with s_nop)
-    float r0, r1, s0, s1;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r0) : "v"(x0), "v"(hp[e] << 16));
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r1) : "v"(x1), "v"(hp[e] & 0xffff0000u));
-    mp[e] = pk(r0, r1);
-    asm("v_sub_f32 %0, %1, %2" : "=v"(s0) : "v"(r0), "v"(mp[e] << 16));
-    asm("v_sub_f32 %0, %1, %2" : "=v"(s1) : "v"(r1), "v"(mp[e] & 0xffff0000u));
-#else                          // plain subtractions; the empty statements keep the SLP vectoriser from pairing them
+    // (the empty statements keep the SLP vectoriser from pairing the subtractions)
     float r0 = x0 - __uint_as_float(hp[e] << 16);
     asm("" : "+v"(r0));
     const float r1 = x1 - __uint_as_float(hp[e] & 0xffff0000u);
@@ -994,22 +835,11 @@ __device__ __forceinline__ void split3(const float4& v, bf16x4& h, bf16x4& m, bf
     float s0 = r0 - __uint_as_float(mp[e] << 16);
     asm("" : "+v"(s0));
     const float s1 = r1 - __uint_as_float(mp[e] & 0xffff0000u);
-#endif
     lp[e] = pk(s0, s1);
   }
   h = __builtin_bit_cast(bf16x4, make_uint2(hp[0], hp[1]));
   m = __builtin_bit_cast(bf16x4, make_uint2(mp[0], mp[1]));
   l = __builtin_bit_cast(bf16x4, make_uint2(lp[0], lp[1]));
-#else
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const bf16_t a = (bf16_t)x[e];
-    const float r1 = x[e] - (float)a;          // exact
-    const bf16_t b = (bf16_t)r1;
-    const float r2 = r1 - (float)b;            // exact
-    h[e] = a; m[e] = b; l[e] = (bf16_t)r2;
-  }
-#endif
 }
 
 // A [K, N] fp32 matrix that was split into three bf16 planes beforehand (t3d_split_x3: the optimiser's weights, once per step): the
@@ -1043,16 +873,6 @@ struct WLoaderX3F {
   int nb;               // 32-wide blocks of the lane index (N / 32 forward, K / 32 data gradient)
   struct Raw {};
   struct Coef {};
-  // one dword of every 128-byte line of the 3 x TN fragments of a wave's k-tile: lane -> (plane, block, line); the lanes past the last
-  // line repeat it.  A prefetch into the XCD's L2 (see x3_iter_il), not a read of the data.
-  template <int TN>
-  __device__ __forceinline__ unsigned touch(int c0, int red0, int lane) const {
-    const int l = lane < 24 * TN ? lane : 24 * TN - 1;
-    const int plane = l / (8 * TN), x = (l / 8) % TN, line = l % 8;
-    const size_t uoff = ((size_t)(red0 >> 4) * (size_t)nb + (size_t)(c0 >> 5)) * 512u;      // uniform
-    return *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(p + uoff) + ((size_t)plane * (size_t)stride + (size_t)x * 512u) * 2u +
-                                              (unsigned)line * 128u);
-  }
   __device__ __forceinline__ bf16x8 gfrag(int plane, int c0, int red0, int lane) const {
     const size_t uoff = (size_t)plane * (size_t)stride + ((size_t)(red0 >> 4) * (size_t)nb + (size_t)(c0 >> 5)) * 512u;      // uniform
     return *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(p + uoff) + (unsigned)lane * 16u);
@@ -1068,57 +888,17 @@ template <class L, class = void> struct PreSplit { static constexpr bool value =
 template <class L> struct PreSplit<L, typename std::enable_if<L::PRESPLIT>::type> { static constexpr bool value = true; };
 
 // one [DIM x BKX] operand tile: fp32 loader -> registers -> three bf16 planes in LDS (R image [DIM][LDRX] / C image [BKX][DIM + 32])
-#ifndef T3D_X3_PF
-#define T3D_X3_PF 1                 // register slots = k-tiles in flight per operand (see gemm_mainloop_x3)
-#endif
-#ifndef T3D_X3_PIECEWISE
-#define T3D_X3_PIECEWISE 1          // refill a slot piece by piece, right behind each piece's store
-#endif
-#ifndef T3D_X3_FRAGPF
-#define T3D_X3_FRAGPF 1             // 1: the next tile's fragments are read behind a mid-iteration barrier (see x3_iter_fp)
-#endif
-#ifndef T3D_X3_SGB
-#define T3D_X3_SGB 0                // > 0: sched_group_barrier pipeline, that many VALU instructions behind each MFMA (see x3_iter)
-#endif
-#ifndef T3D_X3_BRING
-// Two experiments of round 6 on the LATENCY of the global weight-fragment loads, both measured SLOWER and off (step 1.213 / 1.216 against
-// 1.194 ms, same box; forward 512 -> 256 51.6 / 49.8 against 49.5 us): T3D_X3_BRING=1 keeps the fragments in a ring of three register
-// sets loaded two tiles ahead (the 128-wide kernels then spill 10-22 VGPRs); T3D_X3_BTOUCH=n touches the fragment lines of the tile n
-// tiles ahead with one dword load per lane.  What the fragment loads cost is their ISSUE (a global load holds its wave ~50-60 cycles
-// beside MFMAs), not their latency: one more load per iteration only adds to it.
-#define T3D_X3_BRING 0
-#endif
-#ifndef T3D_X3_BTOUCH
-#define T3D_X3_BTOUCH 0
-#endif
-#ifndef T3D_X3_FAIR
-#define T3D_X3_FAIR 1               // the younger workgroup of a CU pair leads the first part of its k loop at wave priority 1 (gemm_mainloop_x3)
-#endif
-#ifndef T3D_X3_FAIR_NUM
-#define T3D_X3_FAIR_NUM 1
-#define T3D_X3_FAIR_DEN 2
-#endif
-#ifndef T3D_X3_PRIO_WGRAD
-#define T3D_X3_PRIO_WGRAD 1         // weight-gradient / Gram tiles at wave priority 1 for their whole k loop (gemm_mainloop_x3)
-#endif
+// gemm_mainloop_x3's fairness rule: the younger workgroup of a CU pair leads this fraction of its k loop at wave priority 1
+constexpr int FAIR_NUM = 1, FAIR_DEN = 2;
 #define T3D_FAIR_CUS 256            // CUs of an MI355X: the first this many workgroups of a launch are the older halves of the CU pairs
-#ifndef T3D_X3_COEF_LDS
-#define T3D_X3_COEF_LDS 1           // fragment-weight kernels: the first operand's per-channel coefficients from a table in LDS (DyLoader::ctab_fill)
-#endif
-#ifndef T3D_X3_LATE_M
-#define T3D_X3_LATE_M 1             // x3_iter_il: the m-plane fragments are read at the head of the iteration that multiplies them (ILSched)
-#endif
-#ifndef T3D_X3_IL
-#define T3D_X3_IL 1                 // 1: the hand-placed iteration (x3_iter_il): ONE MFMA, then its share of the staging pass, fenced
-#endif
 template <int... I, class F>
 __device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F>      // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): compile-time indices (register arrays, if constexpr)
 __device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
 
-template <int DIM, bool TYPE_R, class L, int PF_ = T3D_X3_PF, int NTX = NT>      // NTX: threads that stage the tile (512: the eight-wave tiles)
+template <int DIM, bool TYPE_R, class L, int NTX = NT>      // NTX: threads that stage the tile (512: the eight-wave tiles)
 struct StagerX3 {
-  static constexpr int PF = PF_;
+  static constexpr int PF = 1;      // register slots: one k-tile in flight per operand
   static constexpr int NV = DIM * (BKX / 4) / NTX;
   static constexpr int LDC = DIM + LDCX_PAD;
   static constexpr int PLANE = TYPE_R ? DIM * LDRX : BKX * LDC;      // bf16 elements of one plane
@@ -1127,7 +907,7 @@ struct StagerX3 {
   typename L::Raw raw[PF][NV];
   typename L::Coef coef[PF];      // TYPE_C uses coef[0] only (the thread's column chunk never changes)
   int lane0, red0[PF];
-  static constexpr bool AT = T3D_X3_IL && HasAt<L>::value;      // uniform base + per-lane byte offset (L::fetch_at)
+  static constexpr bool AT = HasAt<L>::value;      // uniform base + per-lane byte offset (L::fetch_at)
   unsigned lbytes[AT ? NV : 1], cbytes;                          // the lane's byte offsets: piece q of the tile; its coefficient chunk
   int ld;
 
@@ -1162,7 +942,7 @@ struct StagerX3 {
       fetch_piece<S>(l, red0_, tid, q);
     }
   }
-  template <int S, bool CT = false>      // CT: the coefficients come from the loader's table in LDS (T3D_X3_COEF_LDS; `ctab`)
+  template <int S, bool CT = false>      // CT: the coefficients come from the loader's table in LDS (`ctab`)
   __device__ __forceinline__ void il_fetch_head(const L& l, int red0_, int tid, const float* ctab = nullptr) {
     if constexpr (AT) {
       red0[S] = red0_;
@@ -1209,14 +989,8 @@ struct StagerX3 {
     }
     bf16_t* dst = tile + (TYPE_R ? x3_r_off(li, ri) : ri * LDC + li);
     *reinterpret_cast<bf16x4*>(dst) = h;
-#ifdef T3D_ABL_X3_WRITE1        // timing ablation (wrong results): one plane written instead of three
-    if (ri == 12345) {
-#endif
     *reinterpret_cast<bf16x4*>(dst + PLANE) = m;
     *reinterpret_cast<bf16x4*>(dst + 2 * PLANE) = lo;
-#ifdef T3D_ABL_X3_WRITE1
-    }
-#endif
   }
   template <int S>
   __device__ __forceinline__ void store(const L& l, bf16_t* tile, int tid) {
@@ -1267,9 +1041,6 @@ struct StagerX3 {
     if constexpr (U == 0) {
       int li, ri; coords(tid, Q, li, ri);
       const typename L::Coef& c = coef[TYPE_R ? S : 0];
-#ifdef T3D_X3_PIN_RAW
-      l.pin(raw[S][Q]);                                          // (the step that consumes the loaded registers: the wait belongs here)
-#endif
       const float4 v = TYPE_R ? l.xform(raw[S][Q], c, lane0 + li, red0[S] + ri) : l.xform(raw[S][Q], c, red0[S] + ri, lane0 + li);
       ilx[0] = v.x; ilx[1] = v.y; ilx[2] = v.z; ilx[3] = v.w;
       // (not when the loader computes nothing -- a weight tile: the asm would tie single registers to parts of the load's 128-bit
@@ -1278,9 +1049,7 @@ struct StagerX3 {
       // The slot's coefficients (batch-norm scale / shift, dy's c0 c1 c2) are requested HERE, right behind their last use, not with
       // the last piece's refill: as the youngest loads of the iteration, a register copy of them at the loop's back edge (the
       // allocator's, for a v_fmac that accumulates into one) waited with s_waitcnt vmcnt(0) on loads two gaps old.
-#ifndef T3D_ABL_IL_NOLOAD
       if constexpr (Q == NV - 1) { asm volatile("" ::: "memory"); il_fetch_head<S, CT>(l, red_fetch, tid, ctab); asm volatile("" ::: "memory"); }
-#endif
     } else if constexpr (U == 1) {
       il_h<0>();
       T3D_PIN3(ilh[0], ilr0, ilr1);
@@ -1299,28 +1068,10 @@ struct StagerX3 {
       il_l<1>();
       int li, ri; coords(tid, Q, li, ri);
       bf16_t* dst = tile + (TYPE_R ? x3_r_off(li, ri) : ri * LDC + li);
-#ifdef T3D_ABL_IL_NOWRITE      // timing ablation (wrong results): the planes are not written (one conditional store keeps the split alive)
-      if (ilh[0] == 0x12345678u && ill[1] == 0x9abcdef0u && ilm[0] == 0x1u && ilm[1] == ilh[1] && ill[0] == 7u) *reinterpret_cast<uint2*>(dst) = make_uint2(ilh[0], ilh[1]);
-#else
       *reinterpret_cast<uint2*>(dst) = make_uint2(ilh[0], ilh[1]);
       *reinterpret_cast<uint2*>(dst + PLANE) = make_uint2(ilm[0], ilm[1]);
       *reinterpret_cast<uint2*>(dst + 2 * PLANE) = make_uint2(ill[0], ill[1]);
-#endif
-#if defined(T3D_ABL_IL_NOLOAD)       // timing ablation (wrong results): the slot is never refilled (the first tile is staged again and again)
-#elif defined(T3D_ABL_IL_NOLOAD_R)   // ... only type-R operands (the [M, C] stream of forward / data gradient) are not refilled
-      if constexpr (!TYPE_R) il_fetch_piece<S>(l, red_fetch, tid, Q);
-#elif defined(T3D_ABL_IL_NOLOAD_C)   // ... only type-C operands
-      if constexpr (TYPE_R) il_fetch_piece<S>(l, red_fetch, tid, Q);
-#elif defined(T3D_ABL_IL_LOADDUMMY)  // ... the loads are issued, their results never used (issue cost without the waits)
-      if constexpr (AT) {
-        const size_t uoff = TYPE_R ? (size_t)lane0 * (size_t)ld + (size_t)red_fetch : (size_t)red_fetch * (size_t)ld + (size_t)lane0;
-        const char* pp = reinterpret_cast<const char*>(l.base_ptr() + uoff) + lbytes[Q];
-        float4 dummy;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dummy) : "v"(pp) : "memory");
-      }
-#else
       il_fetch_piece<S>(l, red_fetch, tid, Q);
-#endif
       asm volatile("" ::: "memory");
     }
   }
@@ -1329,9 +1080,9 @@ struct StagerX3 {
 // ... of a weight matrix that arrives as three bf16 planes (WLoaderX3): the tile is COPIED, sixteen bytes at a time -- chunk f of the
 // tile's 3 x DIM x BKX / 8 chunks is eight consecutive elements of plane f / (2 DIM); no arithmetic, one load and one ds_write_b128 per
 // 8 elements (round 4's form moved 8-byte pieces, three loads and three stores per 4 elements, and lost to the in-kernel split).
-template <int DIM, bool TYPE_R, class L, int PF_ = T3D_X3_PF>
+template <int DIM, bool TYPE_R, class L>
 struct StagerX3W {
-  static constexpr int PF = PF_;
+  static constexpr int PF = 1;
   static constexpr int LDC = DIM + LDCX_PAD;
   static constexpr int PLANE = TYPE_R ? DIM * LDRX : BKX * LDC;
   static constexpr int LDS_ELEMS = 3 * PLANE;
@@ -1360,7 +1111,6 @@ struct StagerX3W {
 #pragma unroll
     for (int q = 0; q < NV; ++q) fetch_piece<S>(l, red0_, tid, q);
   }
-  template <int S> __device__ __forceinline__ void fetch_head(const L&, int, int) {}
   template <int S>
   __device__ __forceinline__ void store_piece(const L&, bf16_t* tile, int tid, int q) {
     int pl, li, ri;
@@ -1384,16 +1134,14 @@ struct StagerX3W {
 };
 
 // ... of a weight matrix in fragment order (WLoaderX3F): nothing is staged -- the main loop reads the fragments from global memory
-template <int DIM, bool TYPE_R, class L, int PF_ = T3D_X3_PF>
+template <int DIM, bool TYPE_R, class L>
 struct StagerX3F {
-  static constexpr int PF = PF_;
   static constexpr bool FROM_GLOBAL = true;
   static constexpr int NV = 0, NU = 1, PLANE = 0, LDS_ELEMS = 0;
   __host__ __device__ __forceinline__ static constexpr int il_cost(int) { return 0; }
   int lane0;      // first column of the workgroup's tile (the fragment planes are indexed by absolute column)
   __device__ __forceinline__ void init(const L&, int lane0_, int) { lane0 = lane0_; }
   __device__ __forceinline__ bf16x8 gfrag(const L& l, int plane, int c_rel, int red0, int lane) const { return l.gfrag(plane, lane0 + c_rel, red0, lane); }
-  template <int TN> __device__ __forceinline__ unsigned touch(const L& l, int c_rel, int red0, int lane) const { return l.template touch<TN>(lane0 + c_rel, red0, lane); }
   template <int S> __device__ __forceinline__ void fetch(const L&, int, int) {}
   template <int S> __device__ __forceinline__ void store(const L&, bf16_t*, int) {}
   template <int S, int Q, int U> __device__ __forceinline__ void il_step(const L&, bf16_t*, int, int) {}
@@ -1416,61 +1164,11 @@ __device__ __forceinline__ bf16x8 frag_x(const bf16_t* img, int c0, int lane) {
   }
 }
 
-// The six products of one 16-deep step, smallest terms first; after each product's TM*TN MFMAs `filler(p)` runs (staging pieces of the
-// next tile: their conversions issue in the shadows of the MFMAs).
-// SYM (Gram matrices, both operands the same tensor): the result must be BITWISE symmetric -- the weight-gradient assembly reads G
-// transposed (t3d_pool_wgrad_finish) -- but G[i][j] sums l_i h_j, h_i l_j, ... and G[j][i] the same values in another order.  Three
-// accumulators make the order irrelevant: A takes l h and m h, B takes h l and h m, C the symmetric m m and h h; then A[j][i] is
-// bit for bit B[i][j], C is symmetric, and (A + B) + C is the same number on both sides (two-term fp32 addition commutes).
-template <bool SYM, int TM, int TN, bool AR, int DIMA, int PLA, bool BR, int DIMB, int PLB, class F>
-__device__ __forceinline__ void mma_x3(const bf16_t* As, const bf16_t* Bs, int a0, int b0, f32x16 (&acc)[TM][TN], f32x16 (&accb)[SYM ? TM : 1][SYM ? TN : 1],
-                                       f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1], int lane, F&& filler) {
-  bf16x8 fa[3][TM], fb[3][TN];
-#pragma unroll
-  for (int pl = 0; pl < 3; ++pl) {
-#ifdef T3D_ABL_X3_READ1         // timing ablation (wrong results): the fragments of one plane read instead of three
-    if (pl > 0) {
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm) fa[pl][tm] = fa[0][tm];
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) fb[pl][tn] = fb[0][tn];
-      continue;
-    }
-#endif
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) fa[pl][tm] = frag_x<AR, DIMA>(As + pl * PLA, a0 + tm * 32, lane);
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) fb[pl][tn] = frag_x<BR, DIMB>(Bs + pl * PLB, b0 + tn * 32, lane);
-  }
-  constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // l h, h l, m m, m h, h m, h h
-  constexpr int TG[6] = {0, 1, 2, 0, 1, 2};                                  // SYM: which accumulator
-#pragma unroll
-  for (int p = 0; p < 6; ++p) {
-#ifdef T3D_ABL_X3_1PROD      // timing ablation (wrong results): one product instead of six
-    if (p == 5)
-#endif
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        if constexpr (SYM) {
-          if (TG[p] == 0) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[p]][tm], fb[PB[p]][tn], acc[tm][tn], 0, 0, 0);
-          else if (TG[p] == 1) accb[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[p]][tm], fb[PB[p]][tn], accb[tm][tn], 0, 0, 0);
-          else accc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[p]][tm], fb[PB[p]][tn], accc[tm][tn], 0, 0, 0);
-        } else {
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA[p]][tm], fb[PB[p]][tn], acc[tm][tn], 0, 0, 0);
-        }
-      }
-    filler(p);
-  }
-}
-
-// ---- fragments carried across the barrier (T3D_X3_FRAGPF) ---------------------------------------------------------------------------
-// In the loop above every iteration begins behind its barrier with twelve fragment reads whose latency nothing covers (the MFMAs need
-// them).  Here the barrier sits in the MIDDLE of an iteration: the staging pieces of tile t + 1 go into the other stage behind the FIRST
-// product groups, then the barrier, then the fragment reads of tile t + 1 into a second register set while the last product groups of
-// tile t still run; iteration t + 1 starts with its fragments in registers.  Still two stages and one barrier per k-tile: the stage
-// written in iteration t held tile t - 1, whose fragments every wave had consumed before it passed the barrier of iteration t - 1.
+// The fragments of one 16-deep k-tile: three planes of each operand.  The main loop carries them across the barrier: the staging
+// pieces of tile t + 1 go into the other stage behind the first products of tile t, then the barrier, then the fragment reads of tile
+// t + 1 into a second register set while the last products of tile t still run; iteration t + 1 starts with its fragments in registers.
+// Two stages and one barrier per k-tile: the stage written in iteration t held tile t - 1, whose fragments every wave had consumed
+// before it passed the barrier of iteration t - 1.
 template <int TM, int TN> struct FragsX3 { bf16x8 a[3][TM], b[3][TN]; };
 
 template <bool AR, int DIMA, int PLA, bool BR, int DIMB, int PLB, int TM, int TN>
@@ -1484,32 +1182,16 @@ __device__ __forceinline__ void load_frags_x3(const bf16_t* As, const bf16_t* Bs
   }
 }
 
-template <bool SYM, int TM, int TN>      // the six products of one tile from fragment arrays (the last tile of the ring form)
-__device__ __forceinline__ void mma_x3_ab(const bf16x8 (&a)[3][TM], const bf16x8 (&b)[3][TN], f32x16 (&acc)[TM][TN],
-                                          f32x16 (&accb)[SYM ? TM : 1][SYM ? TN : 1], f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1]) {
-  constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // l h, h l, m m, m h, h m, h h
-  constexpr int TG[6] = {0, 1, 2, 0, 1, 2};
-#pragma unroll
-  for (int p = 0; p < 6; ++p)
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        if constexpr (SYM) {
-          if (TG[p] == 0) acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[p]][tm], b[PB[p]][tn], acc[tm][tn], 0, 0, 0);
-          else if (TG[p] == 1) accb[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[p]][tm], b[PB[p]][tn], accb[tm][tn], 0, 0, 0);
-          else accc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[p]][tm], b[PB[p]][tn], accc[tm][tn], 0, 0, 0);
-        } else {
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[PA[p]][tm], b[PB[p]][tn], acc[tm][tn], 0, 0, 0);
-        }
-      }
-}
-
-template <bool SYM, int TM, int TN, class F>
+// The six products of one 16-deep step, smallest terms first.
+// SYM (Gram matrices, both operands the same tensor): the result must be BITWISE symmetric -- the weight-gradient assembly reads G
+// transposed (t3d_pool_wgrad_finish) -- but G[i][j] sums l_i h_j, h_i l_j, ... and G[j][i] the same values in another order.  Three
+// accumulators make the order irrelevant: A takes l h and m h, B takes h l and h m, C the symmetric m m and h h; then A[j][i] is
+// bit for bit B[i][j], C is symmetric, and (A + B) + C is the same number on both sides (two-term fp32 addition commutes).
+template <bool SYM, int TM, int TN>
 __device__ __forceinline__ void mma_x3_f(const FragsX3<TM, TN>& f, f32x16 (&acc)[TM][TN], f32x16 (&accb)[SYM ? TM : 1][SYM ? TN : 1],
-                                         f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1], F&& filler) {
+                                         f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1]) {
   constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};      // l h, h l, m m, m h, h m, h h
-  constexpr int TG[6] = {0, 1, 2, 0, 1, 2};
+  constexpr int TG[6] = {0, 1, 2, 0, 1, 2};                                  // SYM: which accumulator
 #pragma unroll
   for (int p = 0; p < 6; ++p) {
 #pragma unroll
@@ -1524,70 +1206,43 @@ __device__ __forceinline__ void mma_x3_f(const FragsX3<TM, TN>& f, f32x16 (&acc)
           acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[PA[p]][tm], f.b[PB[p]][tn], acc[tm][tn], 0, 0, 0);
         }
       }
-    filler(p);
   }
 }
 
-template <int S, bool SYM, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
-__device__ __forceinline__ void x3_iter_fp(SA& sa, SB& sb, const LA& la, const LB& lb, bf16_t* smem, int cur, int red_fetch, int a0, int b0,
-                                           const FragsX3<TM, TN>& fc, FragsX3<TM, TN>& fn, f32x16 (&acc)[TM][TN],
-                                           f32x16 (&accb)[SYM ? TM : 1][SYM ? TN : 1], f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1], int tid) {
-  constexpr int STAGE = SA::LDS_ELEMS + SB::LDS_ELEMS;
-  constexpr int NP = SA::NV + SB::NV;
-  static_assert(NP <= 5, "at least one product group behind the barrier");
-  bf16_t* An = smem + (cur ^ 1) * STAGE;
-  bf16_t* Bn = An + SA::LDS_ELEMS;
-  mma_x3_f<SYM, TM, TN>(fc, acc, accb, accc, [&](int p) {
-    if (p < SA::NV) {
-      sa.template store_piece<S>(la, An, tid, p);
-      sa.template fetch_piece<S>(la, red_fetch, tid, p);
-      if (p == SA::NV - 1) sa.template fetch_head<S>(la, red_fetch, tid);
-    } else if (p < NP) {
-      sb.template store_piece<S>(lb, Bn, tid, p - SA::NV);
-      sb.template fetch_piece<S>(lb, red_fetch, tid, p - SA::NV);
-      if (p == NP - 1) sb.template fetch_head<S>(lb, red_fetch, tid);
-    }
-    if (p == NP - 1) {
-      __syncthreads();
-      load_frags_x3<AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(An, Bn, a0, b0, tid & 63, fn);
-    }
-  });
-}
-
-// ---- the hand-placed iteration (T3D_X3_IL, round 6) ----------------------------------------------------------------------------------
-// x3_iter_fp hands hipcc a product group (TM x TN MFMAs) and then a whole staging piece (~35 vector instructions); the scheduler merges
-// groups further, and the loop it emits has MFMA bursts of 8-12 and runs of 30-67 vector instructions with no MFMA between them
-// (tools/isa_loops.py on round 5's listing).  A wave issues in order: through a burst its vector work cannot start, through a run the
-// matrix pipe has nothing of this wave's to do, and the SIMD's other wave runs the same program.  What the pipe tolerates beside an
-// MFMA is <= 5-6 single-issue vector instructions per 32-cycle gap (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost'; tools/micro/
-// mfma_valu_il.hip: [MFMA, 6 x v_fma_f32] at two waves per SIMD runs at 35.5 cycles per MFMA).  So the iteration is written out as
+// ---- the hand-placed iteration (round 6) --------------------------------------------------------------------------------------------
+// Handed a product group (TM x TN MFMAs) and then a whole staging piece (~35 vector instructions), hipcc merges groups further, and the
+// loop it emits has MFMA bursts of 8-12 and runs of 30-67 vector instructions with no MFMA between them (tools/isa_loops.py on round 5's
+// listing).  A wave issues in order: through a burst its vector work cannot start, through a run the matrix pipe has nothing of this
+// wave's to do, and the SIMD's other wave runs the same program.  What the pipe tolerates beside an MFMA is <= 5-6 single-issue vector
+// instructions per 32-cycle gap (MI355X_MICROARCH.md, 'vector-instruction ISSUE cost'; tools/micro/mfma_valu_il.hip: [MFMA, 6 x
+// v_fma_f32] at two waves per SIMD runs at 35.5 cycles per MFMA).  So the iteration is written out as
 //     MFMA_0 | steps of gap 0 | MFMA_1 | steps of gap 1 | ...                    (every `|` a sched_barrier(0): nothing crosses)
 // where the steps are, in order: the micro-steps of every staging piece (StagerX3::il_step: <= 8 vector instructions each, the piece's
 // three plane stores and its slot's refill in the last one), the workgroup barrier, and the fragment reads of the next tile in the
 // order the next iteration's products need them (l h, h l, m m, ...: a2 b0 a0 b2 a1 b1).  ILSched spreads the steps over the gaps by
-// their issue cost at compile time.  Same MFMAs on the same operands in the same order as x3_iter_fp: bit-identical results.
+// their issue cost at compile time.  Same MFMAs on the same operands in the same order as mma_x3_f.
 template <class SA, class SB, int TM, int TN>
 struct ILSched {
   static constexpr int NM = 6 * TM * TN;                       // MFMAs = gaps of one iteration
-  // T3D_X3_LATE_M: the m-plane fragments of a tile (first needed by product 2, MFMA 2 TM TN) are read at the HEAD of the iteration that
+  // The m-plane fragments of a tile (first needed by product 2, MFMA 2 TM TN) are read at the HEAD of the iteration that
   // multiplies them, into the fragment set it is consuming, instead of with the other planes behind the barrier of the iteration before:
   // 12 instead of 18 LDS reads queue behind the barrier (the four waves of a workgroup pass it together; SQ_LDS_CMD_FIFO_FULL and
   // SQ_WAIT_INST_LDS doubled when the hand-placed iteration packed the 18 reads into four gaps), 6 are spread over the first gaps.
   static constexpr bool GB = FromGlobal<SB>::value;            // the second operand's fragments come from global memory (StagerX3F)
   static constexpr int NG = GB ? 3 * TN : 0;                   // ... 3 TN loads of the NEXT tile's fragments, first in the list (they wait for nothing)
-  static constexpr int NLA = (T3D_X3_IL && T3D_X3_LATE_M) ? TM : 0, NLB = (T3D_X3_IL && T3D_X3_LATE_M && !GB) ? TN : 0;
+  static constexpr int NLA = TM, NLB = GB ? 0 : TN;
   static constexpr int NL = NLA + NLB;                         // late reads: a1[*] then b1[*] of the CURRENT tile
   static constexpr int NSA = SA::NV * SA::NU, NSB = SB::NV * SB::NU;
   static constexpr int L0 = 0;                                 // first late read: FIRST in the list (product 2 needs them at MFMA 2 TM TN)
   static constexpr int G0 = NL;                                // first global fragment load
   static constexpr int ST0 = NG + NL;                          // first staging step
   static constexpr int BAR = ST0 + NSA + NSB;                  // index of the barrier step
-  // fragment reads of the NEXT tile from LDS behind the barrier, in groups a2 b0 a0 b2 [a1 b1] (b groups only when B is staged in LDS)
-  static constexpr int NGRP = (NLA ? 2 : 3) * (GB ? 1 : 2);
+  // fragment reads of the NEXT tile from LDS behind the barrier, in groups a2 b0 a0 b2 (b groups only when B is staged in LDS)
+  static constexpr int NGRP = 2 * (GB ? 1 : 2);
   __host__ __device__ __forceinline__ static constexpr int grp_is_b(int g) { return GB ? 0 : (g & 1); }
   __host__ __device__ __forceinline__ static constexpr int grp_plane(int g) {
-    const int o = GB ? g : g / 2;                              // 0, 1, 2 -> the pair (a2 b0), (a0 b2), (a1 b1)
-    return o == 0 ? (grp_is_b(g) ? 0 : 2) : o == 1 ? (grp_is_b(g) ? 2 : 0) : 1;
+    const int o = GB ? g : g / 2;                              // 0, 1 -> the pair (a2 b0), (a0 b2)
+    return o == 0 ? (grp_is_b(g) ? 0 : 2) : (grp_is_b(g) ? 2 : 0);
   }
   __host__ __device__ __forceinline__ static constexpr int grp_n(int g) { return grp_is_b(g) ? TN : TM; }
   __host__ __device__ __forceinline__ static constexpr int count_nf() { int n = 0; for (int g = 0; g < NGRP; ++g) n += grp_n(g); return n; }
@@ -1622,12 +1277,10 @@ struct ILSched {
 
 template <int S, bool SYM, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
 __device__ __forceinline__ void x3_iter_il(SA& sa, SB& sb, const LA& la, const LB& lb, bf16_t* smem, int cur, int red_next, int red_fetch, int a0, int b0,
-                                           FragsX3<TM, TN>& fc, FragsX3<TM, TN>& fn, bf16x8 (&bcur)[3][TN], bf16x8 (&bload)[3][TN],
-                                           unsigned& touch, int red_touch, f32x16 (&acc)[TM][TN],
+                                           FragsX3<TM, TN>& fc, FragsX3<TM, TN>& fn, f32x16 (&acc)[TM][TN],
                                            f32x16 (&accb)[SYM ? TM : 1][SYM ? TN : 1], f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1], int tid) {
-  // bcur: the B fragments this iteration multiplies; bload: where the B fragments it loads go.  LDS-staged B: fc.b / fn.b (the next
-  // tile's).  Global fragment planes (T3D_X3_BRING): a ring of three sets, the loads run TWO tiles ahead (`red_next` is that tile's
-  // offset) -- see gemm_mainloop_x3.
+  // fc: the fragments this iteration multiplies; fn: those it reads of the next tile (red_next: that tile's offset; red_fetch: the tile
+  // its staging pieces request)
   using SC = ILSched<SA, SB, TM, TN>;
   // the late reads land in gaps well ahead of the first MFMA of product 2 (index 2 TM TN), which multiplies them: a schedule that put
   // them behind the global fragment loads had the eight-wave tiles multiply the m planes of the tile before last
@@ -1638,22 +1291,10 @@ __device__ __forceinline__ void x3_iter_il(SA& sa, SB& sb, const LA& la, const L
   const bf16_t* Ac = smem + cur * STAGE;
   const bf16_t* Bc = Ac + SA::LDS_ELEMS;
   const int lane = tid & 63;
-  // T3D_X3_COEF_LDS: with the second operand read from global memory the LDS its image would take holds the first operand's coefficient
-  // table (gemm_mainloop_x3 fills it); derived from `smem` here so that the reads are ds_read, not flat
-  constexpr bool CTAB = T3D_X3_COEF_LDS && SC::GB && AR && HasCtab<LA>::value;
+  // with the second operand read from global memory the LDS its image would take holds the first operand's coefficient table
+  // (gemm_mainloop_x3 fills it); derived from `smem` here so that the reads are ds_read, not flat
+  constexpr bool CTAB = SC::GB && AR && HasCtab<LA>::value;
   const float* ctab = reinterpret_cast<const float*>(smem + 2 * STAGE);
-#if T3D_X3_BTOUCH
-  if constexpr (SC::GB) {
-    // Every workgroup of an XCD asks for the same k-tile of the weight fragments at about the same time, and the planes were written by
-    // another launch: the first request of a line misses the XCD's L2, and with the fragment loads one tile ahead that miss sat on the
-    // critical path of every iteration (multiply-only timing builds: 48.8 us with global fragments against 37.4 with the LDS-staged
-    // operand, profiles/r06_il_ablations_frag.log).  One dword load per lane, one lane per 128-byte line of the fragments of the tile
-    // T3D_X3_BTOUCH tiles ahead, starts the fill early; its value is "used" one iteration later (an empty asm statement, so that the
-    // wait-count pass sees a use it can place a counted wait for -- by then long satisfied).
-    asm volatile("" :: "v"(touch));
-    touch = sb.template touch<TN>(lb, b0, red_touch, lane);
-  }
-#endif
   static_for<SC::NM>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     constexpr int p = i / (TM * TN), tm = (i / TN) % TM, tn = i % TN;
@@ -1662,335 +1303,154 @@ __device__ __forceinline__ void x3_iter_il(SA& sa, SB& sb, const LA& la, const L
     // (the MFMA between two volatile asm statements on its accumulator: see StagerX3::il_step)
     if constexpr (SYM) {
       if constexpr (p % 3 == 0) {
-        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], bcur[pb][tn], acc[tm][tn], 0, 0, 0);
+        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], fc.b[pb][tn], acc[tm][tn], 0, 0, 0);
         T3D_PIN1(acc[tm][tn]);
       } else if constexpr (p % 3 == 1) {
-        accb[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], bcur[pb][tn], accb[tm][tn], 0, 0, 0);
+        accb[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], fc.b[pb][tn], accb[tm][tn], 0, 0, 0);
         T3D_PIN1(accb[tm][tn]);
       } else {
-        accc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], bcur[pb][tn], accc[tm][tn], 0, 0, 0);
+        accc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], fc.b[pb][tn], accc[tm][tn], 0, 0, 0);
         T3D_PIN1(accc[tm][tn]);
       }
     } else {
-      acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], bcur[pb][tn], acc[tm][tn], 0, 0, 0);
+      acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fc.a[pa][tm], fc.b[pb][tn], acc[tm][tn], 0, 0, 0);
       T3D_PIN1(acc[tm][tn]);
     }
     __builtin_amdgcn_sched_barrier(0);
     constexpr int k0 = SC::first_step(i), k1 = SC::first_step(i + 1);
     static_for<k1 - k0>([&](auto jc) {
       constexpr int k = k0 + decltype(jc)::value;
-      if constexpr (k < SC::NL) {                  // the current tile's m planes (T3D_X3_LATE_M)
+      if constexpr (k < SC::NL) {                  // the current tile's m planes
         constexpr int q = k - SC::L0;
         asm volatile("" ::: "memory");
         if constexpr (q < TM) fc.a[1][q] = frag_x<AR, DIMA>(Ac + SA::PLANE, a0 + q * 32, lane);
-        else bcur[1][q - TM] = frag_x<BR, DIMB>(Bc + SB::PLANE, b0 + (q - TM) * 32, lane);
+        else fc.b[1][q - TM] = frag_x<BR, DIMB>(Bc + SB::PLANE, b0 + (q - TM) * 32, lane);
         asm volatile("" ::: "memory");
       } else if constexpr (k < SC::ST0) {          // the NEXT tile's weight fragments, straight from global memory (WLoaderX3F)
         constexpr int kg = k - SC::G0, o = kg / TN, x = kg % TN, pl = o == 0 ? 0 : o == 1 ? 2 : 1;      // b0, b2, b1: the order the next products need them
         if constexpr (SC::GB) {
-#ifdef T3D_ABL_IL_NOGB      // timing ablation (wrong results): the weight fragments are not reloaded
-          bload[pl][x] = bcur[pl][x];
-#else
           asm volatile("" ::: "memory");
-          bload[pl][x] = sb.gfrag(lb, pl, b0 + x * 32, red_next, lane);
+          fn.b[pl][x] = sb.gfrag(lb, pl, b0 + x * 32, red_next, lane);
           asm volatile("" ::: "memory");
-#endif
         }
       } else if constexpr (k < SC::ST0 + SC::NSA) {
-#ifndef T3D_ABL_IL_NOSTAGE      // timing ablations (wrong results): no staging pass / no barrier / no fragment reads
         sa.template il_step<S, (k - SC::ST0) / SA::NU, (k - SC::ST0) % SA::NU, CTAB>(la, An, tid, red_fetch, ctab);
-#endif
       } else if constexpr (k < SC::BAR) {
-#ifndef T3D_ABL_IL_NOSTAGE
         sb.template il_step<S, (k - SC::ST0 - SC::NSA) / SB::NU, (k - SC::ST0 - SC::NSA) % SB::NU>(lb, Bn, tid, red_fetch);
-#endif
       } else if constexpr (k == SC::BAR) {
-#ifndef T3D_ABL_IL_NOBAR
         __syncthreads();
-#endif
       } else {
         constexpr int j = k - SC::BAR - 1, g = SC::frag_group(j), x = SC::frag_index(j);
         constexpr int pl = SC::grp_plane(g);
         constexpr bool isb = SC::grp_is_b(g) != 0;
-#ifdef T3D_ABL_IL_NOFRAG
-        if constexpr (!isb) fn.a[pl][x] = fc.a[pl][x]; else bload[pl][x] = bcur[pl][x];
-#else
         asm volatile("" ::: "memory");
         if constexpr (!isb) fn.a[pl][x] = frag_x<AR, DIMA>(An + pl * SA::PLANE, a0 + x * 32, lane);
-        else bload[pl][x] = frag_x<BR, DIMB>(Bn + pl * SB::PLANE, b0 + x * 32, lane);
+        else fn.b[pl][x] = frag_x<BR, DIMB>(Bn + pl * SB::PLANE, b0 + x * 32, lane);
         asm volatile("" ::: "memory");
-#endif
       }
     });
     __builtin_amdgcn_sched_barrier(0);
   });
 }
 
-// Two LDS stages, one barrier per 16-deep k-tile, PF register slots per operand.  A k-tile is only 24 MFMAs of 32 cycles per wave
-// (0.3 us): with ONE tile in flight the loop ran at one k-tile per memory round trip (1.7 us per k-tile measured on 512 -> 256, the
-// matrix pipe a third busy; splitting the weights beforehand or a third workgroup per CU changed nothing -- the loop was waiting for its
-// loads).  Tile j travels in slot j % PF: iteration t multiplies tile t from LDS stage t & 1, stores tile t + 1 (requested PF iterations
-// earlier) into the other stage between the MFMAs, and refills that slot with tile t + 1 + PF.
-template <int S, bool SYM, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
-__device__ __forceinline__ void x3_iter(SA& sa, SB& sb, const LA& la, const LB& lb, bf16_t* smem, int cur, int red_fetch, int a0, int b0,
-                                        f32x16 (&acc)[TM][TN], f32x16 (&accb)[SYM ? TM : 1][SYM ? TN : 1],
-                                        f32x16 (&accc)[SYM ? TM : 1][SYM ? TN : 1], int tid) {
-  constexpr int STAGE = SA::LDS_ELEMS + SB::LDS_ELEMS;
-  const bf16_t* As = smem + cur * STAGE;
-  const bf16_t* Bs = As + SA::LDS_ELEMS;
-  bf16_t* An = smem + (cur ^ 1) * STAGE;
-  bf16_t* Bn = An + SA::LDS_ELEMS;
-#if T3D_X3_PIECEWISE
-  mma_x3<SYM, TM, TN, AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(As, Bs, a0, b0, acc, accb, accc, tid & 63, [&](int p) {
-    if (p < SA::NV) {
-      sa.template store_piece<S>(la, An, tid, p);
-      sa.template fetch_piece<S>(la, red_fetch, tid, p);
-      if (p == SA::NV - 1) sa.template fetch_head<S>(la, red_fetch, tid);
-    } else if (p - SA::NV < SB::NV) {
-      sb.template store_piece<S>(lb, Bn, tid, p - SA::NV);
-      sb.template fetch_piece<S>(lb, red_fetch, tid, p - SA::NV);
-      if (p - SA::NV == SB::NV - 1) sb.template fetch_head<S>(lb, red_fetch, tid);
-    }
-  });
-#if T3D_X3_SGB
-  // Prescribe the interleave of this iteration's instructions: hipcc clumps the staging pass into runs of 11-13 VALU instructions
-  // with no MFMA between them (the matrix pipe idles through each run), and the four MFMAs of a product group back to back (the wave
-  // cannot issue the VALU work behind them until the fourth has been accepted).  One MFMA, then its share of the VALU / LDS work.
-#pragma unroll
-  for (int i = 0; i < 6 * TM * TN; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);               // one MFMA
-    __builtin_amdgcn_sched_group_barrier(0x002, T3D_X3_SGB, 0);      // VALU
-    __builtin_amdgcn_sched_group_barrier(0x080, 1, 0);               // one LDS access (fragment read / plane write)
-  }
-#endif
-#else
-  mma_x3<SYM, TM, TN, AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(As, Bs, a0, b0, acc, accb, accc, tid & 63, [&](int p) {
-    if (p < SA::NV) sa.template store_piece<S>(la, An, tid, p);
-    else if (p - SA::NV < SB::NV) sb.template store_piece<S>(lb, Bn, tid, p - SA::NV);
-  });
-  __builtin_amdgcn_sched_barrier(0);      // the new loads stay behind every wait on the older ones (vmcnt counts in issue order)
-  sa.template fetch<S>(la, red_fetch, tid);
-  sb.template fetch<S>(lb, red_fetch, tid);
-#endif
-  __syncthreads();
-}
+// The coefficient tables of the fragment-weight kernels (DyLoader / ActLoaderE::ctab_fill, at most 3 floats per channel) are taken for
+// layers of at most this many channels (t3d_x3_fwd, T3D_BWDX); wider ones take the in-kernel split
+constexpr int X3_CTAB_MAX_CH = 1536;
 
+// Two LDS stages, one barrier per 16-deep k-tile, one register slot per operand.  Iteration t multiplies tile t (its fragments in
+// registers), stores tile t + 1 -- requested during iteration t - 1 -- into the other stage between the MFMAs and refills the slot with
+// tile t + 2, piece by piece right behind each piece's store, then reads the fragments of tile t + 1 behind the barrier (x3_iter_il).
 template <bool SYM, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
 __device__ __forceinline__ void gemm_mainloop_x3(SA& sa, SB& sb, const LA& la, const LB& lb, float* smem_f, int red_begin, int red_end,
                                                  int a0, int b0, f32x16 (&acc)[TM][TN], int tid) {
   static_assert(!SYM || TM * TN == 1, "symmetric accumulation: 64 x 64 tiles (three accumulator sets)");
-  static_assert(SA::PF == SB::PF && SA::PF >= 1 && SA::PF <= 4, "one to four register slots");
-  T3D_MFMA_IN_AGPRS();
-  constexpr int PF = SA::PF;
   f32x16 accb[SYM ? TM : 1][SYM ? TN : 1], accc[SYM ? TM : 1][SYM ? TN : 1];
   if constexpr (SYM) { zero_acc<TM, TN>(accb); zero_acc<TM, TN>(accc); }
   bf16_t* smem = reinterpret_cast<bf16_t*>(smem_f);
   constexpr int STAGE = SA::LDS_ELEMS + SB::LDS_ELEMS;
   static_assert(SA::NV + SB::NV <= 6, "staging pieces must fit the six product groups");
   const int last = red_end - BKX;
-#ifdef T3D_ABL_X3_SAMETILE      // timing ablation (wrong results): every k-tile re-reads the first one (cache hits: no memory latency)
-  auto tile_red = [&](int j) { return min(red_begin + (j & 1) * BKX, last); };
-#else
   auto tile_red = [&](int j) { return min(red_begin + j * BKX, last); };      // past the end the last tile is re-read, never used
-#endif
   sa.template fetch<0>(la, tile_red(0), tid);
   sb.template fetch<0>(lb, tile_red(0), tid);
-  if constexpr (PF > 1) { sa.template fetch<1>(la, tile_red(1), tid); sb.template fetch<1>(lb, tile_red(1), tid); }
-  if constexpr (PF > 2) { sa.template fetch<2>(la, tile_red(2), tid); sb.template fetch<2>(lb, tile_red(2), tid); }
-  if constexpr (PF > 3) { sa.template fetch<3>(la, tile_red(3), tid); sb.template fetch<3>(lb, tile_red(3), tid); }
   sa.template store<0>(la, smem, tid);
   sb.template store<0>(lb, smem + SA::LDS_ELEMS, tid);
-  sa.template fetch<0>(la, tile_red(PF), tid);
-  sb.template fetch<0>(lb, tile_red(PF), tid);
-#if T3D_X3_IL && T3D_X3_COEF_LDS
+  sa.template fetch<0>(la, tile_red(1), tid);
+  sb.template fetch<0>(lb, tile_red(1), tid);
   if constexpr (FromGlobal<SB>::value && AR && HasCtab<LA>::value) {
     // the launcher sized the dynamic LDS for an image of the second operand as well (lds_fwd_x3 / lds_dgrad_x3); the fragment form does
     // not use it: bytes behind the two stages, at least those of that image
     constexpr int FREE_BYTES = 2 * 3 * (BR ? DIMB * LDRX : BKX * (DIMB + LDCX_PAD)) * 2;
-    (void)FREE_BYTES;      // >= 18 KB for every tiling; the launchers take the fragment form for tables of <= 1536 channels only (t3d_x3_fwd ...)
+    static_assert(3 * X3_CTAB_MAX_CH * (int)sizeof(float) <= FREE_BYTES, "the coefficient table must fit the unused operand image");
     la.ctab_fill(reinterpret_cast<float*>(smem + 2 * STAGE), tid, (int)blockDim.x);
   }
-#endif
   __syncthreads();
 #if defined(T3D_TRACE) && T3D_TRACE_STRIDE >= 8
   T3D_TRACE_MARK(4);
 #endif
   const int nt = (red_end - red_begin) / BKX;
   int cur = 0;
-#if T3D_X3_FRAGPF
-  static_assert(PF == 1 || PF == 2, "fragments across the barrier: one or two register slots");
-  {
-#if T3D_X3_IL
-#define T3D_X3_ITER_FP(S_, T_, FC_, FN_) \
-  x3_iter_il<S_, SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, tile_red((T_) + 1), tile_red((T_) + 1 + PF), a0, b0, FC_, FN_, (FC_).b, (FN_).b, btouch, tile_red((T_) + (T3D_X3_BTOUCH > 0 ? T3D_X3_BTOUCH : 1)), acc, accb, accc, tid)
-#else
-#define T3D_X3_ITER_FP(S_, T_, FC_, FN_) \
-  x3_iter_fp<S_, SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, tile_red((T_) + 1 + PF), a0, b0, FC_, FN_, acc, accb, accc, tid)
-#endif
-    constexpr int SODD = PF == 2 ? 1 : 0;      // the slot of tile t + 1 for even t
-    FragsX3<TM, TN> f0, f1;
-    unsigned btouch = 0u;                      // (T3D_X3_BTOUCH: the value of the last prefetch touch, see x3_iter_il)
-#if T3D_X3_IL && T3D_X3_BRING
-    if constexpr (FromGlobal<SB>::value) {
-      // The weight fragments come straight from global memory (WLoaderX3F) and every workgroup of an XCD asks for the same k-tile of
-      // them at the same time: the first request of a k-tile misses the XCD's L2 (the planes were written by another launch), and with
-      // the loads ONE tile ahead that miss was on the critical path of every iteration -- the multiply-only timing build of the
-      // fragment kernels ran 48.8 us against 37.4 for the LDS-staged form (profiles/r06_il_ablations_frag.log).  So the B fragments
-      // live in a ring of THREE register sets and are loaded TWO tiles ahead (3 TN more fragment registers); the A fragments keep their
-      // two sets.  Periods 2 and 3: the steady-state body is six iterations with compile-time set indices.
-      static_assert(PF == 1, "the B ring is written for one register slot per staged operand");
-      bf16x8 br[3][3][TN];
+#define T3D_X3_ITER(T_, FC_, FN_) \
+  x3_iter_il<0, SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, tile_red((T_) + 1), tile_red((T_) + 2), a0, b0, FC_, FN_, acc, accb, accc, tid)
+  FragsX3<TM, TN> f0, f1;
+  if constexpr (FromGlobal<SB>::value) {      // (A from the LDS image, the weight fragments from global memory)
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
+    for (int pl = 0; pl < 3; ++pl) {
 #pragma unroll
-        for (int tm = 0; tm < TM; ++tm) f0.a[pl][tm] = frag_x<AR, DIMA>(smem + pl * SA::PLANE, a0 + tm * 32, tid & 63);
+      for (int tm = 0; tm < TM; ++tm) f0.a[pl][tm] = frag_x<AR, DIMA>(smem + pl * SA::PLANE, a0 + tm * 32, tid & 63);
 #pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-          br[0][pl][tn] = sb.gfrag(lb, pl, b0 + tn * 32, tile_red(0), tid & 63);
-          br[1][pl][tn] = sb.gfrag(lb, pl, b0 + tn * 32, tile_red(1), tid & 63);
-        }
-      }
-      int t = 0;
-#define T3D_X3_ITER_R(PH_)                                                                                                               \
-  do {                                                                                                                                   \
-    x3_iter_il<0, SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, tile_red(t + (PH_) + 2), tile_red(t + (PH_) + 2), \
-        a0, b0, ((PH_) & 1) ? f1 : f0, ((PH_) & 1) ? f0 : f1, br[(PH_) % 3], br[((PH_) + 2) % 3], btouch, tile_red(t + (PH_) + 4), acc, accb, accc, tid);                  \
-    cur ^= 1;                                                                                                                            \
-  } while (0)
-      for (; t + 6 < nt; t += 6) {
-        T3D_X3_ITER_R(0); T3D_X3_ITER_R(1); T3D_X3_ITER_R(2); T3D_X3_ITER_R(3); T3D_X3_ITER_R(4); T3D_X3_ITER_R(5);
-      }
-      // one to six tiles left: an iteration for each but the last
-      if (t + 1 < nt) T3D_X3_ITER_R(0);
-      if (t + 2 < nt) T3D_X3_ITER_R(1);
-      if (t + 3 < nt) T3D_X3_ITER_R(2);
-      if (t + 4 < nt) T3D_X3_ITER_R(3);
-      if (t + 5 < nt) T3D_X3_ITER_R(4);
-#undef T3D_X3_ITER_R
-      const int ph = nt - 1 - t;      // phase of the last tile (0 ... 5); `cur` is its LDS stage
-      auto fin = [&](FragsX3<TM, TN>& f, bf16x8 (&b)[3][TN]) {
-#if T3D_X3_LATE_M
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm) f.a[1][tm] = frag_x<AR, DIMA>(smem + cur * STAGE + SA::PLANE, a0 + tm * 32, tid & 63);
-#endif
-        mma_x3_ab<SYM, TM, TN>(f.a, b, acc, accb, accc);
-      };
-      if (ph == 0) fin(f0, br[0]);
-      else if (ph == 1) fin(f1, br[1]);
-      else if (ph == 2) fin(f0, br[2]);
-      else if (ph == 3) fin(f1, br[0]);
-      else if (ph == 4) fin(f0, br[1]);
-      else fin(f1, br[2]);
-    } else
-#endif
-    if constexpr (FromGlobal<SB>::value) {      // (A from the LDS image, the weight fragments from global memory)
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm) f0.a[pl][tm] = frag_x<AR, DIMA>(smem + pl * SA::PLANE, a0 + tm * 32, tid & 63);
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) f0.b[pl][tn] = sb.gfrag(lb, pl, b0 + tn * 32, tile_red(0), tid & 63);
-      }
-    } else {
-      load_frags_x3<AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(smem, smem + SA::LDS_ELEMS, a0, b0, tid & 63, f0);
+      for (int tn = 0; tn < TN; ++tn) f0.b[pl][tn] = sb.gfrag(lb, pl, b0 + tn * 32, tile_red(0), tid & 63);
     }
-    int t = 0;
-#if T3D_X3_FAIR
-    // The two workgroups of a CU do not advance together: a SIMD's arbiter takes the OLDER wave whenever both are ready, so the workgroup
-    // dispatched first wins every conflict (matrix pipe, vector ports, LDS, the memory pipeline), finishes its k loop early -- in 256 of
-    // 256 CU pairs of the forward 512 -> 256, by 7.6 us of 46 (tools/trace_blocks.py, profiles/r06_trace_blocks_x3.log) -- and leaves the
-    // other one alone on the CU, one wave per SIMD with nobody to overlap its staging pass, for the rest of the launch.  A launch's
-    // first T3D_FAIR_CUS workgroups land one per CU; the later ones are the younger halves of the pairs (and, in launches of more rounds,
-    // always younger than the workgroup they join).  They run the first T3D_X3_FAIR_NUM / T3D_X3_FAIR_DEN of their k loop at wave
-    // priority 1 -- priority beats age -- and the rest at 0: the younger workgroup leads first, the older one catches up, both leave
-    // the loop together.  Scheduling only: the instruction streams and the results are unchanged.
-    // In the fused backward launches the rule is another one: the weight-gradient tiles (both operands reduced over rows: !AR && !BR) are few,
-    // long and first in the launch -- one per CU for 42 ... 86 us while two to four rounds of data-gradient tiles pass through the CU's other
-    // slot, and in every layer but the widest the launch ends when THEY end, alone on their CUs (tools/trace_bwd.py).  They run their whole k
-    // loop at priority 1 (T3D_X3_PRIO_WGRAD); the data-gradient tiles (AR && BR) keep priority 0 and no forward rule.
-    constexpr bool WG_TILE = T3D_X3_PRIO_WGRAD && !AR && !BR, FWD_TILE = AR && !BR;
-    const int fair_sw = (FWD_TILE && (int)blockIdx.x >= T3D_FAIR_CUS) ? ((nt * T3D_X3_FAIR_NUM / T3D_X3_FAIR_DEN) & ~1) : 0;
-    if (WG_TILE || fair_sw > 0) __builtin_amdgcn_s_setprio(1);
-#endif
-#if T3D_X3_IL && T3D_X3_BRING
-    if constexpr (!FromGlobal<SB>::value)
-#endif
-#if T3D_X3_FAIR
-    // (two passes over ONE loop body -- the k-tiles in front of the switch, then the rest -- so that the body stays a single basic block)
-#pragma nounroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const int lim = pass == 0 ? fair_sw : nt;
-      for (; t + 2 < nt && t < lim; t += 2) {
-        T3D_X3_ITER_FP(SODD, t, f0, f1);
-        cur ^= 1;
-        T3D_X3_ITER_FP(0, t + 1, f1, f0);
-        cur ^= 1;
-      }
-      if constexpr (!WG_TILE) __builtin_amdgcn_s_setprio(0);
-    }
-#else
-    for (; t + 2 < nt; t += 2) {
-      T3D_X3_ITER_FP(SODD, t, f0, f1);
-      cur ^= 1;
-      T3D_X3_ITER_FP(0, t + 1, f1, f0);
-      cur ^= 1;
-    }
-#endif
-    // (T3D_X3_LATE_M: the m planes of the last tile are read here -- no iteration follows that would read them at its head)
-    auto load_m = [&](FragsX3<TM, TN>& f, const bf16_t* st) {
-#if T3D_X3_IL && T3D_X3_LATE_M
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm) f.a[1][tm] = frag_x<AR, DIMA>(st + SA::PLANE, a0 + tm * 32, tid & 63);
-      if constexpr (!FromGlobal<SB>::value) {
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) f.b[1][tn] = frag_x<BR, DIMB>(st + SA::LDS_ELEMS + SB::PLANE, b0 + tn * 32, tid & 63);
-      }
-#endif
-    };
-#if T3D_X3_IL && T3D_X3_BRING
-    if constexpr (!FromGlobal<SB>::value)
-#endif
-    {
-      if (t + 1 < nt) {      // two tiles left
-        T3D_X3_ITER_FP(SODD, t, f0, f1);
-        load_m(f1, smem + (cur ^ 1) * STAGE);
-        mma_x3_f<SYM, TM, TN>(f1, acc, accb, accc, [](int) {});
-      } else {
-        load_m(f0, smem + cur * STAGE);
-        mma_x3_f<SYM, TM, TN>(f0, acc, accb, accc, [](int) {});
-      }
-    }
-#undef T3D_X3_ITER_FP
-#if T3D_X3_FAIR
-    if constexpr (T3D_X3_PRIO_WGRAD && !AR && !BR) __builtin_amdgcn_s_setprio(0);
-#endif
+  } else {
+    load_frags_x3<AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(smem, smem + SA::LDS_ELEMS, a0, b0, tid & 63, f0);
   }
-#else
-#define T3D_X3_ITER(S_) x3_iter<S_, SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, cur, tile_red(t + 1 + PF), a0, b0, acc, accb, accc, tid)
-  constexpr int S1 = (PF > 1) ? 1 : 0, S2 = (PF > 2) ? 2 : 0, S3 = (PF > 3) ? 3 : 0;
   int t = 0;
-  if constexpr (PF == 2) {      // slot and LDS stage have the same period: a branch-free body of two iterations
-    for (; t + 2 < nt; t += 2) {
-      T3D_X3_ITER(1);
+  // The two workgroups of a CU do not advance together: a SIMD's arbiter takes the OLDER wave whenever both are ready, so the workgroup
+  // dispatched first wins every conflict (matrix pipe, vector ports, LDS, the memory pipeline), finishes its k loop early -- in 256 of
+  // 256 CU pairs of the forward 512 -> 256, by 7.6 us of 46 (tools/trace_blocks.py, profiles/r06_trace_blocks_x3.log) -- and leaves the
+  // other one alone on the CU, one wave per SIMD with nobody to overlap its staging pass, for the rest of the launch.  A launch's
+  // first T3D_FAIR_CUS workgroups land one per CU; the later ones are the younger halves of the pairs (and, in launches of more rounds,
+  // always younger than the workgroup they join).  They run the first FAIR_NUM / FAIR_DEN of their k loop at wave priority 1 --
+  // priority beats age -- and the rest at 0: the younger workgroup leads first, the older one catches up, both leave the loop together.
+  // Scheduling only: the instruction streams and the results are unchanged.
+  // In the fused backward launches the rule is another one: the weight-gradient tiles (both operands reduced over rows: !AR && !BR) are few,
+  // long and first in the launch -- one per CU for 42 ... 86 us while two to four rounds of data-gradient tiles pass through the CU's other
+  // slot, and in every layer but the widest the launch ends when THEY end, alone on their CUs (tools/trace_bwd.py).  They run their whole k
+  // loop at priority 1; the data-gradient tiles (AR && BR) keep priority 0 and no forward rule.
+  constexpr bool WG_TILE = !AR && !BR, FWD_TILE = AR && !BR;
+  const int fair_sw = (FWD_TILE && (int)blockIdx.x >= T3D_FAIR_CUS) ? ((nt * FAIR_NUM / FAIR_DEN) & ~1) : 0;
+  if (WG_TILE || fair_sw > 0) __builtin_amdgcn_s_setprio(1);
+  // (two passes over ONE loop body -- the k-tiles in front of the switch, then the rest -- so that the body stays a single basic block)
+#pragma nounroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int lim = pass == 0 ? fair_sw : nt;
+    for (; t + 2 < nt && t < lim; t += 2) {
+      T3D_X3_ITER(t, f0, f1);
       cur ^= 1;
-      ++t; T3D_X3_ITER(0); --t;
+      T3D_X3_ITER(t + 1, f1, f0);
       cur ^= 1;
     }
+    if constexpr (!WG_TILE) __builtin_amdgcn_s_setprio(0);
   }
-  for (; t + 1 < nt; ++t) {      // (the slot is workgroup-uniform: a scalar branch per k-tile)
-    const int slot = (t + 1) % PF;
-    if (PF == 1 || slot == 0) T3D_X3_ITER(0);
-    else if (PF == 2 || slot == 1) T3D_X3_ITER(S1);
-    else if (PF == 3 || slot == 2) T3D_X3_ITER(S2);
-    else T3D_X3_ITER(S3);
-    cur ^= 1;
+  // (the m planes of the last tile are read here -- no iteration follows that would read them at its head)
+  auto load_m = [&](FragsX3<TM, TN>& f, const bf16_t* st) {
+#pragma unroll
+    for (int tm = 0; tm < TM; ++tm) f.a[1][tm] = frag_x<AR, DIMA>(st + SA::PLANE, a0 + tm * 32, tid & 63);
+    if constexpr (!FromGlobal<SB>::value) {
+#pragma unroll
+      for (int tn = 0; tn < TN; ++tn) f.b[1][tn] = frag_x<BR, DIMB>(st + SA::LDS_ELEMS + SB::PLANE, b0 + tn * 32, tid & 63);
+    }
+  };
+  if (t + 1 < nt) {      // two tiles left
+    T3D_X3_ITER(t, f0, f1);
+    load_m(f1, smem + (cur ^ 1) * STAGE);
+    mma_x3_f<SYM, TM, TN>(f1, acc, accb, accc);
+  } else {
+    load_m(f0, smem + cur * STAGE);
+    mma_x3_f<SYM, TM, TN>(f0, acc, accb, accc);
   }
 #undef T3D_X3_ITER
-  {
-    const bf16_t* As = smem + cur * STAGE;
-    mma_x3<SYM, TM, TN, AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(As, As + SA::LDS_ELEMS, a0, b0, acc, accb, accc, tid & 63, [](int) {});
-  }
-#endif
+  if constexpr (WG_TILE) __builtin_amdgcn_s_setprio(0);
   if constexpr (SYM) {
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
@@ -2000,137 +1460,6 @@ __device__ __forceinline__ void gemm_mainloop_x3(SA& sa, SB& sb, const LA& la, c
         for (int r = 0; r < 16; ++r) acc[tm][tn][r] = (acc[tm][tn][r] + accb[tm][tn][r]) + accc[tm][tn][r];
   }
   __syncthreads();
-}
-
-
-// ---- producer / consumer wave roles (PathX3PC; 512-thread workgroups) -- an EXPERIMENT of round 5, not the default ---------------------
-// The loop above gives every wave both jobs -- load, batch-norm / ReLU, three-way split, LDS stores AND the six products -- in ONE in-order
-// instruction stream: ~135 vector instructions per wave and 16-deep k-tile queue behind and in front of 24 MFMAs, and the counters say
-// the matrix pipe idles 0.6 of a launch while a SIMD has nothing to issue 0.4 of it (docs/EXPERIMENTS.md, round 4).  Here a workgroup is
-// EIGHT waves: waves 0-3 (consumers, tid 0..255: the 2 x 2 wave grid of the output tile, the only ones with accumulators and an
-// epilogue) issue nothing but fragment reads and MFMAs; waves 4-7 (producers) run the staging pass of the whole tile and end.  A SIMD
-// hosts one wave of each role.  Three LDS stages (101 KB: ONE workgroup per CU), one workgroup barrier per k-tile, tile j in stage j % 3:
-//     iteration t   consumers: read the fragments of tile t + 1 into the other register set, multiply tile t from registers
-//                   producers: convert + store tile t + 2 (register slot (t + 2) % 3), request tile t + 5 into that slot
-//     barrier t + 1: tile t + 2 is complete; every fragment of tile t has been consumed
-// Stage (t + 2) % 3 held tile t - 1, whose fragments were read in iteration t - 2: no wave can still be reading it.  Same products in the
-// same order as the loop above: results are bit-identical (tests/test_kernels_gpu.py).
-// MEASURED (tools/bench_x3_pc.py, MI355X, forward 512 -> 256 at M = 32768): 78-83 us against 56-58 us for the loop above.  Taken apart
-// with timing ablations (tools/pc_abl.sh): the consumers alone (producers only keeping the barrier count) 53 us; the producers alone
-// 52 us; the products alone, no fragment reads and no barrier, 41-44 us -- of which the chip's matrix pipe accounts for 27.7 us (it
-// sustains 1.86 PFLOP/s dense bf16 at the 1.85 GHz it holds under this load, tools/micro/mfma_rate.hip, not the 2.5 PFLOP/s of the
-// data sheet) and the rest is the un-overlapped prologue and epilogue of the one workgroup a CU can hold.  The two roles of a SIMD do NOT
-// run beside each other for free: together they take 1.5 x the longer of the two, whatever the priorities (s_setprio on either role:
-// 78.4 / 82.9 us).  Kept behind T3D_X3_PC=1 for the measurement; nothing selects it.
-constexpr int X3_RING = 3;
-#ifdef T3D_ABL_PC_NOBAR      // timing ablation (wrong results; with _NOPROD and _NOFRAG: the products alone)
-#define T3D_PC_BAR() do {} while (0)
-#else
-#define T3D_PC_BAR() __syncthreads()
-#endif
-template <bool SYM, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB>
-__device__ __forceinline__ void gemm_mainloop_x3_pc(SA& sa, SB& sb, const LA& la, const LB& lb, float* smem_f, int red_begin, int red_end,
-                                                    int a0, int b0, f32x16 (&acc)[TM][TN], int tid) {
-  static_assert(!SYM || TM * TN == 1, "symmetric accumulation: 64 x 64 tiles (three accumulator sets)");
-  static_assert(SA::PF == X3_RING && SB::PF == X3_RING, "three register slots: slot and LDS stage of a tile share their period");
-  bf16_t* smem = reinterpret_cast<bf16_t*>(smem_f);
-  constexpr int STAGE = SA::LDS_ELEMS + SB::LDS_ELEMS;
-  const int last = red_end - BKX;
-  const int nt = (red_end - red_begin) / BKX;
-  auto tile_red = [&](int j) { return min(red_begin + j * BKX, last); };      // past the end the last tile is re-read, never used
-  const bool producer = __builtin_amdgcn_readfirstlane((int)threadIdx.x) >= NT;
-#ifdef T3D_PC_PRIO      // 1: the consumers (matrix instructions) above the producers; 2: the producers above the consumers
-  if ((T3D_PC_PRIO == 1) != producer) __builtin_amdgcn_s_setprio(2);
-#endif
-  if (producer) {
-#ifdef T3D_ABL_PC_NOPROD      // timing ablation (wrong results): producers that only keep the barrier count
-#define T3D_PC_PRODUCE(S_, J_) do {} while (0)
-#else
-#define T3D_PC_PRODUCE(S_, J_)                                                                         \
-  do {                                                                                                 \
-    bf16_t* At_ = smem + (S_) * STAGE;                                                                 \
-    bf16_t* Bt_ = At_ + SA::LDS_ELEMS;                                                                 \
-    const int rf_ = tile_red((J_) + X3_RING);                                                          \
-    _Pragma("unroll") for (int q = 0; q < SA::NV; ++q) {                                               \
-      sa.template store_piece<S_>(la, At_, tid, q);                                                    \
-      sa.template fetch_piece<S_>(la, rf_, tid, q);                                                    \
-    }                                                                                                  \
-    sa.template fetch_head<S_>(la, rf_, tid);                                                          \
-    _Pragma("unroll") for (int q = 0; q < SB::NV; ++q) {                                               \
-      sb.template store_piece<S_>(lb, Bt_, tid, q);                                                    \
-      sb.template fetch_piece<S_>(lb, rf_, tid, q);                                                    \
-    }                                                                                                  \
-    sb.template fetch_head<S_>(lb, rf_, tid);                                                          \
-  } while (0)
-#endif
-    sa.template fetch<0>(la, tile_red(0), tid);
-    sb.template fetch<0>(lb, tile_red(0), tid);
-    sa.template fetch<1>(la, tile_red(1), tid);
-    sb.template fetch<1>(lb, tile_red(1), tid);
-    sa.template fetch<2>(la, tile_red(2), tid);
-    sb.template fetch<2>(lb, tile_red(2), tid);
-    T3D_PC_PRODUCE(0, 0);
-    T3D_PC_PRODUCE(1, 1);
-    T3D_PC_BAR();
-    // Branch-free body of three iterations (a conditional staging pass is a join in front of which hipcc waits for nearly every load in
-    // flight: `s_waitcnt vmcnt(2)` with twelve outstanding): tiles past the end are the last tile again, stored into stages whose tiles
-    // have been consumed (tile nt + i lands on tile nt + i - 3), and the consumers pad their barrier count to the same multiple of three.
-    for (int t = 0; t < nt; t += X3_RING) {
-      T3D_PC_PRODUCE(2, t + 2);
-      T3D_PC_BAR();
-      T3D_PC_PRODUCE(0, t + 3);
-      T3D_PC_BAR();
-      T3D_PC_PRODUCE(1, t + 4);
-      T3D_PC_BAR();
-    }
-#undef T3D_PC_PRODUCE
-    __builtin_amdgcn_endpgm();      // a producer has no accumulators and no epilogue; s_barrier counts the surviving waves only
-  }
-  f32x16 accb[SYM ? TM : 1][SYM ? TN : 1], accc[SYM ? TM : 1][SYM ? TN : 1];
-  if constexpr (SYM) { zero_acc<TM, TN>(accb); zero_acc<TM, TN>(accc); }
-  FragsX3<TM, TN> f0, f1;
-  const int lane = tid & 63;
-  T3D_PC_BAR();
-  load_frags_x3<AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(smem, smem + SA::LDS_ELEMS, a0, b0, lane, f0);
-  int nxt = 1;      // LDS stage of tile t + 1
-  // (the fragments of the tile behind the last one are read from a stage that holds a repeat of the last tile, and never used)
-#ifdef T3D_ABL_PC_NOMMA       // timing ablations (wrong results): consumers without products / without fragment reads
-#define T3D_PC_MMA(FC_) do {} while (0)
-#else
-#define T3D_PC_MMA(FC_) mma_x3_f<SYM, TM, TN>(FC_, acc, accb, accc, [](int) {})
-#endif
-#ifdef T3D_ABL_PC_NOFRAG
-#define T3D_PC_LOADFRAGS(FN_) do {} while (0)
-#else
-#define T3D_PC_LOADFRAGS(FN_) load_frags_x3<AR, DIMA, SA::PLANE, BR, DIMB, SB::PLANE>(smem + nxt * STAGE, smem + nxt * STAGE + SA::LDS_ELEMS, a0, b0, lane, FN_)
-#endif
-#define T3D_PC_CONSUME(FC_, FN_)                                                                                                       \
-  do {                                                                                                                                 \
-    T3D_PC_LOADFRAGS(FN_);                                                                                                             \
-    __builtin_amdgcn_sched_barrier(0);      /* the reads in front of the products (hipcc sinks them to the end, right before their wait) */ \
-    T3D_PC_MMA(FC_);                                                                                                                   \
-    __builtin_amdgcn_sched_barrier(0);      /* the barrier behind the products, not in front of them (hipcc hoists it over the MFMAs) */ \
-    T3D_PC_BAR();                                                                                                                   \
-    nxt = nxt == X3_RING - 1 ? 0 : nxt + 1;                                                                                            \
-  } while (0)
-  int t = 0;
-  for (; t + 2 <= nt; t += 2) {
-    T3D_PC_CONSUME(f0, f1);
-    T3D_PC_CONSUME(f1, f0);
-  }
-  if (t < nt) { T3D_PC_CONSUME(f0, f1); ++t; }
-#undef T3D_PC_CONSUME
-#undef T3D_PC_MMA
-#undef T3D_PC_LOADFRAGS
-  for (const int tb = (nt + X3_RING - 1) / X3_RING * X3_RING; t < tb; ++t) T3D_PC_BAR();      // the producers' barrier count
-  if constexpr (SYM) {
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tm][tn][r] = (acc[tm][tn][r] + accb[tm][tn][r]) + accc[tm][tn][r];
-  }
 }
 
 // Arithmetic of a GEMM kernel: which staging / MFMA loop, and the element type T of the layer tensors it writes.
@@ -2142,9 +1471,8 @@ struct PathF32 {
   typedef WLoaderT<float> WLX;           // ... when every tile lies inside the matrix (the fp32 path keeps its one loader)
   static constexpr bool BF16 = false;
   static constexpr bool X3 = false;
-  static constexpr bool PC = false;
   static constexpr int RED = BK;         // reduction depth of an LDS stage
-  template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false> using Stg = Stager<DIM, TYPE_R, L, PF>;
+  template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false> using Stg = Stager<DIM, TYPE_R, L>;
 };
 struct PathBF16 {
   typedef bf16_t T;
@@ -2154,7 +1482,6 @@ struct PathBF16 {
   typedef WLoaderT<bf16_t, true> WLX;
   static constexpr bool BF16 = true;
   static constexpr bool X3 = false;
-  static constexpr bool PC = false;
   static constexpr int RED = BKH;
   // the first operand of every GEMM here is the [M, C] stream from HBM: two register slots (prefetch distance 2); the second
   // (weights from L2, or the fatter dy operand of the weight gradient) one
@@ -2248,7 +1575,6 @@ struct PathX3 {
   typedef WLoaderT<float, true> WLX;
   static constexpr bool BF16 = false;
   static constexpr bool X3 = true;
-  static constexpr bool PC = false;
   static constexpr int RED = BKX;
   template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false> using Stg = StagerX3<DIM, TYPE_R, L>;
 };
@@ -2270,26 +1596,20 @@ struct PathX3P : PathX3 {      // ... with the layer's weight matrix split befor
 // CU, the same eight waves per CU as two four-wave workgroups.
 struct PathX3W : PathX3 {
   static constexpr int WAVES = 8;
-  template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false> using Stg = StagerX3<DIM, TYPE_R, L, T3D_X3_PF, 2 * NT>;
+  template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false> using Stg = StagerX3<DIM, TYPE_R, L, 2 * NT>;
 };
 struct PathX3WP : PathX3W {      // ... and the weights in fragment order
   typedef WLoaderX3F WL;
   typedef WLoaderX3F WLX;
   template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false>
-  using Stg = std::conditional_t<IsFrag<L>::value, StagerX3F<DIM, TYPE_R, L>, StagerX3<DIM, TYPE_R, L, T3D_X3_PF, 2 * NT>>;
+  using Stg = std::conditional_t<IsFrag<L>::value, StagerX3F<DIM, TYPE_R, L>, StagerX3<DIM, TYPE_R, L, 2 * NT>>;
 };
 template <class PR, class = void> struct WavesOf { static constexpr int value = 4; };
 template <class PR> struct WavesOf<PR, typename std::enable_if<(PR::WAVES > 0)>::type> { static constexpr int value = PR::WAVES; };
-// ... in 512-thread workgroups with producer and consumer waves (gemm_mainloop_x3_pc): three register slots per operand
-struct PathX3PC : PathX3 {
-  static constexpr bool PC = true;
-  template <int DIM, bool TYPE_R, class L, int PF, bool IS_A = false> using Stg = StagerX3<DIM, TYPE_R, L, X3_RING>;
-};
 template <class PR, int TM, int TN, class SA, class SB, class LA, class LB, bool AR, int DIMA, bool BR, int DIMB, bool SYM = false>
 __device__ __forceinline__ void run_mainloop(SA& sa, SB& sb, const LA& la, const LB& lb, float* smem, int red_begin, int red_end,
                                              int a0, int b0, f32x16 (&acc)[TM][TN], int tid) {
-  if constexpr (PR::PC) gemm_mainloop_x3_pc<SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, red_begin, red_end, a0, b0, acc, tid);
-  else if constexpr (PR::X3) gemm_mainloop_x3<SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, red_begin, red_end, a0, b0, acc, tid);
+  if constexpr (PR::X3) gemm_mainloop_x3<SYM, TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, red_begin, red_end, a0, b0, acc, tid);
   else if constexpr (PR::BF16) gemm_mainloop_h<TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, red_begin, red_end, a0, b0, acc, tid);
   else gemm_mainloop<TM, TN, SA, SB, LA, LB, AR, DIMA, BR, DIMB>(sa, sb, la, lb, smem, red_begin, red_end, a0, b0, acc, tid);
 }
@@ -2305,14 +1625,12 @@ __device__ __forceinline__ void fwd_body(const t3d_pointmlp_fwd_args& p, float* 
   static_assert(TN == 1 || TN == 2, "a wave owns 32 or 64 columns");
   using LA = typename PR::template Act<HAS_SUB, XT>;
   using YT = typename PR::T;
-  constexpr int PF = BN == 64 ? T3D_PF_NARROW : T3D_PF_WIDE;
   using WL = std::conditional_t<LA::EXACT, typename PR::WLX, typename PR::WL>;      // K % 64 == 0: every weight tile is whole
   // (bf16 arithmetic on an fp32 source -- a raw input wider than 4 channels, e.g. the Box-PC representation -- at 128 columns: one slot)
-  using SA = typename PR::template Stg<BM, true, LA, (PR::BF16 && BN == 128 && !Elem<XT>::BF16) ? 0 : PF, true>;
-  using SB = typename PR::template Stg<BN, false, WL, PF>;
+  using SA = typename PR::template Stg<BM, true, LA, (PR::BF16 && BN == 128 && !Elem<XT>::BF16) ? 0 : 1, true>;
+  using SB = typename PR::template Stg<BN, false, WL, 1>;
 
-  // (producer / consumer workgroups: the second 256 threads are the staging waves of the same tile coordinates; they end in the main loop)
-  const int tid = PR::PC ? (int)(threadIdx.x & (NT - 1)) : (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int tiles_n = p.N / BN;
   const int lin = xcd_remap(bid, nblk);
@@ -2347,19 +1665,6 @@ __device__ __forceinline__ void fwd_body(const t3d_pointmlp_fwd_args& p, float* 
                                                                      wn * WCOLS, acc, tid);
   T3D_TRACE_MARK(1);
 
-#ifdef T3D_ABL_NOEPI
-  if (p.M > 0) {          // diagnostic build: skip the epilogue but keep the accumulators live
-    if (p.K < 0) {
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) p.y[tm * 32 + tn * 16 + r] = acc[tm][tn][r];
-    }
-    return;
-  }
-#endif
   // epilogue: + bias (+ per-frustum row bias), store y, column statistics, optional pool partials
   const int l31 = lane & 31, h = lane >> 5;
   const int b = row0 / p.rows_per_frustum;
@@ -2488,18 +1793,15 @@ __device__ __forceinline__ void fwd_body(const t3d_pointmlp_fwd_args& p, float* 
 }
 
 template <int BN, bool HAS_SUB, class PR = PathF32, class XT = float>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_fwd(const t3d_pointmlp_fwd_args p) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_fwd(const t3d_pointmlp_fwd_args p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   fwd_body<BN, HAS_SUB, PR, XT>(p, smem, blockIdx.x, gridDim.x);
 }
 
 // The eight-wave kernels hold ONE workgroup per CU, so a launch of more tiles than CUs ran in rounds with the CU idle between a
 // workgroup's exit and its successor's first instruction (1.9 us in the timeline of the 256 -> 512 pooled layer, tools/trace_blocks.py)
-// on top of the epilogue and prologue on either side.  T3D_W8_PERSIST: the launch is min(tiles, CUs) workgroups and a workgroup walks
-// tiles b, b + G, b + 2 G, ... itself (same tile -> XCD assignment as the dispatcher's round robin: xcd_remap sees the same index).
-#ifndef T3D_W8_PERSIST
-#define T3D_W8_PERSIST 1
-#endif
+// on top of the epilogue and prologue on either side.  So the launch is min(tiles, CUs) workgroups and a workgroup walks tiles b,
+// b + G, b + 2 G, ... itself (same tile -> XCD assignment as the dispatcher's round robin: xcd_remap sees the same index).
 template <int BN, class PR>      // eight waves, 128 x 256 tile (PathX3W)
 __global__ __launch_bounds__(2 * NT) void k_pointmlp_fwd_w8(const t3d_pointmlp_fwd_args p, const int n_tiles) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -2526,16 +1828,10 @@ __global__ __launch_bounds__(2 * NT) void k_pointmlp_fwd_w8_r(const t3d_pointmlp
   }
 }
 
-template <int BN, class PR>      // producer / consumer form (gemm_mainloop_x3_pc): eight waves, one workgroup per CU
-__global__ __launch_bounds__(2 * NT) void k_pointmlp_fwd_pc(const t3d_pointmlp_fwd_args p) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  fwd_body<BN, false, PR, float>(p, smem, blockIdx.x, gridDim.x);
-}
-
 // Rider forms (rider_dev.h): the launch's first r.n_wg workgroups run a set of small ops of an independent chain and leave; the
 // GEMM's tiles are the workgroups behind them.  fp32 split-form kernels only; the plain kernels above and below are untouched.
 template <int BN, bool HAS_SUB, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_fwd_r(const t3d_pointmlp_fwd_args p, const t3d_rider_set r) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_fwd_r(const t3d_pointmlp_fwd_args p, const t3d_rider_set r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if ((int)blockIdx.x < r.n_wg) { run_riders(r, smem); return; }
   fwd_body<BN, HAS_SUB, PR, float>(p, smem, blockIdx.x - r.n_wg, gridDim.x - r.n_wg);
@@ -2552,7 +1848,7 @@ __global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_fwd_r(const t3d_poin
 // (copied untouched, from L2) and the epilogue of the generic kernel runs on the tile.  The epilogue's LDS scratch (partial sums +
 // the bf16 output tile) aliases the weight ring: 2 x 64 x (BN + 32) x 2 bytes = 12 x BN x 4 + 128 x (BN + 8) x 2 exactly for BN = 128.
 template <int BN, int KT>      // KT = K / 64 k-tiles resident
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_fwd_res(const t3d_pointmlp_fwd_args p) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_fwd_res(const t3d_pointmlp_fwd_args p) {
   constexpr int TM = 2, TN = BN / 64, ST = BKH / 16;
   using LA = ActLoaderT<false, bf16_t>;
   using WL = WLoaderT<bf16_t, true>;
@@ -2941,11 +2237,7 @@ __device__ __forceinline__ void dgrad_epilogue_body(const DgradEpilogue& p, f32x
         for (int e = 0; e < EB; ++e) {
           const int r = r0 + e;
           const unsigned o = boff0 + (unsigned)(tm * 32 + (r & 3) + 8 * (r >> 2)) * k4;
-#ifdef T3D_ABL_DG_NOLOAD
-          yp[e] = psc + (float)r;
-#else
           yp[e] = MASK ? *reinterpret_cast<const float*>(pyb + o) : 0.f;
-#endif
           if (ADD == 2) ad[e] = ((live >> (tm * 16 + r)) & 1u) ? *reinterpret_cast<const float*>(adb + o) : 0.f;
           else ad[e] = ADD ? *reinterpret_cast<const float*>(adb + o) : 0.f;
         }
@@ -3064,11 +2356,7 @@ __device__ __forceinline__ void dgrad_epilogue_body_h(const DgradEpilogue& p, f3
         for (int e = 0; e < EB; ++e) {
           const int r = r0 + e;
           const unsigned o = off0 + (unsigned)(tm * 32 + (r & 3) + 8 * (r >> 2)) * K;
-#ifdef T3D_ABL_DG_NOLOAD
-          yp[e] = psc + (float)r;
-#else
           yp[e] = MASK ? Elem<T>::ld1(p.prev_y, o) : 0.f;
-#endif
           if (ADD == 2) ad[e] = ((live >> (tm * 16 + r)) & 1u) ? p.add_in[o] : 0.f;      // the sparse rows S: fp32
           else ad[e] = ADD ? Elem<T>::ld1(p.add_in, o) : 0.f;
         }
@@ -3149,11 +2437,10 @@ __device__ __forceinline__ void dgrad_epilogue(const DgradEpilogue& p, f32x16 (&
 template <int BN, bool POOLED, class PR = PathF32>   // BN = tile width over the layer's INPUT channels K
 __device__ __forceinline__ void dgrad_body(const t3d_pointmlp_dgrad_args& p, float* smem, int bid, int nblocks) {
   constexpr int BM = 128, TM = 2, TN = BN / 64;
-  constexpr int PF = BN == 64 ? T3D_PF_NARROW : T3D_PF_WIDE;
   using LA = typename PR::template Dy<POOLED>;
   using WL = typename PR::WLX;            // bf16: K % 64 == 0 and N % 64 == 0 (launcher-checked), every tile is whole
-  using SA = typename PR::template Stg<BM, true, LA, (PR::BF16 && BN == 128) ? 0 : PF, true>;
-  using SB = typename PR::template Stg<BN, true, WL, PF>;
+  using SA = typename PR::template Stg<BM, true, LA, (PR::BF16 && BN == 128) ? 0 : 1, true>;
+  using SB = typename PR::template Stg<BN, true, WL, 1>;
 
   const int tid = threadIdx.x, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
@@ -3179,7 +2466,7 @@ __device__ __forceinline__ void dgrad_body(const t3d_pointmlp_dgrad_args& p, flo
 }
 
 template <int BN, bool POOLED, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_dgrad(const t3d_pointmlp_dgrad_args p) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_dgrad(const t3d_pointmlp_dgrad_args p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   dgrad_body<BN, POOLED, PR>(p, smem, blockIdx.x, gridDim.x);
 }
@@ -3190,9 +2477,8 @@ template <int BN, class PR = PathF32>
 __device__ __forceinline__ void dgrad_gram_body(const t3d_pointmlp_dgrad_gram_args& p, float* smem, int bid, int nblocks) {
   constexpr int BM = 128, TM = 2, TN = BN / 64;
   using LA = typename PR::template Act<false, typename PR::T>;
-  constexpr int PF = BN == 64 ? T3D_PF_NARROW : T3D_PF_GRAM128;
-  using SA = typename PR::template Stg<BM, true, LA, (PR::BF16 && BN == 128) ? 0 : PF, true>;
-  using SB = typename PR::template Stg<BN, false, WLoader, PF>;
+  using SA = typename PR::template Stg<BM, true, LA, (PR::BF16 && BN == 128) ? 0 : 1, true>;
+  using SB = typename PR::template Stg<BN, false, WLoader, 1>;
   const int tid = threadIdx.x, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int tiles_n = p.K / BN;
@@ -3213,7 +2499,7 @@ __device__ __forceinline__ void dgrad_gram_body(const t3d_pointmlp_dgrad_gram_ar
 }
 
 template <int BN, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_dgrad_gram(const t3d_pointmlp_dgrad_gram_args p) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_dgrad_gram(const t3d_pointmlp_dgrad_gram_args p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   dgrad_gram_body<BN, PR>(p, smem, blockIdx.x, gridDim.x);
 }
@@ -3226,9 +2512,8 @@ template <int BMK, int BN, class PR = PathF32, bool SYM = false, class LA, class
 __device__ __forceinline__ void wgrad_body(const LA& la, const LB& lb, float* slabs, int K, int N, int rows_per_split,
                                            float* smem, int bid, int nblocks) {
   constexpr int TM = BMK / 64, TN = BN / 64;
-  constexpr int PF = (BMK == 64 && BN == 64) ? T3D_PF_NARROW : T3D_PF_WIDE;
-  using SA = typename PR::template Stg<BMK, false, LA, (PR::BF16 && BMK == 128 && BN == 128) ? 0 : PF, true>;      // (one slot: see PathBF16::Stg)
-  using SB = typename PR::template Stg<BN, false, LB, PF>;
+  using SA = typename PR::template Stg<BMK, false, LA, (PR::BF16 && BMK == 128 && BN == 128) ? 0 : 1, true>;      // (one slot: see PathBF16::Stg)
+  using SB = typename PR::template Stg<BN, false, LB, 1>;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
   const int tiles_k = (K + BMK - 1) / BMK, tiles_n = N / BN;
@@ -3280,7 +2565,7 @@ __device__ __forceinline__ void wgrad_body(const LA& la, const LB& lb, float* sl
 
 // XT: element type of the layer input `a` (fp32 for the raw inputs: the first layer of each net)
 template <int BMK, int BN, bool HAS_SUB, bool POOLED, class PR = PathF32, class XT = float>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_wgrad(const t3d_pointmlp_wgrad_args p) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_wgrad(const t3d_pointmlp_wgrad_args p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typename PR::template Act<HAS_SUB, XT> la{p.a, p.K, p.rows_per_frustum};
   typename PR::template Dy<POOLED> lb{p.dy, p.N, p.rows_per_frustum};
@@ -3368,7 +2653,7 @@ __global__ __launch_bounds__(NT) void k_pointmlp_wgrad_tinyk(const t3d_pointmlp_
 
 // Gram matrix of a layer input, G = a^T a, as split-row slabs (t3d.h K11e).
 template <int BMK, int BN, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_gram(const t3d_pointmlp_gram_args p) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_gram(const t3d_pointmlp_gram_args p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typename PR::template Act<false, typename PR::T> la{p.a, p.K, p.rows_per_frustum};
   wgrad_body<BMK, BN, PR, true>(la, la, p.slabs, p.K, p.K, p.rows_per_split, smem, blockIdx.x, gridDim.x);
@@ -3378,44 +2663,22 @@ __global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_gram(const t3d_point
 // data-gradient tiles.  The two are independent (both read dy = c0*dz + c1*y + c2), so sharing a launch removes one
 // kernel's fill/drain latency per layer and lets the tiles of one kind fill the holes the other leaves on a CU.
 template <int DBN, int WBMK, int WBN, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_bwd(const t3d_pointmlp_dgrad_args d, const t3d_pointmlp_wgrad_args w,
-                                                                const int n_wgrad, const int interleave) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_bwd(const t3d_pointmlp_dgrad_args d, const t3d_pointmlp_wgrad_args w,
+                                                                const int n_wgrad) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   typename PR::template Act<false, typename PR::T> la{w.a, w.K, w.rows_per_frustum};
   typename PR::template Dy<false> lb{w.dy, w.N, w.rows_per_frustum};
 #ifdef T3D_TRACE      // (tools/trace_bwd.py: entry, exit and the kind of tile of every workgroup; slot 4 = its main loop's prologue done)
   T3D_TRACE_MARK(0);
   if (threadIdx.x == 0 && t3d_trace_ptr) t3d_trace_ptr[(size_t)blockIdx.x * T3D_TRACE_STRIDE + 1] = (int)blockIdx.x < n_wgrad ? 1 : 2;
-  if (!interleave) {
-    if ((int)blockIdx.x < n_wgrad) wgrad_body<WBMK, WBN, PR>(la, lb, w.slabs, w.K, w.N, w.rows_per_split, smem, blockIdx.x, n_wgrad);
-    else dgrad_body<DBN, false, PR>(d, smem, blockIdx.x - n_wgrad, gridDim.x - n_wgrad);
-    T3D_TRACE_MARK(2);
-    return;
-  }
 #endif
-  if (interleave) {
-    // logical order: per row split, its weight-gradient tiles followed by the data-gradient tiles of the same rows; the
-    // XCD remap hands each XCD a contiguous piece of that order, so both readers of a dy row range share one L2
-    const int wt = ((w.K + WBMK - 1) / WBMK) * (w.N / WBN), tiles_nd = d.K / DBN;
-    const int dt = (w.rows_per_split / 128) * tiles_nd, grp_sz = wt + dt;
-    const int l = xcd_remap(blockIdx.x, gridDim.x);
-    const int grp = l / grp_sz, r = l % grp_sz;
-    if (r < wt) wgrad_body<WBMK, WBN, PR>(la, lb, w.slabs, w.K, w.N, w.rows_per_split, smem, grp * wt + r, 0);
-    else dgrad_body<DBN, false, PR>(d, smem, grp * dt + (r - wt), 0);
-  } else if ((int)blockIdx.x < n_wgrad) {
-    wgrad_body<WBMK, WBN, PR>(la, lb, w.slabs, w.K, w.N, w.rows_per_split, smem, blockIdx.x, n_wgrad);
-  } else {
-    dgrad_body<DBN, false, PR>(d, smem, blockIdx.x - n_wgrad, gridDim.x - n_wgrad);
-  }
+  if ((int)blockIdx.x < n_wgrad) wgrad_body<WBMK, WBN, PR>(la, lb, w.slabs, w.K, w.N, w.rows_per_split, smem, blockIdx.x, n_wgrad);
+  else dgrad_body<DBN, false, PR>(d, smem, blockIdx.x - n_wgrad, gridDim.x - n_wgrad);
+  T3D_TRACE_MARK(2);
 }
 
-#ifndef T3D_R64_WAVES
-// (experiment of round 6: 3 caps the rider-hosting <64,64,64> backward at 168 VGPRs -- the GEMM bodies need 148 and the plain kernel runs three
-// workgroups per CU -- but the rider bodies then spill 500 bytes per lane and the hosted launch goes from 28.5 to 35.8 us, the step from 1.15 to 1.25 ms)
-#define T3D_R64_WAVES T3D_WAVES
-#endif
 template <int DBN, int WBMK, int WBN, class PR = PathF32>
-__global__ __launch_bounds__(NT, (DBN == 64 && WBMK == 64 && WBN == 64) ? T3D_R64_WAVES : T3D_WAVES) void k_pointmlp_bwd_r(const t3d_pointmlp_dgrad_args d, const t3d_pointmlp_wgrad_args w,
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_bwd_r(const t3d_pointmlp_dgrad_args d, const t3d_pointmlp_wgrad_args w,
                                                                   const int n_wgrad, const t3d_rider_set r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if ((int)blockIdx.x < r.n_wg) { run_riders(r, smem); return; }
@@ -3428,7 +2691,7 @@ __global__ __launch_bounds__(NT, (DBN == 64 && WBMK == 64 && WBN == 64) ? T3D_R6
 
 // first layer of a net (raw points in, no data gradient): the weight gradient alone
 template <int BMK, int BN, bool HAS_SUB, bool POOLED>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pointmlp_wgrad_r(const t3d_pointmlp_wgrad_args p, const t3d_rider_set r) {
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_wgrad_r(const t3d_pointmlp_wgrad_args p, const t3d_rider_set r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if ((int)blockIdx.x < r.n_wg) { run_riders(r, smem); return; }
   typename PathF32::template Act<HAS_SUB, float> la{p.a, p.K, p.rows_per_frustum};
@@ -3879,9 +3142,7 @@ __global__ __launch_bounds__(NT1) void k_pointmlp_bwd1f(const t3d_pointmlp_dgrad
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         if (g + 1 < NG) fa[(g + 1) & 1] = *reinterpret_cast<const float4*>(ap + 8 * (g + 1));
-#ifndef T3D_BWD1F_NOPIN
         __builtin_amdgcn_sched_barrier(0);      // keep the next group's read AHEAD of this group's four dependent MFMAs
-#endif
         const float4 a = fa[g & 1], b = wf[g];
         accd = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, accd, 0, 0, 0);
         accd = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, accd, 0, 0, 0);
@@ -3906,9 +3167,7 @@ __global__ __launch_bounds__(NT1) void k_pointmlp_bwd1f(const t3d_pointmlp_dgrad
 #pragma unroll
       for (int g = 0; g < BM / 8; ++g) {
         if (g + 1 < BM / 8) ldf((g + 1) & 1, g + 1);
-#ifndef T3D_BWD1F_NOPIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -3988,7 +3247,7 @@ __global__ __launch_bounds__(NT1) void k_pointmlp_bwd1f(const t3d_pointmlp_dgrad
 // Gram-form backward of a pooled layer, stage 1: the three jobs that need nothing but the layer input and the
 // batch-norm-backward coefficients -- Gram slabs a^T a, column sums of a, and the P / rowconst slabs (+ wc) -- in one launch.
 template <int GT, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage1(const t3d_pointmlp_gram_args g, const t3d_act_colsum_args c,
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pool_bwd_stage1(const t3d_pointmlp_gram_args g, const t3d_act_colsum_args c,
                                                                    const t3d_pool_bwd_prep_args q, const int n_gram,
                                                                    const int n_colsum) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -4007,7 +3266,7 @@ __global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage1(const t3d_poi
 // Stage 2: the weight-gradient assembly and the input-gradient GEMM (both after the slab reduction, independent of each
 // other) in one launch.
 template <int BN, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage2(const t3d_pool_wgrad_finish_args f,
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pool_bwd_stage2(const t3d_pool_wgrad_finish_args f,
                                                                    const t3d_pointmlp_dgrad_gram_args d, const int n_finish) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.x;
@@ -4020,7 +3279,7 @@ __global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage2(const t3d_poo
 }
 
 template <int GT, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage1_r(const t3d_pointmlp_gram_args g, const t3d_act_colsum_args c,
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pool_bwd_stage1_r(const t3d_pointmlp_gram_args g, const t3d_act_colsum_args c,
                                                                      const t3d_pool_bwd_prep_args q, const int n_gram,
                                                                      const int n_colsum, const t3d_rider_set r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -4038,7 +3297,7 @@ __global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage1_r(const t3d_p
 }
 
 template <int BN, class PR = PathF32>
-__global__ __launch_bounds__(NT, T3D_WAVES) void k_pool_bwd_stage2_r(const t3d_pool_wgrad_finish_args f,
+__global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pool_bwd_stage2_r(const t3d_pool_wgrad_finish_args f,
                                                                      const t3d_pointmlp_dgrad_gram_args d, const int n_finish,
                                                                      const t3d_rider_set r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -4493,9 +3752,7 @@ struct FwdPool {
           for (int tn = 0; tn < TN; ++tn)
             acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][tm][i], fb[g & 1][tn][i], acc[tm][tn], 0, 0, 0);
         const int slot = g * 4 + i;
-#ifndef T3D_ABL_FP_NOSTAGE
         if (slot >= SLOTS / 2 && slot - SLOTS / 2 < NVB) store_b_piece(stage ^ 1, slot - SLOTS / 2);
-#endif
         if (HAS_PREV && KT_IDX < EPI_TILES) {
           const int sidx = KT_IDX * SLOTS + slot;
           if (sidx % QSTRIDE == 0 && sidx / QSTRIDE < NQUADS) epi_quad(accp, e, addp, sidx / QSTRIDE);
@@ -4511,9 +3768,7 @@ struct FwdPool {
     {
       int nt2 = nt, kt2 = KT_IDX + 2;
       if (kt2 >= KT) { kt2 -= KT; nt2 = min(nt + 1, n_tiles - 1); }
-#ifndef T3D_ABL_FP_NOSTAGE
       fetch_b(nt2, kt2);
-#endif
     }
     __syncthreads();
   }
@@ -4591,11 +3846,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_pointmlp_fwd_pool(const t3d
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) addp[tn] = addn[tn];
     f.load_add(nt, addn);
-#ifdef T3D_ABL_FP_NOEPI
-    f.template ktiles<0, false>(acc, accp, e, addp, nt, n_tiles);
-#else
     f.template ktiles<0, true>(acc, accp, e, addp, nt, n_tiles);
-#endif
   }
   // the last column tile: its epilogue has no MFMAs left to hide under
   f.epi_reset(e);
@@ -4656,7 +3907,6 @@ constexpr size_t lds_wgrad_h(int bmk, int bn) { return 2 * (size_t)BKH * (bmk + 
 constexpr size_t lds_x3_r(int dim) { return (size_t)3 * dim * LDRX * 2; }
 constexpr size_t lds_x3_c(int dim) { return (size_t)3 * BKX * (dim + LDCX_PAD) * 2; }
 constexpr size_t lds_fwd_x3(int bn) { return lds_max(2 * (lds_x3_r(128) + lds_x3_c(bn)), (size_t)12 * bn * sizeof(float)); }
-constexpr size_t lds_fwd_x3_pc(int bn) { return lds_max(X3_RING * (lds_x3_r(128) + lds_x3_c(bn)), (size_t)12 * bn * sizeof(float)); }
 constexpr size_t lds_dgrad_x3(int bn) { return lds_max(2 * (lds_x3_r(128) + lds_x3_r(bn)), (size_t)12 * bn * sizeof(float)); }
 constexpr size_t lds_wgrad_x3(int bmk, int bn) { return 2 * (lds_x3_c(bmk) + lds_x3_c(bn)); }
 constexpr size_t lds_bwd1f(int k, int n) { return (size_t)(64 * ((n + 4) + 3 * (k + 4)) + 2 * 2 * 2 * k + 3 * n + 2 * k) * 4; }      // D, A, 2 x X images, statistics scratch, per-column constants
@@ -4808,7 +4058,7 @@ int t3d_x3_split(const float* src, void* planes, int64_t n, int64_t plane_stride
 int t3d_x3_dgrad(const t3d_pointmlp_dgrad_args* a, bool wide, hipStream_t s) {
   const int tiles_m = a->M / 128;
   if (a->w_x3 && (a->K % 32 != 0 || a->N % 16 != 0 || a->w_x3_stride < (int64_t)a->K * a->N)) return T3D_ERR_SHAPE;      // (fragment planes: whole blocks)
-  if (a->w_x3 && a->N <= 1536) {      // (dy's coefficient table in LDS: 3 N floats <= 18 KB)
+  if (a->w_x3 && a->N <= X3_CTAB_MAX_CH) {      // (dy's coefficient table in LDS: 3 N floats)
     if (wide) launch_lds(k_pointmlp_dgrad<128, false, PathX3P>, dim3(tiles_m * (a->K / 128)), lds_dgrad_x3(128), s, *a);
     else launch_lds(k_pointmlp_dgrad<64, false, PathX3P>, dim3(tiles_m * (a->K / 64)), lds_dgrad_x3(64), s, *a);
   } else if (wide) launch_lds(k_pointmlp_dgrad<128, false, PathX3>, dim3(tiles_m * (a->K / 128)), lds_dgrad_x3(128), s, *a);
@@ -4847,18 +4097,16 @@ int t3d_x3_dgrad_gram(const t3d_pointmlp_dgrad_gram_args* a, bool wide, hipStrea
 int t3d_x3_fwd(const t3d_pointmlp_fwd_args* a, const t3d_rider_set* r, hipStream_t s) {
   const int tiles_m = a->M / 128, nr = r ? r->n_wg : 0;
   // the weights arrive as three bf16 planes in fragment order (t3d_split_x3_frag, forward arrangement); the fragment kernels keep the
-  // input's scale / shift table in LDS (2 K floats <= 18 KB: K <= 1536 -- a wider layer takes the in-kernel split)
-  const bool pre = a->w_x3 != nullptr && a->K <= 1536;
+  // input's scale / shift table in LDS (2 K floats: K <= X3_CTAB_MAX_CH -- a wider layer takes the in-kernel split)
+  const bool pre = a->w_x3 != nullptr && a->K <= X3_CTAB_MAX_CH;
   if (pre && (a->N % 32 != 0 || a->K % 16 != 0 || a->w_x3_stride < (int64_t)a->K * a->N)) return T3D_ERR_SHAPE;
-  const char* e = getenv("T3D_X3_FWD128_MIN");      // (fewest 128-wide tiles for which the forward takes them; experiments)
-  const long min_tiles = e ? atol(e) : 512;
   // eight-wave 128 x 256 tiles where a launch has at least two rounds of them (one workgroup per CU: with a single round nothing
   // covers a workgroup's prologue and epilogue, and 512 -> 256 at M = 32768 measured 57.5 us against 56.7; with two or more, 256 -> 512
   // 52.3 against 56.6 and 128 -> 1024 57.3 against 60.5, profiles/r05_w8.log).  T3D_X3_W8=0: never; =2: whenever N % 256 == 0
-  const int w8 = []() { const char* e_ = getenv("T3D_X3_W8"); return e_ ? atoi(e_) : T3D_X3_W8_DEFAULT; }();
+  const int w8 = []() { const char* e_ = getenv("T3D_X3_W8"); return e_ ? atoi(e_) : 1; }();
   if (w8 && a->N % 256 == 0 && (w8 == 2 || (long)tiles_m * (a->N / 256) >= 512)) {
     const int n_tiles = tiles_m * (a->N / 256);
-    const dim3 grid((T3D_W8_PERSIST && n_tiles > T3D_FAIR_CUS ? T3D_FAIR_CUS : n_tiles) + nr);
+    const dim3 grid((n_tiles > T3D_FAIR_CUS ? T3D_FAIR_CUS : n_tiles) + nr);
     const size_t lds = lds_with(lds_fwd_x3(256), r);
     if (r && pre) {
       auto kern = k_pointmlp_fwd_w8_r<256, PathX3WP>;
@@ -4880,22 +4128,7 @@ int t3d_x3_fwd(const t3d_pointmlp_fwd_args* a, const t3d_rider_set* r, hipStream
     T3D_CHECK_LAUNCH();
     return T3D_OK;
   }
-  const int pc = []() { const char* e_ = getenv("T3D_X3_PC"); return e_ ? atoi(e_) : 0; }();      // producer / consumer kernels (experiment; read per launch like T3D_X3)
-  if (pc && !r && !pre) {
-    const bool wide = a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= (pc == 2 ? 1 : min_tiles);
-    if (wide) {
-      auto kern = k_pointmlp_fwd_pc<128, PathX3PC>;
-      allow_lds(reinterpret_cast<const void*>(kern), lds_fwd_x3_pc(128));
-      T3D_LAUNCH(kern, dim3(tiles_m * (a->N / 128)), dim3(2 * NT), lds_fwd_x3_pc(128), s, *a);
-    } else {
-      auto kern = k_pointmlp_fwd_pc<64, PathX3PC>;
-      allow_lds(reinterpret_cast<const void*>(kern), lds_fwd_x3_pc(64));
-      T3D_LAUNCH(kern, dim3(tiles_m * (a->N / 64)), dim3(2 * NT), lds_fwd_x3_pc(64), s, *a);
-    }
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
-  if (a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= min_tiles) {
+  if (a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512) {
     const dim3 grid(tiles_m * (a->N / 128) + nr);
     if (r && pre) launch_lds_r(k_pointmlp_fwd_r<128, false, PathX3P>, grid, lds_with(lds_fwd_x3(128), r), s, *a, *r);
     else if (r) launch_lds_r(k_pointmlp_fwd_r<128, false, PathX3>, grid, lds_with(lds_fwd_x3(128), r), s, *a, *r);
@@ -4926,10 +4159,10 @@ int t3d_x3_bwd(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* 
     } else {                                                                                       \
       auto kern = k_pointmlp_bwd<DBN, TK, TN_, PR_>;                                               \
       allow_lds(reinterpret_cast<const void*>(kern), lds);                                         \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w, 0);                                    \
+      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w);                                       \
     }                                                                                              \
   } while (0)
-#define T3D_BWDX(DBN, TK, TN_) do { if (d->w_x3 && d->N <= 1536) T3D_BWDX_P(DBN, TK, TN_, PathX3P); else T3D_BWDX_P(DBN, TK, TN_, PathX3); } while (0)
+#define T3D_BWDX(DBN, TK, TN_) do { if (d->w_x3 && d->N <= X3_CTAB_MAX_CH) T3D_BWDX_P(DBN, TK, TN_, PathX3P); else T3D_BWDX_P(DBN, TK, TN_, PathX3); } while (0)
 #define T3D_BWDX_W(DBN)                                  \
   do {                                                   \
     if (tk == 128 && tn == 128) T3D_BWDX(DBN, 128, 128); \
@@ -5026,7 +4259,7 @@ extern "C" int t3d_pointmlp_fwd_r(const t3d_pointmlp_fwd_args* a, const t3d_ride
   if (a->dtype == T3D_BF16) {
     T3D_RIDERS_FIRST(r, stream);
     // bf16 storage + bf16 MFMA (configs[4]); the input is fp32 for the raw point cloud / Box-PC representation, bf16 for a layer output
-    const bool wide = T3D_FORCE_TILE != 64 && a->N % 128 == 0 && (T3D_FORCE_TILE == 128 || (long)tiles_m * (a->N / 128) >= 512);
+    const bool wide = a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512;
     const bool xh = a->a.dtype == T3D_BF16;
     if (xh && a->K % BKH) return T3D_ERR_SHAPE;      // a bf16 input is a layer output: whole 64-deep k-tiles (the loaders do not mask)
     // first layer of a net (xyz [+ 1 channel], fp32 source): the register kernel (T3D_FWD_TINYK=0: the generic one)
@@ -5113,7 +4346,7 @@ extern "C" int t3d_pointmlp_fwd_r(const t3d_pointmlp_fwd_args* a, const t3d_ride
     return T3D_OK;
   }
   T3D_HOSTED(r, stream);
-  if (T3D_FORCE_TILE != 64 && a->N % 128 == 0 && (T3D_FORCE_TILE == 128 || (long)tiles_m * (a->N / 128) >= 512)) {
+  if (a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512) {
     const dim3 grid(tiles_m * (a->N / 128) + (r ? r->n_wg : 0));
     if (r) {
       if (sub) launch_lds_r(k_pointmlp_fwd_r<128, true>, grid, lds_with(lds_fwd(128), r), s, *a, *r);
@@ -5144,10 +4377,7 @@ static int check_dgrad(const t3d_pointmlp_dgrad_args* a) {
   return T3D_OK;
 }
 static bool dgrad_wide(const t3d_pointmlp_dgrad_args* a) {
-  // (T3D_DGRAD_WIDE_MIN: fewest 128-wide tiles for which the data gradient takes them; experiments)
-  const char* e = getenv("T3D_DGRAD_WIDE_MIN");
-  const long min_tiles = e ? atol(e) : 512;
-  return T3D_FORCE_TILE != 64 && a->K % 128 == 0 && (T3D_FORCE_TILE == 128 || (long)(a->M / 128) * (a->K / 128) >= min_tiles);
+  return a->K % 128 == 0 && (long)(a->M / 128) * (a->K / 128) >= 512;
 }
 
 extern "C" int t3d_pointmlp_dgrad(const t3d_pointmlp_dgrad_args* a, t3d_stream_t stream) {
@@ -5536,17 +4766,14 @@ extern "C" int t3d_pointmlp_bwd_r(const t3d_pointmlp_dgrad_args* d, const t3d_po
   T3D_HOSTED(r, stream);      // (bf16 has left above: both fp32 forms below host the set)
   if (!bf16 && d->N % BKX == 0 && w->K % 64 == 0 && w->K % tk == 0 && w->a.dtype == T3D_F32 && x3_layer_bwd(d->arith, d->K, d->N)) return t3d_x3_bwd(d, w, r, tk, tn, wide, n_w, n_d, s);
   const dim3 grid(n_w + n_d + (r ? r->n_wg : 0));
-  // interleaving the two kinds of tile by row range (so that both readers of a dy row range share an L2) measured SLOWER
-  // than weight-gradient tiles first (1.683 vs 1.630 ms per step): the long wgrad tiles are better started early.
-  static const bool il = []() { const char* e = getenv("T3D_BWD_INTERLEAVE"); return e && e[0] == '1'; }();
-  const int interleave = (il && w->rows_per_split % 128 == 0) ? 1 : 0;
+  // weight-gradient tiles first: the long wgrad tiles are better started early
 #define T3D_BWD(DBN, TK, TN_)                                                                                      \
   do {                                                                                                              \
     if (bf16) {                                                                                                     \
       const size_t lds = lds_dgrad_h(DBN) > lds_wgrad_h(TK, TN_) ? lds_dgrad_h(DBN) : lds_wgrad_h(TK, TN_);         \
       auto kern = k_pointmlp_bwd<DBN, TK, TN_, PathBF16>;                                                           \
       allow_lds(reinterpret_cast<const void*>(kern), lds);                                                          \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w, interleave);                                            \
+      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w);                                                        \
     } else if (r) {                                                                                                 \
       const size_t lds = lds_with(lds_dgrad(DBN) > lds_wgrad(TK, TN_) ? lds_dgrad(DBN) : lds_wgrad(TK, TN_), r);    \
       auto kern = k_pointmlp_bwd_r<DBN, TK, TN_>;                                                                   \
@@ -5556,7 +4783,7 @@ extern "C" int t3d_pointmlp_bwd_r(const t3d_pointmlp_dgrad_args* d, const t3d_po
       const size_t lds = lds_dgrad(DBN) > lds_wgrad(TK, TN_) ? lds_dgrad(DBN) : lds_wgrad(TK, TN_);                 \
       auto kern = k_pointmlp_bwd<DBN, TK, TN_>;                                                                     \
       allow_lds(reinterpret_cast<const void*>(kern), lds);                                                          \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w, interleave);                                            \
+      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w);                                                        \
     }                                                                                                               \
   } while (0)
 #define T3D_BWD_W(DBN)                              \
