@@ -1129,6 +1129,52 @@ int t3d_pointmlp_bwd_hosts_riders(const t3d_pointmlp_dgrad_args* dgrad, const t3
 int t3d_pool_bwd_stage1_hosts_riders(const t3d_pointmlp_gram_args* gram, const t3d_act_colsum_args* colsum, const t3d_pool_bwd_prep_args* prep);
 int t3d_pool_bwd_stage2_hosts_riders(const t3d_pool_wgrad_finish_args* finish, const t3d_pointmlp_dgrad_gram_args* dgrad);
 
+/* ---- Frustum extraction from SUN-RGBD scenes (csrc/frustum.hip; sunrgbd_data.py extract_roi_seg / _from_rgb_detection) ----
+ * A batch of scenes: their depth clouds concatenated (upright depth xyz + C_src-3 more channels, fp64), and a list of jobs, one per
+ * (scene, 2-D box, augmentation index), the jobs of scene s at scene_jobs[s] .. scene_jobs[s+1]-1.  Per job:
+ *   box2d_out      the 2-D box used: box2d, or random_shift_box2d of it (utils.py:198-211) when perturb_box2d, on the 4 uniforms of
+ *                  perturb_draws[j] or, when that is NULL, of the hash of job_key[j];
+ *   frustum_angle  -arctan2(z, x) of the box centre back-projected to depth 20 in upright camera coordinates;
+ *   n_in_box       n, the number of points whose image uv lies in the box (xmin <= u < xmax, ymin <= v < ymax), fp64 projection;
+ *   count          min(n, num_points);
+ *   index          [num_points] the scene-local indices of the kept points (-1 beyond count): all n in the cloud's order when
+ *                  n <= num_points; otherwise the frustum points of ranks choice[j][0..num_points) (ranks in [0, n), the reference's
+ *                  np.random.choice) when choice != NULL and choice[j][0] >= 0, else the num_points ranks of smallest hash key
+ *                  mix(seed, job_key[j], rank), in rank order;
+ *   out_points     [num_points, C] the kept points in upright camera coordinates (x, -z, y, channels 3 .. C-1);
+ *   label          [num_points] 1 where the point lies inside or on the 3-D box of corners box3d[j] (8x3, upright camera, corner order of
+ *                  utils.compute_box_3d), else 0; box3d == NULL (detections): label may be NULL.
+ * masks / seg_prefix are scratch of mask_offsets[n_jobs] entries: job j owns ceil(points of its scene / 64) of them from mask_offsets[j].
+ * Nothing is synchronised with the host.  num_points <= 4096. */
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_frustum_extract_args) of the caller's header (see T3D_ABI_VERSION) */
+  const double* points;           /* [P, C_src] */
+  const int64_t* scene_offsets;   /* [n_scenes + 1] */
+  const double* rtilt;            /* [n_scenes, 9] row-major */
+  const double* K;                /* [n_scenes, 9] row-major */
+  const int32_t* scene_jobs;      /* [n_scenes + 1] */
+  int n_scenes; int max_scene_points; int C_src; int C; int n_jobs; int num_points;
+  const double* box2d;            /* [J,4] xmin ymin xmax ymax */
+  int perturb_box2d;
+  const double* perturb_draws;    /* [J,4] uniforms or NULL (hash) */
+  const double* box3d;            /* [J,8,3] or NULL */
+  const int32_t* job_key;         /* [J,3] scene id, job ordinal within the scene, augmentation index */
+  uint32_t seed;
+  const int32_t* choice;          /* [J, num_points] or NULL */
+  const int64_t* mask_offsets;    /* [J + 1] */
+  uint64_t* masks;                /* scratch */
+  int32_t* seg_prefix;            /* scratch */
+  double* box2d_out;              /* [J,4] */
+  double* frustum_angle;          /* [J] */
+  int32_t* n_in_box;              /* [J] */
+  int32_t* count;                 /* [J] */
+  int32_t* index;                 /* [J, num_points] */
+  double* out_points;             /* [J, num_points, C] */
+  int32_t* label;                 /* [J, num_points] or NULL */
+} t3d_frustum_extract_args;
+#define T3D_V2_SIZE_frustum_extract_args 208
+int t3d_frustum_extract(const t3d_frustum_extract_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+"""TEST INFRASTRUCTURE ONLY -- NumPy executable specification of t3d_frustum_extract (include/t3d.h, csrc/frustum.hip), on host
+pointers, so that the host module transferable3d_amd/sunrgbd_data.py runs end to end through Runtime(device='cpu', lib=FakeFrustumLib())."""
+import math
+
+import numpy as np
+
+from fake_t3d import AbiSizeError, FakeLib, _struct, arr
+from transferable3d_amd import abi
+
+M64 = (1 << 64) - 1
+
+
+def mix(x):
+    """data.hip mix_u32 on a uint64 array."""
+    x = np.asarray(x, np.uint64)
+    with np.errstate(over='ignore'):
+        x = x ^ (x >> np.uint64(33)); x = x * np.uint64(0xff51afd7ed558ccd)
+        x = x ^ (x >> np.uint64(33)); x = x * np.uint64(0xc4ceb9fe1a85ec53)
+        x = x ^ (x >> np.uint64(33))
+    return (x >> np.uint64(16)).astype(np.uint32)
+
+
+def job_base(seed, key):
+    s, o, g = [int(v) & 0xFFFFFFFF for v in (key[0], key[1] + 1, key[2] + 1)]
+    return (((seed & 0xFFFFFFFF) << 32) ^ ((s * 0x9E3779B97F4A7C15) & M64) ^ ((o * 0xA24BAED4963EE407) & M64) ^ ((g * 0xC2B2AE3D27D4EB4F) & M64)) & M64
+
+
+def rank_keys(base, n):
+    with np.errstate(over='ignore'):
+        return mix(np.uint64(base) + (np.arange(n, dtype=np.uint64) + np.uint64(1)) * np.uint64(0xD6E8FEB86659FD93))
+
+
+def uniforms(base):
+    with np.errstate(over='ignore'):
+        x = np.uint64(base ^ 0x632BE59BD9B4E019) + (np.arange(4, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x165667B19E3779F9)
+    return (mix(x).astype(np.float64) + 0.5) * (1.0 / 4294967296.0)
+
+
+def generated_ranks(base, n, k):
+    """The k ranks of smallest (hash key, rank) among [0, n), in rank order."""
+    keys = rank_keys(base, n)
+    order = np.lexsort((np.arange(n), keys))
+    return np.sort(order[:k])
+
+
+class FakeFrustumLib(FakeLib):
+    def t3d_frustum_extract(self, a, stream):
+        try:
+            p = _struct(a)
+        except AbiSizeError:
+            return abi.ERR_ABI
+        if p.n_scenes <= 0 or p.num_points <= 0 or p.num_points > 4096 or p.C < 3 or p.C_src < p.C:
+            return -2
+        S, J, NP, Cs, Cc = p.n_scenes, p.n_jobs, p.num_points, p.C_src, p.C
+        if J == 0:
+            return 0
+        so = arr(p.scene_offsets, S + 1)
+        pts = arr(p.points, int(so[-1]), Cs)
+        R, K = arr(p.rtilt, S, 3, 3), arr(p.K, S, 3, 3)
+        sj = arr(p.scene_jobs, S + 1)
+        box2d, key = arr(p.box2d, J, 4), arr(p.job_key, J, 3)
+        draws = arr(p.perturb_draws, J, 4)
+        box3d = arr(p.box3d, J, 8, 3)
+        choice = arr(p.choice, J, NP)
+        out_box, out_ang = arr(p.box2d_out, J, 4), arr(p.frustum_angle, J)
+        n_in, cnt = arr(p.n_in_box, J), arr(p.count, J)
+        index, out_pts = arr(p.index, J, NP), arr(p.out_points, J, NP, Cc)
+        label = arr(p.label, J, NP)
+        for s in range(S):
+            P = pts[so[s]:so[s + 1]]
+            d = np.stack([R[s][0, i] * P[:, 0] + R[s][1, i] * P[:, 1] + R[s][2, i] * P[:, 2] for i in range(3)], 1)
+            c = np.stack([d[:, 0], -d[:, 2], d[:, 1]], 1)
+            w = [c[:, 0] * K[s][i, 0] + c[:, 1] * K[s][i, 1] + c[:, 2] * K[s][i, 2] for i in range(3)]
+            with np.errstate(divide='ignore', invalid='ignore'):
+                u, v = w[0] / w[2], w[1] / w[2]
+            cam = np.concatenate([np.stack([P[:, 0], -P[:, 2], P[:, 1]], 1), P[:, 3:Cc]], 1)
+            for j in range(sj[s], sj[s + 1]):
+                xmin, ymin, xmax, ymax = box2d[j]
+                base = job_base(p.seed, key[j])
+                if p.perturb_box2d:
+                    uu = draws[j] if draws is not None else uniforms(base)
+                    r = 0.1
+                    h, ww = ymax - ymin, xmax - xmin
+                    cx, cy = (xmin + xmax) / 2.0, (ymin + ymax) / 2.0
+                    cx2 = cx + ww * r * (uu[0] * 2 - 1)
+                    cy2 = cy + h * r * (uu[1] * 2 - 1)
+                    h2 = h * (1 + uu[2] * 2 * r - r)
+                    w2 = ww * (1 + uu[3] * 2 * r - r)
+                    xmin, ymin, xmax, ymax = cx2 - w2 / 2.0, cy2 - h2 / 2.0, cx2 + w2 / 2.0, cy2 + h2 / 2.0
+                out_box[j] = (xmin, ymin, xmax, ymax)
+                uc, vc = (xmin + xmax) / 2.0, (ymin + ymax) / 2.0
+                x, y = ((uc - K[s][0, 2]) * 20.0) / K[s][0, 0], ((vc - K[s][1, 2]) * 20.0) / K[s][1, 1]
+                X = R[s][0, 0] * x + R[s][0, 1] * 20.0 + R[s][0, 2] * -y
+                Y = R[s][1, 0] * x + R[s][1, 1] * 20.0 + R[s][1, 2] * -y
+                out_ang[j] = -math.atan2(Y, X)
+                members = np.nonzero((u < xmax) & (u >= xmin) & (v < ymax) & (v >= ymin))[0]
+                n = len(members)
+                if n <= NP:
+                    ranks = np.arange(n)
+                elif choice is not None and choice[j, 0] >= 0:
+                    ranks = choice[j].astype(np.int64)
+                else:
+                    ranks = generated_ranks(base, n, NP)
+                k = min(n, NP)
+                ok = (ranks >= 0) & (ranks < n)
+                idx = np.where(ok, members[np.clip(ranks, 0, max(n - 1, 0))] if n else -1, -1)
+                index[j] = -1
+                index[j, :k] = idx
+                out_pts[j] = 0.0
+                out_pts[j, :k][ok] = cam[idx[ok]]
+                if label is not None:
+                    label[j] = 0
+                    if box3d is not None:
+                        b = box3d[j]
+                        q = cam[idx[ok], 0:3] - b[1]
+                        inside = np.ones(len(q), bool)
+                        for far in (2, 5, 0):
+                            e = b[far] - b[1]
+                            dv = q[:, 0] * e[0] + q[:, 1] * e[1] + q[:, 2] * e[2]
+                            inside &= (dv >= 0.0) & (dv <= e[0] * e[0] + e[1] * e[1] + e[2] * e[2])
+                        lab = np.zeros(k, np.int32)
+                        lab[ok] = inside
+                        label[j, :k] = lab
+                n_in[j], cnt[j] = n, k
+        return 0

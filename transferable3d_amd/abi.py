@@ -8,6 +8,8 @@ import os
 
 F = C.POINTER(C.c_float)
 I = C.POINTER(C.c_int32)
+D = C.POINTER(C.c_double)
+L = C.POINTER(C.c_int64)
 i32, f32 = C.c_int, C.c_float
 
 TILE_ROWS = 128
@@ -294,6 +296,14 @@ class AnchorRegBwdArgs(C.Structure):
     _fields_ = [('box', F), ('ld_box', i32), ('dbox7', F), ('d_dims', F), ('dbox', F), ('dstage1', F), ('B', i32)]
 
 
+class FrustumExtractArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('points', D), ('scene_offsets', L), ('rtilt', D), ('K', D), ('scene_jobs', I),
+                ('n_scenes', i32), ('max_scene_points', i32), ('C_src', i32), ('C', i32), ('n_jobs', i32), ('num_points', i32),
+                ('box2d', D), ('perturb_box2d', i32), ('perturb_draws', D), ('box3d', D), ('job_key', I), ('seed', C.c_uint32),
+                ('choice', I), ('mask_offsets', L), ('masks', C.POINTER(C.c_uint64)), ('seg_prefix', I), ('box2d_out', D),
+                ('frustum_angle', D), ('n_in_box', I), ('count', I), ('index', I), ('out_points', D), ('label', I)]
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -387,6 +397,7 @@ ENTRY_POINTS = {
     't3d_split_x3_frag': [F, VP, VP, C.c_int64, VP, i32, i32, VP],
     't3d_dropout_mask': [F, C.c_int64, f32, C.c_uint32, F, VP],
     't3d_cast_bf16': [F, VP, C.c_int64, VP],
+    't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libt3d.so')
