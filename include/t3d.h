@@ -1175,6 +1175,70 @@ typedef struct {
 #define T3D_V2_SIZE_frustum_extract_args 208
 int t3d_frustum_extract(const t3d_frustum_extract_args* args, t3d_stream_t stream);
 
+/* ---- Official SUN-RGBD detection evaluation of one class (csrc/sunrgbd_eval.hip; evaluate_sunrgbd.py compute_pr_curve_3d) ----
+ * The MATLAB protocol of evaluation/sunrgbd/detection/script_3Deval.m for one class, fp64 throughout:
+ *   computePRCurve3D.m:20        stable descending order of the confidences (NaN first, ties in file order) -> order;
+ *   bb3dOverlapCloseForm.m:17-58 with get_corners_of_bb3d.m:14-44, cuboidVolume.m:3-5, cuboidIntersectionVolume.c:62-88: the overlap
+ *                                (intersection over union of two upright prisms on convex quadrilateral footprints) of every detection
+ *                                with the ground truth OF ITS OWN IMAGE -- computePRCurve3D.m:30-31 zeroes every other entry;
+ *   computePRCurve3D.m:32-36     max_overlap and gt_idx (1-based, first index on ties; 0 where the maximum < eps = 2^-52: `gtIdxAll`);
+ *   computePRCurve3D.m:39-75     a box goes to the first detection in sorted order that chose it with an overlap >= threshold: is_tp;
+ *                                is_fp = not tp; a "difficult" box takes its detection out of both; gt_assignment (the claimed box, 1-based,
+ *                                for the first claimer only); is_missed (a box nobody claimed);
+ *   computePRCurve3D.m:78-81     recall = cumsum(tp) / sum(~difficult), precision = cumsum(tp) / (cumsum(fp) + cumsum(tp)), in sorted
+ *                                order, from integer counts.  0 / 0 (a leading "difficult" match) is NaN, as in MATLAB;
+ *   get_average_precision.m:15-23 ap.
+ * A box is {centroid, basis (3 rows), coeffs (half sizes)}; get_corners_of_bb3d orders the rows, turns them towards the viewer and takes
+ * abs(coeffs), so row order, row signs and coeff signs do not matter.  A box of zero volume overlaps nothing: 0 / union as
+ * in the script, and, as a deliberate difference from it, 0 also for two such boxes (MATLAB: 0 / 0 = NaN).
+ * The ground truth comes grouped by image: image_ids (ascending, distinct), image_gt_offsets, and image_gt, the box indices of image
+ * k at image_gt_offsets[k] .. image_gt_offsets[k+1]-1 in ascending order (the tie rule needs it).
+ * P == 0 or G == 0 are valid (bb3dOverlapCloseForm returns []): every detection is a false positive, every box missed, recall 0 when
+ * G == 0, ap 0.  overlaps != NULL: detection i writes the overlaps with its image's boxes, in image_gt order, from overlap_offsets[i]
+ * (at most overlap_offsets[i+1] - overlap_offsets[i] of them), and the box indices to overlap_gt.
+ * P, G <= T3D_SUNRGBD_EVAL_MAX_BOXES (T3D_ERR_SHAPE beyond): the order is found by counting, P^2 comparisons in one launch, which is meant
+ * for the tens of thousands of detections a class has, not for millions.
+ * workspace: T3D_SUNRGBD_EVAL_WORKSPACE_BYTES(P, G) bytes, 8-byte aligned.  Nothing is allocated or synchronised with the host; the only
+ * atomics are integer minima, so equal inputs give equal bytes. */
+#define T3D_SUNRGBD_EVAL_MAX_BOXES (1 << 20)
+#define T3D_SUNRGBD_EVAL_WORKSPACE_BYTES(P, G) (((uint64_t)(P) + (uint64_t)(G)) * 92u + 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_sunrgbd_eval_args) of the caller's header (see T3D_ABI_VERSION) */
+  int P; int G;
+  const double* det_centroid;      /* [P,3] detections in file order */
+  const double* det_basis;         /* [P,9] three rows */
+  const double* det_coeffs;        /* [P,3] */
+  const double* det_confidence;    /* [P] */
+  const int32_t* det_image;        /* [P] */
+  const double* gt_centroid;       /* [G,3] */
+  const double* gt_basis;          /* [G,9] */
+  const double* gt_coeffs;         /* [G,3] */
+  const int32_t* gt_image;         /* [G] */
+  const uint8_t* gt_difficult;     /* [G] or NULL: none */
+  int n_images;
+  const int32_t* image_ids;        /* [n_images] */
+  const int32_t* image_gt_offsets; /* [n_images + 1] */
+  const int32_t* image_gt;         /* [G] */
+  double threshold;                /* 0.25 in the script */
+  void* workspace;
+  uint64_t workspace_bytes;
+  int32_t* order;                  /* [P] out: sorted position -> file index */
+  double* max_overlap;             /* [P] out, file order */
+  int32_t* gt_idx;                 /* [P] out, file order */
+  uint8_t* is_tp;                  /* [P] out, file order */
+  uint8_t* is_fp;                  /* [P] out, file order */
+  int32_t* gt_assignment;          /* [P] out, file order */
+  uint8_t* is_missed;              /* [G] out */
+  double* precision;               /* [P] out, sorted order */
+  double* recall;                  /* [P] out, sorted order */
+  double* ap;                      /* [1] out */
+  const int64_t* overlap_offsets;  /* [P + 1], read when overlaps != NULL */
+  double* overlaps;                /* out or NULL */
+  int32_t* overlap_gt;             /* out, with overlaps */
+} t3d_sunrgbd_eval_args;
+#define T3D_V2_SIZE_sunrgbd_eval_args 256
+int t3d_sunrgbd_eval(const t3d_sunrgbd_eval_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -304,6 +304,23 @@ class FrustumExtractArgs(Sized):
                 ('frustum_angle', D), ('n_in_box', I), ('count', I), ('index', I), ('out_points', D), ('label', I)]
 
 
+U8 = C.POINTER(C.c_uint8)
+
+
+class SunrgbdEvalArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('P', i32), ('G', i32), ('det_centroid', D), ('det_basis', D), ('det_coeffs', D),
+                ('det_confidence', D), ('det_image', I), ('gt_centroid', D), ('gt_basis', D), ('gt_coeffs', D), ('gt_image', I),
+                ('gt_difficult', U8), ('n_images', i32), ('image_ids', I), ('image_gt_offsets', I), ('image_gt', I),
+                ('threshold', C.c_double), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('order', I), ('max_overlap', D),
+                ('gt_idx', I), ('is_tp', U8), ('is_fp', U8), ('gt_assignment', I), ('is_missed', U8), ('precision', D), ('recall', D),
+                ('ap', D), ('overlap_offsets', L), ('overlaps', D), ('overlap_gt', I)]
+
+
+def sunrgbd_eval_workspace_bytes(P, G):
+    """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
+    return (P + G) * 92 + 8
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -398,6 +415,7 @@ ENTRY_POINTS = {
     't3d_dropout_mask': [F, C.c_int64, f32, C.c_uint32, F, VP],
     't3d_cast_bf16': [F, VP, C.c_int64, VP],
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
+    't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libt3d.so')

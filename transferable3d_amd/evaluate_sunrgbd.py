@@ -1,0 +1,360 @@
+#!/usr/bin/env python3
+"""The official SUN-RGBD 3-D detection AP on the device: evaluation/sunrgbd/detection/script_3Deval.m of the reference without MATLAB.
+
+    python -m transferable3d_amd.evaluate_sunrgbd --pred_dir D --dataset_dir mysunrgbd --idx_path val_data_idx.txt --test_on B
+    python -m transferable3d_amd.evaluate_sunrgbd --official_eval --dataset_dir mysunrgbd --idx_path val_data_idx.txt --test_on AB \
+        --semi_type F --model_path M --data_path frustums/val.zip.pickle ...          # every other flag is test_semisup's
+
+The second form runs test_semisup's inference on a frustum file and scores the predictions it holds in memory (no text round trip).
+
+`--pred_dir` holds the `<class>_pred.txt` files test_semisup --result_dir (or the reference) writes.  Per class the script's chain
+parse_class_predictions -> benchmark_groundtruth -> computePRCurve3D (bb3dOverlapCloseForm, get_average_precision) runs as ONE
+t3d_sunrgbd_eval call (csrc/sunrgbd_eval.hip): footprints, the stable order of the confidences, overlaps with the ground truth of the
+same image, assignment, precision / recall and AP, all fp64 on the device, one copy back.  The lines printed are the script's.
+
+Ground truth: the toolbox's Metadata/groundtruth.mat is replaced by the label files of the data set directory sunrgbd_data.py reads
+(<dataset_dir>/training/label_dimension/%06d.txt): centroid as stored, coeffs (l, w, h) (the file stores half sizes), basis rows
+(o1, o2, 0)/|o|, (-o2, o1, 0)/|o|, (0, 0, 1) -- the rectangle sunrgbd_data.compute_box_3d builds.  imageNum is the file's number.
+
+Two deliberate differences from the script: an empty prediction file counts as zero predictions (importdata stops the script there),
+and two boxes that both have zero volume overlap by 0 (MATLAB: 0 / 0).
+"""
+import argparse
+import ctypes as C
+import math
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import abi
+from . import sunrgbd_data as SD
+
+# script_3Deval.m:20-22
+CLASS_NAMES = {'A': ['bed', 'chair', 'toilet', 'desk', 'bathtub'],
+               'B': ['table', 'sofa', 'dresser', 'night_stand', 'bookshelf'],
+               'AB': ['bed', 'table', 'sofa', 'chair', 'toilet', 'desk', 'dresser', 'night_stand', 'bookshelf', 'bathtub']}
+EPS = 2.0 ** -52
+
+
+def boxes_from_label_format(img_ids, h, w, l, tx, ty, tz, ry, score):
+    """parse_class_predictions.m:24-44 on arrays: coeffs (l, w, h) / 2, centroid (tx, tz, h/2 - ty), basis rotz(deg(-ry))',
+    confidence = score."""
+    h, w, l, tx, ty, tz, ry, score = [np.asarray(v, np.float64).reshape(-1) for v in (h, w, l, tx, ty, tz, ry, score)]
+    n = len(h)
+    c, s = np.cos(ry), np.sin(ry)
+    basis = np.zeros((n, 3, 3))
+    basis[:, 0, 0], basis[:, 0, 1] = c, -s
+    basis[:, 1, 0], basis[:, 1, 1] = s, c
+    basis[:, 2, 2] = 1.0
+    return {'centroid': np.stack([tx, tz, h / 2.0 - ty], 1).reshape(n, 3), 'basis': basis,
+            'coeffs': np.stack([l / 2.0, w / 2.0, h / 2.0], 1).reshape(n, 3), 'confidence': score,
+            'image': np.asarray(img_ids, np.int64).reshape(-1).astype(np.int32)}
+
+
+def parse_class_predictions(path, classname=None):
+    """parse_class_predictions.m: every line `img_id cls -1 -1 -10 box2d(4) h w l tx ty tz ry score` of the file (the class column is
+    not looked at, as in the script) -> {'centroid' [P,3], 'basis' [P,3,3], 'coeffs' [P,3], 'confidence' [P], 'image' [P]}.  The
+    decimal strings are converted with correct rounding."""
+    if not os.path.exists(path):
+        raise FileNotFoundError('no prediction file for class %s: %s' % (classname or os.path.basename(path).replace('_pred.txt', ''), path))
+    ids, rows = [], []
+    with open(path) as fh:
+        for line in fh:
+            t = line.split()
+            if not t:
+                continue
+            if len(t) != 17:
+                raise ValueError('%s: a prediction line has 17 fields, got %d: %r' % (path, len(t), line))
+            ids.append(int(t[0]))
+            rows.append([float(v) for v in t[2:]])
+    d = np.asarray(rows, np.float64).reshape(-1, 15)
+    return boxes_from_label_format(ids, d[:, 7], d[:, 8], d[:, 9], d[:, 10], d[:, 11], d[:, 12], d[:, 13], d[:, 14])
+
+
+def boxes_from_label_objects(objects, image_ids):
+    """Ground-truth boxes from SUNObject3d label lines (see the module text)."""
+    n = len(objects)
+    basis = np.zeros((n, 3, 3))
+    for i, o in enumerate(objects):
+        o1, o2 = o.orientation[0], o.orientation[1]
+        nrm = math.sqrt(o1 * o1 + o2 * o2)
+        basis[i] = [[o1 / nrm, o2 / nrm, 0.0], [-o2 / nrm, o1 / nrm, 0.0], [0.0, 0.0, 1.0]]
+    return {'centroid': np.array([o.centroid for o in objects], np.float64).reshape(n, 3), 'basis': basis,
+            'coeffs': np.array([[o.l, o.w, o.h] for o in objects], np.float64).reshape(n, 3),
+            'image': np.asarray(image_ids, np.int64).reshape(-1).astype(np.int32), 'classname': [o.classname for o in objects]}
+
+
+def select_boxes(boxes, keep):
+    keep = np.asarray(keep)
+    out = {k: np.asarray(v)[keep] for k, v in boxes.items() if k != 'classname'}
+    if 'classname' in boxes:
+        idx = np.nonzero(keep)[0] if keep.dtype == bool else keep
+        out['classname'] = [boxes['classname'][int(i)] for i in idx]
+    return out
+
+
+def benchmark_groundtruth(dataset_dir, idx_list, classname=None, workers=SD.MAX_WORKERS):
+    """benchmark_groundtruth.m on the label files: the ground truth (of one class, or of all) of the test images `idx_list` (ids, or the
+    path of an index file), in image order then line order; the files are read once by a pool of at most sunrgbd_data.MAX_WORKERS
+    threads."""
+    if isinstance(idx_list, str):
+        idx_list = [int(line.rstrip()) for line in open(idx_list) if line.strip()]
+    dataset = SD.sunrgbd_object(dataset_dir)
+    with ThreadPoolExecutor(max_workers=max(1, min(int(workers), SD.MAX_WORKERS))) as pool:
+        per_image = list(pool.map(dataset.get_label_objects, idx_list))
+    objects = [o for objs in per_image for o in objs]
+    ids = [i for i, objs in zip(idx_list, per_image) for _ in objs]
+    gt = boxes_from_label_objects(objects, ids)
+    if classname is not None:
+        gt = select_boxes(gt, np.array([c == classname for c in gt['classname']], bool))
+    return gt
+
+
+def get_average_precision(precision, recall):
+    """get_average_precision.m:15-23 (VOC2011): sentinels, running maximum of the precision from the right, area over the recall steps.
+    MATLAB's max(a, b) ignores a NaN, as np.fmax does."""
+    mrec = np.concatenate([[0.0], np.asarray(recall, np.float64).reshape(-1), [1.0]])
+    mpre = np.concatenate([[0.0], np.asarray(precision, np.float64).reshape(-1), [0.0]])
+    for ii in range(len(mpre) - 2, -1, -1):
+        mpre[ii] = np.fmax(mpre[ii], mpre[ii + 1])
+    ii = np.nonzero(mrec[1:] != mrec[:-1])[0] + 1
+    return float(np.sum((mrec[ii] - mrec[ii - 1]) * mpre[ii]))
+
+
+def _runtime(rt):
+    if rt is not None:
+        return rt
+    from .engine import Runtime
+    return Runtime()
+
+
+class _Packed:
+    """Arrays laid out in one byte buffer (8-byte aligned fields): one copy to the device, or one copy back."""
+
+    def __init__(self):
+        self.fields, self.size = {}, 0
+
+    def add(self, name, dtype, n):
+        self.fields[name] = (self.size, np.dtype(dtype), int(n))
+        self.size += (int(n) * np.dtype(dtype).itemsize + 7) // 8 * 8
+
+    def view(self, host, name):
+        off, dt, n = self.fields[name]
+        return host[off:off + n * dt.itemsize].view(dt)
+
+
+def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False):
+    """One t3d_sunrgbd_eval call on one class -> host arrays of every output."""
+    rt = _runtime(rt)
+    P, G = len(det['confidence']), len(gt['image'])
+    gimg = np.asarray(gt['image'], np.int32)
+    image_gt = np.argsort(gimg, kind='stable').astype(np.int32)             # grouped by image, ascending index inside an image
+    image_ids, first = np.unique(gimg[image_gt], return_index=True)
+    offsets = np.concatenate([first, [G]]).astype(np.int32)
+    n_img = len(image_ids)
+    dimg = np.asarray(det['image'], np.int32)
+    inp = _Packed()
+    host_in = {'det_centroid': (np.float64, det['centroid']), 'det_basis': (np.float64, det['basis']), 'det_coeffs': (np.float64, det['coeffs']),
+               'det_confidence': (np.float64, det['confidence']), 'gt_centroid': (np.float64, gt['centroid']), 'gt_basis': (np.float64, gt['basis']),
+               'gt_coeffs': (np.float64, gt['coeffs']), 'det_image': (np.int32, dimg), 'gt_image': (np.int32, gimg),
+               'image_ids': (np.int32, image_ids), 'image_gt_offsets': (np.int32, offsets), 'image_gt': (np.int32, image_gt)}
+    if difficult is not None:
+        difficult = np.asarray(difficult).reshape(-1)
+        if len(difficult) != G:
+            raise ValueError('inconsistent difficulty size.')               # computePRCurve3D.m:3
+        host_in['gt_difficult'] = (np.uint8, (difficult != 0))
+    if want_overlaps:
+        k = np.searchsorted(image_ids, dimg)
+        hit = (k < n_img) & (image_ids[np.minimum(k, max(n_img - 1, 0))] == dimg) if n_img else np.zeros(P, bool)
+        cnt = np.where(hit, (offsets[1:] - offsets[:-1])[np.minimum(k, max(n_img - 1, 0))], 0) if n_img else np.zeros(P, np.int64)
+        ov_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        host_in['overlap_offsets'] = (np.int64, ov_off)
+    for name, (dt, a) in host_in.items():
+        inp.add(name, dt, np.asarray(a).size)
+    buf = np.zeros(max(inp.size, 8), np.uint8)
+    for name, (dt, a) in host_in.items():
+        inp.view(buf, name)[:] = np.ascontiguousarray(a, dt).reshape(-1)
+    out = _Packed()
+    for name, dt, n in (('max_overlap', np.float64, P), ('precision', np.float64, P), ('recall', np.float64, P), ('ap', np.float64, 1),
+                        ('order', np.int32, P), ('gt_idx', np.int32, P), ('gt_assignment', np.int32, P), ('is_tp', np.uint8, P),
+                        ('is_fp', np.uint8, P), ('is_missed', np.uint8, G)):
+        out.add(name, dt, n)
+    if want_overlaps:
+        n_ov = int(ov_off[-1])
+        out.add('overlaps', np.float64, n_ov)
+        out.add('overlap_gt', np.int32, n_ov)
+    dev = rt.device
+    d_in = torch.from_numpy(buf).to(dev)
+    # zeros, not empty: with P == 0 or G == 0 the entry point leaves the arrays of that length-0 side alone, and the padding between
+    # the packed fields travels back to the host
+    d_out = torch.zeros(max(out.size, 8), dtype=torch.uint8, device=dev)
+    ws_bytes = abi.sunrgbd_eval_workspace_bytes(P, G)
+    d_ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)      # every field is written before it is read
+
+    def ptr(base, pk, name, T):
+        if name not in pk.fields or pk.fields[name][2] == 0:
+            return C.cast(C.c_void_p(0), C.POINTER(T))
+        return C.cast(C.c_void_p(base.data_ptr() + pk.fields[name][0]), C.POINTER(T))
+    i_, o_ = (lambda n, T: ptr(d_in, inp, n, T)), (lambda n, T: ptr(d_out, out, n, T))
+    dbl, i32, u8 = C.c_double, C.c_int32, C.c_uint8
+    a = abi.SunrgbdEvalArgs(P, G, i_('det_centroid', dbl), i_('det_basis', dbl), i_('det_coeffs', dbl), i_('det_confidence', dbl),
+                            i_('det_image', i32), i_('gt_centroid', dbl), i_('gt_basis', dbl), i_('gt_coeffs', dbl), i_('gt_image', i32),
+                            i_('gt_difficult', u8), n_img, i_('image_ids', i32), i_('image_gt_offsets', i32), i_('image_gt', i32),
+                            float(threshold), C.c_void_p(d_ws.data_ptr()), ws_bytes, o_('order', i32), o_('max_overlap', dbl),
+                            o_('gt_idx', i32), o_('is_tp', u8), o_('is_fp', u8), o_('gt_assignment', i32), o_('is_missed', u8),
+                            o_('precision', dbl), o_('recall', dbl), o_('ap', dbl), i_('overlap_offsets', C.c_int64),
+                            o_('overlaps', dbl), o_('overlap_gt', i32))
+    if want_overlaps and int(ov_off[-1]) == 0:
+        a.overlaps, a.overlap_gt = None, None
+    abi.check(rt.lib.t3d_sunrgbd_eval(C.byref(a), rt.stream()), 't3d_sunrgbd_eval')
+    host = d_out.cpu().numpy()                                              # the one copy back (synchronises)
+    res = {name: out.view(host, name).copy() for name in out.fields}
+    if want_overlaps:
+        res['overlap_offsets'] = ov_off
+    return res
+
+
+def compute_pr_curve_3d(classname, det, gt, difficult=None, threshold=0.25, rt=None):
+    """computePRCurve3D.m with its output names.  `gt` may hold several classes ('classname' per box): the boxes of `classname` are
+    picked (:11-14) and isMissed / gtAssignment refer to the whole list, as in the script.  isTp, isFp, gtAssignment are in file order;
+    precision, recall, maxOverlaps, gtIdxAll in sorted order (sortIdx, 0-based: sorted position -> file index), as the script leaves them."""
+    G_all = len(gt['image'])
+    if difficult is None:
+        difficult = np.zeros(G_all, np.uint8)
+    difficult = np.asarray(difficult).reshape(-1)
+    if len(difficult) != G_all:
+        raise ValueError('inconsistent difficulty size.')
+    same = np.array([c == classname for c in gt['classname']], bool) if 'classname' in gt else np.ones(G_all, bool)
+    sel = np.nonzero(same)[0]
+    r = _eval_call(det, select_boxes(gt, same), difficult[same], threshold, rt)
+    order = r['order'].astype(np.int64)
+    is_missed = np.zeros(G_all, bool)
+    is_missed[sel] = r['is_missed'] != 0
+    ga = r['gt_assignment'].astype(np.int64)
+    ga[ga > 0] = sel[ga[ga > 0] - 1] + 1                                     # tmp = find(isSameClass)  (:47-48)
+    return {'apScore': float(r['ap'][0]), 'precision': r['precision'], 'recall': r['recall'], 'isTp': r['is_tp'] != 0, 'isFp': r['is_fp'] != 0,
+            'isMissed': is_missed, 'gtAssignment': ga, 'maxOverlaps': r['max_overlap'][order], 'numOfgt': int(same.sum()),
+            'gtIdxAll': r['gt_idx'][order].astype(np.int64), 'sortIdx': order}
+
+
+def bb3d_overlap_close_form(bb1, bb2, rt=None):
+    """bb3dOverlapCloseForm.m: the dense [len(bb1), len(bb2)] score matrix of two box lists (every box on one pseudo-image)."""
+    P, G = len(bb1['coeffs']), len(bb2['coeffs'])
+    if P == 0 or G == 0:
+        return np.zeros((0, 0))                                              # scoreMatrix = []  (bb3dOverlapCloseForm.m:6-9)
+    det = dict(bb1, confidence=np.zeros(P), image=np.zeros(P, np.int32))
+    gt = {k: bb2[k] for k in ('centroid', 'basis', 'coeffs')}
+    gt['image'] = np.zeros(G, np.int32)
+    r = _eval_call(det, gt, None, 0.25, rt, want_overlaps=True)
+    m = np.zeros((P, G))
+    m[np.repeat(np.arange(P), G), r['overlap_gt']] = r['overlaps']
+    return m
+
+
+def num2str(x):
+    """MATLAB's num2str of a real scalar: an integer as %d, otherwise max(floor(log10(|x|)) + 5, 5) significant digits (at most 16)."""
+    x = float(x)
+    if math.isnan(x):
+        return 'NaN'
+    if math.isinf(x):
+        return 'Inf' if x > 0 else '-Inf'
+    if x == round(x):
+        return '%d' % int(round(x))
+    digits = min(max(int(math.floor(math.log10(abs(x)))) + 5, 5), 16)
+    return ('%.*g' % (digits, x)).strip()
+
+
+def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, threshold=0.25, save_curves=None, predictions=None):
+    """script_3Deval.m:33-60: per class of the set `test_on`, the number of predictions, the AP, and the mean AP, logged as the script
+    displays them.  `predictions` ({class: boxes}, e.g. official_predictions of a test_semisup run) stands in for the files of `pred_dir`.
+    -> ({class: AP}, mean AP).  save_curves: a directory for <class>_pr.npz."""
+    if test_on not in CLASS_NAMES:
+        raise ValueError("test_on is 'A', 'B' or 'AB'")
+    rt = _runtime(rt)
+    gt_all = benchmark_groundtruth(dataset_dir, idx_list)
+    ap = {}
+    if save_curves:
+        os.makedirs(save_curves, exist_ok=True)
+    for name in CLASS_NAMES[test_on]:
+        if predictions is not None:
+            if name not in predictions:
+                raise KeyError('no predictions for class %s' % name)
+            det = predictions[name]
+        else:
+            det = parse_class_predictions(os.path.join(pred_dir, name + '_pred.txt'), name)
+        log('Number of predictions for %s: %d' % (name.upper(), len(det['confidence'])))
+        r = compute_pr_curve_3d(name, det, gt_all, None, threshold, rt)
+        log('AP Score for %s: [%s]' % (name.upper(), num2str(r['apScore'] * 100.0)))
+        ap[name] = r['apScore']
+        if save_curves:
+            np.savez(os.path.join(save_curves, name + '_pr.npz'), precision=r['precision'], recall=r['recall'], isTp=r['isTp'], isFp=r['isFp'],
+                     maxOverlaps=r['maxOverlaps'], gtAssignment=r['gtAssignment'], isMissed=r['isMissed'])
+    mean_ap = float(np.mean([ap[c] for c in CLASS_NAMES[test_on]]))
+    log('Mean AP Score: [%s]' % num2str(mean_ap * 100.0))
+    return ap, mean_ap
+
+
+def official_predictions(test_classes, predictions, class_names):
+    """The boxes parse_class_predictions would read from the files test_semisup.write_detection_results writes, from test_semisup's
+    14-list held in memory (from_prediction_to_label_format per detection, no text round trip): {class: boxes} for `evaluate`."""
+    from .test_semisup import from_prediction_to_label_format
+    _, _, _, center_l, hcls_l, hres_l, scls_l, sres_l, rot_l, score_l, _, id_l, _, _ = predictions
+    rows = {c: [] for c in test_classes}
+    for i in range(len(center_l)):
+        vals = from_prediction_to_label_format(center_l[i], hcls_l[i], hres_l[i], scls_l[i], sres_l[i], float(rot_l[i]))
+        rows[class_names[i]].append((int(id_l[i]),) + tuple(float(v) for v in vals) + (float(score_l[i]),))
+    out = {}
+    for c, r in rows.items():
+        a = np.asarray(r, np.float64).reshape(-1, 9)
+        out[c] = boxes_from_label_format(a[:, 0].astype(np.int64), *[a[:, k] for k in range(1, 9)])
+    return out
+
+
+def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test_on='AB', rt=None, log=print, threshold=0.25, save_curves=None):
+    """test_semisup's run (its own command line: a frustum file with --data_path, or its synthetic frustums, whose image ids are their
+    indices), then `evaluate` on the predictions it returns.  With --result_dir among its flags the same run also writes the
+    <class>_pred.txt files."""
+    from . import test_semisup as TS
+    from .constants import class2type
+    FLAGS = TS.build_flags(list(test_semisup_argv))
+    predictions = TS.test(FLAGS, rt=rt, log=log)
+    names = [class2type[int(c)] for c in predictions[10]]
+    held = official_predictions(sorted(set(CLASS_NAMES[test_on]) | set(names)), predictions, names)
+    if rt is None:
+        rt = _runtime(None)
+    return evaluate(None, dataset_dir, idx_list, test_on, rt=rt, log=log, threshold=threshold, save_curves=save_curves, predictions=held)
+
+
+def parser():
+    p = argparse.ArgumentParser(description='SUN-RGBD 3-D detection AP by the protocol of script_3Deval.m, on the device',
+                                allow_abbrev=False)      # (--test is test_semisup's flag, not a short form of --test_on)
+    p.add_argument('--pred_dir', default=None, help='directory of <class>_pred.txt files (test_semisup --result_dir)')
+    p.add_argument('--official_eval', action='store_true',
+                   help='run test_semisup (every flag this parser does not know is passed to it) and score the predictions it holds in memory')
+    p.add_argument('--dataset_dir', default='mysunrgbd', help='SUN-RGBD root (<dir>/training/label_dimension)')
+    p.add_argument('--idx_path', required=True, help='index file of the test images, e.g. mysunrgbd/training/val_data_idx.txt')
+    p.add_argument('--test_on', default='B', choices=['A', 'B', 'AB'], help='set of classes to test on')
+    p.add_argument('--threshold', type=float, default=0.25, help='overlap a true positive needs (the script: 0.25)')
+    p.add_argument('--save_curves', default=None, help='directory for <class>_pr.npz (precision, recall, isTp, isFp, ...)')
+    p.add_argument('--gpu', type=int, default=0)
+    return p
+
+
+def main(argv=None, rt=None, log=print):
+    FLAGS, rest = parser().parse_known_args(argv)
+    if rt is None and torch.cuda.is_available():
+        torch.cuda.set_device(FLAGS.gpu)
+    if FLAGS.official_eval:
+        rest = list(rest) + ['--gpu', str(FLAGS.gpu)]                     # the one flag both parsers have: test_semisup gets it too
+        return official_eval_of_test_semisup(rest, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log, threshold=FLAGS.threshold,
+                                             save_curves=FLAGS.save_curves)
+    if rest or not FLAGS.pred_dir:
+        parser().error('--pred_dir is required' if not rest else 'unrecognized arguments: %s' % ' '.join(rest))
+    return evaluate(FLAGS.pred_dir, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log, threshold=FLAGS.threshold,
+                    save_curves=FLAGS.save_curves)
+
+
+if __name__ == '__main__':
+    main()
