@@ -942,6 +942,50 @@ typedef struct {
 } t3d_sample_equal_classes_args;
 int t3d_sample_equal_classes(const t3d_sample_equal_classes_args* args, t3d_stream_t stream);
 
+/* How a semi-supervised batch is drawn: SEMI_SAMPLING_METHOD over the two lists of ROISemiDataset (roi_semi_dataset.py:204-275: the
+ * 3-D-label list of TRAIN_CLS and the 2-D-label list of `classes2D`, which holds TRAIN_CLS too under SEMI_USE_LABELS2D_OF_CLASSES3D, so
+ * a frustum may be in both).  One launch per step writes sample[B] (frustum id per slot, for t3d_batch_assemble's explicit-sample mode)
+ * and is_data_2D[B] (for its slot_is_2D); nothing is allocated or synchronised, the step is read from hyper[0] on the device.
+ *   T3D_SEMI_BATCH            get_batch (482-535) over the epoch permutation of the concatenation [list3d | list2d]: slot b of step s
+ *                             takes entry e = perm[(s*B + b) mod perm_len]; e < len3D: list3d[e], flag 0; else list2d[e - len3D], flag 1.
+ *   T3D_SEMI_ALTERNATE_BATCH  (train_semisup.py:351-366) even steps draw all B slots from list2d (flag 1), odd steps from list3d (flag 0).
+ *   T3D_SEMI_MIXED_BATCH      sample_mixed (606-637): slots 0..B/2-1 from list2d (flag 1), slots B/2..B-1 from list3d (flag 0); B even.
+ * A draw of n slots from a list (sample_from_set, 557-569) follows one coin per step, u < equal_prob (the same coin for both halves of
+ * a mixed batch):
+ *   false  n distinct positions of the list, np.random.choice(len, n, replace=False): the first n steps of a Fisher-Yates shuffle of
+ *          0..len-1, step i swapping position i with position i + floor(r_i * (len - i) / 2^32);
+ *   true   "equal classes": the n slots are split over the list's k classes like np.array_split([1]*n, k) -- n mod k classes take one
+ *          slot more, WHICH ones is random (the classes whose key ranks among the n mod k smallest) -- slots are laid out class after
+ *          class and every slot draws a member of its class with replacement.
+ * Every draw comes from the counter-based hash of the other data kernels, keyed by (seed, step, half, slot): a replay is bit-reproducible.
+ * T3D_ERR_SHAPE: B outside 1..256, an odd B under MIXED_BATCH, more than 32 classes, and a list shorter than the slots asked of it
+ * when the coin can come up false (equal_prob < 1; numpy raises there too). */
+enum { T3D_SEMI_BATCH = 0, T3D_SEMI_ALTERNATE_BATCH = 1, T3D_SEMI_MIXED_BATCH = 2 };
+#define T3D_SEMI_SAMPLE_MAX_B 256
+typedef struct {
+  const int32_t* ids;            /* [len] frustum ids of the list, in list order */
+  int len;
+  const int32_t* members;        /* [len] the same ids grouped by class */
+  const int32_t* offsets;        /* [n_groups + 1] into members; every group non-empty */
+  int n_groups;                  /* 0..32 (0: no class groups; the list then cannot serve an equal-classes draw) */
+} t3d_semi_list;
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_semi_sample_args) of the caller's header (see T3D_ABI_VERSION) */
+  int method;                    /* T3D_SEMI_* */
+  t3d_semi_list list3d;          /* is_data_2D = 0 */
+  t3d_semi_list list2d;          /* is_data_2D = 1 */
+  const int32_t* perm;           /* BATCH: [perm_len] entries in [0, len3D + len2D) */
+  int perm_len;
+  int B;                         /* <= T3D_SEMI_SAMPLE_MAX_B */
+  uint32_t seed;
+  float equal_prob;              /* SEMI_SAMPLE_EQUAL_CLASS_WITH_PROB (not read under BATCH) */
+  const float* hyper;            /* device step counter (hyper[0]) */
+  int32_t* sample;               /* [B] out */
+  int32_t* is_data_2D;           /* [B] out */
+} t3d_semi_sample_args;
+#define T3D_V2_SIZE_semi_sample_args 136
+int t3d_semi_sample(const t3d_semi_sample_args* args, t3d_stream_t stream);
+
 /* Box-PC Fit training samples (box_pc_fit_dataset.py:105-185 `get`, 211-244 `perturb_box_to_diff_ious`, fed by
  * train_boxpc.py:343-355): each frustum's label box is perturbed until its 3-D IoU with the label box falls strictly inside the
  * "fit" bounds (with probability proportion_fit) or the "no-fit" bounds.  Candidate t of frustum b:

@@ -316,6 +316,20 @@ class SunrgbdEvalArgs(Sized):
                 ('ap', D), ('overlap_offsets', L), ('overlaps', D), ('overlap_gt', I)]
 
 
+SEMI_BATCH, SEMI_ALTERNATE_BATCH, SEMI_MIXED_BATCH = 0, 1, 2          # t3d.h T3D_SEMI_*
+SEMI_METHODS = {'BATCH': SEMI_BATCH, 'ALTERNATE_BATCH': SEMI_ALTERNATE_BATCH, 'MIXED_BATCH': SEMI_MIXED_BATCH}
+SEMI_SAMPLE_MAX_B = 256
+
+
+class SemiList(C.Structure):
+    _fields_ = [('ids', I), ('len', i32), ('members', I), ('offsets', I), ('n_groups', i32)]
+
+
+class SemiSampleArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('method', i32), ('list3d', SemiList), ('list2d', SemiList), ('perm', I), ('perm_len', i32),
+                ('B', i32), ('seed', C.c_uint32), ('equal_prob', f32), ('hyper', F), ('sample', I), ('is_data_2D', I)]
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -416,6 +430,7 @@ ENTRY_POINTS = {
     't3d_cast_bf16': [F, VP, C.c_int64, VP],
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
+    't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libt3d.so')

@@ -132,7 +132,13 @@ class Graph:
     def use_device_dataset(self, dataset, seed=0, **aug):
         """Feed the training plan from a data set resident in HBM: every Session.run of the train op assembles its own
         batch on the device (t3d_batch_assemble), nothing needs to be fed.  `boxpc_perturb=FLAGS` (the BOXPC_* flags) adds the
-        Box-PC Fit sampler (t3d_boxpc_perturb) behind it."""
+        Box-PC Fit sampler (t3d_boxpc_perturb) behind it.  `semi_sampling='BATCH' | 'ALTERNATE_BATCH' | 'MIXED_BATCH'` (after
+        dataset.semi_lists; with `equal_class_prob`): t3d_semi_sample in front of it draws every slot's frustum and is_data_2D flag."""
+        if aug.get('semi_sampling') is not None:
+            if aug['semi_sampling'] not in abi.SEMI_METHODS:
+                raise ValueError('unknown SEMI_SAMPLING_METHOD %r (known: %s)' % (aug['semi_sampling'], ', '.join(sorted(abi.SEMI_METHODS))))
+            if not getattr(dataset, 'semi', None):
+                raise ValueError('semi_sampling needs dataset.semi_lists(classes3d, classes2d)')
         self.dataset, self.dataset_opts = dataset, dict(seed=seed, **aug)
 
     def ensure_assembly(self, c, use_one_hot=False):

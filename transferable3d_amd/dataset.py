@@ -102,12 +102,13 @@ class DeviceFrustumSet:
         num_batches = len(TRAIN_DATASET) / BATCH_SIZE drops the remainder too (train_semisup.py:330-349).  The walk length is a
         multiple of the batch size, so the device-side position (step * B + b) % length wraps exactly at the epoch boundaries and
         no frustum is repeated or skipped inside a pass.  Returns the number of steps of an epoch (<= `steps` when given)."""
-        per_rank = self.F // world
+        total = self.semi_len if getattr(self, 'semi', None) else self.F       # semi_lists(): len3D + len2D entries (roi_semi_dataset.py:276-277)
+        per_rank = total // world
         n = per_rank // batch_size
         if steps:
             n = min(n, int(steps))
         if n <= 0:
-            raise ValueError('data set of %d frustums is smaller than one batch of %d on each of %d replicas' % (self.F, batch_size, world))
+            raise ValueError('data set of %d frustums is smaller than one batch of %d on each of %d replicas' % (total, batch_size, world))
         self.rank, self.world, self.walk_len = rank, world, n * batch_size
         return n
 
@@ -115,12 +116,14 @@ class DeviceFrustumSet:
         """New epoch order (the reference shuffles train_idxs once per epoch, train_semisup.py:343).  After partition(): the
         replica's slice of the common permutation (the seed must not depend on the rank)."""
         r = np.random.RandomState(seed)
-        perm = r.permutation(self.F).astype(np.int32)
+        semi = getattr(self, 'semi', None)
+        perm = r.permutation(self.semi_len if semi else self.F).astype(np.int32)
+        dst = self.semi_perm if semi else self.perm         # semi_lists(): positions of the concatenation [list3d | list2d]
         if getattr(self, 'walk_len', None):
             mine = perm[self.rank::self.world][:self.walk_len]
-            self.perm[:self.walk_len].copy_(torch.as_tensor(mine))
+            dst[:self.walk_len].copy_(torch.as_tensor(mine))
         else:
-            self.perm.copy_(torch.as_tensor(perm))
+            dst.copy_(torch.as_tensor(perm))
         for lst, dev in getattr(self, 'subsets', []):
             dev.copy_(torch.as_tensor(lst[r.permutation(len(lst))]))
 
@@ -176,6 +179,45 @@ class DeviceFrustumSet:
         self.subsets = [(weak, torch.as_tensor(weak).to(dev)), (strong, torch.as_tensor(strong).to(dev))]
         self.rt.allocs.extend([d for _, d in self.subsets])
         return self
+
+    def semi_lists(self, classes3d, classes2d):
+        """The two lists of ROISemiDataset (roi_semi_dataset.py:204-275) for t3d_semi_sample: the frustums of `classes3d` (class ids
+        trained with their 3-D labels, TRAIN_CLS) and of `classes2d` (2-D labels only: TEST_CLS, or TRAIN_CLS + TEST_CLS under
+        SEMI_USE_LABELS2D_OF_CLASSES3D), each in file order with its per-class groups.  A frustum may be in both; an epoch of
+        SEMI_SAMPLING_METHOD BATCH then walks len3D + len2D entries (partition / shuffle follow).  mark_2d_classes / split_by_class keep
+        their either-or meaning for callers that do not call this."""
+        cls = self.cls.cpu().numpy()
+        dev = self.rt.device
+        self.semi = []
+        for classes in (classes3d, classes2d):
+            ids = np.nonzero(np.isin(cls, list(classes)))[0].astype(np.int32)
+            if len(ids):
+                members, offsets, n = self.class_groups(ids)
+            else:
+                members = offsets = None
+                n = 0
+            self.semi.append(dict(host=ids, ids=torch.as_tensor(ids).to(dev), members=members, offsets=offsets, n_groups=n))
+        self.semi_len = sum(len(l['host']) for l in self.semi)
+        if self.semi_len == 0:
+            raise ValueError('no frustum of classes %s / %s' % (list(classes3d), list(classes2d)))
+        self.semi_perm = torch.arange(self.semi_len, dtype=torch.int32, device=dev)
+        self.rt.allocs.extend([l['ids'] for l in self.semi] + [self.semi_perm])
+        return self
+
+    def semi_sample_args(self, hyper, B, sample_out, is_data_2D, method='BATCH', seed=0, equal_prob=0.0):
+        """Argument struct of t3d_semi_sample over semi_lists(): the frustum id and the is_data_2D flag of every batch slot."""
+        if method not in abi.SEMI_METHODS:
+            raise ValueError('unknown SEMI_SAMPLING_METHOD %r (known: %s)' % (method, ', '.join(sorted(abi.SEMI_METHODS))))
+        a = abi.SemiSampleArgs()
+        a.method = abi.SEMI_METHODS[method]
+        for dst, l in zip((a.list3d, a.list2d), self.semi):
+            dst.ids, dst.len, dst.members, dst.offsets, dst.n_groups = iptr(l['ids']), len(l['host']), iptr(l['members']), \
+                iptr(l['offsets']), l['n_groups']
+        a.perm, a.perm_len = iptr(self.semi_perm), (getattr(self, 'walk_len', None) or self.semi_len)
+        a.B, a.seed, a.equal_prob, a.hyper = B, seed & 0xffffffff, float(equal_prob), fptr(hyper)
+        a.sample, a.is_data_2D = iptr(sample_out), iptr(is_data_2D)
+        a._keep = (sample_out, is_data_2D)
+        return a
 
     def assemble_args(self, inputs, hyper, B, N, C, seed=0, sample=None, choice=None, aug=None, rotate_to_center=True,
                       random_flip=True, random_shift=True, alternate=False):

@@ -121,6 +121,19 @@ class Graph:
         """The input pipeline as a launch of the step: batch slot b of step s takes frustum perm[(s*B + b) % F] of the
         HBM-resident data set (dataset.DeviceFrustumSet) -- recorded before the schedule kernel advances the step counter."""
         equal_prob = aug.pop('equal_class_prob', 0.0)
+        semi = aug.pop('semi_sampling', None)
+        if semi is not None:
+            # SEMI_SAMPLING_METHOD over dataset.semi_lists(): t3d_semi_sample writes the frustum and the is_data_2D flag of every slot,
+            # the assembly runs in its explicit-sample mode and reads the flag per slot
+            slots = self.rt.zeros(self.B, dtype=torch.int32)
+            plan.add('t3d_semi_sample', dataset.semi_sample_args(self.hyper, self.B, slots, inputs.is_data_2D, method=semi,
+                                                                 seed=seed ^ 0x2545F491, equal_prob=equal_prob))
+            if aug.pop('alternate', False):
+                raise ValueError('alternate=True (the two-list walk of split_by_class) and semi_sampling=%r exclude each other' % semi)
+            a = dataset.assemble_args(inputs, self.hyper, self.B, self.rpf, self.C, seed=seed, sample=slots, **aug)
+            a.is_data_2D, a.frustum_is_2D, a.slot_is_2D = iptr(None), iptr(None), iptr(inputs.is_data_2D)
+            plan.add('t3d_batch_assemble', a)
+            return
         if equal_prob > 0.0:
             # class-balanced composition (equal_samples_per_class): a sampler launch writes the frustum index of every slot, the
             # assembly then runs in its explicit-sample mode

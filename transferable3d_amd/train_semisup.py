@@ -14,6 +14,7 @@ Example (README.md:58-67 recipe a, synthetic data):
   python -m transferable3d_amd.train_semisup --SEMI_MODEL A --WEAK_WEIGHT_REPROJECTION 0 --WEAK_WEIGHT_SURFACE 0 \
       --num_point 1024 --no_rgb_channels 4 --max_epoch 1 --steps_per_epoch 100
 """
+import argparse
 import os
 import sys
 import time
@@ -72,10 +73,60 @@ def build_flags(argv=None):
                           'launches cost 22 us of a 1.2 ms step (+1.9 %%) and change nothing that is trained -- SURVEY Appendix E item 4 '
                           'sanctions skipping zero-weight terms; with a non-zero weight they are always evaluated')
     cfg.add_argument('--no_weak_loss_summaries', action='store_true', help='(accepted for round-5 command lines: the default now)')
-    FLAGS = cfg.parse_special_args(argv)
+    given = sampling_method_on_command_line(cfg, argv)
+    FLAGS = StageAFlags(**vars(cfg.parse_special_args(argv)))
+    FLAGS.SEMI_SAMPLING_METHOD_GIVEN = given
     FLAGS.WEAK_LOSS_SUMMARIES = bool(FLAGS.weak_loss_summaries) and not FLAGS.no_weak_loss_summaries
     FLAGS.NUM_CHANNELS = FLAGS.num_channels if FLAGS.num_channels else (3 if FLAGS.no_rgb else 6)
     return FLAGS
+
+
+SEMI_SAMPLING_METHODS = ('BATCH', 'ALTERNATE_BATCH', 'MIXED_BATCH')
+_PARSER_DEFAULT_METHOD = 'ALTERNATE_BATCH'       # config.py, as in the reference
+
+
+def sampling_method_on_command_line(parser, argv=None):
+    """Does the command line (`argv` None: sys.argv) set SEMI_SAMPLING_METHOD?  Asked of the parser itself -- a parse with no default
+    for the flag -- so that every spelling argparse accepts counts (`--SEMI_SAMPLING_METHOD=X`, an unambiguous abbreviation)."""
+    default = parser.get_default('SEMI_SAMPLING_METHOD')
+    parser.set_defaults(SEMI_SAMPLING_METHOD=None)
+    try:
+        return parser.parse_args(argv).SEMI_SAMPLING_METHOD is not None
+    finally:
+        parser.set_defaults(SEMI_SAMPLING_METHOD=default)
+
+
+class StageAFlags(argparse.Namespace):
+    """The namespace build_flags returns: assigning SEMI_SAMPLING_METHOD afterwards (a caller that passes FLAGS to train) counts as
+    asking for that method, the parser's default value included."""
+
+    def __setattr__(self, name, value):
+        if name == 'SEMI_SAMPLING_METHOD':
+            object.__setattr__(self, 'SEMI_SAMPLING_METHOD_GIVEN', True)
+        object.__setattr__(self, name, value)
+
+
+def requested_sampling_method(FLAGS):
+    """(method, asked): the SEMI_SAMPLING_METHOD the user asked for, or (None, False).  Stage a has always walked the combined data
+    set (BATCH) whatever the parser's default (ALTERNATE_BATCH, the reference's) said, and existing command lines rely on it -- so the
+    flag counts only when it was given: on the command line (build_flags asks the parser), by a caller that assigns it in the FLAGS
+    build_flags returned (StageAFlags notes it) or sets FLAGS.SEMI_SAMPLING_METHOD_GIVEN, or -- a namespace from elsewhere -- by a value
+    other than the parser's default.  A method that is asked for is honoured or refused, never replaced."""
+    method = getattr(FLAGS, 'SEMI_SAMPLING_METHOD', _PARSER_DEFAULT_METHOD)
+    asked = bool(getattr(FLAGS, 'SEMI_SAMPLING_METHOD_GIVEN', False)) or method != _PARSER_DEFAULT_METHOD
+    if not asked:
+        return None, False
+    if method not in SEMI_SAMPLING_METHODS:
+        raise ValueError('unknown SEMI_SAMPLING_METHOD %r (known: %s)' % (method, ', '.join(SEMI_SAMPLING_METHODS)))
+    return method, True
+
+
+def classes_2d(FLAGS, test_cls=None):
+    """train_semisup.py:97 / train_semisup_adv.py:105: the classes of the 2-D-label list."""
+    test_cls = list(FLAGS.SUNRGBD_SEMI_TEST_CLS if test_cls is None else test_cls)
+    if FLAGS.SEMI_USE_LABELS2D_OF_CLASSES3D:
+        return sorted(set(list(FLAGS.SUNRGBD_SEMI_TRAIN_CLS) + test_cls))
+    return test_cls
 
 
 def eval_one_epoch(sess, ops, FLAGS, epoch, log, source=None):
@@ -158,11 +209,13 @@ def end_points_logits(end_points, sess):
 
 
 def train(FLAGS, rt=None, log=print):
+    method, asked = requested_sampling_method(FLAGS)      # (an unknown method raises before anything is built)
     world, rank, pg = api.init_data_parallel(rt, FLAGS.gpu)
     B, N, C = FLAGS.batch_size, FLAGS.num_point, FLAGS.NUM_CHANNELS
     os.makedirs(FLAGS.log_dir, exist_ok=True)
     if rank == 0:
         log(FLAGS.config_str)
+    iters = 1
     with api.Graph(rt=rt, seed=FLAGS.seed, inline_dropout=True, dtype=FLAGS.dtype).as_default() as g:
         pls = MODEL.placeholder_inputs(B, N, C)
         pc_pl, bg_pc_pl, img_pl, one_hot_vec_pl, y_seg_pl, y_centers_pl, y_orient_cls_pl, y_orient_reg_pl, y_dims_cls_pl, \
@@ -187,13 +240,30 @@ def train(FLAGS, rt=None, log=print):
         ds = open_training_set(g.rt, FLAGS, C, classes=list(FLAGS.SUNRGBD_SEMI_TRAIN_CLS) + list(FLAGS.SUNRGBD_SEMI_TEST_CLS),
                                seed=FLAGS.seed + 17 * rank)
         if ds is not None:
-            # SEMI_SAMPLING_METHOD BATCH over the combined data set (train_semisup.py:97-110, 343-349): frustums of the classes that
+            # SEMI_SAMPLING_METHOD (train_semisup.py:97-110, 340-380).  BATCH over the combined data set: frustums of the classes that
             # have 2-D labels only (SUNRGBD_SEMI_TEST_CLS) run through the net with is_data_2D = 1 -- no strong loss, their points
-            # still enter the batch statistics.  (SEMI_USE_LABELS2D_OF_CLASSES3D also repeats the 3-D-label frustums as zero-loss
-            # 2-D samples; not reproduced.)
+            # still enter the batch statistics.  Known deviation: the method is taken from the flag only when it was asked for
+            # (requested_sampling_method); otherwise stage a runs BATCH, as it always has, and says so.
             from transferable3d_amd.constants import type2class
-            ds.mark_2d_classes([type2class[t] for t in FLAGS.SUNRGBD_SEMI_TEST_CLS])
-            g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank)
+            ids = lambda names: [type2class[t] for t in names]
+            run = method if asked else 'BATCH'
+            if rank == 0 and not asked:
+                log('SEMI_SAMPLING_METHOD not given: stage a runs BATCH (the parsed default %s is not applied; pass '
+                    '--SEMI_SAMPLING_METHOD to choose)' % getattr(FLAGS, 'SEMI_SAMPLING_METHOD', _PARSER_DEFAULT_METHOD))
+            if run == 'BATCH' and not FLAGS.SEMI_USE_LABELS2D_OF_CLASSES3D:
+                # every frustum is in exactly one list: a per-frustum flag on the one epoch permutation
+                ds.mark_2d_classes(ids(FLAGS.SUNRGBD_SEMI_TEST_CLS))
+                g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank)
+            else:
+                # t3d_semi_sample in front of the assembly: the 3-D-label list of TRAIN_CLS and the 2-D-label list (TEST_CLS, and
+                # TRAIN_CLS once more as zero-loss 2-D samples under SEMI_USE_LABELS2D_OF_CLASSES3D); BATCH walks len3D + len2D entries
+                ds.semi_lists(ids(FLAGS.SUNRGBD_SEMI_TRAIN_CLS), ids(classes_2d(FLAGS)))
+                g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank, semi_sampling=run,
+                                     equal_class_prob=float(FLAGS.SEMI_SAMPLE_EQUAL_CLASS_WITH_PROB))
+                iters = 2 if run == 'ALTERNATE_BATCH' else 1      # train_semisup.py:340: a 2-D and a 3-D batch per batch index
+                if rank == 0:
+                    log('SEMI_SAMPLING_METHOD %s on the device: %d frustums with 3-D labels, %d with 2-D labels' % (
+                        run, len(ds.semi[0]['host']), len(ds.semi[1]['host'])))
             # an epoch = ONE pass (train_semisup.py:330-349: num_batches = len(TRAIN_DATASET) / BATCH_SIZE); data parallel: every
             # replica walks its own slice of the common epoch permutation, so the replicas see disjoint frustums
             n = ds.partition(rank, world, B, FLAGS.steps_per_epoch)
@@ -215,8 +285,9 @@ def train(FLAGS, rt=None, log=print):
                 # device pipeline: nothing is fed; the loss is fetched (a D2H sync) every 10th step only
                 ds.shuffle(FLAGS.seed * 1000003 + epoch)      # train_semisup.py:343 (the same permutation on every replica)
                 n_logged = 0
-                for it in range(FLAGS.steps_per_epoch):
-                    if it % 10 == 9 or it == FLAGS.steps_per_epoch - 1:
+                n_steps = FLAGS.steps_per_epoch * iters
+                for it in range(n_steps):
+                    if it % 10 == 9 or it >= n_steps - iters:
                         loss_val, nc, i2, i3, _, *wk = sess.run([semi_loss, n_correct, iou2ds, iou3ds, train_op] + weak_t)
                         weak_sum, weak_n = weak_sum + np.array([float(np.mean(v)) for v in wk]), weak_n + 1
                         loss_sum += float(loss_val)
@@ -228,7 +299,7 @@ def train(FLAGS, rt=None, log=print):
                     step += 1
                 if rank == 0:
                     log('**** EPOCH %03d ****  mean loss: %f  accuracy: %f  (%.1f frustums/s, batches assembled on the device)' % (
-                        epoch, loss_sum / n_logged, correct / (n_logged * B * N), FLAGS.steps_per_epoch * B * world / (time.time() - t0)))
+                        epoch, loss_sum / n_logged, correct / (n_logged * B * N), n_steps * B * world / (time.time() - t0)))
                     log('Strong Box IoU (ground/3D): %f / %f' % (iou2_sum / (n_logged * B), iou3_sum / (n_logged * B)))
                 loss_sum = loss_sum / n_logged * FLAGS.steps_per_epoch
             for it in range(0 if ds is not None else FLAGS.steps_per_epoch):
