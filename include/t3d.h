@@ -12,7 +12,8 @@
  *     scratch (partials, slabs) is passed in explicitly.
  *   - all matrices are row-major, channel fastest: a (B, N, C) point tensor is an (M = B*N, C)
  *     matrix, exactly the reference's NHWC layout with H = N, W = 1.
- *   - `stream` is a hipStream_t; kernels are enqueued, never synchronised.  No global state.
+ *   - `stream` is a hipStream_t; kernels are enqueued, never synchronised (one exception, outside the training step:
+ *     t3d_label_subset).  No global state.
  *   - "partials" are per-128-row-tile column reductions ([M/128, C], T3D_TILE_ROWS rows each) that a
  *     finalize kernel combines deterministically (no float atomics anywhere on the path).
  *   - M must be a multiple of T3D_TILE_ROWS and rows_per_frustum (the point count N) a multiple of
@@ -985,6 +986,51 @@ typedef struct {
 } t3d_semi_sample_args;
 #define T3D_V2_SIZE_semi_sample_args 136
 int t3d_semi_sample(const t3d_semi_sample_args* args, t3d_stream_t stream);
+
+/* The lists and class groups of a data set object, built where the data set lives: the membership pass of ROISemiDataset.__init__
+ * (roi_semi_dataset.py:226-274: idx_3Dl / idx_2Dl and cls_to_idx_map3D / cls_to_idx_map2D) and of BoxPCFitDataset.__init__
+ * (box_pc_fit_dataset.py:71-100: idx_l, cls_to_idx_map).  It replaces the host constructions of DeviceFrustumSet.semi_lists and
+ * split_by_class (transferable3d_amd/dataset.py), which copied cls[F] to the host and uploaded the lists again, and serves the new
+ * DeviceFrustumSet.restrict; none of the older constructions could leave a frustum of a 3-D class out of the 3-D list
+ * (--train_data3D_keep_prob, --add3D_for_classes2D_prob, --classes_to_drop_prob).
+ * Which frustums are selected:
+ *   member != NULL  frustum f iff member[f] != 0.  The reference decides membership with a serial, short-circuiting walk of the global
+ *                   np.random stream; dataset.reference_label_subset / reference_drop_subset replay it on the host and hand the
+ *                   flags in.
+ *   member == NULL  frustum f iff (class_mask[cls[f]] != 0 and u1 <= keep_prob) or u2 < add_prob, u1 and u2 two draws of the
+ *                   counter-based hash of the other data kernels keyed by (seed, f): the same distribution without the serial
+ *                   dependence, for seeded subsets that need not be NumPy's.
+ * One launch of one workgroup (F is tens of thousands at the most): a pass of wave ballots counts the selected frustums per class,
+ * a second pass ranks every selected frustum inside its 1024-frustum chunk (ballot, population count below the lane, the totals of
+ * the waves before it through LDS) and stores it at its place.  No atomic decides a place: equal input gives equal bytes.
+ *   ids[0 .. len)             the selected frustum ids in file order (a stable compaction)
+ *   members[0 .. len)         the same ids grouped by class in ascending class id, file order inside a class
+ *   offsets[0 .. n_groups]    start of every group in members, over the classes present only; offsets[n_groups .. NUM_CLASS] = len
+ *   present[c]                1 iff a selected frustum has class c
+ *   summary[0..3]             len, n_groups, 1 iff some cls[f] lies outside [0, T3D_NUM_CLASS), 0
+ * ids and members are filled with -1 behind len.  ids / members / offsets / n_groups are the fields of t3d_semi_list and
+ * t3d_class_groups.  This entry point belongs to the construction of a data set, not to a step: it is the one call of the library
+ * that waits for its launch (it reads `summary` back), so that it can answer T3D_ERR_ARG for a class id outside the range, and it
+ * must not be called while a stream is captured.  T3D_ERR_SHAPE: F <= 0. */
+#define T3D_NUM_CLASS 10
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_label_subset_args) of the caller's header (see T3D_ABI_VERSION) */
+  int F;
+  const int32_t* cls;            /* [F] */
+  const uint8_t* member;         /* [F] flags, or NULL: hash draws */
+  const int32_t* class_mask;     /* [T3D_NUM_CLASS] (member == NULL) */
+  float keep_prob;               /* train_data3D_keep_prob (member == NULL) */
+  float add_prob;                /* add3D_for_classes2D_prob (member == NULL) */
+  uint32_t seed;
+  int reserved;                  /* 0 */
+  int32_t* ids;                  /* [F] out */
+  int32_t* members;              /* [F] out */
+  int32_t* offsets;              /* [T3D_NUM_CLASS + 1] out */
+  int32_t* present;              /* [T3D_NUM_CLASS] out */
+  int32_t* summary;              /* [4] out */
+} t3d_label_subset_args;
+#define T3D_V2_SIZE_label_subset_args 88
+int t3d_label_subset(const t3d_label_subset_args* args, t3d_stream_t stream);
 
 /* Box-PC Fit training samples (box_pc_fit_dataset.py:105-185 `get`, 211-244 `perturb_box_to_diff_ious`, fed by
  * train_boxpc.py:343-355): each frustum's label box is perturbed until its 3-D IoU with the label box falls strictly inside the

@@ -330,6 +330,14 @@ class SemiSampleArgs(Sized):
                 ('B', i32), ('seed', C.c_uint32), ('equal_prob', f32), ('hyper', F), ('sample', I), ('is_data_2D', I)]
 
 
+NUM_CLASS = 10                # t3d.h T3D_NUM_CLASS
+
+
+class LabelSubsetArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('F', i32), ('cls', I), ('member', U8), ('class_mask', I), ('keep_prob', f32), ('add_prob', f32),
+                ('seed', C.c_uint32), ('reserved', i32), ('ids', I), ('members', I), ('offsets', I), ('present', I), ('summary', I)]
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -431,6 +439,7 @@ ENTRY_POINTS = {
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
+    't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'libt3d.so')
@@ -483,6 +492,10 @@ def fptr(t):
 
 def iptr(t):
     return C.cast(C.c_void_p(0 if t is None else t.data_ptr()), I)
+
+
+def u8ptr(t):
+    return C.cast(C.c_void_p(0 if t is None else t.data_ptr()), U8)
 
 
 def check(rc, what):

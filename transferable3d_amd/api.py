@@ -418,6 +418,17 @@ def init_data_parallel(rt=None, gpu=0):
     return 1, 0, None
 
 
+def assert_ranks_agree(pg, world, value, what):
+    """Every replica must have built the same thing (e.g. the lengths of the label subset: it depends on the file and its seed only,
+    never on the rank) -- one all-gather of a small Python value when the data set is opened."""
+    if world > 1:
+        import torch.distributed as dist
+        got = [None] * world
+        dist.all_gather_object(got, value, group=pg)
+        if any(g != got[0] for g in got):
+            raise RuntimeError('%s differs between the replicas: %s' % (what, got))
+
+
 def finish_data_parallel(world):
     if world > 1:
         import torch.distributed as dist

@@ -102,7 +102,7 @@ class DeviceFrustumSet:
         num_batches = len(TRAIN_DATASET) / BATCH_SIZE drops the remainder too (train_semisup.py:330-349).  The walk length is a
         multiple of the batch size, so the device-side position (step * B + b) % length wraps exactly at the epoch boundaries and
         no frustum is repeated or skipped inside a pass.  Returns the number of steps of an epoch (<= `steps` when given)."""
-        total = self.semi_len if getattr(self, 'semi', None) else self.F       # semi_lists(): len3D + len2D entries (roi_semi_dataset.py:276-277)
+        total = self.semi_len if getattr(self, 'semi', None) else self.n_active       # semi_lists(): len3D + len2D entries (roi_semi_dataset.py:276-277)
         per_rank = total // world
         n = per_rank // batch_size
         if steps:
@@ -117,8 +117,10 @@ class DeviceFrustumSet:
         replica's slice of the common permutation (the seed must not depend on the rank)."""
         r = np.random.RandomState(seed)
         semi = getattr(self, 'semi', None)
-        perm = r.permutation(self.semi_len if semi else self.F).astype(np.int32)
+        perm = r.permutation(self.semi_len if semi else self.n_active).astype(np.int32)
         dst = self.semi_perm if semi else self.perm         # semi_lists(): positions of the concatenation [list3d | list2d]
+        if not semi and getattr(self, 'active', None):
+            perm = self.active['host'][perm]                # restrict(): the epoch walks the kept frustums only
         if getattr(self, 'walk_len', None):
             mine = perm[self.rank::self.world][:self.walk_len]
             dst[:self.walk_len].copy_(torch.as_tensor(mine))
@@ -129,7 +131,9 @@ class DeviceFrustumSet:
 
     def class_groups(self, subset=None):
         """Per-class index lists of the frustums in `subset` (default: all), cls_to_idx_map of the reference data sets
-        (roi_semi_dataset.py:222-238), on the device for t3d_sample_equal_classes."""
+        (roi_semi_dataset.py:222-238), on the device for t3d_sample_equal_classes.  After restrict(): of the kept frustums."""
+        if subset is None and getattr(self, 'active', None):
+            return self.active['members'], self.active['offsets'], self.active['n_groups']
         cls = self.cls.cpu().numpy()
         idx = np.arange(self.F, dtype=np.int32) if subset is None else np.asarray(subset, np.int32)
         present = sorted(set(int(c) for c in cls[idx]))
@@ -139,6 +143,71 @@ class DeviceFrustumSet:
         t = (torch.as_tensor(members).to(dev), torch.as_tensor(offsets).to(dev), len(present))
         self.rt.allocs.extend(t[:2])
         return t
+
+    @property
+    def n_active(self):
+        """Frustums an epoch walks: all of them, or the ones restrict() kept."""
+        return len(self.active['host']) if getattr(self, 'active', None) else self.F
+
+    def label_subset(self, member=None, classes=(), keep_prob=1.0, add_prob=-1.0, seed=20):
+        """t3d_label_subset: the list of the selected frustums and its class groups, built on the device from `cls` as it lies in HBM.
+        `member` (uint8 flags [F], e.g. reference_label_subset): exactly these; else the frustums of `classes` (class ids), each kept by a
+        hash draw <= keep_prob, plus any frustum whose second draw < add_prob -- at the defaults (1, -1) exactly the classes' frustums.
+        Returns dict(host = ids as a NumPy array, ids / members / offsets = device tensors as t3d_semi_list and t3d_class_groups take
+        them, n_groups, present); members and offsets are None for an empty list."""
+        rt, dev, F = self.rt, self.rt.device, self.F
+        if member is not None:
+            member = np.ascontiguousarray(np.asarray(member).reshape(-1) != 0, dtype=np.uint8)
+            if len(member) != F:
+                raise ValueError('%d membership flags for %d frustums' % (len(member), F))
+        if dev.type == 'cpu' and not hasattr(rt.lib, 't3d_label_subset'):
+            # a host-memory specification library written before the entry point existed (tests/fake_t3d.py): the plain NumPy
+            # construction that defines the layout.  The HIP library always has the kernel (abi.load refuses one without it).
+            cls = self.cls.numpy()
+            sel = member.astype(bool) if member is not None else np.isin(cls, list(classes))
+            if member is None and (keep_prob < 1.0 or add_prob > 0.0):
+                raise abi.T3DError('hash-drawn label subsets need t3d_label_subset')
+            ids = np.nonzero(sel)[0].astype(np.int32)
+            present = sorted(set(int(c) for c in cls[ids]))
+            out = dict(host=ids, ids=torch.as_tensor(ids), members=None, offsets=None, n_groups=len(present), present=present)
+            rt.allocs.append(out['ids'])
+            if len(ids):
+                out['members'] = torch.as_tensor(np.concatenate([ids[cls[ids] == c] for c in present]).astype(np.int32))
+                out['offsets'] = torch.as_tensor(np.concatenate([[0], np.cumsum([int((cls[ids] == c).sum()) for c in present])]).astype(np.int32))
+                rt.allocs.extend([out['members'], out['offsets']])
+            return out
+        z = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+        ids, members, small = z(F), z(F), z(2 * NUM_CLASS + 5)           # small: offsets | present | summary, read back in one copy
+        offsets, present, summary = small[:NUM_CLASS + 1], small[NUM_CLASS + 1:2 * NUM_CLASS + 1], small[2 * NUM_CLASS + 1:]
+        flags = torch.as_tensor(member).to(dev) if member is not None else None
+        mask = torch.as_tensor(np.isin(np.arange(NUM_CLASS), list(classes)).astype(np.int32)).to(dev)
+        a = abi.LabelSubsetArgs()
+        a.F, a.cls, a.member, a.class_mask = F, iptr(self.cls), abi.u8ptr(flags), iptr(mask)
+        a.keep_prob, a.add_prob, a.seed = float(keep_prob), float(add_prob), int(seed) & 0xffffffff
+        a.ids, a.members, a.offsets, a.present, a.summary = iptr(ids), iptr(members), iptr(offsets), iptr(present), iptr(summary)
+        abi.check(rt.lib.t3d_label_subset(abi.C.byref(a), rt.stream()), 't3d_label_subset')
+        back = small.cpu().tolist()
+        n, n_groups = back[2 * NUM_CLASS + 1], back[2 * NUM_CLASS + 2]
+        out = dict(host=ids[:n].cpu().numpy(), ids=ids[:n], members=None, offsets=None, n_groups=n_groups,
+                   present=[c for c in range(NUM_CLASS) if back[NUM_CLASS + 1 + c]])
+        if n:
+            out['members'], out['offsets'] = members[:n], offsets[:n_groups + 1]
+            rt.allocs.extend([members, small])
+        rt.allocs.append(ids)
+        return out
+
+    def restrict(self, member):
+        """The data set of BoxPCFitDataset (box_pc_fit_dataset.py:71-100): only the frustums with a non-zero flag in `member` [F] (e.g.
+        reference_drop_subset) are ever drawn -- the epoch permutation, the class groups of the class-balanced batches and the epoch
+        length (partition / shuffle) follow.  The frustums themselves stay where they are: ids remain file positions."""
+        self.active = self.label_subset(member=member)
+        n = self.n_active
+        if n == 0:
+            raise ValueError('the restriction keeps none of the %d frustums (every class dropped with probability 1?)' % self.F)
+        self.whole_perm = self.perm
+        self.perm = self.whole_perm[:n]
+        self.perm.copy_(self.active['ids'])
+        return self
 
     def sample_equal_args(self, hyper, B, sample_out, is_data_2D=None, seed=0, equal_prob=1.0, alternate=False, order_draws=None,
                           member_draws=None, prob_draw=None):
@@ -150,7 +219,8 @@ class DeviceFrustumSet:
             sets = [(None, self.perm)]
         keep = []
         for i, (lst, perm) in enumerate(sets):
-            m, o, n = self.class_groups(lst)
+            cached = getattr(self, 'subset_groups', None)
+            m, o, n = cached[1][i] if alternate and cached and cached[0] is self.subsets else self.class_groups(lst)
             a.set[i] = abi.ClassGroups(iptr(m), iptr(o), n, iptr(perm), int(perm.numel()))
             keep += [m, o]
         a.B, a.seed, a.hyper = B, seed, fptr(hyper)
@@ -171,37 +241,29 @@ class DeviceFrustumSet:
         """ALTERNATE_BATCH sampling (train_semisup_adv.py:538-565): the frustums of `classes_2d` (class ids whose 3-D labels
         are withheld, SUNRGBD_SEMI_TEST_CLS) form the weak list, the rest the strong list; each is walked in its own shuffled
         order on alternate steps."""
-        cls = self.cls.cpu().numpy()
-        weak = np.nonzero(np.isin(cls, list(classes_2d)))[0].astype(np.int32)
-        strong = np.nonzero(~np.isin(cls, list(classes_2d)))[0].astype(np.int32)
-        assert len(weak) and len(strong), 'both lists must be non-empty'
-        dev = self.rt.device
-        self.subsets = [(weak, torch.as_tensor(weak).to(dev)), (strong, torch.as_tensor(strong).to(dev))]
-        self.rt.allocs.extend([d for _, d in self.subsets])
+        weak = self.label_subset(classes=classes_2d)
+        strong = self.label_subset(classes=[c for c in range(NUM_CLASS) if c not in set(classes_2d)])
+        assert len(weak['host']) and len(strong['host']), 'both lists must be non-empty'
+        self.subsets = [(weak['host'], weak['ids']), (strong['host'], strong['ids'])]
+        # the groups belong to exactly these lists: a caller that assigns `subsets` afterwards gets its groups from class_groups
+        self.subset_groups = (self.subsets, [(l['members'], l['offsets'], l['n_groups']) for l in (weak, strong)])
         return self
 
-    def semi_lists(self, classes3d, classes2d):
+    def semi_lists(self, classes3d, classes2d, member3d=None):
         """The two lists of ROISemiDataset (roi_semi_dataset.py:204-275) for t3d_semi_sample: the frustums of `classes3d` (class ids
         trained with their 3-D labels, TRAIN_CLS) and of `classes2d` (2-D labels only: TEST_CLS, or TRAIN_CLS + TEST_CLS under
-        SEMI_USE_LABELS2D_OF_CLASSES3D), each in file order with its per-class groups.  A frustum may be in both; an epoch of
-        SEMI_SAMPLING_METHOD BATCH then walks len3D + len2D entries (partition / shuffle follow).  mark_2d_classes / split_by_class keep
-        their either-or meaning for callers that do not call this."""
-        cls = self.cls.cpu().numpy()
+        SEMI_USE_LABELS2D_OF_CLASSES3D), each in file order with its per-class groups, both built by t3d_label_subset.  `member3d`
+        (uint8 flags [F], reference_label_subset): the 3-D list is exactly these frustums instead -- some of `classes3d` left out
+        (--train_data3D_keep_prob), some of other classes taken in (--add3D_for_classes2D_prob).  A frustum may be in both lists; an
+        epoch of SEMI_SAMPLING_METHOD BATCH then walks len3D + len2D entries (partition / shuffle follow).  mark_2d_classes /
+        split_by_class keep their either-or meaning for callers that do not call this."""
         dev = self.rt.device
-        self.semi = []
-        for classes in (classes3d, classes2d):
-            ids = np.nonzero(np.isin(cls, list(classes)))[0].astype(np.int32)
-            if len(ids):
-                members, offsets, n = self.class_groups(ids)
-            else:
-                members = offsets = None
-                n = 0
-            self.semi.append(dict(host=ids, ids=torch.as_tensor(ids).to(dev), members=members, offsets=offsets, n_groups=n))
+        self.semi = [self.label_subset(member=member3d, classes=classes3d), self.label_subset(classes=classes2d)]
         self.semi_len = sum(len(l['host']) for l in self.semi)
         if self.semi_len == 0:
             raise ValueError('no frustum of classes %s / %s' % (list(classes3d), list(classes2d)))
         self.semi_perm = torch.arange(self.semi_len, dtype=torch.int32, device=dev)
-        self.rt.allocs.extend([l['ids'] for l in self.semi] + [self.semi_perm])
+        self.rt.allocs.append(self.semi_perm)
         return self
 
     def semi_sample_args(self, hyper, B, sample_out, is_data_2D, method='BATCH', seed=0, equal_prob=0.0):
@@ -229,7 +291,7 @@ class DeviceFrustumSet:
         a.frustum_angle, a.box_center, a.heading, a.size, a.cls = fptr(self.frustum_angle), fptr(self.box_center), fptr(self.heading), \
             fptr(self.size), iptr(self.cls)
         if sample is None:
-            a.sample, a.sample_len = iptr(self.perm), (getattr(self, 'walk_len', None) or self.F)
+            a.sample, a.sample_len = iptr(self.perm), (getattr(self, 'walk_len', None) or self.n_active)
         else:
             a.sample, a.sample_len = iptr(sample), 0
         a.choice, a.aug = iptr(choice), fptr(aug)
@@ -252,6 +314,42 @@ class DeviceFrustumSet:
             a.sample, a.sample_len, a.sample2, a.sample2_len = iptr(weak), int(weak.numel()), iptr(strong), int(strong.numel())
         a._keep = (sample, choice, aug)
         return a
+
+
+def _checked_prob(name, value):
+    if not -1.0 <= float(value) <= 1.0:
+        raise ValueError('%s = %r lies outside [-1, 1]' % (name, value))
+    return float(value)
+
+
+def reference_label_subset(cls_names, classes3d, keep_prob, add_prob, seed=20):
+    """Which frustums ROISemiDataset.__init__ puts into its 3-D-label list (roi_semi_dataset.py:226-253), as uint8 flags [F] in file
+    order: the reference seeds the global stream with 20 and walks the file once, `(cls_type in classes3D and rand() <= keep_prob) or
+    (rand() < add_prob)` -- a frustum of a 3-D class draws once, and a second time only when the first draw rejected it; every other
+    frustum draws once.  The default add_prob = -1 never adds, but its draw is still consumed.  The stream is serial by construction:
+    this stays on the host (t3d_label_subset takes the flags).  `cls_names` / `classes3d`: class names or ids, alike."""
+    keep_prob, add_prob = _checked_prob('train_data3D_keep_prob', keep_prob), _checked_prob('add3D_for_classes2D_prob', add_prob)
+    r = np.random.RandomState(seed)
+    classes3d = set(classes3d)
+    out = np.zeros(len(cls_names), np.uint8)
+    for i, t in enumerate(cls_names):
+        if (t in classes3d and r.rand() <= keep_prob) or (r.rand() < add_prob):
+            out[i] = 1
+    return out
+
+
+def reference_drop_subset(cls_names, classes, classes_to_drop, drop_prob, seed=20):
+    """Which frustums BoxPCFitDataset.__init__ keeps (box_pc_fit_dataset.py:71-86), as uint8 flags [F] in file order: every frustum of
+    `classes`, except that a frustum of `classes_to_drop` is left out when its draw `rand() < drop_prob` says so.  Only the frustums of
+    `classes_to_drop` (that are in `classes`) draw."""
+    drop_prob = _checked_prob('classes_to_drop_prob', drop_prob)
+    r = np.random.RandomState(seed)
+    classes, classes_to_drop = set(classes), set(classes_to_drop)
+    out = np.zeros(len(cls_names), np.uint8)
+    for i, t in enumerate(cls_names):
+        if t in classes and not (t in classes_to_drop and r.rand() < drop_prob):
+            out[i] = 1
+    return out
 
 
 def load_zipped_pickle(path):

@@ -32,8 +32,7 @@ from transferable3d_amd.tf_checkpoint import Saver, restore_model   # noqa: E402
 def build_flags(argv=None):
     cfg = make_parser()
     cfg.add_argument('--train_data', type=str, default='synthetic', choices=['train_mini', 'train_aug5x', 'trainval_aug5x', 'synthetic'])
-    cfg.add_argument('--train_data3D_keep_prob', type=float, default=1)
-    cfg.add_argument('--add3D_for_classes2D_prob', type=float, default=-1)
+    add_label_subset_arguments(cfg)
     cfg.add_argument('--gpu', type=int, default=0, help='GPU to use [default: GPU 0]')
     cfg.add_argument('--model', default='semisup_v1_sunrgbd', help='Model name [default: model]')
     cfg.add_argument('--log_dir', default='log', help='Log dir [default: log]')
@@ -78,7 +77,41 @@ def build_flags(argv=None):
     FLAGS.SEMI_SAMPLING_METHOD_GIVEN = given
     FLAGS.WEAK_LOSS_SUMMARIES = bool(FLAGS.weak_loss_summaries) and not FLAGS.no_weak_loss_summaries
     FLAGS.NUM_CHANNELS = FLAGS.num_channels if FLAGS.num_channels else (3 if FLAGS.no_rgb else 6)
+    label_subset_flags(FLAGS)          # (a probability outside [-1, 1] raises here)
     return FLAGS
+
+
+def add_label_subset_arguments(cfg):
+    """train_semisup.py:35-36 / train_semisup_adv.py:29-30: how much of the 3-D supervision the 3-D-label list keeps."""
+    cfg.add_argument('--train_data3D_keep_prob', type=float, default=1,
+                     help='every frustum of the classes with 3-D labels stays in the 3-D-label list with this probability')
+    cfg.add_argument('--add3D_for_classes2D_prob', type=float, default=-1,
+                     help='a frustum that did not enter the 3-D-label list that way (any class) is added to it with this probability')
+    cfg.add_argument('--label_subset_seed', type=int, default=20,
+                     help="seed of the serial np.random walk that decides the subset [the reference's fixed 20]")
+
+
+def label_subset_flags(FLAGS):
+    """(keep_prob, add_prob, seed, asked): `asked` when either probability differs from its default."""
+    from transferable3d_amd.dataset import _checked_prob
+    keep = _checked_prob('train_data3D_keep_prob', getattr(FLAGS, 'train_data3D_keep_prob', 1))
+    add = _checked_prob('add3D_for_classes2D_prob', getattr(FLAGS, 'add3D_for_classes2D_prob', -1))
+    return keep, add, int(getattr(FLAGS, 'label_subset_seed', 20)), (keep != 1.0 or add != -1.0)
+
+
+def label_subset_member(FLAGS, ds):
+    """uint8 flags [F] of the 3-D-label list under --train_data3D_keep_prob / --add3D_for_classes2D_prob (the reference's serial walk
+    replayed on the host, dataset.reference_label_subset), or None when both flags have their defaults."""
+    from transferable3d_amd.constants import type2class
+    from transferable3d_amd.dataset import reference_label_subset
+    keep, add, seed, asked = label_subset_flags(FLAGS)
+    if not asked:
+        return None
+    names = getattr(ds, 'class_names', None)                 # a frustum file; a synthetic set has class ids only
+    classes3d = list(FLAGS.SUNRGBD_SEMI_TRAIN_CLS)
+    if names is None:
+        names, classes3d = ds.cls.cpu().numpy().tolist(), [type2class[t] for t in classes3d]
+    return reference_label_subset(names, classes3d, keep, add, seed)
 
 
 SEMI_SAMPLING_METHODS = ('BATCH', 'ALTERNATE_BATCH', 'MIXED_BATCH')
@@ -250,20 +283,29 @@ def train(FLAGS, rt=None, log=print):
             if rank == 0 and not asked:
                 log('SEMI_SAMPLING_METHOD not given: stage a runs BATCH (the parsed default %s is not applied; pass '
                     '--SEMI_SAMPLING_METHOD to choose)' % getattr(FLAGS, 'SEMI_SAMPLING_METHOD', _PARSER_DEFAULT_METHOD))
-            if run == 'BATCH' and not FLAGS.SEMI_USE_LABELS2D_OF_CLASSES3D:
+            member3d = label_subset_member(FLAGS, ds)
+            if run == 'BATCH' and not FLAGS.SEMI_USE_LABELS2D_OF_CLASSES3D and member3d is None:
                 # every frustum is in exactly one list: a per-frustum flag on the one epoch permutation
                 ds.mark_2d_classes(ids(FLAGS.SUNRGBD_SEMI_TEST_CLS))
                 g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank)
+                len2d = int(ds.is_2D.sum())
+                lengths = (len2d, ds.F - len2d)
             else:
                 # t3d_semi_sample in front of the assembly: the 3-D-label list of TRAIN_CLS and the 2-D-label list (TEST_CLS, and
                 # TRAIN_CLS once more as zero-loss 2-D samples under SEMI_USE_LABELS2D_OF_CLASSES3D); BATCH walks len3D + len2D entries
-                ds.semi_lists(ids(FLAGS.SUNRGBD_SEMI_TRAIN_CLS), ids(classes_2d(FLAGS)))
+                # (a label subset -- --train_data3D_keep_prob / --add3D_for_classes2D_prob -- takes this path under every method: the
+                # per-frustum flag cannot leave a frustum of a 3-D class out of the 3-D list)
+                ds.semi_lists(ids(FLAGS.SUNRGBD_SEMI_TRAIN_CLS), ids(classes_2d(FLAGS)), member3d=member3d)
+                lengths = (len(ds.semi[1]['host']), len(ds.semi[0]['host']))
                 g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank, semi_sampling=run,
                                      equal_class_prob=float(FLAGS.SEMI_SAMPLE_EQUAL_CLASS_WITH_PROB))
                 iters = 2 if run == 'ALTERNATE_BATCH' else 1      # train_semisup.py:340: a 2-D and a 3-D batch per batch index
                 if rank == 0:
                     log('SEMI_SAMPLING_METHOD %s on the device: %d frustums with 3-D labels, %d with 2-D labels' % (
                         run, len(ds.semi[0]['host']), len(ds.semi[1]['host'])))
+            api.assert_ranks_agree(pg, world, lengths, 'the label subset (2D, 3D)')
+            if rank == 0:
+                log('Length of Train Dataset: (2D: %d, 3D: %d)' % lengths)       # train_semisup.py:104
             # an epoch = ONE pass (train_semisup.py:330-349: num_batches = len(TRAIN_DATASET) / BATCH_SIZE); data parallel: every
             # replica walks its own slice of the common epoch permutation, so the replicas see disjoint frustums
             n = ds.partition(rank, world, B, FLAGS.steps_per_epoch)

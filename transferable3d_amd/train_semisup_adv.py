@@ -21,7 +21,8 @@ from transferable3d_amd.config import make_parser                        # noqa:
 from transferable3d_amd.constants import type2class                      # noqa: E402
 from transferable3d_amd.synthetic import make_batch                      # noqa: E402
 from transferable3d_amd.tf_checkpoint import Saver, load_state, restore_model   # noqa: E402
-from transferable3d_amd.train_semisup import SEMI_SAMPLING_METHODS, ap_by_label_kind, classes_2d      # noqa: E402
+from transferable3d_amd.train_semisup import (SEMI_SAMPLING_METHODS, add_label_subset_arguments, ap_by_label_kind, classes_2d,      # noqa: E402
+                                              label_subset_flags, label_subset_member)
 
 ALL_CLASSES = ['bed', 'table', 'sofa', 'chair', 'toilet', 'desk', 'dresser', 'night_stand', 'bookshelf', 'bathtub']
 
@@ -29,6 +30,7 @@ ALL_CLASSES = ['bed', 'table', 'sofa', 'chair', 'toilet', 'desk', 'dresser', 'ni
 def build_flags(argv=None):
     cfg = make_parser()
     cfg.add_argument('--train_data', type=str, default='synthetic')
+    add_label_subset_arguments(cfg)          # train_semisup_adv.py:29-30
     cfg.add_argument('--gpu', type=int, default=0)
     cfg.add_argument('--model', default='semisup_v1_sunrgbd')
     cfg.add_argument('--log_dir', default='log_adv')
@@ -62,6 +64,7 @@ def build_flags(argv=None):
     FLAGS = cfg.parse_special_args(argv)
     FLAGS.NUM_CHANNELS = FLAGS.num_channels if FLAGS.num_channels else (3 if FLAGS.no_rgb else 6)
     FLAGS.TEST_CLS = FLAGS.SUNRGBD_SEMI_TEST_CLS
+    label_subset_flags(FLAGS)          # (a probability outside [-1, 1] raises here)
     return FLAGS
 
 
@@ -194,22 +197,27 @@ def train(FLAGS, rt=None, log=print):
         ds = open_training_set(g.rt, FLAGS, C, classes=None, seed=FLAGS.seed + 17 * rank)
         if ds is not None:
             method = FLAGS.SEMI_SAMPLING_METHOD
-            if method == 'ALTERNATE_BATCH' and not FLAGS.SEMI_USE_LABELS2D_OF_CLASSES3D:
+            member3d = label_subset_member(FLAGS, ds)      # --train_data3D_keep_prob / --add3D_for_classes2D_prob
+            if method == 'ALTERNATE_BATCH' and not FLAGS.SEMI_USE_LABELS2D_OF_CLASSES3D and member3d is None:
                 # every frustum is in exactly one list: the two lists of split_by_class, walked on alternate steps
                 ds.split_by_class(test_ids)
+                lengths = (len(ds.subsets[0][0]), len(ds.subsets[1][0]))
                 g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank, alternate=True,
                                      equal_class_prob=float(FLAGS.SEMI_SAMPLE_EQUAL_CLASS_WITH_PROB))   # train_semisup_adv.py:557,573
             else:
                 # t3d_semi_sample: BATCH / MIXED_BATCH, and the 2-D-label list that holds TRAIN_CLS too
                 # (SEMI_USE_LABELS2D_OF_CLASSES3D, train_semisup_adv.py:105)
                 ds.semi_lists([type2class[t] for t in FLAGS.SUNRGBD_SEMI_TRAIN_CLS],
-                              [type2class[t] for t in classes_2d(FLAGS, FLAGS.TEST_CLS)])
+                              [type2class[t] for t in classes_2d(FLAGS, FLAGS.TEST_CLS)], member3d=member3d)
+                lengths = (len(ds.semi[1]['host']), len(ds.semi[0]['host']))
                 g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank, semi_sampling=method,
                                      equal_class_prob=float(FLAGS.SEMI_SAMPLE_EQUAL_CLASS_WITH_PROB))
                 if method == 'BATCH':      # one pass over len3D + len2D entries at the most; every replica its slice of the permutation
                     FLAGS.steps_per_epoch = ds.partition(rank, world, B, FLAGS.steps_per_epoch)
                 log('SEMI_SAMPLING_METHOD %s on the device: %d frustums with 3-D labels, %d with 2-D labels' % (
                     method, len(ds.semi[0]['host']), len(ds.semi[1]['host'])))
+            api.assert_ranks_agree(pg, world, lengths, 'the label subset (2D, 3D)')
+            log('Length of Train Dataset: (2D: %d, 3D: %d)' % lengths)       # train_semisup_adv.py:112
         for epoch in range(FLAGS.max_epoch):
             t0, loss_sum = time.time(), 0.0
             if ds is not None:
