@@ -1329,6 +1329,49 @@ typedef struct {
 #define T3D_V2_SIZE_sunrgbd_eval_args 256
 int t3d_sunrgbd_eval(const t3d_sunrgbd_eval_args* args, t3d_stream_t stream);
 
+/* ---- Detection decode of one inference batch (csrc/detect.hip; semisup_infer.inference(decode='device'), detect.Detector) ----
+ * What the reference does on the host after every batch (test_semisup.py:236-262, roi_seg_box3d_dataset.py:86-101, 461-466), in one
+ * launch, one workgroup of 256 threads per frustum, fp32 throughout:
+ *   seg[n]         = logits[n][1] > logits[n][0]                      (np.argmax: a tie is background)
+ *   mask_count     = sum_n seg[n];  mask_mean_prob = sum_n seg[n] * softmax(logits[n])[1] / (mask_count + 1)   (the "+ 1" is the reference's)
+ *   heading_cls    = argmax box_out[3:15], size_cls = argmax box_out[27:37]   (the lowest index on ties, as np.argmax; a NaN wins)
+ *   score          = log(mask_mean_prob + .01) + log(max softmax(heading scores) + .01) + log(max softmax(size scores) + .01)
+ *                    [+ log(fit_prob + .01)]
+ *   center         = box_out[0:3] + stage1_center - total_delta[0:3]
+ *   heading_res    = box_out[15 + heading_cls] * pi/12 - total_delta[6]
+ *   size_res       = box_out[37 + 3*size_cls ..] * mean_size[size_cls] - total_delta[3:6]
+ *   label          = (h, w, l, tx, ty, tz, ry) of from_prediction_to_label_format: (l, w, h) = mean_size[size_cls] + size_res,
+ *                    ry = heading_cls * 2pi/12 + heading_res, minus 2pi where it exceeds pi, plus rot_angle; (tx, tz) = the centre turned
+ *                    by -rot_angle about y; ty = center y + h/2 (the bottom of the box)
+ *   corners        = get_3d_box((l, w, h), ry, (tx, ty - h/2, tz)): rows 0-3 the +h/2 face
+ * box_out is a head output in BoxHeads order (centre 3, heading scores 12, normalised heading residuals 12, size scores 10, normalised
+ * size residuals 30), rows ld_box floats apart.  total_delta NULL: no F2_ refinement (zeros); fit_prob NULL: the three-term score;
+ * rot_angle NULL: 0; seg NULL: the mask is not written.  Frustums >= n_valid (the padding of a last batch) are not visited: their
+ * outputs keep what they held.  logits must be 8-byte aligned.  The mask sum is a fixed tree (per thread in point order, 64 lanes by
+ * shuffles, four waves in index order): equal inputs give equal bits, whatever B is.  No atomics, no host synchronisation. */
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_decode_args) of the caller's header (see T3D_ABI_VERSION) */
+  int B; int N; int n_valid; int ld_box;
+  const float* logits;          /* [B, N, 2] */
+  const float* box_out;         /* [B, ld_box], ld_box >= 67 */
+  const float* stage1_center;   /* [B, 3] */
+  const float* total_delta;     /* [B, 7] or NULL */
+  const float* fit_prob;        /* [B] or NULL */
+  const float* rot_angle;       /* [B] or NULL */
+  uint8_t* seg;                 /* [B, N] out or NULL */
+  float* score;                 /* [B] out */
+  int32_t* mask_count;          /* [B] out */
+  int32_t* heading_cls;         /* [B] out */
+  int32_t* size_cls;            /* [B] out */
+  float* center;                /* [B, 3] out */
+  float* heading_res;           /* [B] out */
+  float* size_res;              /* [B, 3] out */
+  float* label;                 /* [B, 7] out */
+  float* corners;               /* [B, 8, 3] out */
+} t3d_detect_decode_args;
+#define T3D_V2_SIZE_detect_decode_args 152
+int t3d_detect_decode(const t3d_detect_decode_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

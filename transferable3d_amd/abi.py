@@ -338,6 +338,12 @@ class LabelSubsetArgs(Sized):
                 ('seed', C.c_uint32), ('reserved', i32), ('ids', I), ('members', I), ('offsets', I), ('present', I), ('summary', I)]
 
 
+class DetectDecodeArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('B', i32), ('N', i32), ('n_valid', i32), ('ld_box', i32), ('logits', F), ('box_out', F),
+                ('stage1_center', F), ('total_delta', F), ('fit_prob', F), ('rot_angle', F), ('seg', U8), ('score', F), ('mask_count', I),
+                ('heading_cls', I), ('size_cls', I), ('center', F), ('heading_res', F), ('size_res', F), ('label', F), ('corners', F)]
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -438,6 +444,7 @@ ENTRY_POINTS = {
     't3d_cast_bf16': [F, VP, C.c_int64, VP],
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
+    't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }

@@ -90,6 +90,48 @@ class DeviceFrustumSet:
         return ds
 
     @classmethod
+    def from_device(cls, rt, extracted, keep, counts, cls_ids):
+        """The set from_detection_pickle would build from the frustum file of the same detections, without the file and without the
+        host: `extracted` is what sunrgbd_data.FrustumExtractor.run(on_device=True) returned (or a list of such launches), `keep` the jobs
+        of each launch that become frustums, `counts` their point counts on the host (the one thing read back: the reference drops
+        frustums of fewer than 5 points), `cls_ids` the class id of every kept frustum.  The fp64 points are gathered into the ragged
+        fp32 layout by torch indexing on the device (only the kept job numbers and counts go up) -- the cast is the rounding the pickle
+        route applies when it uploads."""
+        if isinstance(extracted, dict):
+            extracted, keep, counts = [extracted], [keep], [counts]
+        dev = rt.device
+        pts, ang = [], []
+        for o, k, c in zip(extracted, keep, counts):
+            k, c = np.asarray(k, np.int64), np.asarray(c, np.int64)
+            if len(k) == 0:
+                continue
+            J, NP, C_src = o['out_points'].shape
+            total = int(c.sum())
+            kd, cd = torch.as_tensor(k).to(dev), torch.as_tensor(c).to(dev)
+            # row of point i of kept job j: j * NP + (i - first point of j); the output size is known here, so nothing waits for the device
+            first = torch.cumsum(cd, 0) - cd
+            rows = torch.repeat_interleave(kd * NP - first, cd, output_size=total) + torch.arange(total, device=dev)
+            pts.append(o['out_points'].view(J * NP, C_src)[rows].to(torch.float32))
+            ang.append(o['frustum_angle'][kd].to(torch.float32))
+        counts = np.concatenate([np.asarray(c, np.int64) for c in counts]) if len(counts) else np.zeros(0, np.int64)
+        cls_ids = np.asarray(cls_ids, np.int64)
+        if not pts:
+            raise ValueError('no frustum is kept: a DeviceFrustumSet cannot be empty')
+        if len(cls_ids) != len(counts):
+            raise ValueError('%d class ids for %d kept frustums' % (len(cls_ids), len(counts)))
+        up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(dev)
+        ds = cls.__new__(cls)
+        ds.rt, ds.F = rt, len(counts)
+        ds.points, ds.frustum_angle = torch.cat(pts), torch.cat(ang)
+        ds.C_src = int(ds.points.shape[1])
+        ds.seg = torch.zeros(ds.points.shape[0], dtype=torch.int32, device=dev)
+        ds.offsets = up(np.concatenate([[0], np.cumsum(counts)]), torch.int64)
+        ds.box_center, ds.heading = torch.zeros(ds.F, 3, device=dev), torch.zeros(ds.F, device=dev)      # no 3-D labels, as from_detection_pickle
+        ds.size, ds.cls = up(MEAN_DIMS_ARR[cls_ids], torch.float32), up(cls_ids, torch.int32)
+        ds.perm = torch.arange(ds.F, dtype=torch.int32, device=dev)
+        return ds
+
+    @classmethod
     def synthetic(cls, rt, n_frustums, num_channel=6, seed=0, min_points=400, max_points=3000):
         """Frustums of the SURVEY 8d distribution with ragged point counts (real frustums have a few hundred to a few thousand)."""
         host = synthetic_frustums(n_frustums, num_channel, seed, min_points, max_points)
@@ -466,11 +508,11 @@ class DeviceEvalSource:
         """Indices (file order) of the frustums in batch i."""
         return (i * self.B + np.arange(self.B)) % self.ds.F
 
-    def load(self, i):
-        """Assemble batch i; returns its per-point labels [B, N]."""
+    def load(self, i, labels=True):
+        """Assemble batch i; returns its per-point labels [B, N] (labels=False: nothing is copied back, nothing waits for the device)."""
         self.counter[0] = float(i)
         self.plan.run()
-        return self.g.inputs.y_seg.view(self.B, -1).cpu().numpy()
+        return self.g.inputs.y_seg.view(self.B, -1).cpu().numpy() if labels else None
 
 
 def open_eval_source(graph, FLAGS, classes=None, boxpc_perturb=None):

@@ -126,13 +126,18 @@ def get_3d_box(box_size, heading_angle, center):
 
 def predictions_to_boxes(predictions, classes, test_classes=None):
     """The `B) Get PRED boxes` half of evaluate_predictions (evaluate.py:56-72): class2angle / class2size / get_3d_box in the
-    centre view, rotated back by -rot_angle.  -> {img_id: [(classname, corners (8,3), score)]}."""
+    centre view, rotated back by -rot_angle.  -> {img_id: [(classname, corners (8,3), score)]}.  Predictions that carry device-decoded
+    records (semisup_infer.Predictions.decoded) hand over their corners as they are."""
     _, _, _, center_l, hcls_l, hres_l, scls_l, sres_l, rot_l, score_l, cls_l, file_l = predictions[:12]
     out = {}
+    decoded = getattr(predictions, 'decoded', None)          # semisup_infer.Decoded: the corners came from t3d_detect_decode
     for i in range(len(center_l)):
         name = classes[int(cls_l[i])]
         if test_classes is not None and name not in test_classes:
             raise Exception('Not supposed to have class: %s' % name)              # evaluate.py:60
+        if decoded is not None:
+            out.setdefault(file_l[i], []).append((name, decoded.corners[i], float(score_l[i])))
+            continue
         heading = int(hcls_l[i]) * (2 * np.pi / NUM_HEADING_BIN) + float(hres_l[i])
         if heading > np.pi:
             heading -= 2 * np.pi

@@ -302,8 +302,12 @@ def official_predictions(test_classes, predictions, class_names):
     from .test_semisup import from_prediction_to_label_format
     _, _, _, center_l, hcls_l, hres_l, scls_l, sres_l, rot_l, score_l, _, id_l, _, _ = predictions
     rows = {c: [] for c in test_classes}
+    decoded = getattr(predictions, 'decoded', None)          # semisup_infer --device_decode: the label rows of t3d_detect_decode
     for i in range(len(center_l)):
-        vals = from_prediction_to_label_format(center_l[i], hcls_l[i], hres_l[i], scls_l[i], sres_l[i], float(rot_l[i]))
+        if decoded is not None:
+            vals = decoded.label[i]
+        else:
+            vals = from_prediction_to_label_format(center_l[i], hcls_l[i], hres_l[i], scls_l[i], sres_l[i], float(rot_l[i]))
         rows[class_names[i]].append((int(id_l[i]),) + tuple(float(v) for v in vals) + (float(score_l[i]),))
     out = {}
     for c, r in rows.items():
@@ -316,7 +320,7 @@ def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test
     """test_semisup's run (its own command line: a frustum file with --data_path, or its synthetic frustums, whose image ids are their
     indices), then `evaluate` on the predictions it returns.  With --result_dir among its flags the same run also writes the
     <class>_pred.txt files."""
-    from . import test_semisup as TS
+    from . import semisup_infer as TS              # test_semisup's driver, plus --device_decode
     from .constants import class2type
     FLAGS = TS.build_flags(list(test_semisup_argv))
     predictions = TS.test(FLAGS, rt=rt, log=log)

@@ -1,0 +1,221 @@
+#!/usr/bin/env python3
+"""test_semisup with the detections decoded on the device (t3d_detect_decode, csrc/detect.hip).
+
+    python -m transferable3d_amd.semisup_infer --device_decode <test_semisup's flags>
+
+test_semisup's `inference` fetches every batch's logits and six head tensors and decodes them in fp64 NumPy, and its result writers
+loop over the detections.  `inference(decode='device')` here follows a batch's graph with one t3d_detect_decode launch on the same
+stream, fetches nothing in between, and copies the decoded records (plus the uint8 masks where the caller needs them) back once at
+the end.  `test` is test_semisup's driver run with that inference (device_decode_driver); without --device_decode every function
+here hands over to test_semisup's, so nothing that exists changes its numbers.
+"""
+import contextlib
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import torch
+
+if __package__ in (None, ''):
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from transferable3d_amd import abi, test_semisup as TS                   # noqa: E402
+from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
+
+
+def build_flags(argv=None):
+    """test_semisup.build_flags plus --device_decode (test_semisup's parser is built inside its build_flags and refuses a flag it does
+    not declare, so the flag is taken out of argv here)."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    device = '--device_decode' in argv
+    FLAGS = TS.build_flags([a for a in argv if a != '--device_decode'])
+    FLAGS.device_decode = device
+    return FLAGS
+
+
+class Decoded:
+    """The records of t3d_detect_decode in host memory, one row per detection: score, mask_count, heading_cls, size_cls, center [n,3],
+    heading_res, size_res [n,3], label [n,7] = (h, w, l, tx, ty, tz, ry) as from_prediction_to_label_format, corners [n,8,3] as
+    get_3d_box in the camera frame.  It travels beside the 14-list; write_detection_results, evaluate_sunrgbd.official_predictions and
+    eval_det.evaluate_predictions read label / corners from it instead of looping over the detections."""
+    FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
+
+    def __init__(self, **fields):
+        for k in self.FIELDS:
+            setattr(self, k, fields[k])
+
+    def __len__(self):
+        return len(self.score)
+
+    def __getitem__(self, sel):
+        """Rows `sel` (a slice or an index array)."""
+        return Decoded(**{k: getattr(self, k)[sel] for k in self.FIELDS})
+
+
+class Predictions(list):
+    """test_semisup's 14-list; `.decoded` (Decoded or None) holds the device-decoded records of the same detections."""
+    decoded = None
+
+
+class InferenceResult(tuple):
+    """The 7-tuple of `inference`; `.decoded` as above."""
+    decoded = None
+
+
+class DeviceDecode:
+    """Output buffers of t3d_detect_decode for `n` frustums (planar sections of one fp32 and one int32 allocation, so that everything
+    comes back in two copies) and the launch of one batch of them."""
+    WIDTH = (('score', 1), ('center', 3), ('heading_res', 1), ('size_res', 3), ('label', 7), ('corners', 24))
+    INTS = ('mask_count', 'heading_cls', 'size_cls')
+
+    def __init__(self, rt, n, num_point, want_seg=False):
+        self.rt, self.n, self.N = rt, n, num_point
+        self.f = rt.zeros(n * sum(w for _, w in self.WIDTH))
+        self.i = rt.zeros(n * len(self.INTS), dtype=torch.int32)
+        self.seg = rt.zeros(n, num_point, dtype=torch.uint8) if want_seg else None
+        self.sec, o = {}, 0
+        for k, w in self.WIDTH:
+            self.sec[k] = self.f[o:o + n * w].view(n, w)
+            o += n * w
+        for j, k in enumerate(self.INTS):
+            self.sec[k] = self.i[j * n:(j + 1) * n]
+
+    def launch(self, first, B, n_valid, logits, box_out, stage1_center, total_delta=None, fit_prob=None, rot_angle=None):
+        """Decode the batch whose frustums are rows first .. first + B - 1 of the outputs; the first `n_valid` of them are real."""
+        assert 0 <= first and first + B <= self.n and logits.numel() == B * self.N * 2
+        o = {k: v[first:first + B] for k, v in self.sec.items()}
+        a = abi.DetectDecodeArgs(B, self.N, int(n_valid), int(box_out.stride(0)), fptr(logits), fptr(box_out), fptr(stage1_center),
+                                 fptr(total_delta), fptr(fit_prob), fptr(rot_angle), abi.u8ptr(None if self.seg is None else self.seg[first:]),
+                                 fptr(o['score']), iptr(o['mask_count']), iptr(o['heading_cls']), iptr(o['size_cls']), fptr(o['center']),
+                                 fptr(o['heading_res']), fptr(o['size_res']), fptr(o['label']), fptr(o['corners']))
+        abi.check(self.rt.lib.t3d_detect_decode(C.byref(a), self.rt.stream()), 't3d_detect_decode')
+
+    def fetch(self):
+        """-> (Decoded, masks [n, N] uint8 or None): the copies back."""
+        f, i = self.f.cpu().numpy().astype(np.float64), self.i.cpu().numpy().astype(np.int64)
+        n, out, o = self.n, {}, 0
+        for k, w in self.WIDTH:
+            out[k] = f[o:o + n * w].reshape((n, w) if w > 1 else (n,))
+            o += n * w
+        out['corners'] = out['corners'].reshape(n, 8, 3)
+        for j, k in enumerate(self.INTS):
+            out[k] = i[j * n:(j + 1) * n]
+        return Decoded(**out), (None if self.seg is None else self.seg.cpu().numpy())
+
+
+def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
+    """The device buffers behind the heads `prefix` of an inference graph: (logits, box_out [B, >= 67], stage1_center, total_delta or
+    None, fit_prob or None).  The F2_ heads are the F_ heads minus the accumulated Box-PC deltas (semisup_v1_sunrgbd.get_semi_model_final)."""
+    ep = ops['end_points']
+    box = ep[prefix + 'heading_scores'].src                 # semisup_models.BoxHeads slices the [B, 67] head output
+    delta = None
+    src = getattr(ep[prefix + 'center'], 'src', None)
+    if src is not box:                                      # a refined centre: its source is the accumulated deltas
+        if getattr(src, 'name', None) != 'total_delta':
+            raise NotImplementedError('decode on the device: the %s heads are not a head output minus total_delta' % prefix)
+        delta = src.buf
+    fit = ep['boxpc_fit_prob'].buf if use_boxpc_fit_prob else None
+    bufs = (ops['logits'].buf, box.buf, ep['stage1_center'].buf, delta, fit)
+    if any(t is not None and t.element_size() < 4 for t in bufs):
+        raise NotImplementedError('decode on the device reads fp32 logits and heads')
+    return bufs
+
+
+def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
+              decode='host', want_seg=True):
+    """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
+    returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
+    padded last batch are zeros."""
+    if decode == 'host':
+        return TS.inference(sess, ops, pc, one_hot_vec, batch_size, prefix=prefix, use_boxpc_fit_prob=use_boxpc_fit_prob, source=source,
+                            n_batches=n_batches, oracle_mask=oracle_mask)
+    if decode != 'device':
+        raise ValueError("decode is 'host' or 'device'")
+    if source is not None:
+        n, npts = n_batches * batch_size, sess.g.engine.rpf
+    else:
+        assert pc.shape[0] % batch_size == 0
+        n, npts = pc.shape[0], pc.shape[1]
+    rt = sess.g.rt
+    logits, box, s1, delta, fit = decode_sources(ops, prefix, use_boxpc_fit_prob)
+    dec = DeviceDecode(rt, n, npts, want_seg=want_seg)
+    total = source.ds.F if source is not None else n                 # the frustums past it pad the last batch
+    rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
+    for i in range(n // batch_size):
+        sl = slice(i * batch_size, (i + 1) * batch_size)
+        if source is not None:
+            source.load(i, labels=False)
+            sess.run([])
+        else:
+            feed = {ops['pc_pl']: pc[sl], ops['one_hot_vec_pl']: one_hot_vec[sl]}
+            if oracle_mask is not None:
+                feed[ops['y_seg_pl']] = np.asarray(oracle_mask[sl], np.int32)
+            sess.run([], feed_dict=feed)
+        dec.launch(sl.start, batch_size, max(0, min(batch_size, total - sl.start)), logits, box, s1, delta, fit, rot)
+    d, seg = dec.fetch()
+    res = InferenceResult((None if seg is None else seg.astype(np.int64), d.center, d.heading_cls, d.heading_res, d.size_cls, d.size_res,
+                           d.score))
+    res.decoded = d
+    return res
+
+
+def write_detection_results(result_dir, test_classes, predictions, class_names):
+    """test_semisup.write_detection_results; predictions that carry decoded records are written from their label rows."""
+    decoded = getattr(predictions, 'decoded', None)
+    if decoded is None:
+        return TS.write_detection_results(result_dir, test_classes, predictions, class_names)
+    os.makedirs(result_dir, exist_ok=True)
+    files = {c: open(os.path.join(result_dir, c + '_pred.txt'), 'w') for c in test_classes}
+    score_l, id_l, box2d_l = predictions[9], predictions[11], predictions[12]
+    for i in range(len(decoded)):
+        box2d = box2d_l[i] if box2d_l is not None else (0.0, 0.0, 0.0, 0.0)
+        files[class_names[i]].write('%d %s -1 -1 -10 %f %f %f %f %f %f %f %f %f %f %f %f\n' % (
+            (int(id_l[i]), class_names[i], box2d[0], box2d[1], box2d[2], box2d[3]) + tuple(decoded.label[i]) + (float(score_l[i]),)))
+    for f in files.values():
+        f.close()
+
+
+@contextlib.contextmanager
+def device_decode_driver(FLAGS):
+    """test_semisup's driver functions (`test`, `test_on_frustum_file`) look three names up at the moment they call them: `inference` and
+    `write_detection_results` in their own module, `evaluate_predictions` in eval_det.  For the length of one run those names are bound
+    to the versions that decode on the device and that read the decoded records; everything else of the driver -- weights, batches, the
+    14-list, the ground truth of --evaluate, --gt_path, --output -- is test_semisup's own code, run once, not copied.  Yields the
+    function that attaches the run's records to its 14-list.  One run at a time per process: the binding is module-wide."""
+    from transferable3d_amd import eval_det
+    run = {}
+
+    def attach(predictions):
+        p = Predictions(predictions)
+        p.decoded = run.get('decoded')
+        return p
+
+    def infer(sess, ops, pc, one_hot_vec, batch_size, **kw):
+        source = kw.get('source')
+        res = inference(sess, ops, pc, one_hot_vec, batch_size, decode='device', want_seg=source is None or bool(FLAGS.output), **kw)
+        run['decoded'] = res.decoded[slice(0, source.ds.F if source is not None else len(res.decoded))]      # without the padding
+        seg = res[0] if res[0] is not None else np.full(len(res.decoded), None)      # (no --output: the masks stayed on the device)
+        return (seg,) + tuple(res[1:])
+
+    real_evaluate = eval_det.evaluate_predictions
+    saved = (TS.inference, TS.write_detection_results)
+    TS.inference = infer
+    TS.write_detection_results = lambda d, classes, predictions, names: write_detection_results(d, classes, attach(predictions), names)
+    eval_det.evaluate_predictions = lambda predictions, *a, **kw: real_evaluate(attach(predictions), *a, **kw)
+    try:
+        yield attach
+    finally:
+        TS.inference, TS.write_detection_results = saved
+        eval_det.evaluate_predictions = real_evaluate
+
+
+def test(FLAGS, rt=None, log=print):
+    """test_semisup.test -> Predictions (its 14-list; with FLAGS.device_decode the decoded records as `.decoded`)."""
+    if not getattr(FLAGS, 'device_decode', False):
+        return Predictions(TS.test(FLAGS, rt=rt, log=log))
+    with device_decode_driver(FLAGS) as attach:
+        return attach(TS.test(FLAGS, rt=rt, log=log))
+
+
+if __name__ == '__main__':
+    test(build_flags())

@@ -152,13 +152,15 @@ class FrustumExtractor:
         self.rt, self.num_points, self.seed = rt, num_points, seed
         self.last_kernel_ms = None
 
-    def run(self, scenes, jobs, perturb_box2d=False, timed=False):
+    def run(self, scenes, jobs, perturb_box2d=False, timed=False, on_device=False):
         """scenes: [{'points': (N, C) fp64 upright depth, 'Rtilt', 'K'}]; jobs (grouped by scene, in scene order): [{'scene': batch index,
         'box2d', 'box3d': (8,3) or None, 'key': (scene id, ordinal, aug), 'perturb': 4 uniforms or None, 'choice': ranks or None}].
-        Returns per job {'box2d', 'frustum_angle', 'n', 'index', 'points', 'label'}."""
+        Returns per job {'box2d', 'frustum_angle', 'n', 'index', 'points', 'label'}.  on_device=True: nothing is copied back; returns the
+        device tensors of the launch instead ({'box2d_out' [J,4], 'frustum_angle' [J], 'n_in_box' [J], 'count' [J], 'index' [J,NP],
+        'out_points' [J,NP,C] fp64, 'label' [J,NP]}; DeviceFrustumSet.from_device takes them), None for no jobs."""
         dev, NP, J, S = self.rt.device, self.num_points, len(jobs), len(scenes)
         if J == 0:
-            return []
+            return None if on_device else []
         sc = np.array([j['scene'] for j in jobs])
         if np.any(np.diff(sc) < 0) or sc.min() < 0 or sc.max() >= S:
             raise ValueError('jobs must be grouped by scene, in scene order')
@@ -217,6 +219,8 @@ class FrustumExtractor:
         abi.check(self.rt.lib.t3d_frustum_extract(C.byref(a), self.rt.stream()), 't3d_frustum_extract')
         if cuda and timed:
             ev[1].record()
+        if on_device:
+            return {k: v for k, v in o.items() if k not in ('masks', 'seg_prefix')}
         h = {k: v.cpu().numpy() for k, v in o.items() if k not in ('masks', 'seg_prefix')}     # the one copy back (synchronises)
         if cuda and timed:
             self.last_kernel_ms = ev[0].elapsed_time(ev[1])
