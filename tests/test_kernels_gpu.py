@@ -1,6 +1,10 @@
-"""GPU: every HIP entry point of libt3d.so against the NumPy executable specification (tests/fake_t3d.py)
+"""GPU: the HIP entry points of libt3d.so against the NumPy executable specification (tests/fake_t3d.py)
 on identical seeded inputs, called through the C ABI (ctypes).  Sizes are small enough that the fp64 spec
-finishes in seconds; tolerances are fp32 accumulation bounds, written per test."""
+finishes in seconds; tolerances are fp32 accumulation bounds, written per test.  The Box-PC, refinement and
+glue entry points this module does not reach (t3d_box_refine_step_bwd, t3d_boxpc_rep_b, t3d_box2d_feats,
+t3d_act_dropout, t3d_pool_bwd_mid) and the remaining argument branches of t3d_box_refine_step, t3d_boxpc_rep,
+t3d_boxpc_rep_bwd and t3d_boxpc_loss are in tests/test_kernels_glue_gpu.py; the bf16 variants in
+tests/test_kernels_bf16_gpu.py."""
 import ctypes as C
 
 import numpy as np
