@@ -1091,6 +1091,17 @@ int t3d_adam_tf_step(float* params, const float* grads, float* m, float* v, int6
                      const float* hyper, float beta1, float beta2, float eps, float grad_scale,
                      t3d_stream_t stream);
 
+/* t3d_reduce_slabs + t3d_adam_tf_step in one pass over the elements (single replica, Adam over every variable): the workgroups that
+ * sum a slab tensor's elements (t3d_reduce_slabs' grid, order and accumulators) write the gradient and apply the update to the same
+ * elements from registers; `n_range_blocks` more workgroups apply it to the elements no slab tensor covers, whose gradients were
+ * written directly: range i = [off, off + n) of the flat buffers, its first workgroup blk0 (ascending over the table; a range owns
+ * ceil(n / 1024) workgroups, n_range_blocks = their sum).  params / m / v share grad_base's element offsets.  The caller guarantees
+ * that slab tensors and ranges are disjoint: every element is updated once.  Same bits as the two separate launches. */
+typedef struct { int64_t off; int64_t n; int32_t blk0; int32_t reserved; } t3d_adam_range;
+int t3d_reduce_slabs_adam(const float* slab_base, float* grad_base, const t3d_slab_desc* table_dev, int n_tensors, int max_numel,
+                          float* params, float* m, float* v, const t3d_adam_range* ranges_dev, int n_ranges, int n_range_blocks,
+                          const float* hyper, float beta1, float beta2, float eps, float grad_scale, t3d_stream_t stream);
+
 /* fp32 GEMMs on the bf16 matrix pipe (csrc/pointmlp.hip PathX3): x = h + m + l exactly with h = bf16(x), m = bf16(x - h),
  * l = bf16(x - h - m).  Writes the three planes of src[0..n): planes[p * plane_stride + i] (bf16 elements, plane_stride >= n).  The
  * optimiser's fp32 weights are split ONCE per step this way instead of once per tile that stages them. */
@@ -1113,6 +1124,16 @@ typedef struct {
 /* n_blocks = the sum of ceil(K N / 2048) over the table (one 256-thread workgroup per 256 eight-element fragments) */
 int t3d_split_x3_frag(const float* params, void* planes_fwd, void* planes_dgrad, int64_t plane_stride, const t3d_x3_frag_entry* table,
                       int n_entries, int n_blocks, t3d_stream_t stream);
+
+/* The head of a training step in one launch: t3d_schedule_step, t3d_split_x3_frag and the forward of a net's first layer
+ * (t3d_pointmlp_fwd on fp32 with K <= 4, N = 64 or 128 and a raw input -- no scale / shift / sub: the register kernel, which reads the fp32 weights) are independent of each
+ * other -- none reads `hyper` or the planes -- and run as workgroup roles: M / 128 forward tiles, then n_blocks split workgroups,
+ * then one workgroup for the schedule.  Same bits as the three launches.  T3D_ERR_ARG if `fwd` is not such a layer. */
+/* 1 / 0: would t3d_step_head accept this forward struct (the library's own statement of which launch is such a layer) */
+int t3d_step_head_takes(const t3d_pointmlp_fwd_args* fwd);
+int t3d_step_head(const t3d_pointmlp_fwd_args* fwd, const float* params, void* planes_fwd, void* planes_dgrad, int64_t plane_stride,
+                  const t3d_x3_frag_entry* table, int n_entries, int n_blocks, float* hyper, const t3d_schedule* sched,
+                  t3d_stream_t stream);
 
 /* tf.train.MomentumOptimizer(learning_rate, momentum) of `--optimizer momentum` (train_semisup.py:226-228, train_boxpc.py:247,
  * train_semisup_adv.py:296), TF form without Nesterov: accum = momentum * accum + g * grad_scale;  w -= lr * accum, with

@@ -245,6 +245,32 @@ class SlabDesc(C.Structure):
     _fields_ = [('slab_off', C.c_int64), ('grad_off', C.c_int64), ('numel', C.c_int32), ('n_slabs', C.c_int32)]
 
 
+class AdamRange(C.Structure):      # t3d_adam_range (t3d_reduce_slabs_adam)
+    _fields_ = [('off', C.c_int64), ('n', C.c_int64), ('blk0', C.c_int32), ('reserved', C.c_int32)]
+
+
+ADAM_RANGE_ELEMS = 1024      # elements per workgroup of a range (csrc/bn_optim.hip)
+
+
+def adam_range_table(n_total, slab_tensors):
+    """([(off, n, blk0), ...], number of workgroups): the ranges of [0, n_total) that no slab tensor [(grad_off, numel), ...] covers.
+    Raises unless the slab tensors lie inside [0, n_total) and do not overlap -- with the ranges they then partition it, so that
+    t3d_reduce_slabs_adam updates every element exactly once."""
+    out, pos, blk = [], 0, 0
+    for off, n in sorted(slab_tensors):
+        if n <= 0 or off < pos or off + n > n_total:
+            raise T3DError('slab tensors overlap or leave the parameter buffer: (%d, %d) after %d of %d' % (off, n, pos, n_total))
+        if off > pos:
+            out.append((pos, off - pos, blk))
+            blk += (off - pos + ADAM_RANGE_ELEMS - 1) // ADAM_RANGE_ELEMS
+        pos = off + n
+    if pos < n_total:
+        out.append((pos, n_total - pos, blk))
+        blk += (n_total - pos + ADAM_RANGE_ELEMS - 1) // ADAM_RANGE_ELEMS
+    assert sum(n for _, n, _ in out) + sum(n for _, n in slab_tensors) == n_total
+    return out, blk
+
+
 class Schedule(C.Structure):
     _fields_ = [('base_lr', f32), ('lr_decay_rate', f32), ('lr_decay_step', f32), ('bn_init_decay', f32),
                 ('bn_decay_rate', f32), ('bn_decay_step', f32), ('bn_decay_clip', f32), ('beta1', f32), ('beta2', f32),
@@ -436,6 +462,9 @@ ENTRY_POINTS = {
     't3d_anchor_reg_bwd': [C.POINTER(AnchorRegBwdArgs), VP],
     't3d_reduce_slabs': [F, F, C.POINTER(SlabDesc), i32, i32, VP],
     't3d_schedule_step': [F, C.POINTER(Schedule), VP],
+    't3d_reduce_slabs_adam': [F, F, C.POINTER(SlabDesc), i32, i32, F, F, F, C.POINTER(AdamRange), i32, i32, F, f32, f32, f32, f32, VP],
+    't3d_step_head_takes': [C.POINTER(PointMlpFwdArgs)],
+    't3d_step_head': [C.POINTER(PointMlpFwdArgs), F, VP, VP, C.c_int64, VP, i32, i32, F, C.POINTER(Schedule), VP],
     't3d_adam_tf_step': [F, F, F, F, C.c_int64, F, f32, f32, f32, f32, VP],
     't3d_momentum_step': [F, F, F, C.c_int64, F, f32, f32, VP],
     't3d_split_x3': [F, VP, C.c_int64, C.c_int64, VP],

@@ -229,21 +229,58 @@ __device__ __forceinline__ void dy_colsum_body(const t3d_dy_colsum_args& p, cons
   p.out[i] = (float)((double)p.alpha * v);
 }
 
+// tf.train.AdamOptimizer, TF form, on one element: updates the moments and returns what the weight loses.  The ONE place the update
+// is written (k_adam_tf and the fused slab reduction + Adam launch inline it, so that both round alike).
+__device__ __forceinline__ float adam_tf_elem(const float g, float& m, float& v, const float lr_t, const float b1, const float b2,
+                                              const float eps, const float gscale) {
+  // every product and sum rounded on its own, as k_adam_tf has always computed it (left to the compiler, whether a product is
+  // contracted into an fma depends on the code around the inlined update)
+#pragma clang fp contract(off)
+  const float gi = g * gscale;
+  const float mi = b1 * m + (1.f - b1) * gi;
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi;
+  v = vi;
+  return lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// what the fused slab reduction + Adam launch (t3d_reduce_slabs_adam) adds to the reduction: params / m / v share the gradient
+// buffer's element offsets
+struct adam_tail {
+  float* w;
+  float* m;
+  float* v;
+  const float* hyper;
+  float b1, b2, eps, gscale;
+};
+
 // every slab region starts 16-byte aligned and numel % 4 == 0 for the engine's allocations (float4 path); anything
 // else takes the scalar path.  A block = 32 float4 elements x 8 slab groups: thread (e, g) sums slabs g, g+8, ... with
 // four loads in flight, the 8 group sums are combined through LDS in a fixed order.  Splitting the slab chain over
 // threads is what keeps the many-slab / few-element tensors (64x64 layers with 256 slabs) from being one long latency
 // chain while the rest of the chip idles.
+// ADAM: the thread that writes a reduced gradient element also applies the optimiser's update to it, from registers (its m / v / w
+// loads are issued before the slab loop and are in flight beside it).  The sums, their order and the gradient store are the same in
+// both forms.
+template <bool ADAM = false>
 __device__ __forceinline__ void reduce_slabs_body(const float* __restrict__ slab_base, float* __restrict__ grad_base,
                                                   const t3d_slab_desc* __restrict__ table, float4 (*part)[32], int bx, int by,
-                                                  int gx) {
+                                                  int gx, const adam_tail* ad = nullptr) {
   const t3d_slab_desc d = table[by];
+  float lr_t = 0.f;
+  if constexpr (ADAM) lr_t = ad->hyper[3];
   const bool vec = ((d.slab_off | d.grad_off | (int64_t)d.numel) & 3) == 0;
   const int n4 = vec ? (d.numel >> 2) : 0;
   const int el = threadIdx.x & 31, grp = threadIdx.x >> 5;
   for (int e0 = bx * 32; e0 < n4; e0 += gx * 32) {
     const int e = e0 + el;
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+    float4 w4, m4, v4;
+    if constexpr (ADAM) if (grp == 0 && e < n4) {
+      w4 = reinterpret_cast<const float4*>(ad->w + d.grad_off)[e];
+      m4 = reinterpret_cast<const float4*>(ad->m + d.grad_off)[e];
+      v4 = reinterpret_cast<const float4*>(ad->v + d.grad_off)[e];
+    }
     if (e < n4) {
       const float4* s = reinterpret_cast<const float4*>(slab_base + d.slab_off) + e;
       int k = grp;
@@ -285,6 +322,15 @@ __device__ __forceinline__ void reduce_slabs_body(const float* __restrict__ slab
         t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
       }
       reinterpret_cast<float4*>(grad_base + d.grad_off)[e] = t;
+      if constexpr (ADAM) {
+        w4.x -= adam_tf_elem(t.x, m4.x, v4.x, lr_t, ad->b1, ad->b2, ad->eps, ad->gscale);
+        w4.y -= adam_tf_elem(t.y, m4.y, v4.y, lr_t, ad->b1, ad->b2, ad->eps, ad->gscale);
+        w4.z -= adam_tf_elem(t.z, m4.z, v4.z, lr_t, ad->b1, ad->b2, ad->eps, ad->gscale);
+        w4.w -= adam_tf_elem(t.w, m4.w, v4.w, lr_t, ad->b1, ad->b2, ad->eps, ad->gscale);
+        reinterpret_cast<float4*>(ad->m + d.grad_off)[e] = m4;
+        reinterpret_cast<float4*>(ad->v + d.grad_off)[e] = v4;
+        reinterpret_cast<float4*>(ad->w + d.grad_off)[e] = w4;
+      }
     }
     __syncthreads();
   }
@@ -293,8 +339,38 @@ __device__ __forceinline__ void reduce_slabs_body(const float* __restrict__ slab
       float acc = 0.f;
       for (int k = 0; k < d.n_slabs; ++k) acc += slab_base[d.slab_off + (size_t)k * d.numel + e];
       grad_base[d.grad_off + e] = acc;
+      if constexpr (ADAM) {
+        const size_t o = (size_t)d.grad_off + e;
+        float mi = ad->m[o], vi = ad->v[o];
+        const float dw = adam_tf_elem(acc, mi, vi, lr_t, ad->b1, ad->b2, ad->eps, ad->gscale);
+        ad->m[o] = mi;
+        ad->v[o] = vi;
+        ad->w[o] -= dw;
+      }
     }
   }
+}
+
+// One wave (every lane of it calls this).  The four pow() of the schedule are independent dependent-chains of a few hundred
+// instructions each: lanes 0-3 take one each (same function, same arguments as the one-thread form: bit-identical), lane 0 combines them.
+__device__ __forceinline__ void schedule_step_body(float* hyper, const t3d_schedule s, const int lane) {
+  // global step BEFORE this update drives lr / bn_decay (tf: minimize() increments after use)
+  const double step = (double)hyper[0] + (double)s.step_offset;
+  const double seen = step * (double)s.batch_size;
+  const double t = step + 1.0;   // Adam's t starts at 1
+  const double base = lane == 0 ? (double)s.lr_decay_rate : lane == 1 ? (double)s.bn_decay_rate : lane == 2 ? (double)s.beta2 : (double)s.beta1;
+  const double expo = lane == 0 ? floor(seen / (double)s.lr_decay_step) : lane == 1 ? floor(seen / (double)s.bn_decay_step) : t;
+  const double pw = lane < 4 ? pow(base, expo) : 0.0;
+  const double p_lr = __shfl(pw, 0), p_bn = __shfl(pw, 1), p_b2 = __shfl(pw, 2), p_b1 = __shfl(pw, 3);
+  if (lane != 0) return;
+  const double lr = (double)s.base_lr * p_lr;
+  const double bnm = (double)s.bn_init_decay * p_bn;
+  const double bnd = fmin((double)s.bn_decay_clip, 1.0 - bnm);
+  const double lr_t = lr * sqrt(1.0 - p_b2) / (1.0 - p_b1);
+  hyper[1] = (float)lr;
+  hyper[2] = (float)bnd;
+  hyper[3] = (float)lr_t;
+  hyper[0] = (float)t;
 }
 
 

@@ -53,28 +53,9 @@ __global__ __launch_bounds__(256) void k_pool_bwd_mid(const float* __restrict__ 
   }
 }
 
-// One wave.  The four pow() of the schedule are independent dependent-chains of a few hundred instructions each: lanes 0-3 take one
-// each (same function, same arguments as the one-thread form: bit-identical), lane 0 combines them.
 __global__ __launch_bounds__(64) void k_schedule_step(float* hyper, const t3d_schedule s) {
   if (blockIdx.x != 0) return;
-  const int lane = threadIdx.x;
-  // global step BEFORE this update drives lr / bn_decay (tf: minimize() increments after use)
-  const double step = (double)hyper[0] + (double)s.step_offset;
-  const double seen = step * (double)s.batch_size;
-  const double t = step + 1.0;   // Adam's t starts at 1
-  const double base = lane == 0 ? (double)s.lr_decay_rate : lane == 1 ? (double)s.bn_decay_rate : lane == 2 ? (double)s.beta2 : (double)s.beta1;
-  const double expo = lane == 0 ? floor(seen / (double)s.lr_decay_step) : lane == 1 ? floor(seen / (double)s.bn_decay_step) : t;
-  const double pw = lane < 4 ? pow(base, expo) : 0.0;
-  const double p_lr = __shfl(pw, 0), p_bn = __shfl(pw, 1), p_b2 = __shfl(pw, 2), p_b1 = __shfl(pw, 3);
-  if (lane != 0) return;
-  const double lr = (double)s.base_lr * p_lr;
-  const double bnm = (double)s.bn_init_decay * p_bn;
-  const double bnd = fmin((double)s.bn_decay_clip, 1.0 - bnm);
-  const double lr_t = lr * sqrt(1.0 - p_b2) / (1.0 - p_b1);
-  hyper[1] = (float)lr;
-  hyper[2] = (float)bnd;
-  hyper[3] = (float)lr_t;
-  hyper[0] = (float)t;
+  schedule_step_body(hyper, s, threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_adam_tf(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
@@ -82,12 +63,49 @@ __global__ __launch_bounds__(256) void k_adam_tf(float* __restrict__ w, const fl
                                                  float b1, float b2, float eps, float gscale) {
   const float lr_t = hyper[3];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    float mi = m[i], vi = v[i];
+    const float dw = adam_tf_elem(g[i], mi, vi, lr_t, b1, b2, eps, gscale);
     m[i] = mi;
     v[i] = vi;
-    w[i] -= lr_t * mi / (sqrtf(vi) + eps);
+    w[i] -= dw;
+  }
+}
+
+// Slab reduction and Adam in one pass: blocks [0, n_reduce) reduce (logical grid gx x n_tensors) and update the elements they reduced
+// from registers; the rest walk the elements of the parameter buffer no slab tensor covers (FC weights, biases, gamma / beta: their
+// gradients were written directly), ADAM_RANGE_ELEMS per block of a range of the device table (a range's first block in `blk0`,
+// ascending).  The host guarantees that slab tensors and ranges partition the updated elements: each is updated exactly once.
+constexpr int ADAM_RANGE_ELEMS = 1024;
+__global__ __launch_bounds__(256) void k_reduce_slabs_adam(const float* __restrict__ slab_base, float* __restrict__ grad_base,
+                                                           const t3d_slab_desc* __restrict__ table, const int gx, const int n_reduce,
+                                                           const t3d_adam_range* __restrict__ ranges, const int n_ranges,
+                                                           const adam_tail ad) {
+  __shared__ float4 part[8][32];
+  const int b = blockIdx.x;
+  if (b < n_reduce) {
+    reduce_slabs_body<true>(slab_base, grad_base, table, part, b % gx, b / gx, gx, &ad);
+    return;
+  }
+  const int r = b - n_reduce;
+  int lo = 0, hi = n_ranges - 1;      // the last range whose first block is <= r
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (ranges[mid].blk0 <= r) lo = mid; else hi = mid - 1;
+  }
+  const t3d_adam_range rg = ranges[lo];
+  const float lr_t = ad.hyper[3];
+  const int64_t i0 = (int64_t)(r - rg.blk0) * ADAM_RANGE_ELEMS + threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < ADAM_RANGE_ELEMS / 256; ++u) {
+    const int64_t i = i0 + 256 * u;
+    if (i < rg.n) {
+      const int64_t o = rg.off + i;
+      float mi = ad.m[o], vi = ad.v[o];
+      const float dw = adam_tf_elem(grad_base[o], mi, vi, lr_t, ad.b1, ad.b2, ad.eps, ad.gscale);
+      ad.m[o] = mi;
+      ad.v[o] = vi;
+      ad.w[o] -= dw;
+    }
   }
 }
 
@@ -209,6 +227,23 @@ extern "C" int t3d_adam_tf_step(float* params, const float* grads, float* m, flo
   if (blocks > 2048) blocks = 2048;
   T3D_LAUNCH(k_adam_tf, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), params, grads, m,
                      v, n, hyper, beta1, beta2, eps, grad_scale);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+extern "C" int t3d_reduce_slabs_adam(const float* slab_base, float* grad_base, const t3d_slab_desc* table_dev, int n_tensors,
+                                     int max_numel, float* params, float* m, float* v, const t3d_adam_range* ranges_dev, int n_ranges,
+                                     int n_range_blocks, const float* hyper, float beta1, float beta2, float eps, float grad_scale,
+                                     t3d_stream_t stream) {
+  if (!slab_base || !grad_base || !table_dev || n_tensors <= 0 || !params || !m || !v || !hyper) return T3D_ERR_ARG;
+  if (n_ranges < 0 || n_range_blocks < 0 || (n_ranges == 0) != (n_range_blocks == 0) || (n_ranges > 0 && !ranges_dev)) return T3D_ERR_ARG;
+  int gx = (max_numel / 4 + 31) / 32;      // (t3d_reduce_slabs' grid: the same blocks sum the same elements)
+  if (gx > 256) gx = 256;
+  if (gx < 1) gx = 1;
+  const int n_reduce = gx * n_tensors;
+  const adam_tail ad = {params, m, v, hyper, beta1, beta2, eps, grad_scale};
+  T3D_LAUNCH(k_reduce_slabs_adam, dim3(n_reduce + n_range_blocks), dim3(256), 0, static_cast<hipStream_t>(stream), slab_base, grad_base,
+             table_dev, gx, n_reduce, ranges_dev, n_ranges, ad);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }

@@ -2080,13 +2080,13 @@ __global__ __launch_bounds__(NT, MIN_WAVES_PER_EU) void k_pointmlp_fwd_res(const
 // order (the MFMA path sums the same products in a permuted k order: results agree to the last bits, not bit for bit).  At
 // B=32 N=1024 the generic kernel took 9.2 us per launch for the two 3 -> 128 layers and 7.6 us for 4 -> 64, against 2.7 / 1.4 us of
 // HBM time for the output.
-template <int N, class YT = bf16_t>
-__global__ __launch_bounds__(NT) void k_pointmlp_fwd_tinyk(const t3d_pointmlp_fwd_args p) {
+// (a __device__ body: the stand-alone kernel and the step-head kernel k_step_head run it; `red`: 2 * NT / (N / 8) * N floats = 16 KB)
+template <int N, class YT>
+__device__ __forceinline__ void pointmlp_fwd_tinyk_body(const t3d_pointmlp_fwd_args& p, float (*red)[NT / (N / 8)][N], const int tile) {
   constexpr bool H = Elem<YT>::BF16;
   constexpr int CPR = N / 8, RPP = NT / CPR, NP = 128 / RPP;      // column chunks per row, rows per pass, passes
-  __shared__ float red[2][RPP][N];
   const int tid = threadIdx.x, ch = tid % CPR, r0 = tid / CPR;
-  const int tile = blockIdx.x, row0 = tile * 128, b = row0 / p.rows_per_frustum;
+  const int row0 = tile * 128, b = row0 / p.rows_per_frustum;
   float w[4][8], add[8];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -2162,6 +2162,12 @@ __global__ __launch_bounds__(NT) void k_pointmlp_fwd_tinyk(const t3d_pointmlp_fw
     p.psum[(size_t)tile * p.N + tid] = t1;
     p.psumsq[(size_t)tile * p.N + tid] = t2;
   }
+}
+
+template <int N, class YT = bf16_t>
+__global__ __launch_bounds__(NT) void k_pointmlp_fwd_tinyk(const t3d_pointmlp_fwd_args p) {
+  __shared__ float red[2][NT / (N / 8)][N];
+  pointmlp_fwd_tinyk_body<N, YT>(p, red, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3966,6 +3972,8 @@ int t3d_x3_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_
                   int n_finish, int n_d, size_t lds_other, hipStream_t s);
 int t3d_x3_split(const float* src, void* planes, int64_t n, int64_t plane_stride, hipStream_t s);
 int t3d_x3_split_frag(const float* params, void* pf, void* pd, int64_t stride, const t3d_x3_frag_entry* tab, int n, int n_blocks, hipStream_t s);
+int t3d_x3_step_head(const t3d_pointmlp_fwd_args* a, const float* params, void* pf, void* pd, int64_t stride, const t3d_x3_frag_entry* tab, int n,
+                     int n_blocks, float* hyper, const t3d_schedule* sched, hipStream_t s);
 int t3d_x3_dgrad(const t3d_pointmlp_dgrad_args* a, bool wide, hipStream_t s);
 int t3d_x3_wgrad(const t3d_pointmlp_wgrad_args* a, int tk, int tn, int n_blocks, hipStream_t s);
 int t3d_x3_gram(const t3d_pointmlp_gram_args* a, int tk, int n_blocks, hipStream_t s);
@@ -3995,16 +4003,16 @@ __global__ __launch_bounds__(256) void k_split_x3(const float* __restrict__ src,
 // the weights of every x3 layer as fragment-order planes (WLoaderX3F), both arrangements, ONE launch per step: entry e of the device
 // table = a [K, N] matrix at params + off; its planes live at the same offset of the plane buffers (a plane is as long as `params`)
 namespace {
-__global__ __launch_bounds__(256) void k_split_x3_frag(const float* __restrict__ params, bf16_t* __restrict__ pf, bf16_t* __restrict__ pd, long stride,
-                                                       const t3d_x3_frag_entry* __restrict__ tab, int n) {
+__device__ __forceinline__ void split_x3_frag_body(const float* __restrict__ params, bf16_t* __restrict__ pf, bf16_t* __restrict__ pd, long stride,
+                                                   const t3d_x3_frag_entry* __restrict__ tab, int n, const int blk) {
   // block -> (matrix, its 256 fragments): the table carries each matrix's first block (ascending); every matrix in parallel (one
   // after the other, the ~20 matrices of a step took 16 us of dependent round trips for 20 MB)
   int e = 0;
-  while (e + 1 < n && (int)blockIdx.x >= tab[e + 1].blk0) ++e;
+  while (e + 1 < n && blk >= tab[e + 1].blk0) ++e;
   const t3d_x3_frag_entry en = tab[e];
   const float* w = params + en.off;
   const long nfr = (long)en.K * en.N / 8;      // eight-element fragments per plane
-  const long f = (long)((int)blockIdx.x - en.blk0) * 256 + threadIdx.x;
+  const long f = (long)(blk - en.blk0) * 256 + threadIdx.x;
   if (f >= nfr) return;
   const int lane = (int)(f & 63);
   const long q = f >> 6;
@@ -4041,7 +4049,37 @@ __global__ __launch_bounds__(256) void k_split_x3_frag(const float* __restrict__
     *reinterpret_cast<bf16x8*>(d + 2 * stride) = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
   }
 }
+__global__ __launch_bounds__(256) void k_split_x3_frag(const float* __restrict__ params, bf16_t* __restrict__ pf, bf16_t* __restrict__ pd, long stride,
+                                                       const t3d_x3_frag_entry* __restrict__ tab, int n) {
+  split_x3_frag_body(params, pf, pd, stride, tab, n, (int)blockIdx.x);
+}
+
+// The head of a training step in one launch (t3d_step_head): the schedule, the fragment planes and the first layer's forward do not
+// depend on each other (the register kernel reads the fp32 weights and the raw input: neither `hyper` nor the planes), so they are
+// workgroup roles of one grid instead of three graph nodes in a row.  The forward tiles come first (the longest role), then the split
+// workgroups, then one workgroup whose first wave evaluates the schedule.
+template <int N>
+__global__ __launch_bounds__(NT) void k_step_head(const t3d_pointmlp_fwd_args p, const int n_fwd, const float* __restrict__ params,
+                                                  bf16_t* __restrict__ pf, bf16_t* __restrict__ pd, const long stride,
+                                                  const t3d_x3_frag_entry* __restrict__ tab, const int n, const int n_split, float* hyper,
+                                                  const t3d_schedule sched) {
+  __shared__ float red[2][NT / (N / 8)][N];
+  const int b = blockIdx.x;
+  if (b < n_fwd) pointmlp_fwd_tinyk_body<N, float>(p, red, b);
+  else if (b < n_fwd + n_split) split_x3_frag_body(params, pf, pd, stride, tab, n, b - n_fwd);
+  else if (threadIdx.x < 64) schedule_step_body(hyper, sched, threadIdx.x);
+}
 }  // namespace
+int t3d_x3_step_head(const t3d_pointmlp_fwd_args* a, const float* params, void* pf, void* pd, int64_t stride, const t3d_x3_frag_entry* tab, int n,
+                     int n_blocks, float* hyper, const t3d_schedule* sched, hipStream_t s) {
+  static_assert(NT == 256, "the three roles of k_step_head are 256-thread workgroups");
+  const int n_fwd = a->M / 128;
+  const dim3 grid(n_fwd + n_blocks + 1);
+  if (a->N == 64) T3D_LAUNCH(k_step_head<64>, grid, dim3(NT), 0, s, *a, n_fwd, params, static_cast<bf16_t*>(pf), static_cast<bf16_t*>(pd), (long)stride, tab, n, n_blocks, hyper, *sched);
+  else T3D_LAUNCH(k_step_head<128>, grid, dim3(NT), 0, s, *a, n_fwd, params, static_cast<bf16_t*>(pf), static_cast<bf16_t*>(pd), (long)stride, tab, n, n_blocks, hyper, *sched);
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
 int t3d_x3_split_frag(const float* params, void* pf, void* pd, int64_t stride, const t3d_x3_frag_entry* tab, int n, int n_blocks, hipStream_t s) {
   T3D_LAUNCH(k_split_x3_frag, dim3(n_blocks), dim3(256), 0, s, params, static_cast<bf16_t*>(pf), static_cast<bf16_t*>(pd), (long)stride, tab, n);
   T3D_CHECK_LAUNCH();
@@ -4240,6 +4278,14 @@ int t3d_x3_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_
     }                                                       \
   } while (0)
 
+// an fp32 launch (dtype and a.dtype T3D_F32, checked by the caller) that goes to the fp32 register kernel k_pointmlp_fwd_tinyk: the
+// ONE statement of that rule (t3d_pointmlp_fwd_r's dispatch, t3d_step_head, t3d_step_head_takes)
+static bool fwd_takes_tinyk32(const t3d_pointmlp_fwd_args* a) {
+  static const bool use_tiny32 = []() { const char* e = getenv("T3D_FWD_TINYK"); return !(e && e[0] == '0'); }();
+  return use_tiny32 && a->K <= 4 && a->y && !a->pmax && !a->rowbias && (a->N == 64 || a->N == 128) && a->a.ldx % 4 == 0 &&
+         a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx;
+}
+
 extern "C" int t3d_pointmlp_fwd(const t3d_pointmlp_fwd_args* a, t3d_stream_t stream) { return t3d_pointmlp_fwd_r(a, nullptr, stream); }
 
 extern "C" int t3d_pointmlp_fwd_r(const t3d_pointmlp_fwd_args* a, const t3d_rider_set* r, t3d_stream_t stream) {
@@ -4307,9 +4353,7 @@ extern "C" int t3d_pointmlp_fwd_r(const t3d_pointmlp_fwd_args* a, const t3d_ride
   }
   if (a->a.dtype != T3D_F32) return T3D_ERR_ARG;
   {   // first layer of a net (xyz [+ 1 channel]): the register kernel (T3D_FWD_TINYK=0: the generic one)
-    static const bool use_tiny32 = []() { const char* e = getenv("T3D_FWD_TINYK"); return !(e && e[0] == '0'); }();
-    if (use_tiny32 && a->K <= 4 && a->y && !a->pmax && !a->rowbias && (a->N == 64 || a->N == 128) && a->a.ldx % 4 == 0 &&
-        a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx) {
+    if (fwd_takes_tinyk32(a)) {
       T3D_RIDERS_FIRST(r, stream);
       if (a->N == 64) T3D_LAUNCH((k_pointmlp_fwd_tinyk<64, float>), dim3(tiles_m), dim3(NT), 0, s, *a);
       else T3D_LAUNCH((k_pointmlp_fwd_tinyk<128, float>), dim3(tiles_m), dim3(NT), 0, s, *a);
@@ -4945,6 +4989,37 @@ extern "C" int t3d_split_x3_frag(const float* params, void* planes_fwd, void* pl
       (reinterpret_cast<uintptr_t>(params) & 15) || (reinterpret_cast<uintptr_t>(planes_fwd) & 15) || (reinterpret_cast<uintptr_t>(planes_dgrad) & 15))
     return T3D_ERR_ARG;
   return t3d_x3_split_frag(params, planes_fwd, planes_dgrad, plane_stride, table, n_entries, n_blocks, static_cast<hipStream_t>(stream));
+}
+
+// 0 / T3D_ERR_*: what t3d_step_head answers to this forward struct before it launches anything
+static int step_head_fwd_check(const t3d_pointmlp_fwd_args* a) {
+  if (!a || !a->w || !a->psum || !a->psumsq || !act_ok(a->a, a->K)) return T3D_ERR_ARG;
+  if (a->M <= 0 || a->K <= 0 || a->N <= 0 || a->M % T3D_TILE_ROWS || a->rows_per_frustum % T3D_TILE_ROWS ||
+      a->M % a->rows_per_frustum || a->N % 64 || (long)a->M * a->N >= (1L << 30))
+    return T3D_ERR_SHAPE;
+  // only the layer t3d_pointmlp_fwd gives to the fp32 register kernel, on a raw input: beside the input, the fp32 weights and the
+  // bias that kernel then reads nothing -- no `hyper`, no planes, no scale / shift / per-frustum offset another launch could write
+  if (a->dtype != T3D_F32 || a->a.dtype != T3D_F32 || !fwd_takes_tinyk32(a) || a->a.scale || a->a.shift || a->a.sub) return T3D_ERR_ARG;
+  return T3D_OK;
+}
+
+extern "C" int t3d_step_head_takes(const t3d_pointmlp_fwd_args* a) {
+  T3D_ABI_TAKE(pointmlp_fwd_args, a);
+  return step_head_fwd_check(a) == T3D_OK ? 1 : 0;
+}
+
+extern "C" int t3d_step_head(const t3d_pointmlp_fwd_args* a, const float* params, void* planes_fwd, void* planes_dgrad, int64_t plane_stride,
+                             const t3d_x3_frag_entry* table, int n_entries, int n_blocks, float* hyper, const t3d_schedule* sched,
+                             t3d_stream_t stream) {
+  T3D_ABI_TAKE(pointmlp_fwd_args, a);
+  // the argument checks of the three entry points it stands for
+  if (!hyper || !sched) return T3D_ERR_ARG;
+  if (!params || !planes_fwd || !planes_dgrad || !table || n_entries <= 0 || n_blocks <= 0 || plane_stride <= 0 || (plane_stride & 7) ||
+      (reinterpret_cast<uintptr_t>(params) & 15) || (reinterpret_cast<uintptr_t>(planes_fwd) & 15) || (reinterpret_cast<uintptr_t>(planes_dgrad) & 15))
+    return T3D_ERR_ARG;
+  const int rc = step_head_fwd_check(a);
+  if (rc != T3D_OK) return rc;
+  return t3d_x3_step_head(a, params, planes_fwd, planes_dgrad, plane_stride, table, n_entries, n_blocks, hyper, sched, static_cast<hipStream_t>(stream));
 }
 
 // ---- does the `_r` launcher host a rider set for these arguments? (1 / 0; negative: the arguments are rejected) ----

@@ -127,9 +127,10 @@ class Plan:
         self.calls.append((name, lambda s, fn=fn, ref=ref: fn(ref, s), args))
         self.lanes.append(self._lane)
 
-    def add_raw(self, name, thunk, *keep):
+    def add_raw(self, name, thunk, *keep, arg=None):
+        """`arg`: what the thunk launches with, for a program pass that merges launches (step.TrainStep._fuse_head_tail)."""
         self.keep.extend(keep)
-        self.calls.append((name, thunk, None))
+        self.calls.append((name, thunk, arg))
         self.lanes.append(self._lane)
 
     def mark(self, tag):

@@ -82,7 +82,7 @@ class Graph:
         def thunk(s):
             return lib.t3d_reduce_slabs(fptr(ws.buf), fptr(vs.grads),
                                         C.cast(C.c_void_p(ws.table.data_ptr() + i0 * stride), C.POINTER(abi.SlabDesc)), i1 - i0, mx, s)
-        plan.add_raw('t3d_reduce_slabs', thunk)
+        plan.add_raw('t3d_reduce_slabs', thunk, arg={'i0': i0, 'i1': i1, 'max_numel': mx})
 
     def emit_cast_weights(self, plan):
         """bf16 path: refresh the bf16 copy of the weights the GEMM kernels read (the optimiser updates the fp32 master copy).
@@ -99,7 +99,7 @@ class Graph:
                     pf, pd = vs.x3_frag_planes
                     return lib.t3d_split_x3_frag(fptr(vs.params), C.c_void_p(pf.data_ptr()), C.c_void_p(pd.data_ptr()), vs.x3_frag_stride,
                                                  C.c_void_p(t.data_ptr()), n, nblk, s)
-                plan.add_raw('t3d_split_x3_frag', thunk)
+                plan.add_raw('t3d_split_x3_frag', thunk, arg={'vars': vs})
             return
         p16 = vs.enable_bf16()
         plan.add_raw('t3d_cast_bf16', lambda s: lib.t3d_cast_bf16(fptr(vs.params), C.c_void_p(p16.data_ptr()), vs.used, s))
@@ -159,7 +159,8 @@ class Graph:
 
     def emit_schedule(self, plan, sched):
         lib, hyper = self.rt.lib, self.hyper
-        plan.add_raw('t3d_schedule_step', lambda s: lib.t3d_schedule_step(fptr(hyper), C.byref(sched), s), sched)
+        plan.add_raw('t3d_schedule_step', lambda s: lib.t3d_schedule_step(fptr(hyper), C.byref(sched), s), sched,
+                     arg={'hyper': hyper, 'sched': sched})
 
     def emit_dropout_masks(self, plan, seed=1234):
         lib, hyper = self.rt.lib, self.hyper
@@ -178,7 +179,8 @@ class Graph:
             plan.add_raw('t3d_adam_tf_step',
                          lambda s, off=off, n=n: lib.t3d_adam_tf_step(
                              fptr(vs.params[off:]), fptr(vs.grads[off:]), fptr(vs.adam_m[off:]), fptr(vs.adam_v[off:]),
-                             n, fptr(hyper), beta1, beta2, eps, grad_scale, s))
+                             n, fptr(hyper), beta1, beta2, eps, grad_scale, s),
+                         arg={'off': off, 'n': n, 'beta1': beta1, 'beta2': beta2, 'eps': eps, 'grad_scale': grad_scale})
         self._emit_optimizer(plan, prefixes, adam)
 
     def emit_momentum(self, plan, prefixes=None, momentum=0.9, grad_scale=1.0):

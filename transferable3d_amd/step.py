@@ -11,11 +11,14 @@ backward (the seg-net's gradients do not depend on the box / T-Net gradients: se
 The optimiser plan carries `bucket wait` markers in front of each bucket's Adam launch.  With one rank the markers are ignored and
 the whole step is ONE graph.
 """
+import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import abi
+from .abi import fptr
 from .engine import Plan
 
 
@@ -24,11 +27,16 @@ OPTIMIZER_CALLS = ('t3d_adam_tf_step', 't3d_momentum_step')
 
 class TrainStep:
     def __init__(self, engine, pre, fwd, bwd=None, opt=None, process_group=None, use_hip_graph=None, force_dist=False,
-                 one_graph=None):
+                 one_graph=None, fuse_head_tail=None):
         """engine: nets.Graph; pre/fwd/bwd/opt: engine.Plan (bwd/opt None for a forward-only step).
         process_group: torch.distributed group (None: single replica).  force_dist: take the multi-rank code path (segments,
-        collectives) even with one rank -- how a 1-GPU box exercises it."""
+        collectives) even with one rank -- how a 1-GPU box exercises it.  fuse_head_tail: merge the launches at the two ends of the
+        step where the library can (_fuse_head_tail; default: T3D_FUSE_HEAD_TAIL, on)."""
         self.e, self.rt = engine, engine.rt
+        if fuse_head_tail is None:
+            fuse_head_tail = os.environ.get('T3D_FUSE_HEAD_TAIL', '1') != '0'
+        self.fuse_head_tail = bool(fuse_head_tail)
+        self.fused = []            # names of the merged launches of the last program built
         self.pre, self.fwd, self.bwd, self.opt = pre, fwd, bwd, opt
         self.train = bwd is not None
         self.pg = process_group
@@ -93,6 +101,8 @@ class TrainStep:
             calls.append((Plan.JOIN, lambda s: 0, None))      # plans are serial with respect to each other
             lanes.append(0)
             two = two or p.two_streams
+        if self.fuse_head_tail:
+            calls, lanes = self._fuse_head_tail(calls, lanes)
         if self.dist and not any(c[0] == Plan.BUCKET for c in calls):
             # a backward plan without markers: ONE bucket (every trained range), reduced between the backward and the optimiser
             k = next((i for i, c in enumerate(calls) if c[0] in OPTIMIZER_CALLS), len(calls))
@@ -137,6 +147,73 @@ class TrainStep:
                     merged.lanes.extend(x.lanes)
             prog = prog[:k] + [t for t in tail if t[0] == 'wait'] + [('run', merged)]
         return prog
+
+    def _fuse_head_tail(self, calls, lanes):
+        """The launches at the two ends of the step that have no neighbour to ride in, merged where they are independent:
+          head  t3d_schedule_step, t3d_split_x3_frag, the first layer's register-kernel forward -> ONE t3d_step_head launch (none of
+                the three reads what another writes: the register kernel takes the fp32 weights and the raw input);
+          tail  t3d_reduce_slabs, t3d_adam_tf_step -> ONE t3d_reduce_slabs_adam launch (single replica, Adam over every variable:
+                with data parallelism the all-reduce sits between the two).
+        Only adjacent launches are merged, and only when the library exports the merged entry point (the CPU specification library
+        does not: the separate launches stay); same bits either way."""
+        lib, e = self.rt.lib, self.e
+        self.fused = []
+        real = [i for i, c in enumerate(calls) if not c[0].startswith('__') or c[0] in (Plan.BUCKET, Plan.WAIT, Plan.FLUSH)]
+        names = [calls[i][0] for i in real]
+        drop = set()
+
+        def adjacent(*want):
+            for k in range(len(names) - len(want) + 1):
+                if tuple(names[k:k + len(want)]) == want:
+                    idx = real[k:k + len(want)]
+                    if all(calls[i][2] is not None for i in idx) and not any(lanes[i] for i in idx):
+                        return idx
+            return None
+
+        # ---- head ----
+        idx = adjacent('t3d_schedule_step', 't3d_split_x3_frag', 't3d_pointmlp_fwd')
+        if idx is not None and self.on_gpu and hasattr(lib, 't3d_step_head') and self.rt.arith == abi.ARITH_BF16X3 and \
+                names.count('t3d_schedule_step') == 1:
+            sc, vs, a = calls[idx[0]][2], calls[idx[1]][2]['vars'], calls[idx[2]][2]
+            # (which forward launch is the register kernel on a raw input is the library's to say: t3d_step_head_takes)
+            if lib.t3d_step_head_takes(C.byref(a)) == 1 and getattr(vs, 'x3_frag_entries', None):
+                hyper, sched = sc['hyper'], sc['sched']
+
+                def head(s, a=a, vs=vs, hyper=hyper, sched=sched):
+                    t, n, nblk = vs.frag_table()
+                    pf, pd = vs.x3_frag_planes
+                    return lib.t3d_step_head(C.byref(a), fptr(vs.params), C.c_void_p(pf.data_ptr()), C.c_void_p(pd.data_ptr()),
+                                             vs.x3_frag_stride, C.c_void_p(t.data_ptr()), n, nblk, fptr(hyper), C.byref(sched), s)
+                calls[idx[0]] = ('t3d_step_head', head, None)
+                drop.update(idx[1:])
+                self.fused.append('t3d_step_head')
+        # ---- tail ----
+        idx = adjacent('t3d_reduce_slabs', 't3d_adam_tf_step')
+        vs = e.vars
+        if idx is not None and self.on_gpu and hasattr(lib, 't3d_reduce_slabs_adam') and not self.dist and e.dt == abi.F32 and \
+                names.count('t3d_adam_tf_step') == 1 and idx[1] == real[-1] and getattr(e, 'trained_prefixes', None) is None:
+            rd, ad = calls[idx[0]][2], calls[idx[1]][2]
+            if (ad['off'], ad['n']) == (0, vs.used) and e.finalized:
+                ws = e.ws
+                ent = ws.entries[rd['i0']:rd['i1']]
+                ranges, nblk = abi.adam_range_table(vs.used, [(go, ne) for _, go, ne, _ in ent])      # (raises unless they partition [0, used))
+                host = (abi.AdamRange * max(len(ranges), 1))()
+                for i, (off, n, blk0) in enumerate(ranges):
+                    host[i] = abi.AdamRange(off, n, blk0, 0)
+                table = torch.as_tensor(np.frombuffer(bytes(host), dtype=np.uint8).copy()).to(self.rt.device)
+                stride = C.sizeof(abi.SlabDesc)
+
+                def tail(s, rd=rd, ad=ad, table=table, n_ranges=len(ranges), nblk=nblk):
+                    return lib.t3d_reduce_slabs_adam(
+                        fptr(ws.buf), fptr(vs.grads), C.cast(C.c_void_p(ws.table.data_ptr() + rd['i0'] * stride), C.POINTER(abi.SlabDesc)),
+                        rd['i1'] - rd['i0'], rd['max_numel'], fptr(vs.params), fptr(vs.adam_m), fptr(vs.adam_v),
+                        C.cast(C.c_void_p(table.data_ptr()), C.POINTER(abi.AdamRange)), n_ranges, nblk, fptr(e.hyper),
+                        ad['beta1'], ad['beta2'], ad['eps'], ad['grad_scale'], s)
+                calls[idx[0]] = ('t3d_reduce_slabs_adam', tail, None)
+                drop.add(idx[1])
+                self.fused.append('t3d_reduce_slabs_adam')
+        keep = [i for i in range(len(calls)) if i not in drop]
+        return [calls[i] for i in keep], [lanes[i] for i in keep]
 
     def _overlap(self, calls, lanes):
         """Interleave the two independent chains the plans marked (nets.ModelAssembly: `T_begin` in the forward plan, `S_begin` /
@@ -391,7 +468,7 @@ STAGE_C_TRAIN_CLASSES = [i in (1, 2, 6, 7, 8) for i in range(10)]     # SUNRGBD_
 
 def build_training_step(rt, workload, B, N, C, world=1, rank=0, process_group=None, force_dist=False, flat_allreduce=False,
                         use_hip_graph=None, inline_dropout=True, dropout_seed=1234, seed=0, state_dict=None, c=None, dtype='f32',
-                        one_graph=None):
+                        one_graph=None, fuse_head_tail=None):
     """The step bench.py times and the trajectory tests check: graph + model of `workload` ('A' = BASELINE configs[1],
     'boxpc' = configs[2], 'F' = configs[3]), the device-side schedules (train_semisup.py:127-145), forward, backward, TF-form Adam
     over the recipe's var_list, wrapped in a TrainStep.  Returns (engine graph, model, step, loss buffer)."""
@@ -425,7 +502,7 @@ def build_training_step(rt, workload, B, N, C, world=1, rank=0, process_group=No
     g.emit_adam(g.opt, prefixes=prefixes, grad_scale=1.0 / world)
     g.finalize()
     step = TrainStep(g, g.pre, g.fwd, g.bwd, g.opt, process_group=process_group, use_hip_graph=use_hip_graph,
-                     force_dist=force_dist, one_graph=one_graph)
+                     force_dist=force_dist, one_graph=one_graph, fuse_head_tail=fuse_head_tail)
     return g, model, step, loss
 
 
