@@ -1393,6 +1393,57 @@ typedef struct {
 #define T3D_V2_SIZE_detect_decode_args 152
 int t3d_detect_decode(const t3d_detect_decode_args* args, t3d_stream_t stream);
 
+/* ---- Greedy non-maximum suppression of decoded 3-D boxes, many small groups in one call (csrc/nms.hip; nms.DeviceNms, detect
+ *      --nms_iou) ----
+ * A group is the boxes of one class in one image: group g holds the box indices members[group_offsets[g] .. group_offsets[g+1]-1].
+ * The reference has no such step; it is opt-in (a duplicate 2-D detection becomes a duplicate 3-D box, which script_3Deval.m counts as
+ * a false positive).  fp32 throughout; the IoU is box3d_iou_corners of csrc/boxgeom_dev.h, the one t3d_box3d_iou_corners returns:
+ * metric T3D_NMS_IOU3D the volume IoU, T3D_NMS_IOU2D that of the ground-plane rectangles (bird's-eye view).
+ *   Order within a group   a comes before b iff score[a] > score[b], or the scores are equal and a < b.  A NaN score counts as -inf
+ *                          (so it ties with a real -inf, and the box index decides).  rank[a] = a's position in that order.
+ *   Sweep                  the group is walked in that order.  Box j is suppressed iff some EARLIER KEPT box i has IoU(i, j) > threshold,
+ *                          strictly, where IoU(i, j) is computed with i as the first argument.  A NaN IoU (two boxes of zero volume)
+ *                          suppresses nothing.  keep[j] = 0 and suppressed_by[j] = the best-ranked such i; a kept box gets 1 and -1.
+ *                          A box that a suppressed box would have suppressed is kept (A > B > C, A covers B, B covers C, A not C: C stays).
+ *   Groups                 a group of one keeps its box; an empty group is valid.
+ *   Unlisted boxes         a box in no group is not visited: its outputs keep what they held (as the frustums >= n_valid of the decode).
+ *   Empty input            n == 0, n_groups == 0 or max_group == 0: T3D_OK without a launch.
+ *   max_group              the size of the largest group, declared by the caller (who built the lists): the entry point cannot read
+ *                          device memory without waiting for it.  It sets the row stride of the workspace.  max_group >
+ *                          T3D_DETECT_NMS_MAX_GROUP is T3D_ERR_SHAPE, before anything is launched; a group that turns out larger than
+ *                          declared, or a list that leaves [0, n), is not visited.
+ *   workspace              T3D_DETECT_NMS_WORKSPACE_BYTES(n, max_group) bytes, 8-byte aligned: the sorted order of every group and one
+ *                          bit per (earlier, later) pair of a group, ceil(max_group / 64) 64-bit words per box.  T3D_ERR_ARG if smaller
+ *                          or misaligned, and for a null corners / score / group_offsets / members / keep / suppressed_by, n or n_groups
+ *                          < 0, or an unknown metric.
+ * Three launches on `stream`: the order by counting (size^2 comparisons per group, as t3d_sunrgbd_eval); the pair bits, one thread per
+ * (box, 64 later boxes), consecutive lanes on consecutive boxes of the concatenated lists, so that a wave covers several small groups and
+ * nothing below the diagonal is computed; the sweep, ceil(max_group / 64) lanes (rounded up to a power of two) per group, 64 groups per
+ * wave when every group has at most 64 boxes.  No allocation, no host synchronisation, no atomics: equal inputs give equal bytes, and a
+ * group's answers depend on its own boxes only, wherever they sit in the call. */
+#define T3D_NMS_IOU3D 0
+#define T3D_NMS_IOU2D 1
+#define T3D_DETECT_NMS_MAX_GROUP 1024
+#define T3D_DETECT_NMS_WORKSPACE_BYTES(n, max_group) \
+  ((((uint64_t)(n) + 1u) / 2u) * 8u + (uint64_t)(n) * ((((uint64_t)(max_group)) + 63u) / 64u) * 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_nms_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_groups; int metric;
+  const float* corners;            /* [n,8,3], get_3d_box order: what t3d_detect_decode writes */
+  const float* score;              /* [n] */
+  const int32_t* group_offsets;    /* [n_groups + 1], ascending from 0, the last <= n */
+  const int32_t* members;          /* [group_offsets[n_groups]] box indices; a box appears at most once */
+  float threshold;
+  int max_group;
+  void* workspace;
+  uint64_t workspace_bytes;
+  uint8_t* keep;                   /* [n] out */
+  int32_t* suppressed_by;          /* [n] out: -1 for a kept box, else the box index of the best-ranked kept box that suppresses it */
+  int32_t* rank;                   /* [n] out or NULL */
+} t3d_detect_nms_args;
+#define T3D_V2_SIZE_detect_nms_args 96
+int t3d_detect_nms(const t3d_detect_nms_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

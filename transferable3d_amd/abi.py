@@ -370,6 +370,22 @@ class DetectDecodeArgs(Sized):
                 ('heading_cls', I), ('size_cls', I), ('center', F), ('heading_res', F), ('size_res', F), ('label', F), ('corners', F)]
 
 
+NMS_IOU3D, NMS_IOU2D = 0, 1           # t3d.h T3D_NMS_*
+NMS_METRICS = {'3d': NMS_IOU3D, 'bev': NMS_IOU2D}
+DETECT_NMS_MAX_GROUP = 1024           # t3d.h T3D_DETECT_NMS_MAX_GROUP
+
+
+class DetectNmsArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_groups', i32), ('metric', i32), ('corners', F), ('score', F), ('group_offsets', I),
+                ('members', I), ('threshold', f32), ('max_group', i32), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('keep', U8),
+                ('suppressed_by', I), ('rank', I)]
+
+
+def detect_nms_workspace_bytes(n, max_group):
+    """t3d.h T3D_DETECT_NMS_WORKSPACE_BYTES"""
+    return (n + 1) // 2 * 8 + n * ((max_group + 63) // 64) * 8
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -474,6 +490,7 @@ ENTRY_POINTS = {
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
+    't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }

@@ -2,12 +2,16 @@
 """test_semisup with the detections decoded on the device (t3d_detect_decode, csrc/detect.hip).
 
     python -m transferable3d_amd.semisup_infer --device_decode <test_semisup's flags>
+    python -m transferable3d_amd.semisup_infer --device_decode --from_rgb_detection --nms_iou 0.25 [--nms_metric bev] [--nms_score score] ...
 
 test_semisup's `inference` fetches every batch's logits and six head tensors and decodes them in fp64 NumPy, and its result writers
 loop over the detections.  `inference(decode='device')` here follows a batch's graph with one t3d_detect_decode launch on the same
 stream, fetches nothing in between, and copies the decoded records (plus the uint8 masks where the caller needs them) back once at
 the end.  `test` is test_semisup's driver run with that inference (device_decode_driver); without --device_decode every function
 here hands over to test_semisup's, so nothing that exists changes its numbers.
+
+--nms_iou T (with --from_rgb_detection): before the copy back, t3d_detect_nms (nms.py) suppresses, per image and class, every box that
+overlaps a better-ranked kept box by more than T; the suppressed detections are absent from the 14-list, the result files and --evaluate.
 """
 import contextlib
 import ctypes as C
@@ -19,8 +23,9 @@ import torch
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import abi, test_semisup as TS                   # noqa: E402
+from transferable3d_amd import abi, nms as NMS, test_semisup as TS       # noqa: E402
 from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
+from transferable3d_amd.constants import type2class                     # noqa: E402
 
 
 def build_flags(argv=None):
@@ -28,28 +33,57 @@ def build_flags(argv=None):
     not declare, so the flag is taken out of argv here)."""
     argv = list(sys.argv[1:] if argv is None else argv)
     device = '--device_decode' in argv
-    FLAGS = TS.build_flags([a for a in argv if a != '--device_decode'])
+    import argparse
+    own = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    NMS.add_arguments(own)
+    nms, rest = own.parse_known_args([a for a in argv if a != '--device_decode'])
+    FLAGS = TS.build_flags(rest)
     FLAGS.device_decode = device
+    FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score = NMS.check_options(nms.nms_iou, nms.nms_metric, nms.nms_score)
+    if FLAGS.nms_iou is not None and not (device and FLAGS.from_rgb_detection):
+        raise ValueError('--nms_iou runs on the device-decoded boxes of a detection file: it needs --device_decode and --from_rgb_detection')
     return FLAGS
+
+
+class NmsRequest:
+    """What `inference(decode='device', nms=...)` needs to run t3d_detect_nms on its decoded corners: the threshold, the metric ('3d' /
+    'bev'), what ranks ('prob': the 2-D detection confidences given here; 'score': the decoded network score) and, per detection, the
+    image id and the class id that make its group."""
+
+    def __init__(self, threshold, metric, score, image_ids, class_ids, prob=None):
+        self.threshold, self.metric, self.score = NMS.check_options(threshold, metric, score)
+        if self.threshold is None:
+            raise ValueError('an NMS request needs a threshold')
+        self.image_ids, self.class_ids = np.asarray(image_ids, np.int64), np.asarray(class_ids, np.int64)
+        self.prob = None if prob is None else np.asarray(prob, np.float32)
+        if self.score == 'prob' and (self.prob is None or len(self.prob) != len(self.image_ids)):
+            raise ValueError("ranking by 'prob' needs one detection confidence per detection")
 
 
 class Decoded:
     """The records of t3d_detect_decode in host memory, one row per detection: score, mask_count, heading_cls, size_cls, center [n,3],
     heading_res, size_res [n,3], label [n,7] = (h, w, l, tx, ty, tz, ry) as from_prediction_to_label_format, corners [n,8,3] as
     get_3d_box in the camera frame.  It travels beside the 14-list; write_detection_results, evaluate_sunrgbd.official_predictions and
-    eval_det.evaluate_predictions read label / corners from it instead of looping over the detections."""
+    eval_det.evaluate_predictions read label / corners from it instead of looping over the detections.
+    keep [n] bool and suppressed_by [n] (-1: kept; else the row of the better-ranked box that suppressed this one) are what t3d_detect_nms
+    answered, or None where no suppression was asked for.  A sliced Decoded carries its rows' values; suppressed_by keeps naming rows of
+    the unsliced run."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
+    OPTIONAL = ('keep', 'suppressed_by')
 
     def __init__(self, **fields):
         for k in self.FIELDS:
             setattr(self, k, fields[k])
+        for k in self.OPTIONAL:
+            setattr(self, k, fields.get(k))
 
     def __len__(self):
         return len(self.score)
 
     def __getitem__(self, sel):
         """Rows `sel` (a slice or an index array)."""
-        return Decoded(**{k: getattr(self, k)[sel] for k in self.FIELDS})
+        return Decoded(**{k: getattr(self, k)[sel] for k in self.FIELDS},
+                       **{k: getattr(self, k)[sel] for k in self.OPTIONAL if getattr(self, k) is not None})
 
 
 class Predictions(list):
@@ -67,6 +101,8 @@ class DeviceDecode:
     comes back in two copies) and the launch of one batch of them."""
     WIDTH = (('score', 1), ('center', 3), ('heading_res', 1), ('size_res', 3), ('label', 7), ('corners', 24))
     INTS = ('mask_count', 'heading_cls', 'size_cls')
+
+    nms_out = None
 
     def __init__(self, rt, n, num_point, want_seg=False):
         self.rt, self.n, self.N = rt, n, num_point
@@ -90,6 +126,21 @@ class DeviceDecode:
                                  fptr(o['heading_res']), fptr(o['size_res']), fptr(o['label']), fptr(o['corners']))
         abi.check(self.rt.lib.t3d_detect_decode(C.byref(a), self.rt.stream()), 't3d_detect_decode')
 
+    def nms(self, req, total):
+        """t3d_detect_nms over the first `total` rows (the rest pad a last batch), on the corners and scores where the decode wrote them;
+        `fetch` then brings keep / suppressed_by back with the records.  -> the DeviceNms that holds them."""
+        if len(req.image_ids) != total:
+            raise ValueError('%d image ids for %d detections' % (len(req.image_ids), total))
+        offsets, members = NMS.groups_of(req.image_ids, req.class_ids)
+        if req.score == 'prob':
+            score = self.rt.zeros(self.n)
+            score[:total] = torch.from_numpy(req.prob).to(self.rt.device)
+        else:
+            score = self.sec['score'].view(-1)
+        self.nms_out = NMS.DeviceNms(self.rt)
+        self.nms_out.run(self.sec['corners'], score, offsets, members, req.threshold, req.metric)
+        return self.nms_out
+
     def fetch(self):
         """-> (Decoded, masks [n, N] uint8 or None): the copies back."""
         f, i = self.f.cpu().numpy().astype(np.float64), self.i.cpu().numpy().astype(np.int64)
@@ -100,6 +151,9 @@ class DeviceDecode:
         out['corners'] = out['corners'].reshape(n, 8, 3)
         for j, k in enumerate(self.INTS):
             out[k] = i[j * n:(j + 1) * n]
+        if self.nms_out is not None:
+            out['keep'] = self.nms_out.keep[:n].cpu().numpy().astype(bool)
+            out['suppressed_by'] = self.nms_out.suppressed_by[:n].cpu().numpy().astype(np.int64)
         return Decoded(**out), (None if self.seg is None else self.seg.cpu().numpy())
 
 
@@ -122,10 +176,13 @@ def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
 
 
 def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
-              decode='host', want_seg=True):
+              decode='host', want_seg=True, nms=None):
     """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
-    padded last batch are zeros."""
+    padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
+    copied back; `.decoded.keep` / `.suppressed_by` hold its answer (None without it).  Nothing is removed here: the callers drop the rows."""
+    if decode == 'host' and nms is not None:
+        raise ValueError("nms runs on the device-decoded boxes: decode='device'")
     if decode == 'host':
         return TS.inference(sess, ops, pc, one_hot_vec, batch_size, prefix=prefix, use_boxpc_fit_prob=use_boxpc_fit_prob, source=source,
                             n_batches=n_batches, oracle_mask=oracle_mask)
@@ -152,6 +209,8 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
                 feed[ops['y_seg_pl']] = np.asarray(oracle_mask[sl], np.int32)
             sess.run([], feed_dict=feed)
         dec.launch(sl.start, batch_size, max(0, min(batch_size, total - sl.start)), logits, box, s1, delta, fit, rot)
+    if nms is not None:
+        dec.nms(nms, total)
     d, seg = dec.fetch()
     res = InferenceResult((None if seg is None else seg.astype(np.int64), d.center, d.heading_cls, d.heading_res, d.size_cls, d.size_res,
                            d.score))
@@ -175,6 +234,14 @@ def write_detection_results(result_dir, test_classes, predictions, class_names):
         f.close()
 
 
+def kept_predictions(predictions, d):
+    """The 14-list and the records `d` of the same detections without the rows t3d_detect_nms suppressed (d.keep)."""
+    rows = np.nonzero(d.keep)[0]
+    p = Predictions([l if l is None else [l[i] for i in rows] for l in predictions])
+    p.decoded = d[rows]
+    return p
+
+
 @contextlib.contextmanager
 def device_decode_driver(FLAGS):
     """test_semisup's driver functions (`test`, `test_on_frustum_file`) look three names up at the moment they call them: `inference` and
@@ -186,13 +253,28 @@ def device_decode_driver(FLAGS):
     run = {}
 
     def attach(predictions):
+        d = run.get('decoded')
+        if d is not None and d.keep is not None and len(predictions[3]) == len(d):        # drop what t3d_detect_nms suppressed
+            return kept_predictions(predictions, d)
         p = Predictions(predictions)
-        p.decoded = run.get('decoded')
+        p.decoded = d if d is None or d.keep is None else d[np.nonzero(d.keep)[0]]
         return p
+
+    def kept_names(names):
+        d = run.get('decoded')
+        return names if d is None or d.keep is None else [names[i] for i in np.nonzero(d.keep)[0]]
 
     def infer(sess, ops, pc, one_hot_vec, batch_size, **kw):
         source = kw.get('source')
-        res = inference(sess, ops, pc, one_hot_vec, batch_size, decode='device', want_seg=source is None or bool(FLAGS.output), **kw)
+        req = None
+        if getattr(FLAGS, 'nms_iou', None) is not None:
+            ds = source.ds
+            req = NmsRequest(FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob)
+        res = inference(sess, ops, pc, one_hot_vec, batch_size, decode='device', want_seg=source is None or bool(FLAGS.output), nms=req, **kw)
+        if req is not None:
+            log = run.get('log') or print
+            log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
+                % (req.metric, req.threshold, req.score, int(res.decoded.keep[:ds.F].sum()), ds.F))
         run['decoded'] = res.decoded[slice(0, source.ds.F if source is not None else len(res.decoded))]      # without the padding
         seg = res[0] if res[0] is not None else np.full(len(res.decoded), None)      # (no --output: the masks stayed on the device)
         return (seg,) + tuple(res[1:])
@@ -200,8 +282,10 @@ def device_decode_driver(FLAGS):
     real_evaluate = eval_det.evaluate_predictions
     saved = (TS.inference, TS.write_detection_results)
     TS.inference = infer
-    TS.write_detection_results = lambda d, classes, predictions, names: write_detection_results(d, classes, attach(predictions), names)
+    TS.write_detection_results = lambda d, classes, predictions, names: write_detection_results(d, classes, attach(predictions),
+                                                                                                kept_names(names))
     eval_det.evaluate_predictions = lambda predictions, *a, **kw: real_evaluate(attach(predictions), *a, **kw)
+    attach.run = run
     try:
         yield attach
     finally:
@@ -214,6 +298,7 @@ def test(FLAGS, rt=None, log=print):
     if not getattr(FLAGS, 'device_decode', False):
         return Predictions(TS.test(FLAGS, rt=rt, log=log))
     with device_decode_driver(FLAGS) as attach:
+        attach.run['log'] = log
         return attach(TS.test(FLAGS, rt=rt, log=log))
 
 
