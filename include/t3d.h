@@ -1444,6 +1444,106 @@ typedef struct {
 #define T3D_V2_SIZE_detect_nms_args 96
 int t3d_detect_nms(const t3d_detect_nms_args* args, t3d_stream_t stream);
 
+/* ---- Headless rasteriser: z-buffered points, 3-D box wireframes and 2-D rectangles into uint8 RGB images (csrc/render.hip;
+ *      render.Renderer, detect --vis_dir) ----
+ * One call paints n_views pictures ("views") into the caller's `out`.  Every table is a device array with a count; fp32 throughout,
+ * every product and sum below is its own fp32 operation (no contraction), in the order written.
+ *   Transform        (X, Y, D, W) = P . (x, y, z, 1), P row-major 4x4: each component ((p0*x + p1*y) + p2*z) + p3.  A primitive (a point,
+ *                    a box, a rectangle) with a non-finite transformed coordinate -- for a box, of any of its 8 corners -- is dropped.
+ *   Pixels           u = X / W, v = Y / W; pixel centres sit on integers: px = floor(u + 0.5), py = floor(v + 0.5), px a column in
+ *                    [0, W_view), py a row in [0, H_view).  Images are row-major, 3 bytes (R, G, B) per pixel.
+ *   Points           a point range {view, first, count, mode, colour0, colour1, splat} shows the points first .. first+count-1 of the
+ *                    point array (xyz rows ld_xyz floats apart) in one view.  A point is visible iff W >= w_near and D >= 0.  Per
+ *                    pixel the visible point of the smallest D wins, on equal D (-0 is 0) the lowest index in the point array: a 64-bit
+ *                    atomicMin of (bits(D) << 32) | index.  splat 1, 3 or 5 stamps that square centred on (px, py), clipped to the view.
+ *                    Colour by mode: T3D_RENDER_RGB rgb[index] (fp32 in [0,1], rows of 3), T3D_RENDER_LABEL colour1 where label[index]
+ *                    != 0 else colour0, T3D_RENDER_FLAT colour0.  The ranges of one view should not overlap in the point array (where
+ *                    they do, the first range in table order that holds the winning index colours it).
+ *   Segments         the 12 edges of a box entry {view, box, colour, thickness} over corners[box] ([8,3], get_3d_box order, what
+ *                    t3d_detect_decode writes): (i, (i+1)%4), (4+i, 4+(i+1)%4), (i, i+4) for i = 0..3; the 4 sides of a rectangle
+ *                    entry {view, xmin, ymin, xmax, ymax, colour, thickness}, whose corners are pixel coordinates (u, v) as they stand
+ *                    (no transform, no near plane).  An endpoint a with Wa < w_near is moved to the crossing with the other endpoint b:
+ *                    t = (w_near - Wa) / (Wb - Wa), X = Xa + t*(Xb - Xa), Y likewise, W = w_near; both behind: the segment is dropped.
+ *                    u, v non-finite after the division: dropped.  Endpoints are rounded to pixels as above and clamped to +-2^20.
+ *                    The pixel set is all-integer: the major axis is x when |dx| >= |dy|, else y; A is the endpoint of the smaller
+ *                    major coordinate (the smaller minor one on a tie); for every major coordinate m from A's to B's the minor one
+ *                    is a_minor + floor((2*(m - a_major)*d_minor + d_major) / (2*d_major)) (64-bit, floor division); dx = dy = 0 is
+ *                    the single pixel.  Thickness t (1..5) stamps the offsets -floor((t-1)/2) .. +floor(t/2) in both axes.
+ *   Painting order   the background (the view's image in `bg` where bg_offset >= 0, else bg_colour), then the z-buffered points, then
+ *                    the box entries in table order, then the rectangles in table order, each later one over the earlier: a 32-bit
+ *                    atomicMax of the primitive's ordinal (1 + box entry, 1 + n_boxes + rectangle) per pixel, then a resolve pass.
+ *   Colours          a float colour c becomes the byte min(255, max(0, floor(c*255 + 0.5))) (a NaN: 0).
+ *   Reproducible     integer min / max atomics only, no float atomics: equal inputs give equal bytes.
+ *   Untouched        bytes of `out` outside the listed views keep what they held; a view with no primitives shows its background.
+ *   Layout           the caller lays the views out back to back in the workspace, in table order: view.pixel_first = the sum of H*W of
+ *                    the views before it, total_pixels the sum over all; likewise range.pos_first = the sum of `count` of the ranges
+ *                    before it and total_point_items the sum over all (the entry point cannot read device memory without waiting for
+ *                    it, and the launches are sized from the two totals).
+ *   workspace        T3D_RENDER_WORKSPACE_BYTES(total_pixels) = 12 bytes per pixel (a 64-bit depth word and a 32-bit ordinal),
+ *                    8-byte aligned.
+ *   Errors           n_views == 0: T3D_OK without a launch.  T3D_ERR_ARG: a null args / views / out / workspace, a null table or
+ *                    point / corner array with a positive count, a negative count or total, total_pixels == 0, a workspace that is
+ *                    smaller or misaligned.  The tables themselves live on the device; a caller that still holds them on the host
+ *                    passes the same bytes as views_host / ranges_host / boxes_host / rects_host (each may be NULL), and then
+ *                    T3D_ERR_ARG is also: H*W == 0 (or H, W < 0), an entry naming a view >= n_views, a box >= n_corner_boxes, a
+ *                    range outside [0, n_points), a splat other than 1, 3, 5, a thickness outside 1..5, an unknown mode, a mode whose
+ *                    array is NULL, a pixel_first / pos_first / total that is not the running sum, an image that leaves out_bytes /
+ *                    bg_bytes.  Independently, the kernels check every entry again: one that breaks these rules paints nothing, and
+ *                    nothing is ever written outside [out, out + out_bytes) and the workspace.
+ * Three launches on `stream`: clear (depth words, ordinals, backgrounds), paint (a thread per position of the concatenated point
+ * ranges, then a wave per segment striding over the major-axis steps that can touch the view), resolve.  No allocation, no host
+ * synchronisation. */
+#define T3D_RENDER_RGB 0
+#define T3D_RENDER_LABEL 1
+#define T3D_RENDER_FLAT 2
+#define T3D_RENDER_WORKSPACE_BYTES(pixels) ((uint64_t)(pixels) * 12u)
+typedef struct {
+  float P[16];             /* row-major 4x4 */
+  float w_near;
+  int H; int W;
+  int pixel_first;         /* the view's first pixel in the workspace (see Layout) */
+  int64_t out_offset;      /* byte offset of the view's image [H,W,3] in out */
+  int64_t bg_offset;       /* byte offset of its background image [H,W,3] in bg, or -1: bg_colour */
+  float bg_colour[3];
+  int reserved;
+} t3d_render_view;
+typedef struct {
+  int view; int first; int count; int mode;
+  float colour0[3]; float colour1[3];
+  int splat;
+  int reserved;
+  int64_t pos_first;       /* the sum of `count` of the ranges before this one (see Layout) */
+} t3d_render_points;
+typedef struct { int view; int box; float colour[3]; int thickness; } t3d_render_box;
+typedef struct { int view; float xmin; float ymin; float xmax; float ymax; float colour[3]; int thickness; } t3d_render_rect;
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_render_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n_views; int n_points; int n_ranges; int n_corner_boxes; int n_boxes; int n_rects;
+  int ld_xyz;                          /* floats between two rows of xyz, >= 3 */
+  const t3d_render_view* views;        /* [n_views] */
+  const float* xyz;                    /* [n_points, ld_xyz] */
+  const float* rgb;                    /* [n_points, 3] or NULL */
+  const uint8_t* label;                /* [n_points] or NULL */
+  const t3d_render_points* ranges;     /* [n_ranges] */
+  const float* corners;                /* [n_corner_boxes, 8, 3] */
+  const t3d_render_box* boxes;         /* [n_boxes] box entries */
+  const t3d_render_rect* rects;        /* [n_rects] */
+  int64_t total_pixels;
+  int64_t total_point_items;
+  const uint8_t* bg;                   /* background images or NULL */
+  uint64_t bg_bytes;
+  uint8_t* out;
+  uint64_t out_bytes;
+  void* workspace;
+  uint64_t workspace_bytes;
+  const t3d_render_view* views_host;   /* host copies of the four tables, each or NULL (see Errors) */
+  const t3d_render_points* ranges_host;
+  const t3d_render_box* boxes_host;
+  const t3d_render_rect* rects_host;
+} t3d_render_args;
+#define T3D_V2_SIZE_render_args 192
+int t3d_render(const t3d_render_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -331,6 +331,7 @@ class FrustumExtractArgs(Sized):
 
 
 U8 = C.POINTER(C.c_uint8)
+VP_ = C.c_void_p              # a table of structs, passed as an address
 
 
 class SunrgbdEvalArgs(Sized):
@@ -384,6 +385,40 @@ class DetectNmsArgs(Sized):
 def detect_nms_workspace_bytes(n, max_group):
     """t3d.h T3D_DETECT_NMS_WORKSPACE_BYTES"""
     return (n + 1) // 2 * 8 + n * ((max_group + 63) // 64) * 8
+
+
+RENDER_RGB, RENDER_LABEL, RENDER_FLAT = 0, 1, 2      # t3d.h T3D_RENDER_*
+
+
+class RenderView(C.Structure):
+    _fields_ = [('P', f32 * 16), ('w_near', f32), ('H', i32), ('W', i32), ('pixel_first', i32), ('out_offset', C.c_int64),
+                ('bg_offset', C.c_int64), ('bg_colour', f32 * 3), ('reserved', i32)]
+
+
+class RenderPoints(C.Structure):
+    _fields_ = [('view', i32), ('first', i32), ('count', i32), ('mode', i32), ('colour0', f32 * 3), ('colour1', f32 * 3), ('splat', i32),
+                ('reserved', i32), ('pos_first', C.c_int64)]
+
+
+class RenderBox(C.Structure):
+    _fields_ = [('view', i32), ('box', i32), ('colour', f32 * 3), ('thickness', i32)]
+
+
+class RenderRect(C.Structure):
+    _fields_ = [('view', i32), ('xmin', f32), ('ymin', f32), ('xmax', f32), ('ymax', f32), ('colour', f32 * 3), ('thickness', i32)]
+
+
+class RenderArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n_views', i32), ('n_points', i32), ('n_ranges', i32), ('n_corner_boxes', i32), ('n_boxes', i32),
+                ('n_rects', i32), ('ld_xyz', i32), ('views', VP_), ('xyz', F), ('rgb', F), ('label', U8), ('ranges', VP_), ('corners', F),
+                ('boxes', VP_), ('rects', VP_), ('total_pixels', C.c_int64), ('total_point_items', C.c_int64), ('bg', U8),
+                ('bg_bytes', C.c_uint64), ('out', U8), ('out_bytes', C.c_uint64), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64),
+                ('views_host', VP_), ('ranges_host', VP_), ('boxes_host', VP_), ('rects_host', VP_)]
+
+
+def render_workspace_bytes(pixels):
+    """t3d.h T3D_RENDER_WORKSPACE_BYTES"""
+    return int(pixels) * 12
 
 
 def sunrgbd_eval_workspace_bytes(P, G):
@@ -491,6 +526,7 @@ ENTRY_POINTS = {
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
+    't3d_render': [C.POINTER(RenderArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }

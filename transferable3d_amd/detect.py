@@ -4,6 +4,7 @@
     python -m transferable3d_amd.detect --dataset_dir D --idx_path I --rgb_detection_path DETS --model_path M [--boxpc_model_path P] \
         --result_dir R [--official_eval]       # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}]]
+        [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -18,9 +19,16 @@ a part of them does not.
 them as false positives.  With the flag, t3d_detect_nms (nms.py) suppresses, per image and class, every box whose IoU with a
 better-ranked kept box exceeds T, on the decoded corners where they lie; the suppressed detections are absent from everything this
 module hands out.  Without it nothing changes.
+
+--vis_dir DIR: for each of the first --vis_max scenes (default 50) with at least one detection, DIR/<id>.png -- the camera image with the
+kept 3-D boxes in class colours and their 2-D rectangles, beside a bird's-eye panel of the scene's points with the same boxes -- and
+DIR/<id>.json, the legend (there is no text in the pictures).  t3d_render (render.py) paints them from the corners where the decode
+wrote them and from the device copy of the points the extraction made; only the finished panels come back.  --vis_gt adds the label
+boxes in green, --vis_suppressed (with --nms_iou) the boxes NMS dropped in grey.  Nothing else changes with these flags.
 """
 import argparse
 import collections
+import json
 import os
 import sys
 
@@ -28,7 +36,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import nms as NMS, semisup_infer as SI, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
+from transferable3d_amd import nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -47,6 +55,110 @@ def flags_from_keywords(**kw):
         elif v is not None:
             argv += ['--' + k, str(v)]
     return TS.build_flags(argv)
+
+
+class Vis:
+    """detect --vis_dir: which scenes are drawn, what is kept of them between the extraction and the decode, and the pictures."""
+    SCENES_PER_CALL = 8          # scenes painted by one t3d_render call (two views each)
+
+    def __init__(self, vis_dir, vis_max=50, vis_gt=False, vis_suppressed=False, nms=False):
+        if vis_suppressed and not nms:
+            raise ValueError('--vis_suppressed shows what --nms_iou dropped: it needs --nms_iou')
+        if int(vis_max) < 0:
+            raise ValueError('--vis_max must not be negative')
+        self.dir, self.max, self.gt, self.suppressed = vis_dir, int(vis_max), bool(vis_gt), bool(vis_suppressed)
+        self.taken = 0
+        self.written = []
+
+    def take(self, rt, part, scenes, scene_ids, last_scene):
+        """After an extraction launch: keep, for the scenes of this part that have a frustum (so will have a detection), the device
+        copy of their points as fp32 upright camera coordinates, until the budget of --vis_max is spent."""
+        import torch
+        part['vis'] = {}
+        if last_scene is None:
+            return
+        points, offsets = last_scene
+        for s in sorted(set(m[0] for m in part['meta'])):
+            if self.taken >= self.max:
+                break
+            p = points[int(offsets[s]):int(offsets[s + 1])]
+            xyz = torch.stack([p[:, 0], -p[:, 2], p[:, 1]], 1).to(torch.float32).contiguous()          # upright depth -> upright camera
+            rgb = p[:, 3:6].to(torch.float32).contiguous() if p.shape[1] >= 6 else None
+            host = SD.flip_axis_to_camera(np.asarray(scenes[s]['points'], np.float64)[:, :3])
+            part['vis'][s] = dict(id=scene_ids[s], xyz=xyz, rgb=rgb, ranges=RD.ranges_of(host), Rtilt=scenes[s]['Rtilt'], K=scenes[s]['K'],
+                                  image=scenes[s].get('image'), gt=scenes[s].get('gt_corners'), gt_classes=scenes[s].get('gt_classes'))
+            self.taken += 1
+
+    def write(self, rt, parts, d, corners):
+        """parts as Detector.decode_all took them, d its Decoded (every detection in its place), corners the decode's device buffer
+        [n, 24].  -> the scene ids written."""
+        os.makedirs(self.dir, exist_ok=True)
+        todo, i = [], 0
+        for p in parts:
+            rows = {}
+            for m in p['meta']:
+                rows.setdefault(m[0], []).append((i, m))
+                i += 1
+            for s, rec in sorted(p.get('vis', {}).items()):
+                rec['rows'] = rows.get(s, [])
+                if any(d.keep is None or d.keep[r] for r, _ in rec['rows']):
+                    todo.append(rec)
+        ren = RD.Renderer(rt)
+        k3 = corners.view(-1, 8, 3)
+        for lo in range(0, len(todo), self.SCENES_PER_CALL):
+            batch = todo[lo:lo + self.SCENES_PER_CALL]
+            views, legends = [], []
+            for rec in batch:
+                v, legend = self.views_of(rec, d, k3)
+                views += v
+                legends.append(legend)
+            panels = ren.render(views)
+            for k, (rec, legend) in enumerate(zip(batch, legends)):
+                RD.write_png(os.path.join(self.dir, '%06d.png' % rec['id']), RD.side_by_side(panels[2 * k:2 * k + 2]))
+                with open(os.path.join(self.dir, '%06d.json' % rec['id']), 'w') as fh:
+                    json.dump(legend, fh, indent=1)
+                self.written.append(rec['id'])
+        for p in parts:
+            p.pop('vis', None)
+        return self.written
+
+    def views_of(self, rec, d, k3):
+        """-> ([image view, bird's-eye view], legend) of one scene."""
+        K = np.asarray(rec['K'], np.float64).reshape(3, 3)
+        image = rec['image']
+        H, W = image.shape[:2] if image is not None else (int(2 * K[1, 2] + 0.5), int(2 * K[0, 2] + 0.5))
+        cam = RD.image_view(rec['Rtilt'], K, H, W, image=image)
+        xr, yr, zr = rec['ranges']
+        bev = RD.bev_view(xr, zr, H, H, y_top=yr[0], bg_colour=RD._rgb(20, 20, 24))
+        if image is None:
+            cam.points(rec['xyz'], rgb=rec['rgb'])
+        bev.points(rec['xyz'], rgb=rec['rgb'])
+        legend = {'scene': int(rec['id']), 'panels': {'image': [int(H), int(W)], 'bev': [int(H), int(H)]}, 'boxes': []}
+        byte = lambda c: [int(v * 255.0 + 0.5) for v in c]
+        if self.gt and rec['gt'] is not None and len(rec['gt']):
+            gt = np.asarray(rec['gt'], np.float32).reshape(-1, 8, 3)
+            for v in (cam, bev):
+                v.boxes(gt, RD.GT_COLOUR, thickness=1)
+            names = rec['gt_classes'] or [None] * len(gt)
+            legend['boxes'] += [{'kind': 'gt', 'class': n, 'colour': byte(RD.GT_COLOUR)} for n in names]
+        rows = rec['rows']
+        local = {r: j for j, (r, _) in enumerate(rows)}
+        kept = [(r, m) for r, m in rows if d.keep is None or d.keep[r]]
+        dropped = [(r, m) for r, m in rows if not (d.keep is None or d.keep[r])] if self.suppressed else []
+        for group, kind in ((dropped, 'suppressed'), (kept, 'kept')):              # the kept boxes lie over the suppressed ones
+            if not group:
+                continue
+            colours = [RD.SUPPRESSED_COLOUR if kind == 'suppressed' else RD.class_colour(m[2]) for _, m in group]
+            for v in (cam, bev):
+                v.boxes(k3, colours, thickness=1 if kind == 'suppressed' else 2, index=[r for r, _ in group])
+            cam.rects([m[3] for _, m in group], colours, thickness=1)
+            for (r, m), c in zip(group, colours):
+                entry = {'kind': kind, 'detection': local[r], 'class': m[2], 'prob': float(m[4]), 'score': float(d.score[r]),
+                         'box2d': [float(x) for x in m[3]], 'colour': byte(c), 'kept': kind == 'kept'}
+                if kind == 'suppressed':
+                    entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
+                legend['boxes'].append(entry)
+        return [cam, bev], legend
 
 
 class Detector:
@@ -77,8 +189,9 @@ class Detector:
         self.whitelist = list(type_whitelist)
         self.classes = list(FLAGS.SUNRGBD_SEMI_TEST_CLS) or None
 
-    def extract(self, scenes, detections, scene_ids=None):
-        """One t3d_frustum_extract launch over `scenes`; -> a part for `decode` (device tensors + what the host knows of the kept jobs)."""
+    def extract(self, scenes, detections, scene_ids=None, vis=None):
+        """One t3d_frustum_extract launch over `scenes`; -> a part for `decode` (device tensors + what the host knows of the kept jobs).
+        vis (Vis): the scenes it will draw keep their points on the device."""
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
         jobs, meta = [], []
         for s, dets in enumerate(detections):
@@ -87,12 +200,17 @@ class Detector:
                     continue
                 jobs.append({'scene': s, 'box2d': np.asarray(box2d, np.float64), 'box3d': None, 'key': (scene_ids[s], o, 0), 'choice': None})
                 meta.append((s, scene_ids[s], name, np.asarray(box2d, np.float64), float(prob)))
-        out = self.extractor.run(scenes, jobs, on_device=True)
+        want_scene = vis is not None and vis.taken < vis.max
+        out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene)
         if out is None:
             return dict(out=None, keep=[], counts=[], meta=[], n_scenes=len(scenes))
         counts = out['count'].cpu().numpy()                          # the one copy back of this launch
         keep = np.nonzero(counts >= MIN_POINTS)[0]
-        return dict(out=out, keep=keep, counts=counts[keep], meta=[meta[j] for j in keep], n_scenes=len(scenes))
+        part = dict(out=out, keep=keep, counts=counts[keep], meta=[meta[j] for j in keep], n_scenes=len(scenes))
+        if want_scene:
+            vis.take(self.rt, part, scenes, scene_ids, self.extractor.last_scene)
+            self.extractor.last_scene = None
+        return part
 
     def decode(self, parts):
         """The network and t3d_detect_decode over the frustums of `parts` (in order) -> (meta, semisup_infer.Decoded); with nms_iou, of
@@ -119,27 +237,36 @@ class Detector:
                                self.nms_iou, self.nms_metric, self.nms_score, [m[1] for m in meta], [type2class[m[2]] for m in meta],
                                [m[4] for m in meta]))
         d = res.decoded[slice(0, ds.F)]
+        self.device_corners = res.device.sec['corners']          # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there)
         if d.keep is not None and self.log:
             self.log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
                      % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), ds.F))
         return meta, d
 
-    def detect(self, scenes, detections, scene_ids=None, batch_scenes=16):
+    def detect(self, scenes, detections, scene_ids=None, batch_scenes=16, vis_dir=None, vis_max=50, vis_gt=False, vis_suppressed=False):
         """scenes: [{'points' (n, C) fp64 upright depth, 'Rtilt', 'K'}] (FrustumExtractor.run); detections[s]: [(class name, box2d
         (xmin, ymin, xmax, ymax), prob)] of scene s.  -> per scene, a list of {'class', 'box2d', 'prob', 'score', 'label' (7,) = (h, w, l,
         tx, ty, tz, ry), 'corners' (8, 3)} in detection order; a detection whose frustum holds fewer than 5 points, or whose class is
         not whitelisted (or not among FLAGS.SUNRGBD_SEMI_TEST_CLS), or which t3d_detect_nms suppressed, has no entry.  (With nms_iou,
-        scenes that share a scene id share their groups: give distinct ids.)"""
+        scenes that share a scene id share their groups: give distinct ids.)
+        vis_dir: write <id>.png / <id>.json of the first vis_max scenes with a detection there (module docstring); a scene may carry
+        'image' (uint8 [H,W,3], RGB) for the camera panel, and 'gt_corners' [g,8,3] (upright camera) / 'gt_classes' for vis_gt.  The
+        records do not depend on it."""
+        vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
         parts, first = [], []
         for lo in range(0, len(scenes), batch_scenes):
             hi = min(lo + batch_scenes, len(scenes))
-            parts.append(self.extract(scenes[lo:hi], detections[lo:hi], scene_ids[lo:hi]))
+            parts.append(self.extract(scenes[lo:hi], detections[lo:hi], scene_ids[lo:hi], vis=vis))
             first.append(lo)
         meta, d = self.decode_all(parts)
         out = [[] for _ in scenes]
+        if d is None:
+            return out
+        if vis is not None:
+            vis.write(self.rt, parts, d, self.device_corners)
         i = 0
         for lo, p in zip(first, parts):
             for s, _, name, box2d, prob in p['meta']:
@@ -165,6 +292,16 @@ class Detector:
         return p
 
 
+def scene_pictures(dataset, idx, with_gt, type_whitelist):
+    """What --vis_dir reads of a scene besides its points: the image (RGB) and, for --vis_gt, the label boxes."""
+    out = {'image': np.ascontiguousarray(dataset.get_image(idx)[:, :, ::-1])}
+    if with_gt:
+        objs = [o for o in dataset.get_label_objects(idx) if o.classname in type_whitelist]
+        out['gt_corners'] = np.stack([SD.compute_box_3d(o) for o in objs]) if objs else np.zeros((0, 8, 3))
+        out['gt_classes'] = [o.classname for o in objs]
+    return out
+
+
 def parser():
     p = argparse.ArgumentParser(description='3-D detections from SUN-RGBD scenes and 2-D detections, on the device', allow_abbrev=False)
     p.add_argument('--dataset_dir', default='mysunrgbd', help='SUN-RGBD root (<dir>/training/{image,calib,depth,label_dimension})')
@@ -174,6 +311,10 @@ def parser():
     p.add_argument('--official_eval', action='store_true', help='print the lines of script_3Deval.m for the detections (evaluate_sunrgbd)')
     p.add_argument('--test_on', default='AB', choices=['A', 'B', 'AB'], help='set of classes --official_eval scores')
     NMS.add_arguments(p)
+    p.add_argument('--vis_dir', default=None, help='write <id>.png (camera image + bird\'s-eye panel with the 3-D boxes) and <id>.json (legend) of detected scenes here')
+    p.add_argument('--vis_max', type=int, default=50, help='how many scenes --vis_dir draws (the first ones with a detection)')
+    p.add_argument('--vis_gt', action='store_true', help='--vis_dir: add the label boxes of label_dimension in green')
+    p.add_argument('--vis_suppressed', action='store_true', help='--vis_dir: add the boxes --nms_iou dropped, in grey')
     return p
 
 
@@ -183,6 +324,12 @@ def main(argv=None, rt=None, log=print):
     FLAGS = TS.build_flags(list(rest))
     try:
         NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
+    except ValueError as e:
+        parser().error(str(e))
+    if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
+        parser().error('--vis_gt / --vis_suppressed need --vis_dir')
+    try:
+        vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None) if args.vis_dir else None
     except ValueError as e:
         parser().error(str(e))
     det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=args.nms_metric,
@@ -198,8 +345,19 @@ def main(argv=None, rt=None, log=print):
     parts = []
     for batch in SD._scenes_in_batches(load, ids, 16, 8):
         scenes = [{'points': depth, 'Rtilt': calib.Rtilt, 'K': calib.K} for _, (calib, depth) in batch]
-        parts.append(det.extract(scenes, [per_scene[idx] for idx, _ in batch], [idx for idx, _ in batch]))
-    meta, d = det.decode(parts)
+        if vis is not None and vis.taken < vis.max:
+            for (idx, _), scene in zip(batch, scenes):
+                scene.update(scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist))
+        parts.append(det.extract(scenes, [per_scene[idx] for idx, _ in batch], [idx for idx, _ in batch], vis=vis))
+    if vis is None:
+        meta, d = det.decode(parts)
+    else:
+        meta, d = det.decode_all(parts)
+        if d is not None:
+            log('%d scenes drawn to %s' % (len(vis.write(det.rt, parts, d, det.device_corners)), args.vis_dir))
+            if d.keep is not None:
+                rows = np.nonzero(d.keep)[0]
+                meta, d = [meta[i] for i in rows], d[rows]
     predictions = det.predictions(meta, d)
     names = [m[2] for m in meta]
     log('%d detections of %d images' % (len(meta), len(ids)))

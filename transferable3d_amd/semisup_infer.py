@@ -92,8 +92,9 @@ class Predictions(list):
 
 
 class InferenceResult(tuple):
-    """The 7-tuple of `inference`; `.decoded` as above."""
+    """The 7-tuple of `inference`; `.decoded` as above; `.device` the DeviceDecode whose buffers still hold the records on the device."""
     decoded = None
+    device = None
 
 
 class DeviceDecode:
@@ -215,6 +216,7 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     res = InferenceResult((None if seg is None else seg.astype(np.int64), d.center, d.heading_cls, d.heading_res, d.size_cls, d.size_res,
                            d.score))
     res.decoded = d
+    res.device = dec
     return res
 
 

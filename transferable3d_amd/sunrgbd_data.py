@@ -151,13 +151,16 @@ class FrustumExtractor:
     def __init__(self, rt, num_points=NUM_POINTS, seed=0):
         self.rt, self.num_points, self.seed = rt, num_points, seed
         self.last_kernel_ms = None
+        self.last_scene = None
 
-    def run(self, scenes, jobs, perturb_box2d=False, timed=False, on_device=False):
+    def run(self, scenes, jobs, perturb_box2d=False, timed=False, on_device=False, keep_scene=False):
         """scenes: [{'points': (N, C) fp64 upright depth, 'Rtilt', 'K'}]; jobs (grouped by scene, in scene order): [{'scene': batch index,
         'box2d', 'box3d': (8,3) or None, 'key': (scene id, ordinal, aug), 'perturb': 4 uniforms or None, 'choice': ranks or None}].
         Returns per job {'box2d', 'frustum_angle', 'n', 'index', 'points', 'label'}.  on_device=True: nothing is copied back; returns the
         device tensors of the launch instead ({'box2d_out' [J,4], 'frustum_angle' [J], 'n_in_box' [J], 'count' [J], 'index' [J,NP],
-        'out_points' [J,NP,C] fp64, 'label' [J,NP]}; DeviceFrustumSet.from_device takes them), None for no jobs."""
+        'out_points' [J,NP,C] fp64, 'label' [J,NP]}; DeviceFrustumSet.from_device takes them), None for no jobs.  keep_scene=True:
+        `last_scene` = (the device copy of the scenes' points [sum N, C] fp64, the scenes' row offsets) of this launch, for a caller
+        that goes on reading them there (detect --vis_dir)."""
         dev, NP, J, S = self.rt.device, self.num_points, len(jobs), len(scenes)
         if J == 0:
             return None if on_device else []
@@ -191,6 +194,8 @@ class FrustumExtractor:
                  scene_jobs=up(scene_jobs, torch.int32), box2d=up(np.stack([np.asarray(j['box2d'], np.float64) for j in jobs]), torch.float64),
                  job_key=up(np.array([j['key'] for j in jobs], np.int64).astype(np.int32), torch.int32),
                  mask_offsets=up(mask_offsets, torch.int64))
+        if keep_scene:
+            self.last_scene = (t['points'], scene_offsets)
         if with_perturb:
             t['perturb_draws'] = up(np.array([j['perturb'] for j in jobs], np.float64), torch.float64)
         if with_box3d:
