@@ -1325,51 +1325,151 @@ class FakeLib:
               7: ('t3d_pool_bwd_mid', 'mid')}
 
     def t3d_riders_plan(self, r):
+        """csrc/pair.hip: which ops may ride (csrc/rider_dev.h rider_op_blocks), the workgroups and the LDS of the set."""
         rs = _struct(r)
         if rs.n_ops <= 0 or rs.n_ops > abi.RIDER_MAX_OPS:
             return -1
+        n_wg, lds = 1, 0
         for k in range(rs.n_ops):
             o = rs.ops[k]
             if o.kind not in self._RIDER:
                 return -1
             u = getattr(o.u, self._RIDER[o.kind][1])
+            nb, op_lds = -1, 8 * 32 * 33 * 4          # fc_lds_bytes(32): eight reduction tiles of 32 rows x 33 floats
             if o.kind == 7:
-                if rs.n_ops != 1:
-                    return -1
-                if 128 * 128 * 4 + (4 * u.sparse.N + 128) * 4 > 76 * 1024:
-                    return -2
-                continue
-            if o.kind in (2, 3, 6) and u.B > 32:
+                sp = u.sparse
+                ok = bool(u.slab_base) and bool(u.grad_base) and bool(u.table_dev) and u.n_tensors > 0 and bool(sp.argidx) and \
+                    bool(sp.dpool) and bool(sp.wc) and bool(sp.s)
+                op_lds = 128 * 128 * 4 + (4 * sp.N + 128) * 4
+                if ok and op_lds <= 76 * 1024:          # above: the host GEMM would drop to one workgroup per CU
+                    gx = min(256, max(1, (u.max_numel // 4 + 31) // 32))
+                    nb = gx * u.n_tensors + (sp.B * sp.rows_per_frustum // 128) * (sp.K // 128)
+            elif o.kind in (2, 6):
+                nb = (u.N + 31) // 32 if u.B <= 32 else -1
+            elif o.kind == 3:
+                nb = (u.K + 31) // 32 if u.B <= 32 else -1
+            elif o.kind == 5:
+                nb = (u.N + 15) // 16 if u.n_tiles <= 512 else -1
+            elif o.kind == 1:
+                nb = (u.N + 15) // 16 if u.coef and not (u.psum_dz and u.n_tiles > 512) else -1
+            elif o.kind == 4:
+                nb = (u.B * u.N + 255) // 256
+            if nb <= 0:
                 return -2
-            if (o.kind == 5 and u.n_tiles > 512) or (o.kind == 1 and u.psum_dz and u.n_tiles > 512):
-                return -2
-        rs.n_wg, rs.lds_bytes = 1, 0
+            if o.kind == 7 and rs.n_ops != 1:
+                return -1
+            n_wg, lds = max(n_wg, nb), max(lds, op_lds)
+        wide = rs.n_ops == 1 and rs.ops[0].kind == 7
+        rs.n_wg, rs.lds_bytes = min(n_wg, 2048 if wide else 32), lds
+        return 0
+
+    # ---- the launchers' argument checks (csrc/pointmlp.hip, csrc/poolbwd_dev.h), as far as the `_hosts_riders` queries answer them ----
+    @staticmethod
+    def _act_ok(a, K):
+        return bool(a.x) and a.ldx % 4 == 0 and a.coff % 4 == 0 and a.coff + (K + 3) // 4 * 4 <= a.ldx and (not a.scale or bool(a.shift))
+
+    @staticmethod
+    def _dy_ok(d):
+        return bool(d.y) and bool(d.coef) and (bool(d.dz) or (bool(d.argidx) and bool(d.dpool)))
+
+    @staticmethod
+    def _rows_ok(M, rpf):
+        return M > 0 and M % 128 == 0 and rpf > 0 and rpf % 128 == 0 and M % rpf == 0
+
+    def _check_fwd(self, p):
+        if not (p.w and p.psum and p.psumsq and self._act_ok(p.a, p.K)) or (p.pmax and not (p.pmin and p.pamax and p.pamin)):
+            return -1
+        if not self._rows_ok(p.M, p.rows_per_frustum) or p.K <= 0 or p.N <= 0 or p.N % 64 or p.M * p.N >= 1 << 30:
+            return -2
+        return 0
+
+    def _check_dgrad(self, p):
+        if not (p.w and p.out and self._dy_ok(p.dy)) or (p.prev_y and not (p.prev_scale and p.prev_shift)) or \
+                (p.psum_dz and not (p.psum_dzy and p.prev_y)) or p.dtype != p.dy.dtype:
+            return -1
+        if not self._rows_ok(p.M, p.rows_per_frustum) or p.K % 64 or p.N % 4 or p.M * p.K >= 1 << 30:
+            return -2
+        return 0
+
+    def _check_wgrad(self, p):
+        if not (p.slabs and self._act_ok(p.a, p.K) and self._dy_ok(p.dy)):
+            return -1
+        red = 64 if p.dy.dtype == abi.BF16 else 32
+        if p.M <= 0 or p.rows_per_split <= 0 or p.rows_per_split % red or p.M % p.rows_per_split or p.N % 64 or \
+                p.rows_per_frustum <= 0 or p.rows_per_frustum % red or p.M % p.rows_per_frustum:
+            return -2
+        return 0
+
+    def _check_gram(self, p):
+        if not (p.slabs and self._act_ok(p.a, p.K)) or p.a.sub:
+            return -1
+        red = 64 if p.a.dtype == abi.BF16 else 32
+        if p.M <= 0 or p.rows_per_split <= 0 or p.rows_per_split % red or p.M % p.rows_per_split or p.K % 64 or \
+                p.rows_per_frustum <= 0 or p.rows_per_frustum % red or p.M % p.rows_per_frustum:
+            return -2
         return 0
 
     # (specification library: every fp32 GEMM launch "hosts" -- the set simply runs beside it)
     def t3d_pointmlp_fwd_hosts_riders(self, a):
-        return int(_struct(a).dtype == 0)
+        p = _struct(a)
+        return self._check_fwd(p) or int(p.dtype == 0)
 
     def t3d_pointmlp_wgrad_hosts_riders(self, a):
         p = _struct(a)
-        return int(p.dy.dtype == 0 and p.K <= 64 and p.N <= 128 and bool(p.dy.dz))
+        return self._check_wgrad(p) or int(p.dy.dtype == 0 and p.K <= 64 and p.N <= 128 and bool(p.dy.dz))
 
     def t3d_pointmlp_bwd_hosts_riders(self, d, w):
-        return int(_struct(d).dtype == 0)
+        pd, pw = _struct(d), _struct(w)
+        rc = self._check_dgrad(pd) or self._check_wgrad(pw)
+        if rc:
+            return rc
+        if not (pd.dy.dz and pw.dy.dz) or pw.a.sub:
+            return -1
+        if (pd.M, pd.K, pd.N) != (pw.M, pw.K, pw.N):
+            return -2
+        return int(pd.dtype == 0)
 
     def t3d_pool_bwd_stage1_hosts_riders(self, g, c, q):
-        return int(_struct(g).a.dtype == 0)
+        pg, pc, pq = _struct(g), _struct(c), _struct(q)
+        rc = self._check_gram(pg)
+        if rc:
+            return rc
+        if not (pc.part and pc.a.x) or not (pq.w and pq.coef and pq.p_slabs and pq.rc_slabs):
+            return -1
+        if pc.M <= 0 or pc.M % 128 or pc.K not in (64, 128, 256) or pq.K <= 0 or pq.K % 32 or pq.N <= 0 or pq.N % 4:
+            return -2
+        return int(pg.a.dtype == 0)
 
     def t3d_pool_bwd_stage2_hosts_riders(self, f, d):
-        return int(_struct(d).dtype == 0)
+        pf, pd = _struct(f), _struct(d)
+        if not (pf.argidx and pf.dpool and pf.coef and pf.w and pf.g and pf.abar and pf.dw and pf.a.x):
+            return -1
+        if pf.K <= 0 or pf.K % 32 or pf.K > 256 or pf.N <= 0 or pf.N % 16 or pf.B <= 0:
+            return -2
+        if not (pd.p and pd.out and self._act_ok(pd.a, pd.K)) or pd.a.sub or (pd.add_live and not pd.add_in) or \
+                (pd.prev_y and not (pd.prev_scale and pd.prev_shift)) or (pd.psum_dz and not (pd.psum_dzy and pd.prev_y)) or pd.dtype != pd.a.dtype:
+            return -1
+        if not self._rows_ok(pd.M, pd.rows_per_frustum) or pd.K % 64 or pd.M * pd.K >= 1 << 30:
+            return -2
+        return int(pd.dtype == 0)
+
+    @staticmethod
+    def _riders_ok(rs):
+        return bool(rs.sync) and 0 < rs.n_ops <= abi.RIDER_MAX_OPS and 0 < rs.n_wg <= (2048 if rs.n_ops == 1 else 32) and rs.lds_bytes >= 0
 
     def t3d_run_riders(self, r, stream):
+        """The ops in order.  The barrier words as the device leaves them (csrc/rider_dev.h): barrier i, in front of op i >= 1 with
+        `depends`, has reset its arrival count sync[2i] and moved its generation sync[2i + 1] once."""
         if not r:
-            return 0
+            return -1
         rs = _struct(r)
+        if not self._riders_ok(rs):
+            return -1
         for k in range(rs.n_ops):
             o = rs.ops[k]
             fn, field = self._RIDER[o.kind]
+            if k > 0 and o.depends:
+                rs.sync[2 * k + 1] += 1
             if o.kind == 7:
                 m = o.u.mid
                 rc = self.t3d_pool_bwd_mid(m.slab_base, m.grad_base, m.table_dev, m.n_tensors, m.max_numel, C.byref(m.sparse), stream)
@@ -1379,20 +1479,30 @@ class FakeLib:
                 return rc
         return 0
 
+    def _with_riders(self, r, stream, host, riders_first):
+        """An `_r` launch: riders == NULL is the plain launch; a malformed set is refused before anything runs."""
+        if not r:
+            return host()
+        if not self._riders_ok(_struct(r)):
+            return -1
+        if riders_first:
+            return self.t3d_run_riders(r, stream) or host()
+        return host() or self.t3d_run_riders(r, stream)
+
     def t3d_pointmlp_fwd_r(self, a, r, stream):
-        return self.t3d_run_riders(r, stream) or self.t3d_pointmlp_fwd(a, stream)
+        return self._with_riders(r, stream, lambda: self.t3d_pointmlp_fwd(a, stream), True)
 
     def t3d_pointmlp_wgrad_r(self, a, r, stream):
-        return self.t3d_run_riders(r, stream) or self.t3d_pointmlp_wgrad(a, stream)
+        return self._with_riders(r, stream, lambda: self.t3d_pointmlp_wgrad(a, stream), True)
 
     def t3d_pointmlp_bwd_r(self, d, w, r, stream):
-        return self.t3d_pointmlp_bwd(d, w, stream) or self.t3d_run_riders(r, stream)
+        return self._with_riders(r, stream, lambda: self.t3d_pointmlp_bwd(d, w, stream), False)
 
     def t3d_pool_bwd_stage1_r(self, g, c, q, r, stream):
-        return self.t3d_pool_bwd_stage1(g, c, q, stream) or self.t3d_run_riders(r, stream)
+        return self._with_riders(r, stream, lambda: self.t3d_pool_bwd_stage1(g, c, q, stream), False)
 
     def t3d_pool_bwd_stage2_r(self, f, d, r, stream):
-        return self.t3d_run_riders(r, stream) or self.t3d_pool_bwd_stage2(f, d, stream)
+        return self._with_riders(r, stream, lambda: self.t3d_pool_bwd_stage2(f, d, stream), True)
 
     def t3d_anchor_reg_bwd(self, a, stream):
         p = _struct(a)
