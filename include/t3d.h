@@ -557,7 +557,7 @@ typedef struct {
         cross_entropy;
 } t3d_strong_weights;
 typedef struct {
-  const float* box; int ld_box;          /* [B,67] head output (centre residual first) */
+  const float* box; int ld_box;          /* [B,67] head output (centre residual first), rows ld_box >= 67 floats apart (less: T3D_ERR_SHAPE) */
   const float* stage1_center;            /* [B,3] */
   const float* seg_loss;                 /* [B] or NULL */
   const float* y_center; const int32_t* y_orient_cls; const float* y_orient_reg;
@@ -750,7 +750,7 @@ int t3d_semi_final_loss(const t3d_semi_final_loss_args* args, t3d_stream_t strea
 /* Backward of the anchor->reg conversion (tf_util.py:1017-1031): accumulates the gradient of (centre, dims, theta)
  * -- dbox7[B,7] from the Box-PC path and/or d_dims[B,3] -- into dbox[B,67] and dstage1[B,3] (both in/out). */
 typedef struct {
-  const float* box; int ld_box;   /* [B,67] head output (scores pick the bins) */
+  const float* box; int ld_box;   /* [B,67] head output (scores pick the bins), rows ld_box >= 67 floats apart (less: T3D_ERR_SHAPE) */
   const float* dbox7;             /* [B,7] or NULL */
   const float* d_dims;            /* [B,3] or NULL */
   float* dbox;                    /* [B,67] in/out */

@@ -138,6 +138,112 @@ def _dy(src, M, N, rpf):
     return coef[0] * dz + coef[1] * y + coef[2]
 
 
+def strong_loss_f64(box, s1, yc, yoc, yor, ydc, ydr, is2d, seg, W, normalize_by_3d_count, with_iou=False):
+    """t3d_strong_loss in float64 on fp32 inputs: {output name: fp64 array} (the values FakeLib.t3d_strong_loss stores as fp32)."""
+    box, s1, yc, yor, ydr = [np.asarray(v).astype(np.float64) for v in (box, s1, yc, yor, ydr)]
+    B = box.shape[0]
+    w3d = (1 - np.asarray(is2d)).astype(np.float64)
+    norm = 1.0 / (w3d.sum() + 1e-3) if normalize_by_3d_count else 1.0 / B
+    seg = np.asarray(seg).astype(np.float64) if seg is not None else np.zeros(B)
+    dbox, ds1, terms, tot = np.zeros((B, 67)), np.zeros((B, 3)), np.zeros((B, 8)), np.zeros(B)
+    center, reg_dims, reg_theta, iou3d, iou2d = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B), np.zeros(B), np.zeros(B)
+    mean = MEAN32.astype(np.float64)
+    bins = BINS32.astype(np.float64)
+    sx = np.array([1, 1, -1, -1, 1, 1, -1, -1.])
+    sy = np.array([1, 1, 1, 1, -1, -1, -1, -1.])
+    sz = np.array([1, -1, -1, 1, 1, -1, -1, 1.])
+
+    def hub(e, d):
+        q = min(abs(e), d)
+        return 0.5 * q * q + d * (abs(e) - q)
+
+    def ce(z, lab, g, gsc):
+        m = z.max()
+        lse = m + math.log(np.exp(z - m).sum())
+        g += gsc * (np.exp(z - lse) - np.eye(len(z))[lab])
+        return lse - z[lab]
+
+    total_sum = 0.0
+    for b in range(B):
+        o = box[b]
+        g = np.zeros(67)
+        gc, gs1 = np.zeros(3), np.zeros(3)
+        gs = w3d[b] * norm
+        bm = W.box_multiplier
+        cen = o[0:3] + s1[b]
+        j, k = int(yoc[b]), int(ydc[b])
+        dist = np.linalg.norm(yc[b] - cen)
+        l_c = hub(dist, 2.0)
+        if dist > 0:
+            gc += gs * bm * W.center * min(dist, 2.0) / dist * (cen - yc[b])
+        dist = np.linalg.norm(yc[b] - s1[b])
+        l_s1 = hub(dist, 1.0)
+        if dist > 0:
+            gs1 += gs * bm * W.tnet_center * min(dist, 1.0) / dist * (s1[b] - yc[b])
+        l_hc = ce(o[3:3 + NH], j, g[3:3 + NH], gs * bm * W.orient_cls)
+        hrn = o[3 + NH + j]
+        eh = hrn - yor[b] / (np.pi / NH)
+        l_hr = hub(eh, 1.0)
+        g[3 + NH + j] += gs * bm * W.orient_reg * np.clip(eh, -1, 1)
+        l_sc = ce(o[3 + 2 * NH:3 + 2 * NH + NS], k, g[3 + 2 * NH:3 + 2 * NH + NS], gs * bm * W.dims_cls)
+        so = 3 + 2 * NH + NS + 3 * k
+        srn = o[so:so + 3]
+        dsv = srn - ydr[b] / mean[k]
+        sd = np.linalg.norm(dsv)
+        l_sr = hub(sd, 1.0)
+        if sd > 0:
+            g[so:so + 3] += gs * bm * W.dims_reg * min(sd, 1.0) / sd * dsv
+        th = bins[j] + hrn * (np.pi / NH)
+        c, s = math.cos(th), math.sin(th)
+        size = mean[k] + 2 * srn * mean[k]
+        hl = bins[j] + yor[b]
+        gl = mean[k] + ydr[b]
+        l_co = 0.0
+        gth = 0.0
+        gsize = np.zeros(3)
+        for i in range(8):
+            x, y, z = sx[i] * size[0] / 2, sy[i] * size[2] / 2, sz[i] * size[1] / 2
+            cp = np.array([c * x + s * z, y, -s * x + c * z]) + cen
+            xg, yg, zg = sx[i] * gl[0] / 2, sy[i] * gl[2] / 2, sz[i] * gl[1] / 2
+            tg = []
+            for ang in (hl, hl + np.pi):
+                ca, sa = math.cos(ang), math.sin(ang)
+                tg.append(np.array([ca * xg + sa * zg, yg, -sa * xg + ca * zg]) + yc[b])
+            d1, d2 = np.linalg.norm(cp - tg[0]), np.linalg.norm(cp - tg[1])
+            t, dm = (tg[0], d1) if d1 <= d2 else (tg[1], d2)
+            l_co += hub(dm, 1.0) / 8
+            if dm > 0:
+                gv = gs * W.corner / 8 * min(dm, 1.0) / dm * (cp - t)
+                gc += gv
+                gth += gv[0] * (-s * x + c * z) + gv[2] * (-c * x - s * z)
+                gsize[0] += (gv[0] * c - gv[2] * s) * sx[i] / 2
+                gsize[2] += gv[1] * sy[i] / 2
+                gsize[1] += (gv[0] * s + gv[2] * c) * sz[i] / 2
+        g[3 + NH + j] += gth * (np.pi / NH)
+        g[so:so + 3] += gsize * 2 * mean[k]
+        g[0:3] = gc
+        box_l = bm * (W.center * l_c + W.orient_cls * l_hc + W.dims_cls * l_sc + W.orient_reg * l_hr
+                      + W.dims_reg * l_sr + W.tnet_center * l_s1) + W.corner * l_co
+        t_b = w3d[b] * (W.cross_entropy * seg[b] + box_l)
+        total_sum += t_b
+        dbox[b] = g
+        ds1[b] = gc + gs1
+        center[b] = cen
+        terms[b] = [seg[b], l_c, l_s1, l_hc, l_hr, l_sc, l_sr, l_co]
+        tot[b] = t_b
+        js = int(np.argmax(o[3:3 + NH]))
+        ks = int(np.argmax(o[3 + 2 * NH:3 + 2 * NH + NS]))
+        so2 = 3 + 2 * NH + NS + 3 * ks
+        reg_dims[b] = np.maximum(mean[ks] + o[so2:so2 + 3] * mean[ks], 1e-5)
+        reg_theta[b] = np.float32(bins[js] + o[3 + NH + js] * (np.pi / NH))      # (the IoU below reads the stored fp32 value)
+        if with_iou:
+            sp = mean[ks] + o[so2:so2 + 3] * mean[ks]
+            i3, i2 = box3d_iou_spec(cen, sp, reg_theta[b], yc[b], mean[k] + ydr[b], bins[j] + yor[b])
+            iou3d[b], iou2d[b] = i3, i2
+    return dict(dbox=dbox, dstage1=ds1, terms=terms, total_losses=tot, loss=np.array([total_sum * norm]), center=center, reg_dims=reg_dims,
+                reg_theta=reg_theta, iou3d=iou3d, iou2d=iou2d)
+
+
 class FakeLib:
     """Drop-in for the ctypes library object (same call signatures, host pointers)."""
 
@@ -941,6 +1047,8 @@ class FakeLib:
         from oracle import ref_weak as W
         p = _struct(a)
         B, N = p.B, p.N
+        if B <= 0 or B > 256 or N <= 0 or N % 128:
+            return -2
         t64 = lambda x, *shape: torch.as_tensor(np.array(arr(x, *shape)), dtype=torch.float64)
         center, dims, theta = t64(p.center, B, 3).requires_grad_(True), t64(p.reg_dims, B, 3).requires_grad_(True), \
             t64(p.reg_theta, B).requires_grad_(True)
@@ -999,114 +1107,19 @@ class FakeLib:
         return 0
 
     def t3d_strong_loss(self, a, stream):
-        """Analytic restatement in float64 of the loss kernel (forward and hand-derived backward)."""
+        """Analytic restatement in float64 of the loss kernel (forward and hand-derived backward): strong_loss_f64, stored as fp32."""
         p = _struct(a)
         B = p.B
-        W = p.wts
-        box = arr(p.box, B, p.ld_box)[:, :67].astype(np.float64)
-        s1 = arr(p.stage1_center, B, 3).astype(np.float64)
-        yc = arr(p.y_center, B, 3).astype(np.float64)
-        yoc, yor = arr(p.y_orient_cls, B), arr(p.y_orient_reg, B).astype(np.float64)
-        ydc, ydr = arr(p.y_dims_cls, B), arr(p.y_dims_reg, B, 3).astype(np.float64)
-        w3d = (1 - arr(p.is_data_2D, B)).astype(np.float64)
-        norm = 1.0 / (w3d.sum() + 1e-3) if p.normalize_by_3d_count else 1.0 / B
-        seg = arr(p.seg_loss, B).astype(np.float64) if p.seg_loss else np.zeros(B)
-        dbox, ds1 = arr(p.dbox, B, 67), arr(p.dstage1, B, 3)
-        terms, tot = arr(p.terms, B, 8), arr(p.total_losses, B)
-        mean = MEAN32.astype(np.float64)
-        bins = BINS32.astype(np.float64)
-        sx = np.array([1, 1, -1, -1, 1, 1, -1, -1.])
-        sy = np.array([1, 1, 1, 1, -1, -1, -1, -1.])
-        sz = np.array([1, -1, -1, 1, 1, -1, -1, 1.])
-
-        def hub(e, d):
-            q = min(abs(e), d)
-            return 0.5 * q * q + d * (abs(e) - q)
-
-        def ce(z, lab, g, gsc):
-            m = z.max()
-            lse = m + math.log(np.exp(z - m).sum())
-            g += gsc * (np.exp(z - lse) - np.eye(len(z))[lab])
-            return lse - z[lab]
-
-        total_sum = 0.0
-        for b in range(B):
-            o = box[b]
-            g = np.zeros(67)
-            gc, gs1 = np.zeros(3), np.zeros(3)
-            gs = w3d[b] * norm
-            bm = W.box_multiplier
-            cen = o[0:3] + s1[b]
-            j, k = int(yoc[b]), int(ydc[b])
-            dist = np.linalg.norm(yc[b] - cen)
-            l_c = hub(dist, 2.0)
-            if dist > 0:
-                gc += gs * bm * W.center * min(dist, 2.0) / dist * (cen - yc[b])
-            dist = np.linalg.norm(yc[b] - s1[b])
-            l_s1 = hub(dist, 1.0)
-            if dist > 0:
-                gs1 += gs * bm * W.tnet_center * min(dist, 1.0) / dist * (s1[b] - yc[b])
-            l_hc = ce(o[3:3 + NH], j, g[3:3 + NH], gs * bm * W.orient_cls)
-            hrn = o[3 + NH + j]
-            eh = hrn - yor[b] / (np.pi / NH)
-            l_hr = hub(eh, 1.0)
-            g[3 + NH + j] += gs * bm * W.orient_reg * np.clip(eh, -1, 1)
-            l_sc = ce(o[3 + 2 * NH:3 + 2 * NH + NS], k, g[3 + 2 * NH:3 + 2 * NH + NS], gs * bm * W.dims_cls)
-            so = 3 + 2 * NH + NS + 3 * k
-            srn = o[so:so + 3]
-            dsv = srn - ydr[b] / mean[k]
-            sd = np.linalg.norm(dsv)
-            l_sr = hub(sd, 1.0)
-            if sd > 0:
-                g[so:so + 3] += gs * bm * W.dims_reg * min(sd, 1.0) / sd * dsv
-            th = bins[j] + hrn * (np.pi / NH)
-            c, s = math.cos(th), math.sin(th)
-            size = mean[k] + 2 * srn * mean[k]
-            hl = bins[j] + yor[b]
-            gl = mean[k] + ydr[b]
-            l_co = 0.0
-            gth = 0.0
-            gsize = np.zeros(3)
-            for i in range(8):
-                x, y, z = sx[i] * size[0] / 2, sy[i] * size[2] / 2, sz[i] * size[1] / 2
-                cp = np.array([c * x + s * z, y, -s * x + c * z]) + cen
-                xg, yg, zg = sx[i] * gl[0] / 2, sy[i] * gl[2] / 2, sz[i] * gl[1] / 2
-                tg = []
-                for ang in (hl, hl + np.pi):
-                    ca, sa = math.cos(ang), math.sin(ang)
-                    tg.append(np.array([ca * xg + sa * zg, yg, -sa * xg + ca * zg]) + yc[b])
-                d1, d2 = np.linalg.norm(cp - tg[0]), np.linalg.norm(cp - tg[1])
-                t, dm = (tg[0], d1) if d1 <= d2 else (tg[1], d2)
-                l_co += hub(dm, 1.0) / 8
-                if dm > 0:
-                    gv = gs * W.corner / 8 * min(dm, 1.0) / dm * (cp - t)
-                    gc += gv
-                    gth += gv[0] * (-s * x + c * z) + gv[2] * (-c * x - s * z)
-                    gsize[0] += (gv[0] * c - gv[2] * s) * sx[i] / 2
-                    gsize[2] += gv[1] * sy[i] / 2
-                    gsize[1] += (gv[0] * s + gv[2] * c) * sz[i] / 2
-            g[3 + NH + j] += gth * (np.pi / NH)
-            g[so:so + 3] += gsize * 2 * mean[k]
-            g[0:3] = gc
-            box_l = bm * (W.center * l_c + W.orient_cls * l_hc + W.dims_cls * l_sc + W.orient_reg * l_hr
-                          + W.dims_reg * l_sr + W.tnet_center * l_s1) + W.corner * l_co
-            t_b = w3d[b] * (W.cross_entropy * seg[b] + box_l)
-            total_sum += t_b
-            dbox[b] = g
-            ds1[b] = gc + gs1
-            arr(p.center, B, 3)[b] = cen
-            terms[b] = [seg[b], l_c, l_s1, l_hc, l_hr, l_sc, l_sr, l_co]
-            tot[b] = t_b
-            js = int(np.argmax(o[3:3 + NH]))
-            ks = int(np.argmax(o[3 + 2 * NH:3 + 2 * NH + NS]))
-            so2 = 3 + 2 * NH + NS + 3 * ks
-            arr(p.reg_dims, B, 3)[b] = np.maximum(mean[ks] + o[so2:so2 + 3] * mean[ks], 1e-5)
-            arr(p.reg_theta, B)[b] = bins[js] + o[3 + NH + js] * (np.pi / NH)
-            if p.iou3d:
-                sp = mean[ks] + o[so2:so2 + 3] * mean[ks]
-                i3, i2 = box3d_iou_spec(cen, sp, arr(p.reg_theta, B)[b], yc[b], mean[k] + ydr[b], bins[j] + yor[b])
-                arr(p.iou3d, B)[b], arr(p.iou2d, B)[b] = i3, i2
-        arr(p.loss, 1)[0] = total_sum * norm
+        if B <= 0 or B > 1024 or p.ld_box < 67:
+            return -2
+        if bool(p.iou2d) != bool(p.iou3d):
+            return -1
+        r = strong_loss_f64(arr(p.box, B, p.ld_box)[:, :67], arr(p.stage1_center, B, 3), arr(p.y_center, B, 3), arr(p.y_orient_cls, B),
+                            arr(p.y_orient_reg, B), arr(p.y_dims_cls, B), arr(p.y_dims_reg, B, 3), arr(p.is_data_2D, B),
+                            arr(p.seg_loss, B) if p.seg_loss else None, p.wts, p.normalize_by_3d_count, bool(p.iou3d))
+        for name, shape in (('dbox', (B, 67)), ('dstage1', (B, 3)), ('terms', (B, 8)), ('total_losses', (B,)), ('loss', (1,)),
+                            ('center', (B, 3)), ('reg_dims', (B, 3)), ('reg_theta', (B,))) + ((('iou3d', (B,)), ('iou2d', (B,))) if p.iou3d else ()):
+            arr(getattr(p, name), *shape)[:] = r[name]
         return 0
 
     # ---- 3-D IoU (K13) ----------------------------------------------------------------------------------
@@ -1138,6 +1151,8 @@ class FakeLib:
     def t3d_box_head_iou(self, a, stream):
         p = _struct(a)
         B = p.B
+        if B <= 0 or p.ld_box < 67:
+            return -2
         box = arr(p.box, B, p.ld_box)[:, :67].astype(np.float64)
         s1 = arr(p.stage1_center, B, 3).astype(np.float64) if p.stage1_center else np.zeros((B, 3))
         yc, yoc, yor = arr(p.y_center, B, 3).astype(np.float64), arr(p.y_orient_cls, B), arr(p.y_orient_reg, B).astype(np.float64)
@@ -1265,6 +1280,8 @@ class FakeLib:
     # ---- stage-c glue --------------------------------------------------------------------------------
     def t3d_pointmlp_dgrad_narrow(self, a, stream):
         p = _struct(a)
+        if p.M <= 0 or p.M % 64 or p.N % 128 or p.kn <= 0 or p.kn > 8 or p.ld_out < p.kn:
+            return -2
         dy = _dy(p.dy, p.M, p.N, p.M)
         K = p.k0 + p.kn
         w = arr(p.w, K, p.N).astype(np.float64)[p.k0:]
@@ -1274,6 +1291,8 @@ class FakeLib:
     def t3d_semi_final_loss(self, a, stream):
         p = _struct(a)
         B = p.B
+        if B <= 0 or B > 1024:
+            return -2
         dims = arr(p.reg_dims, B, 3).astype(np.float64)
         cls = arr(p.one_hot, B, 10).argmax(1)
         tc = [bool(p.train_classes[i]) for i in range(10)]
@@ -1507,6 +1526,8 @@ class FakeLib:
     def t3d_anchor_reg_bwd(self, a, stream):
         p = _struct(a)
         B = p.B
+        if B <= 0 or B > 1024 or p.ld_box < 67:
+            return -2
         o = arr(p.box, B, p.ld_box)[:, :67].astype(np.float64)
         g, ds1 = arr(p.dbox, B, 67), arr(p.dstage1, B, 3)
         js, ks = o[:, 3:15].argmax(1), o[:, 27:37].argmax(1)
@@ -1568,6 +1589,18 @@ class FakeLib:
         lr = arr(hyper, 4)[1]
         a[:] = np.float32(momentum) * a + g * np.float32(gscale)
         w[:] = w - lr * a
+        return 0
+
+    def t3d_cast_bf16(self, src, dst, n, stream):
+        """fp32 -> bf16, round to nearest even (NaN stays NaN); both pointers 16-byte aligned."""
+        addr = lambda q: q if isinstance(q, int) else (C.cast(q, C.c_void_p).value or 0)
+        if not addr(src) or not addr(dst) or n <= 0 or addr(src) % 16 or addr(dst) % 16:
+            return -1
+        x = np.ctypeslib.as_array(C.cast(src, C.POINTER(C.c_uint32)), shape=(n,)).astype(np.uint64)
+        out = np.ctypeslib.as_array(C.cast(dst, C.POINTER(C.c_uint16)), shape=(n,))
+        r = ((x + 0x7FFF + ((x >> 16) & 1)) >> 16).astype(np.uint16)
+        nan = (x & 0x7FFFFFFF) > 0x7F800000
+        out[:] = np.where(nan, ((x >> 16) | 0x40).astype(np.uint16), r)
         return 0
 
     def t3d_dropout_mask(self, mask, n, keep, seed, hyper, stream):

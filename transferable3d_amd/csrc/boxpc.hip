@@ -468,7 +468,7 @@ extern "C" int t3d_semi_final_loss(const t3d_semi_final_loss_args* a, t3d_stream
 
 extern "C" int t3d_anchor_reg_bwd(const t3d_anchor_reg_bwd_args* a, t3d_stream_t stream) {
   if (!a || !a->box || !a->dbox || !a->dstage1) return T3D_ERR_ARG;
-  if (a->B <= 0 || a->B > 1024) return T3D_ERR_SHAPE;
+  if (a->B <= 0 || a->B > 1024 || a->ld_box < 67) return T3D_ERR_SHAPE;
   T3D_LAUNCH(k_anchor_reg_bwd, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), *a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;

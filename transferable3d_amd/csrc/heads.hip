@@ -492,7 +492,7 @@ extern "C" int t3d_strong_loss(const t3d_strong_loss_args* a, t3d_stream_t strea
       !a->y_dims_reg || !a->is_data_2D || !a->dbox || !a->dstage1 || !a->terms || !a->total_losses || !a->loss ||
       !a->center || !a->reg_dims || !a->reg_theta)
     return T3D_ERR_ARG;
-  if (a->B <= 0 || a->B > 1024) return T3D_ERR_SHAPE;
+  if (a->B <= 0 || a->B > 1024 || a->ld_box < 67) return T3D_ERR_SHAPE;      // (a narrower row would read the next frustum's heads)
   if ((a->iou2d == nullptr) != (a->iou3d == nullptr)) return T3D_ERR_ARG;
   if (a->B <= 128) T3D_LAUNCH(k_strong_loss<true>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), *a);
   else T3D_LAUNCH(k_strong_loss<false>, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), *a);
