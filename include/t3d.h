@@ -433,7 +433,7 @@ int t3d_pool_bwd_stage2(const t3d_pool_wgrad_finish_args* finish, const t3d_poin
  * drop_mask holds 0/1 keep flags; out *= mask/keep_prob. */
 typedef struct {
   const float* in;  int ld_in;  int K;
-  const float* in2; int ld_in2; int K2;      /* optional concat (one_hot_vec), K2 = 0 if none */
+  const float* in2; int ld_in2; int K2;      /* optional concat (one_hot_vec), K2 = 0 if none (in2 is then not read, whatever it holds) */
   const float* w;                            /* [K+K2, N]; NULL = identity (K == N, K2 == 0): y = in, i.e. a standalone
                                               * tf_util.batch_norm_for_fc (tf_util.py:1666-1677) / tf_util.dropout (1720-1741) node */
   const float* bias;                         /* [N] or NULL */
@@ -461,7 +461,11 @@ typedef struct {
   const float* in2; int ld_in2; int K2;
   const float* y; const float* out; int ld_out;
   const float* gamma; const float* beta; const float* mean; const float* invstd;
-  int bn_training;                                         /* 0: gamma*invstd only (frozen) */
+  int bn_training;                                         /* 0: gamma*invstd only (frozen): dy = gamma * invstd * dz.  With batch-norm and
+                                                            * bn_training == 0, dbias is written as 0 and dgamma / dbeta are left untouched --
+                                                            * not the gradients of a frozen layer's parameters (those would be sum dz * gamma *
+                                                            * invstd, sum dz * xhat, sum dz).  No plan asks for them: a frozen net runs without
+                                                            * parameter gradients (dw = dbias = dgamma = dbeta = NULL). */
   int act; float leaky_alpha;
   const float* drop_mask; float keep_prob;
   float* dy;                                               /* [B,N] */
@@ -1167,7 +1171,10 @@ int t3d_dropout_mask(float* mask, int64_t n, float keep_prob, uint32_t seed, con
 /* ---- two independent small launches in one ---------------------------------------------------------------------------
  * a and b must not depend on each other (the box / T-Net backward and the segmentation-net backward: semisup_models.py:150-151).
  * Same arguments, same results (bit for bit) as the two stand-alone calls; what is saved is one kernel boundary (~3-5 us).
- * Kinds: t3d_bn_bwd_finalize (up to 512 row tiles), t3d_fc_bwd, t3d_fc_dinput, t3d_dy_colsum. */
+ * Kinds: t3d_bn_bwd_finalize (up to 512 row tiles), t3d_fc_bwd, t3d_fc_dinput, t3d_dy_colsum.
+ * Each op passes the argument checks of its stand-alone launcher first, and the pair answers what that launcher would (a's before b's);
+ * then T3D_ERR_ARG for NULL, another kind or a dense finalizer of more than 512 tiles, T3D_ERR_SHAPE for an FC op of at most 32 rows beside one
+ * of more.  Nothing is launched when the pair is refused. */
 enum { T3D_SMALL_BN_BWD_FINALIZE = 1, T3D_SMALL_FC_BWD = 2, T3D_SMALL_FC_DINPUT = 3, T3D_SMALL_DY_COLSUM = 4,
        T3D_SMALL_BN_FWD_FINALIZE = 5, T3D_SMALL_FC_FWD = 6, T3D_SMALL_POOL_BWD_MID = 7 };      /* 5 .. 7: rider sets only */
 /* the arguments of t3d_pool_bwd_mid as a struct (kind 7: a WIDE rider -- hundreds of workgroups, alone in its set, no barrier) */
@@ -1220,7 +1227,7 @@ typedef struct {
   unsigned* sync;
 } t3d_rider_set;
 /* validates the set's ops (kinds, shapes that can ride: B <= 32 for the FC ops, <= 512 row tiles for the finalizers) and fills in n_wg and
- * lds_bytes; T3D_ERR_ARG / T3D_ERR_SHAPE if one of them cannot ride */
+ * lds_bytes (and clears `in2` of an FC op of the set whose K2 is 0); T3D_ERR_ARG / T3D_ERR_SHAPE if one of them cannot ride */
 int t3d_riders_plan(t3d_rider_set* riders);
 int t3d_run_riders(const t3d_rider_set* riders, t3d_stream_t stream);      /* the set as a launch of its own */
 int t3d_pointmlp_fwd_r(const t3d_pointmlp_fwd_args* args, const t3d_rider_set* riders, t3d_stream_t stream);

@@ -817,8 +817,69 @@ class FakeLib:
         rps._obj.value, tk._obj.value, tn._obj.value = M // s, ck, cn
         return 0
 
+    # the launchers' argument checks (csrc/bn_dev.h, csrc/fc_dev.h check_*), shared with t3d_small_pair as in the library
+    @staticmethod
+    def _check_bn_bwd(p):
+        if not p.coef:
+            return -1
+        if not p.psum_dz and not (p.dpool_in and p.pooled and p.ysel and p.dpool):
+            return -1
+        if p.psum_dz and not p.psum_dzy:
+            return -1
+        if (not p.scale) if p.frozen else not (p.gamma and p.mean and p.invstd):
+            return -1
+        return 0
+
+    @staticmethod
+    def _check_dy_colsum(p):
+        return 0 if (p.psum_dz and p.psum_y and p.coef and p.out) else -1
+
+    @staticmethod
+    def _check_fc_fwd(p):
+        if not p.in_ or not p.out or (p.K2 > 0 and not p.in2):
+            return -1
+        if not p.w and (p.K != p.N or p.K2 != 0):
+            return -2
+        if p.gamma and not (p.beta and p.moving_mean and p.moving_var and p.mean and p.invstd and p.y):
+            return -1
+        if p.gamma and p.is_training and not p.decay:
+            return -1
+        if p.B <= 0 or p.B > 128 or p.N <= 0 or p.K <= 0:
+            return -2
+        return 0
+
+    @staticmethod
+    def _check_fc_bwd(p):
+        if not p.dy or (not p.dout and not (p.dy_next and p.w_next)):
+            return -1
+        if p.dw and (not p.in_ or (p.K2 > 0 and not p.in2)):
+            return -1
+        if p.gamma and not (p.beta and p.mean and p.invstd and p.y):
+            return -1
+        if p.act != abi.ACT_NONE and not p.y:
+            return -1
+        if p.B <= 0 or p.B > 128 or p.N <= 0:
+            return -2
+        return 0
+
+    @staticmethod
+    def _check_fc_dinput(p):
+        if not p.dy or not p.w or not p.din:
+            return -1
+        if p.bn_coef and not (p.bn_pooled and p.bn_ysel and p.bn_dpool and p.bn_scale and
+                              (p.bn_frozen or (p.bn_gamma and p.bn_mean and p.bn_invstd))):
+            return -1
+        if p.B <= 0 or p.B > 128 or p.N <= 0 or p.K <= 0:
+            return -2
+        return 0
+
     def t3d_bn_bwd_finalize(self, a, stream):
+        if a is None:
+            return -1
         p = _struct(a)
+        rc = self._check_bn_bwd(p)
+        if rc:
+            return rc
         N = p.N
         if p.psum_dz:
             s1 = arr(p.psum_dz, p.n_tiles, N).astype(np.float64).sum(0)
@@ -852,7 +913,12 @@ class FakeLib:
         return 0
 
     def t3d_dy_colsum(self, a, stream):
+        if a is None:
+            return -1
         p = _struct(a)
+        rc = self._check_dy_colsum(p)
+        if rc:
+            return rc
         B, N, tpf = p.B, p.N, p.tiles_per_frustum
         sdz = arr(p.psum_dz, B, tpf, N).astype(np.float64).sum(1)
         sy = arr(p.psum_y, B, tpf, N).astype(np.float64).sum(1)
@@ -888,8 +954,24 @@ class FakeLib:
             return 1 - np.tanh(z) ** 2
         return np.ones_like(z)
 
+    @staticmethod
+    def _fc_stats(y):
+        """batch statistics of the B rows (biased variance)"""
+        mean = y.mean(0)
+        return mean, ((y - mean) ** 2).mean(0)
+
+    @staticmethod
+    def _w_next(p):
+        """rows 0..N-1 of the next layer's weights [*, N_next]"""
+        return arr(p.w_next, p.N, p.N_next).astype(np.float64)
+
     def t3d_fc_fwd(self, a, stream):
+        if a is None:
+            return -1
         p = _struct(a)
+        rc = self._check_fc_fwd(p)
+        if rc:
+            return rc
         B, N = p.B, p.N
         x = self._fc_in(p)
         y = x @ arr(p.w, p.K + p.K2, N).astype(np.float64) if p.w else x.copy()      # w == NULL: identity (standalone BN / dropout)
@@ -902,8 +984,7 @@ class FakeLib:
         if p.gamma:
             mm, mv = arr(p.moving_mean, N), arr(p.moving_var, N)
             if p.is_training:
-                mean = y.mean(0)
-                var = ((y - mean) ** 2).mean(0)
+                mean, var = self._fc_stats(y)
                 d = float(arr(p.decay, 1)[0])
                 var_ema = var * (B / max(B - 1, 1)) if p.unbiased_ema else var
                 mm[:] = mm * d + mean * (1 - d)
@@ -931,12 +1012,17 @@ class FakeLib:
         return 0
 
     def t3d_fc_bwd(self, a, stream):
+        if a is None:
+            return -1
         p = _struct(a)
+        rc = self._check_fc_bwd(p)
+        if rc:
+            return rc
         B, N = p.B, p.N
         if p.dout:
             g = arr(p.dout, B, p.ld_dout)[:, :N].astype(np.float64)
         else:
-            wn = arr(p.w_next, N, p.N_next).astype(np.float64)
+            wn = self._w_next(p)
             g = arr(p.dy_next, B, p.N_next).astype(np.float64) @ wn.T
         y = arr(p.y, B, N).astype(np.float64) if p.y else np.zeros((B, N))
         bn = bool(p.gamma)
@@ -973,7 +1059,12 @@ class FakeLib:
         return 0
 
     def t3d_fc_dinput(self, a, stream):
+        if a is None:
+            return -1
         p = _struct(a)
+        rc = self._check_fc_dinput(p)
+        if rc:
+            return rc
         v = p.alpha * (arr(p.dy, p.B, p.N).astype(np.float64) @ arr(p.w, p.K, p.N).astype(np.float64).T)
         if p.add_in:
             v = v + arr(p.add_in, p.B, p.ld_add)[:, :p.K]
@@ -1327,11 +1418,39 @@ class FakeLib:
         return 0
 
     def t3d_small_pair(self, a, b, stream):
-        """Two independent small launches in one: by specification the two stand-alone calls."""
-        names = {1: ('t3d_bn_bwd_finalize', 'bn_bwd'), 2: ('t3d_fc_bwd', 'fc_bwd'), 3: ('t3d_fc_dinput', 'fc_dinput'),
-                 4: ('t3d_dy_colsum', 'dy_colsum')}
-        for op in (_struct(a), _struct(b)):
-            fn, field = names[op.kind]
+        """Two independent small launches in one: by specification the two stand-alone calls -- after the checks of csrc/pair.hip, which
+        refuses the pair as a whole (nothing runs): NULL, each op's own launcher checks (a's first), kinds other than the four, a dense
+        finalizer of more than 512 tiles, an FC op of at most 32 rows beside one of more."""
+        names = {1: ('t3d_bn_bwd_finalize', 'bn_bwd', self._check_bn_bwd), 2: ('t3d_fc_bwd', 'fc_bwd', self._check_fc_bwd),
+                 3: ('t3d_fc_dinput', 'fc_dinput', self._check_fc_dinput), 4: ('t3d_dy_colsum', 'dy_colsum', self._check_dy_colsum)}
+        if not a or not b:
+            return -1
+        ops = (_struct(a), _struct(b))
+        for op in ops:
+            if op.kind not in names:
+                return -1
+            rc = names[op.kind][2](getattr(op.u, names[op.kind][1]))
+            if rc:
+                return rc
+        rows = []
+        for op in ops:
+            u = getattr(op.u, names[op.kind][1])
+            if op.kind == 1:
+                nb = -1 if (u.psum_dz and u.n_tiles > 512) else (u.N + 15) // 16
+            elif op.kind == 2:
+                nb = (u.N + 31) // 32
+            elif op.kind == 3:
+                nb = (u.K + 31) // 32
+            else:
+                nb = (u.B * u.N + 255) // 256
+            if nb <= 0:
+                return -1
+            if op.kind in (2, 3):
+                rows.append(u.B)
+        if len(rows) == 2 and (rows[0] <= 32) != (rows[1] <= 32):
+            return -2
+        for op in ops:
+            fn, field, _ = names[op.kind]
             rc = getattr(self, fn)(C.byref(getattr(op.u, field)), stream)
             if rc:
                 return rc

@@ -84,7 +84,12 @@ __device__ __forceinline__ void bn_bwd_finalize_body(const t3d_bn_bwd_finalize_a
   const int c = bid * CH + cl;
   const bool ok = act && c < p.N;
   const int cc = ok ? c : 0;
-  const float mean_f = p.mean[cc], invstd_f = p.invstd[cc], gamma_f = p.gamma[cc];   // ahead of the reduction
+  // ahead of the reduction.  A frozen call uses `scale` alone and may leave the three NULL: its loads then go to `scale` (a scalar select
+  // of the base address, no branch: a branch here made the 1024-thread form spill) and their values are not used
+  const float* const mean_p = p.frozen ? p.scale : p.mean;
+  const float* const invstd_p = p.frozen ? p.scale : p.invstd;
+  const float* const gamma_p = p.frozen ? p.scale : p.gamma;
+  const float mean_f = mean_p[cc], invstd_f = invstd_p[cc], gamma_f = gamma_p[cc];
   double acc[2] = {0.0, 0.0};   // sum dz, sum dz*y
   if (p.psum_dz != nullptr) {
     const float* const src[2] = {p.psum_dz, p.psum_dzy};
@@ -227,6 +232,19 @@ __device__ __forceinline__ void dy_colsum_body(const t3d_dy_colsum_args& p, cons
   const double v = (double)p.coef[c] * sdz + (double)p.coef[p.N + c] * sy +
                    (double)p.coef[2 * p.N + c] * (double)p.rows_per_frustum;
   p.out[i] = (float)((double)p.alpha * v);
+}
+
+// The stand-alone launchers' argument checks (bn_optim.hip), shared with the paired launch (pair.hip): T3D_OK or what the launcher answers.
+inline int check_bn_bwd_finalize(const t3d_bn_bwd_finalize_args* a) {
+  if (!a || !a->coef) return T3D_ERR_ARG;
+  if (a->psum_dz == nullptr && (!a->dpool_in || !a->pooled || !a->ysel || !a->dpool)) return T3D_ERR_ARG;
+  if (a->psum_dz != nullptr && !a->psum_dzy) return T3D_ERR_ARG;
+  if (a->frozen ? !a->scale : (!a->gamma || !a->mean || !a->invstd)) return T3D_ERR_ARG;
+  return T3D_OK;
+}
+inline int check_dy_colsum(const t3d_dy_colsum_args* a) {
+  if (!a || !a->psum_dz || !a->psum_y || !a->coef || !a->out) return T3D_ERR_ARG;
+  return T3D_OK;
 }
 
 // tf.train.AdamOptimizer, TF form, on one element: updates the moments and returns what the weight loses.  The ONE place the update

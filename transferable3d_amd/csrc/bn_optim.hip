@@ -179,10 +179,8 @@ extern "C" int t3d_pool_finalize(const t3d_pool_finalize_args* a, t3d_stream_t s
 }
 
 extern "C" int t3d_bn_bwd_finalize(const t3d_bn_bwd_finalize_args* a, t3d_stream_t stream) {
-  if (!a || !a->coef) return T3D_ERR_ARG;
-  if (a->psum_dz == nullptr && (!a->dpool_in || !a->pooled || !a->ysel || !a->dpool)) return T3D_ERR_ARG;
-  if (a->psum_dz != nullptr && !a->psum_dzy) return T3D_ERR_ARG;
-  if (a->frozen ? !a->scale : (!a->gamma || !a->mean || !a->invstd)) return T3D_ERR_ARG;
+  const int rc = check_bn_bwd_finalize(a);
+  if (rc != T3D_OK) return rc;
   if (a->psum_dz != nullptr && a->n_tiles >= fin_wide_tiles() && a->N <= FC_WIDE_MAX_N)
     T3D_LAUNCH((k_bn_bwd_finalize<FC_GR_WIDE, FC_CH_WIDE>), dim3((a->N + FC_CH_WIDE - 1) / FC_CH_WIDE), dim3(FC_GR_WIDE * FC_CH_WIDE), 0,
                static_cast<hipStream_t>(stream), *a);
@@ -195,7 +193,8 @@ extern "C" int t3d_bn_bwd_finalize(const t3d_bn_bwd_finalize_args* a, t3d_stream
 }
 
 extern "C" int t3d_dy_colsum(const t3d_dy_colsum_args* a, t3d_stream_t stream) {
-  if (!a || !a->psum_dz || !a->psum_y || !a->coef || !a->out) return T3D_ERR_ARG;
+  const int rc = check_dy_colsum(a);
+  if (rc != T3D_OK) return rc;
   T3D_LAUNCH(k_dy_colsum, dim3((a->B * a->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;

@@ -43,30 +43,28 @@ extern "C" int t3d_fc_fwd(const t3d_fc_fwd_args* a, t3d_stream_t stream) {
   // at 32 / 16 / 8 columns, step 1.4489 / 1.4480 / 1.4476 ms: the launch is a latency chain, not a bandwidth problem per CU; off.
   static const int narrow = []() { const char* e = getenv("T3D_FC_CB"); const int v = e ? atoi(e) : 32; return (v == 8 || v == 16 || v == 32) ? v : 32; }();
   const int cb = (a->w && (long)a->K * a->N >= (1L << 18) && a->N >= 8 * narrow) ? narrow : CB;
-  if (a->B <= 32) T3D_LAUNCH(k_fc_fwd<1>, dim3((a->N + cb - 1) / cb), dim3(NTH), fc_lds_bytes(32), static_cast<hipStream_t>(stream), *a, cb);
-  else T3D_LAUNCH(k_fc_fwd<MAXRB>, dim3((a->N + cb - 1) / cb), dim3(NTH), fc_lds_bytes(128), static_cast<hipStream_t>(stream), *a, cb);
+  t3d_fc_fwd_args p = *a;
+  drop_empty_in2(p);
+  if (a->B <= 32) T3D_LAUNCH(k_fc_fwd<1>, dim3((a->N + cb - 1) / cb), dim3(NTH), fc_lds_bytes(32), static_cast<hipStream_t>(stream), p, cb);
+  else T3D_LAUNCH(k_fc_fwd<MAXRB>, dim3((a->N + cb - 1) / cb), dim3(NTH), fc_lds_bytes(128), static_cast<hipStream_t>(stream), p, cb);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 extern "C" int t3d_fc_bwd(const t3d_fc_bwd_args* a, t3d_stream_t stream) {
-  if (!a || !a->dy || (!a->dout && (!a->dy_next || !a->w_next))) return T3D_ERR_ARG;
-  if (a->dw && (!a->in || (a->K2 > 0 && !a->in2))) return T3D_ERR_ARG;
-  if (a->gamma && (!a->beta || !a->mean || !a->invstd || !a->y)) return T3D_ERR_ARG;
-  if (a->act != T3D_ACT_NONE && !a->y) return T3D_ERR_ARG;
-  if (a->B <= 0 || a->B > 32 * MAXRB || a->N <= 0) return T3D_ERR_SHAPE;
-  if (a->B <= 32) T3D_LAUNCH(k_fc_bwd<1>, dim3((a->N + CB - 1) / CB), dim3(NTH), fc_lds_bytes(32), static_cast<hipStream_t>(stream), *a);
-  else T3D_LAUNCH(k_fc_bwd<MAXRB>, dim3((a->N + CB - 1) / CB), dim3(NTH), fc_lds_bytes(128), static_cast<hipStream_t>(stream), *a);
+  const int rc = check_fc_bwd(a);
+  if (rc != T3D_OK) return rc;
+  t3d_fc_bwd_args p = *a;
+  drop_empty_in2(p);
+  if (a->B <= 32) T3D_LAUNCH(k_fc_bwd<1>, dim3((a->N + CB - 1) / CB), dim3(NTH), fc_lds_bytes(32), static_cast<hipStream_t>(stream), p);
+  else T3D_LAUNCH(k_fc_bwd<MAXRB>, dim3((a->N + CB - 1) / CB), dim3(NTH), fc_lds_bytes(128), static_cast<hipStream_t>(stream), p);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 extern "C" int t3d_fc_dinput(const t3d_fc_dinput_args* a, t3d_stream_t stream) {
-  if (!a || !a->dy || !a->w || !a->din) return T3D_ERR_ARG;
-  if (a->bn_coef && (!a->bn_pooled || !a->bn_ysel || !a->bn_dpool || !a->bn_scale ||
-                     (!a->bn_frozen && (!a->bn_gamma || !a->bn_mean || !a->bn_invstd))))
-    return T3D_ERR_ARG;
-  if (a->B <= 0 || a->B > 32 * MAXRB || a->N <= 0 || a->K <= 0) return T3D_ERR_SHAPE;
+  const int rc = check_fc_dinput(a);
+  if (rc != T3D_OK) return rc;
   if (a->B <= 32) T3D_LAUNCH(k_fc_dinput<1>, dim3((a->K + CB - 1) / CB), dim3(NTH), fc_lds_bytes(32), static_cast<hipStream_t>(stream), *a);
   else T3D_LAUNCH(k_fc_dinput<MAXRB>, dim3((a->K + CB - 1) / CB), dim3(NTH), fc_lds_bytes(128), static_cast<hipStream_t>(stream), *a);
   T3D_CHECK_LAUNCH();

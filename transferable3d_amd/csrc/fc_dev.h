@@ -318,6 +318,15 @@ __device__ __forceinline__ void fc_fwd_body(const t3d_fc_fwd_args& p, float* sm,
   FC_MARK(4);
 }
 
+// Training-mode batch-norm backward of one element.  Every product and difference is rounded on its own (as in adam_tf_elem, bn_dev.h):
+// left to the compiler, the 256-thread rider form contracted the last difference into an fma and the 512-thread form did not, so the
+// two gave the same bits only where 1 / B is a power of two (tests/fc_check.py, the rider form at B = 31).  This is the 512-thread
+// form's arithmetic.
+__device__ __forceinline__ float bn_train_dy(float c1, float dz, float dbeta, float dgamma, float xh, float invB) {
+#pragma clang fp contract(off)
+  return c1 * (dz - dbeta * invB - xh * dgamma * invB);
+}
+
 template <int RBT, int NWP = NW>
 __device__ __forceinline__ void fc_bwd_body(const t3d_fc_bwd_args& p, float* sm, const int bid) {
   constexpr int RB = RBT, NVAL = RBT * 32 / RG, V = NW / NWP, RGP = NWP * 2;
@@ -400,7 +409,7 @@ __device__ __forceinline__ void fc_bwd_body(const t3d_fc_bwd_args& p, float* sm,
 #pragma unroll
     for (int v = 0; v < V; ++v)
 #pragma unroll
-      for (int j = 0; j < NVAL; ++j) gout[v][j] = c1 * (gout[v][j] - dbeta * invB - xh[v][j] * dgamma * invB);
+      for (int j = 0; j < NVAL; ++j) gout[v][j] = bn_train_dy(c1, gout[v][j], dbeta, dgamma, xh[v][j], invB);
   } else if (bn) {
     const float c1 = g * invstd;
 #pragma unroll
@@ -537,6 +546,29 @@ __device__ __forceinline__ void fc_dinput_body(const t3d_fc_dinput_args& p, floa
   }
 }
 
+
+// The stand-alone launchers' argument checks (fc.hip), shared with the paired launch (pair.hip): T3D_OK or what the launcher answers.
+inline int check_fc_bwd(const t3d_fc_bwd_args* a) {
+  if (!a || !a->dy || (!a->dout && (!a->dy_next || !a->w_next))) return T3D_ERR_ARG;
+  if (a->dw && (!a->in || (a->K2 > 0 && !a->in2))) return T3D_ERR_ARG;
+  if (a->gamma && (!a->beta || !a->mean || !a->invstd || !a->y)) return T3D_ERR_ARG;
+  if (a->act != T3D_ACT_NONE && !a->y) return T3D_ERR_ARG;
+  if (a->B <= 0 || a->B > 32 * MAXRB || a->N <= 0) return T3D_ERR_SHAPE;
+  return T3D_OK;
+}
+inline int check_fc_dinput(const t3d_fc_dinput_args* a) {
+  if (!a || !a->dy || !a->w || !a->din) return T3D_ERR_ARG;
+  if (a->bn_coef && (!a->bn_pooled || !a->bn_ysel || !a->bn_dpool || !a->bn_scale ||
+                     (!a->bn_frozen && (!a->bn_gamma || !a->bn_mean || !a->bn_invstd))))
+    return T3D_ERR_ARG;
+  if (a->B <= 0 || a->B > 32 * MAXRB || a->N <= 0 || a->K <= 0) return T3D_ERR_SHAPE;
+  return T3D_OK;
+}
+// RowSrc clamps an index into in2 with K2 - 1: without a second block there must be no second pointer (a launcher's own copy of the struct)
+template <class Args>
+inline void drop_empty_in2(Args& a) {
+  if (a.K2 <= 0) a.in2 = nullptr;
+}
 
 inline size_t fc_lds_bytes(int B) {
   const int RB = (B + 31) / 32;

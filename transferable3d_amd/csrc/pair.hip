@@ -26,10 +26,21 @@ __global__ __launch_bounds__(NTH) void k_small_pair(const t3d_small_op a, const 
   else run_small<RBT>(b, sm, blockIdx.x - n_a);
 }
 
+// the stand-alone launcher's argument checks on one op of a pair: T3D_OK, or what that launcher answers (an unknown kind: T3D_ERR_ARG)
+int small_check(const t3d_small_op& o) {
+  switch (o.kind) {
+    case T3D_SMALL_BN_BWD_FINALIZE: return check_bn_bwd_finalize(&o.u.bn_bwd);
+    case T3D_SMALL_FC_BWD: return check_fc_bwd(&o.u.fc_bwd);
+    case T3D_SMALL_FC_DINPUT: return check_fc_dinput(&o.u.fc_dinput);
+    case T3D_SMALL_DY_COLSUM: return check_dy_colsum(&o.u.dy_colsum);
+    default: return T3D_ERR_ARG;
+  }
+}
+
 int small_blocks(const t3d_small_op& o, int* rows) {
   switch (o.kind) {
     case T3D_SMALL_BN_BWD_FINALIZE:
-      if (!o.u.bn_bwd.coef || (o.u.bn_bwd.psum_dz != nullptr && o.u.bn_bwd.n_tiles > 512)) return -1;      // (the 64-group form stays alone)
+      if (o.u.bn_bwd.psum_dz != nullptr && o.u.bn_bwd.n_tiles > 512) return -1;      // (the 64-group form stays alone)
       return (o.u.bn_bwd.N + FC_CH - 1) / FC_CH;
     case T3D_SMALL_FC_BWD: *rows = o.u.fc_bwd.B; return (o.u.fc_bwd.N + CB - 1) / CB;
     case T3D_SMALL_FC_DINPUT: *rows = o.u.fc_dinput.B; return (o.u.fc_dinput.K + CB - 1) / CB;
@@ -55,6 +66,8 @@ extern "C" int t3d_riders_plan(t3d_rider_set* r) {
     const int nb = rider_op_blocks(r->ops[i]);
     if (nb <= 0) return r->ops[i].kind >= 1 && r->ops[i].kind <= 7 ? T3D_ERR_SHAPE : T3D_ERR_ARG;
     if (r->ops[i].kind == T3D_SMALL_POOL_BWD_MID && r->n_ops != 1) return T3D_ERR_ARG;      // a wide rider is alone in its set
+    if (r->ops[i].kind == T3D_SMALL_FC_FWD) drop_empty_in2(r->ops[i].u.fc_fwd);
+    if (r->ops[i].kind == T3D_SMALL_FC_BWD) drop_empty_in2(r->ops[i].u.fc_bwd);
     if (nb > m) m = nb;
     const size_t l = rider_op_lds(r->ops[i]);
     if (l > lds) lds = l;
@@ -78,14 +91,19 @@ extern "C" int t3d_run_riders(const t3d_rider_set* r, t3d_stream_t stream) {
 
 extern "C" int t3d_small_pair(const t3d_small_op* a, const t3d_small_op* b, t3d_stream_t stream) {
   if (!a || !b) return T3D_ERR_ARG;
+  const int rc_a = small_check(*a), rc_b = rc_a != T3D_OK ? rc_a : small_check(*b);
+  if (rc_b != T3D_OK) return rc_b;
   int rows_a = 0, rows_b = 0;
   const int na = small_blocks(*a, &rows_a), nb = small_blocks(*b, &rows_b);
   if (na <= 0 || nb <= 0) return T3D_ERR_ARG;
   const int rows = rows_a > rows_b ? rows_a : rows_b;
   if (rows > 32 * MAXRB || (rows_a && rows_b && (rows_a <= 32) != (rows_b <= 32))) return T3D_ERR_SHAPE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (rows <= 32) T3D_LAUNCH(k_small_pair<1>, dim3(na + nb), dim3(NTH), fc_lds_bytes(32), s, *a, *b, na);
-  else T3D_LAUNCH(k_small_pair<MAXRB>, dim3(na + nb), dim3(NTH), fc_lds_bytes(128), s, *a, *b, na);
+  t3d_small_op pa = *a, pb = *b;
+  if (pa.kind == T3D_SMALL_FC_BWD) drop_empty_in2(pa.u.fc_bwd);
+  if (pb.kind == T3D_SMALL_FC_BWD) drop_empty_in2(pb.u.fc_bwd);
+  if (rows <= 32) T3D_LAUNCH(k_small_pair<1>, dim3(na + nb), dim3(NTH), fc_lds_bytes(32), s, pa, pb, na);
+  else T3D_LAUNCH(k_small_pair<MAXRB>, dim3(na + nb), dim3(NTH), fc_lds_bytes(128), s, pa, pb, na);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
