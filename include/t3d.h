@@ -1357,6 +1357,84 @@ typedef struct {
 #define T3D_V2_SIZE_sunrgbd_eval_args 256
 int t3d_sunrgbd_eval(const t3d_sunrgbd_eval_args* args, t3d_stream_t stream);
 
+/* ---- Diagnosis of one class's detection errors (csrc/sunrgbd_diagnose.hip; evaluate_sunrgbd.py diagnose_class) ----
+ * The error breakdown of Bolya et al., "TIDE" (ECCV 2020), restated for the protocol above: its prism overlap, its argmax-then-claim
+ * matching, its VOC2011 AP.  `eval` is one class's evaluation exactly as t3d_sunrgbd_eval takes it, and every one of its outputs is
+ * written with the bytes t3d_sunrgbd_eval writes for the same input; eval->gt_difficult must be NULL (a diagnosis with "difficult"
+ * boxes is not defined), eval->overlaps may be NULL.  eval->threshold is t_f, diag->bg_threshold is t_b, 0 <= t_b < t_f.
+ * diag adds the ground truth of the OTHER evaluated classes, Go boxes grouped by image as eval's own are: other_image_ids (ascending,
+ * distinct), other_image_offsets, other_image_list.  All arithmetic is fp64; the overlap is the evaluation's own, on its footprints.
+ * Per detection i, in file order:
+ *   other_overlap[i]  the largest overlap with an other-class box of its own image; other_gt[i] that box, 1-based into the other list,
+ *                     the first in other_image_list order on ties, 0 where the maximum < eps = 2^-52 (the rules of max_overlap / gt_idx);
+ *   kind[i]           with o_s = max_overlap[i], o_o = other_overlap[i], own-class evidence first, as in TIDE:
+ *                       T3D_DIAG_TP   is_tp;
+ *                       T3D_DIAG_DUP  is_fp and o_s >= t_f: its box was claimed by a better-ranked detection;
+ *                       T3D_DIAG_LOC  is_fp and t_b <= o_s < t_f;
+ *                       T3D_DIAG_CLS  is_fp, o_s < t_b, o_o >= t_f;
+ *                       T3D_DIAG_BOTH is_fp, o_s < t_b, t_b <= o_o < t_f;
+ *                       T3D_DIAG_BKG  every other false positive (a detection whose image has no ground truth among them).
+ * Per own-class box g: gt_state[g] = 1 claimed; 2 missed but localised (is_missed, and a LOC detection has gt_idx == g + 1); 3 missed.
+ * counts[6]: the detections of each kind 0..5; gt_counts[3]: the boxes in states 1..3.
+ * ap_fixed[8]: the AP of eight variants of the evaluation, each by the curve code that computes `ap` (integer cumulative sums in rank
+ * order, recall = ctp / n_pos, precision = ctp / (cfp + ctp), the VOC2011 envelope, the same fixed summation tree); a removed detection
+ * counts in neither sum, like a "difficult" match:
+ *   T3D_DIAG_FIX_CLS, _BOTH, _DUP, _BKG  the detections of that kind are removed;
+ *   T3D_DIAG_FIX_LOC     per box g in state 2 the best-ranked LOC detection with gt_idx == g + 1 becomes a true positive (an integer
+ *                        minimum over ranks, as the first claimer is found); every other LOC detection is removed;
+ *   T3D_DIAG_FIX_MISSED  the boxes in state 3 leave the ground truth: n_pos = G minus their number;
+ *   T3D_DIAG_FIX_FP      every false positive is removed;
+ *   T3D_DIAG_FIX_FN      every missed box (states 2 and 3) leaves the ground truth.
+ * A variant whose ground truth is empty has AP 0 (so every variant when G == 0), and so has every variant when P == 0; then every box
+ * is in state 3.  Go == 0 is valid: no CLS, no BOTH.  dAP = ap_fixed - ap is left to the host.
+ * Deliberate differences from TIDE: classes are diagnosed independently, so CLS is fixed by removal, not by re-labelling; and a missed
+ * box that a detection of another class covers is still "missed" for its own class.
+ * workspace: T3D_SUNRGBD_DIAGNOSE_WORKSPACE_BYTES(P, G, Go) bytes, 8-byte aligned, separate from eval->workspace (which is read).
+ * Four launches behind the evaluation's, the eight curves one workgroup each in one of them.  Nothing is allocated or synchronised
+ * with the host; the only atomics are integer minima, so equal inputs give equal bytes.
+ * T3D_ERR_ABI: a struct of another size (either one).  T3D_ERR_ARG: a NULL struct or array, gt_difficult != NULL, not 0 <= t_b < t_f,
+ * a workspace that is too small, and whatever t3d_sunrgbd_eval refuses.  T3D_ERR_SHAPE: Go < 0 or > T3D_SUNRGBD_EVAL_MAX_BOXES,
+ * n_other_images < 0, and eval's shapes.  Nothing is launched then. */
+#define T3D_DIAG_TP 0
+#define T3D_DIAG_CLS 1
+#define T3D_DIAG_LOC 2
+#define T3D_DIAG_BOTH 3
+#define T3D_DIAG_DUP 4
+#define T3D_DIAG_BKG 5
+#define T3D_DIAG_FIX_CLS 0
+#define T3D_DIAG_FIX_LOC 1
+#define T3D_DIAG_FIX_BOTH 2
+#define T3D_DIAG_FIX_DUP 3
+#define T3D_DIAG_FIX_BKG 4
+#define T3D_DIAG_FIX_MISSED 5
+#define T3D_DIAG_FIX_FP 6
+#define T3D_DIAG_FIX_FN 7
+#define T3D_SUNRGBD_DIAGNOSE_WORKSPACE_BYTES(P, G, Go) ((uint64_t)(Go) * 88u + (uint64_t)(G) * 4u + (uint64_t)(P) * 0u + 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_sunrgbd_diagnose_args) of the caller's header (see T3D_ABI_VERSION) */
+  int Go;
+  const double* other_centroid;        /* [Go,3] ground truth of the other evaluated classes */
+  const double* other_basis;           /* [Go,9] */
+  const double* other_coeffs;          /* [Go,3] */
+  const int32_t* other_image;          /* [Go] */
+  int n_other_images;
+  const int32_t* other_image_ids;      /* [n_other_images] */
+  const int32_t* other_image_offsets;  /* [n_other_images + 1] */
+  const int32_t* other_image_list;     /* [Go] */
+  double bg_threshold;                 /* t_b */
+  void* workspace;
+  uint64_t workspace_bytes;
+  double* other_overlap;               /* [P] out, file order */
+  int32_t* other_gt;                   /* [P] out, file order */
+  uint8_t* kind;                       /* [P] out, file order: T3D_DIAG_* */
+  uint8_t* gt_state;                   /* [G] out */
+  int32_t* counts;                     /* [6] out */
+  int32_t* gt_counts;                  /* [3] out */
+  double* ap_fixed;                    /* [8] out: T3D_DIAG_FIX_* */
+} t3d_sunrgbd_diagnose_args;
+#define T3D_V2_SIZE_sunrgbd_diagnose_args 152
+int t3d_sunrgbd_diagnose(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_diagnose_args* diag, t3d_stream_t stream);
+
 /* ---- Detection decode of one inference batch (csrc/detect.hip; semisup_infer.inference(decode='device'), detect.Detector) ----
  * What the reference does on the host after every batch (test_semisup.py:236-262, roi_seg_box3d_dataset.py:86-101, 461-466), in one
  * launch, one workgroup of 256 threads per frustum, fp32 throughout:

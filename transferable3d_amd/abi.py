@@ -343,6 +343,17 @@ class SunrgbdEvalArgs(Sized):
                 ('ap', D), ('overlap_offsets', L), ('overlaps', D), ('overlap_gt', I)]
 
 
+DIAG_KINDS = ('tp', 'cls', 'loc', 'both', 'dup', 'bkg')                          # t3d.h T3D_DIAG_*: kind[i], counts[6]
+DIAG_FIXES = ('cls', 'loc', 'both', 'dup', 'bkg', 'missed', 'fp', 'fn')         # t3d.h T3D_DIAG_FIX_*: ap_fixed[8]
+
+
+class SunrgbdDiagnoseArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('Go', i32), ('other_centroid', D), ('other_basis', D), ('other_coeffs', D), ('other_image', I),
+                ('n_other_images', i32), ('other_image_ids', I), ('other_image_offsets', I), ('other_image_list', I),
+                ('bg_threshold', C.c_double), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('other_overlap', D),
+                ('other_gt', I), ('kind', U8), ('gt_state', U8), ('counts', I), ('gt_counts', I), ('ap_fixed', D)]
+
+
 SEMI_BATCH, SEMI_ALTERNATE_BATCH, SEMI_MIXED_BATCH = 0, 1, 2          # t3d.h T3D_SEMI_*
 SEMI_METHODS = {'BATCH': SEMI_BATCH, 'ALTERNATE_BATCH': SEMI_ALTERNATE_BATCH, 'MIXED_BATCH': SEMI_MIXED_BATCH}
 SEMI_SAMPLE_MAX_B = 256
@@ -424,6 +435,11 @@ def render_workspace_bytes(pixels):
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
+
+
+def sunrgbd_diagnose_workspace_bytes(P, G, Go):
+    """t3d.h T3D_SUNRGBD_DIAGNOSE_WORKSPACE_BYTES"""
+    return Go * 88 + G * 4 + 8
 
 
 VP = C.c_void_p
@@ -524,6 +540,7 @@ ENTRY_POINTS = {
     't3d_cast_bf16': [F, VP, C.c_int64, VP],
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
+    't3d_sunrgbd_diagnose': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdDiagnoseArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],

@@ -2,7 +2,8 @@
 """Scenes and 2-D detections in, 3-D boxes out, in one process and without a frustum file.
 
     python -m transferable3d_amd.detect --dataset_dir D --idx_path I --rgb_detection_path DETS --model_path M [--boxpc_model_path P] \
-        --result_dir R [--official_eval]       # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
+        --result_dir R [--official_eval [--diagnose [--diagnose_bg 0.1] [--diagnose_json FILE]]]
+        # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}]]
         [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
 
@@ -310,6 +311,8 @@ def parser():
     p.add_argument('--type_whitelist', nargs='+', default=list(SD.TYPE_WHITELIST), help='classes of detections to take')
     p.add_argument('--official_eval', action='store_true', help='print the lines of script_3Deval.m for the detections (evaluate_sunrgbd)')
     p.add_argument('--test_on', default='AB', choices=['A', 'B', 'AB'], help='set of classes --official_eval scores')
+    from transferable3d_amd.evaluate_sunrgbd import add_diagnose_arguments
+    add_diagnose_arguments(p)                 # with --official_eval: the kinds of errors behind every AP (evaluate_sunrgbd --diagnose)
     NMS.add_arguments(p)
     p.add_argument('--vis_dir', default=None, help='write <id>.png (camera image + bird\'s-eye panel with the 3-D boxes) and <id>.json (legend) of detected scenes here')
     p.add_argument('--vis_max', type=int, default=50, help='how many scenes --vis_dir draws (the first ones with a detection)')
@@ -326,6 +329,10 @@ def main(argv=None, rt=None, log=print):
         NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
     except ValueError as e:
         parser().error(str(e))
+    from transferable3d_amd import evaluate_sunrgbd as ES
+    diagnose = ES.diagnose_options(parser(), args)
+    if diagnose is not None and not args.official_eval:
+        parser().error('--diagnose breaks down the score of --official_eval: it needs --official_eval')
     if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
         parser().error('--vis_gt / --vis_suppressed need --vis_dir')
     try:
@@ -365,9 +372,8 @@ def main(argv=None, rt=None, log=print):
         SI.write_detection_results(FLAGS.result_dir, det.classes or sorted(set(names)), predictions, names)
         log('detection results written to %s' % FLAGS.result_dir)
     if args.official_eval:
-        from transferable3d_amd import evaluate_sunrgbd as ES
         held = ES.official_predictions(sorted(set(ES.CLASS_NAMES[args.test_on]) | set(names)), predictions, names)
-        ES.evaluate(None, args.dataset_dir, args.idx_path, args.test_on, rt=det.rt, log=log, predictions=held)
+        ES.evaluate(None, args.dataset_dir, args.idx_path, args.test_on, rt=det.rt, log=log, predictions=held, diagnose=diagnose)
     return predictions
 
 

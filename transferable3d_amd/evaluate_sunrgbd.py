@@ -18,9 +18,17 @@ Ground truth: the toolbox's Metadata/groundtruth.mat is replaced by the label fi
 
 Two deliberate differences from the script: an empty prediction file counts as zero predictions (importdata stops the script there),
 and two boxes that both have zero volume overlap by 0 (MATLAB: 0 / 0).
+
+--diagnose [--diagnose_bg 0.1] [--diagnose_json FILE] (either form): why the AP is what it is.  Per class ONE t3d_sunrgbd_diagnose call
+(csrc/sunrgbd_diagnose.hip) in place of the t3d_sunrgbd_eval call: the same evaluation, then every false positive sorted into a kind
+(cls: on a box of another evaluated class; loc: on its own box, too loose; both; dup: its box was already claimed; bkg), every
+missed box into localised or not, and the AP the class would have if each kind of error were fixed -- the breakdown of Bolya et al.,
+"TIDE" (ECCV 2020) under this protocol's overlap, matching and AP (include/t3d.h has the rules).  Two lines per class follow its AP line
+and one the mean; without the flag nothing changes.
 """
 import argparse
 import ctypes as C
+import json
 import math
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -145,14 +153,29 @@ class _Packed:
         return host[off:off + n * dt.itemsize].view(dt)
 
 
-def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False):
-    """One t3d_sunrgbd_eval call on one class -> host arrays of every output."""
+def _by_image(img):
+    """Boxes grouped by image: (image_ids ascending and distinct, offsets [n + 1], list: ascending index inside an image)."""
+    lst = np.argsort(img, kind='stable').astype(np.int32)
+    ids, first = np.unique(img[lst], return_index=True)
+    return ids, np.concatenate([first, [len(img)]]).astype(np.int32), lst
+
+
+def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None):
+    """One t3d_sunrgbd_eval call on one class -> host arrays of every output.  other (boxes of the other evaluated classes) and
+    bg_threshold: one t3d_sunrgbd_diagnose call instead, the diagnosis' outputs beside the evaluation's.  Either way one copy to the
+    device and one copy back."""
+    launch, fetch = _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps, other, bg_threshold)
+    launch()
+    return fetch()
+
+
+def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None):
+    """_eval_call in its three steps: packs and uploads the inputs (the one copy to the device) -> (launch: the entry point's launches
+    on the runtime's stream, fetch: the one copy back as host arrays).  tools/bench_sunrgbd_diagnose.py times `launch` alone."""
     rt = _runtime(rt)
     P, G = len(det['confidence']), len(gt['image'])
     gimg = np.asarray(gt['image'], np.int32)
-    image_gt = np.argsort(gimg, kind='stable').astype(np.int32)             # grouped by image, ascending index inside an image
-    image_ids, first = np.unique(gimg[image_gt], return_index=True)
-    offsets = np.concatenate([first, [G]]).astype(np.int32)
+    image_ids, offsets, image_gt = _by_image(gimg)
     n_img = len(image_ids)
     dimg = np.asarray(det['image'], np.int32)
     inp = _Packed()
@@ -171,6 +194,13 @@ def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False):
         cnt = np.where(hit, (offsets[1:] - offsets[:-1])[np.minimum(k, max(n_img - 1, 0))], 0) if n_img else np.zeros(P, np.int64)
         ov_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         host_in['overlap_offsets'] = (np.int64, ov_off)
+    if other is not None:
+        Go = len(other['image'])
+        oimg = np.asarray(other['image'], np.int32)
+        other_ids, other_offsets, other_list = _by_image(oimg)
+        host_in.update({'other_centroid': (np.float64, other['centroid']), 'other_basis': (np.float64, other['basis']),
+                        'other_coeffs': (np.float64, other['coeffs']), 'other_image': (np.int32, oimg), 'other_image_ids': (np.int32, other_ids),
+                        'other_image_offsets': (np.int32, other_offsets), 'other_image_list': (np.int32, other_list)})
     for name, (dt, a) in host_in.items():
         inp.add(name, dt, np.asarray(a).size)
     buf = np.zeros(max(inp.size, 8), np.uint8)
@@ -181,6 +211,10 @@ def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False):
                         ('order', np.int32, P), ('gt_idx', np.int32, P), ('gt_assignment', np.int32, P), ('is_tp', np.uint8, P),
                         ('is_fp', np.uint8, P), ('is_missed', np.uint8, G)):
         out.add(name, dt, n)
+    if other is not None:
+        for name, dt, n in (('other_overlap', np.float64, P), ('ap_fixed', np.float64, len(abi.DIAG_FIXES)), ('other_gt', np.int32, P),
+                            ('counts', np.int32, len(abi.DIAG_KINDS)), ('gt_counts', np.int32, 3), ('kind', np.uint8, P), ('gt_state', np.uint8, G)):
+            out.add(name, dt, n)
     if want_overlaps:
         n_ov = int(ov_off[-1])
         out.add('overlaps', np.float64, n_ov)
@@ -208,12 +242,29 @@ def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False):
                             o_('overlaps', dbl), o_('overlap_gt', i32))
     if want_overlaps and int(ov_off[-1]) == 0:
         a.overlaps, a.overlap_gt = None, None
-    abi.check(rt.lib.t3d_sunrgbd_eval(C.byref(a), rt.stream()), 't3d_sunrgbd_eval')
-    host = d_out.cpu().numpy()                                              # the one copy back (synchronises)
-    res = {name: out.view(host, name).copy() for name in out.fields}
-    if want_overlaps:
-        res['overlap_offsets'] = ov_off
-    return res
+    held = [d_in, d_out, d_ws]                 # what the argument structs point into lives as long as `launch` does
+    if other is None:
+        def launch(held=held):
+            abi.check(rt.lib.t3d_sunrgbd_eval(C.byref(a), rt.stream()), 't3d_sunrgbd_eval')
+    else:
+        dws_bytes = abi.sunrgbd_diagnose_workspace_bytes(P, G, Go)
+        d_dws = torch.empty((dws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        d = abi.SunrgbdDiagnoseArgs(Go, i_('other_centroid', dbl), i_('other_basis', dbl), i_('other_coeffs', dbl), i_('other_image', i32),
+                                    len(other_ids), i_('other_image_ids', i32), i_('other_image_offsets', i32), i_('other_image_list', i32),
+                                    float(bg_threshold), C.c_void_p(d_dws.data_ptr()), dws_bytes, o_('other_overlap', dbl), o_('other_gt', i32),
+                                    o_('kind', u8), o_('gt_state', u8), o_('counts', i32), o_('gt_counts', i32), o_('ap_fixed', dbl))
+        held.append(d_dws)
+
+        def launch(held=held):
+            abi.check(rt.lib.t3d_sunrgbd_diagnose(C.byref(a), C.byref(d), rt.stream()), 't3d_sunrgbd_diagnose')
+
+    def fetch(held=held):
+        host = d_out.cpu().numpy()                                          # the one copy back (synchronises)
+        res = {name: out.view(host, name).copy() for name in out.fields}
+        if want_overlaps:
+            res['overlap_offsets'] = ov_off
+        return res
+    return launch, fetch
 
 
 def compute_pr_curve_3d(classname, det, gt, difficult=None, threshold=0.25, rt=None):
@@ -227,8 +278,12 @@ def compute_pr_curve_3d(classname, det, gt, difficult=None, threshold=0.25, rt=N
     if len(difficult) != G_all:
         raise ValueError('inconsistent difficulty size.')
     same = np.array([c == classname for c in gt['classname']], bool) if 'classname' in gt else np.ones(G_all, bool)
-    sel = np.nonzero(same)[0]
-    r = _eval_call(det, select_boxes(gt, same), difficult[same], threshold, rt)
+    return _pr_curve_result(_eval_call(det, select_boxes(gt, same), difficult[same], threshold, rt), same)
+
+
+def _pr_curve_result(r, same):
+    """compute_pr_curve_3d's dictionary from the arrays of one call; same: the boxes of the whole ground-truth list that took part."""
+    G_all, sel = len(same), np.nonzero(same)[0]
     order = r['order'].astype(np.int64)
     is_missed = np.zeros(G_all, bool)
     is_missed[sel] = r['is_missed'] != 0
@@ -237,6 +292,38 @@ def compute_pr_curve_3d(classname, det, gt, difficult=None, threshold=0.25, rt=N
     return {'apScore': float(r['ap'][0]), 'precision': r['precision'], 'recall': r['recall'], 'isTp': r['is_tp'] != 0, 'isFp': r['is_fp'] != 0,
             'isMissed': is_missed, 'gtAssignment': ga, 'maxOverlaps': r['max_overlap'][order], 'numOfgt': int(same.sum()),
             'gtIdxAll': r['gt_idx'][order].astype(np.int64), 'sortIdx': order}
+
+
+GT_STATES = ('claimed', 'localised', 'missed')              # gt_state 1, 2, 3 of t3d_sunrgbd_diagnose
+
+
+def diagnose_class(classname, det, gt_all, threshold=0.25, bg_threshold=0.1, rt=None, classes=None):
+    """compute_pr_curve_3d(classname, det, gt_all) and the diagnosis of its errors (t3d_sunrgbd_diagnose, include/t3d.h), one call.
+    gt_all holds the ground truth of every class ('classname' per box); classes: the evaluated set (default: every class of gt_all) --
+    the boxes of its other members are what a detection can be confused with.  -> compute_pr_curve_3d's dictionary plus, in file
+    order, kind (abi.DIAG_KINDS), otherOverlap, otherGt (1-based into gt_all, 0 = none); gtState over gt_all (1 claimed, 2 missed but
+    localised, 3 missed; 0 for the boxes of other classes); counts {tp cls loc both dup bkg}, gtCounts {claimed localised missed},
+    apFixed and dAP = apFixed - apScore {cls loc both dup bkg missed fp fn}."""
+    names = gt_all['classname']
+    same = np.array([c == classname for c in names], bool)
+    others = np.array([c != classname and (classes is None or c in classes) for c in names], bool)
+    osel = np.nonzero(others)[0]
+    r = _eval_call(det, select_boxes(gt_all, same), None, threshold, rt, other=select_boxes(gt_all, others), bg_threshold=bg_threshold)
+    out = _pr_curve_result(r, same)
+    og = r['other_gt'].astype(np.int64)
+    og[og > 0] = osel[og[og > 0] - 1] + 1
+    state = np.zeros(len(names), np.uint8)
+    state[same] = r['gt_state']
+    ap_fixed = {k: float(v) for k, v in zip(abi.DIAG_FIXES, r['ap_fixed'])}
+    out.update(kind=r['kind'], otherOverlap=r['other_overlap'], otherGt=og, gtState=state,
+               counts={k: int(v) for k, v in zip(abi.DIAG_KINDS, r['counts'])}, gtCounts={k: int(v) for k, v in zip(GT_STATES, r['gt_counts'])},
+               apFixed=ap_fixed, dAP={k: v - out['apScore'] for k, v in ap_fixed.items()})
+    return out
+
+
+def _dap_text(dap):
+    v = ['%s %.2f' % (k, 100.0 * dap[k]) for k in abi.DIAG_FIXES]
+    return ' '.join(v[:6]) + ' | ' + ' '.join(v[6:])
 
 
 def bb3d_overlap_close_form(bb1, bb2, rt=None):
@@ -266,15 +353,19 @@ def num2str(x):
     return ('%.*g' % (digits, x)).strip()
 
 
-def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, threshold=0.25, save_curves=None, predictions=None):
+def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, threshold=0.25, save_curves=None, predictions=None,
+             diagnose=None):
     """script_3Deval.m:33-60: per class of the set `test_on`, the number of predictions, the AP, and the mean AP, logged as the script
     displays them.  `predictions` ({class: boxes}, e.g. official_predictions of a test_semisup run) stands in for the files of `pred_dir`.
-    -> ({class: AP}, mean AP).  save_curves: a directory for <class>_pr.npz."""
+    -> ({class: AP}, mean AP).  save_curves: a directory for <class>_pr.npz.
+    diagnose: None, or {'bg': the background overlap t_b (0.1), 'json': a path or None}: diagnose_class per class -- two more lines
+    behind each AP line (the detections per kind and the boxes per state; 100 x dAP per fix), one behind the mean (the class means),
+    the summary as JSON at the path, and the per-detection arrays in <class>_pr.npz."""
     if test_on not in CLASS_NAMES:
         raise ValueError("test_on is 'A', 'B' or 'AB'")
     rt = _runtime(rt)
     gt_all = benchmark_groundtruth(dataset_dir, idx_list)
-    ap = {}
+    ap, summary = {}, {}
     if save_curves:
         os.makedirs(save_curves, exist_ok=True)
     for name in CLASS_NAMES[test_on]:
@@ -285,14 +376,33 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
         else:
             det = parse_class_predictions(os.path.join(pred_dir, name + '_pred.txt'), name)
         log('Number of predictions for %s: %d' % (name.upper(), len(det['confidence'])))
-        r = compute_pr_curve_3d(name, det, gt_all, None, threshold, rt)
+        if diagnose is None:
+            r = compute_pr_curve_3d(name, det, gt_all, None, threshold, rt)
+        else:
+            r = diagnose_class(name, det, gt_all, threshold, diagnose.get('bg', 0.1), rt, classes=CLASS_NAMES[test_on])
         log('AP Score for %s: [%s]' % (name.upper(), num2str(r['apScore'] * 100.0)))
         ap[name] = r['apScore']
+        curves = dict(precision=r['precision'], recall=r['recall'], isTp=r['isTp'], isFp=r['isFp'], maxOverlaps=r['maxOverlaps'],
+                      gtAssignment=r['gtAssignment'], isMissed=r['isMissed'])
+        if diagnose is not None:
+            c, g = r['counts'], r['gtCounts']
+            log('Diagnosis for %s: %s | boxes %d missed %d localised %d' % (name.upper(), ' '.join('%s %d' % (k, c[k]) for k in abi.DIAG_KINDS),
+                                                                           r['numOfgt'], g['missed'], g['localised']))
+            log('dAP for %s: %s' % (name.upper(), _dap_text(r['dAP'])))
+            summary[name] = {'ap': r['apScore'], 'predictions': len(det['confidence']), 'boxes': r['numOfgt'], 'counts': c, 'gtCounts': g,
+                             'apFixed': r['apFixed'], 'dAP': r['dAP']}
+            curves.update(kind=r['kind'], otherOverlap=r['otherOverlap'], otherGt=r['otherGt'], gtState=r['gtState'])
         if save_curves:
-            np.savez(os.path.join(save_curves, name + '_pr.npz'), precision=r['precision'], recall=r['recall'], isTp=r['isTp'], isFp=r['isFp'],
-                     maxOverlaps=r['maxOverlaps'], gtAssignment=r['gtAssignment'], isMissed=r['isMissed'])
+            np.savez(os.path.join(save_curves, name + '_pr.npz'), **curves)
     mean_ap = float(np.mean([ap[c] for c in CLASS_NAMES[test_on]]))
     log('Mean AP Score: [%s]' % num2str(mean_ap * 100.0))
+    if diagnose is not None:
+        mean_dap = {k: float(np.mean([summary[c]['dAP'][k] for c in CLASS_NAMES[test_on]])) for k in abi.DIAG_FIXES}
+        log('Mean dAP: %s' % _dap_text(mean_dap))
+        if diagnose.get('json'):
+            with open(diagnose['json'], 'w') as fh:
+                json.dump({'test_on': test_on, 'threshold': threshold, 'bg_threshold': diagnose.get('bg', 0.1), 'kinds': list(abi.DIAG_KINDS),
+                           'fixes': list(abi.DIAG_FIXES), 'classes': summary, 'mean_ap': mean_ap, 'mean_dAP': mean_dap}, fh, indent=1)
     return ap, mean_ap
 
 
@@ -316,7 +426,8 @@ def official_predictions(test_classes, predictions, class_names):
     return out
 
 
-def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test_on='AB', rt=None, log=print, threshold=0.25, save_curves=None):
+def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test_on='AB', rt=None, log=print, threshold=0.25, save_curves=None,
+                                  diagnose=None):
     """test_semisup's run (its own command line: a frustum file with --data_path, or its synthetic frustums, whose image ids are their
     indices), then `evaluate` on the predictions it returns.  With --result_dir among its flags the same run also writes the
     <class>_pred.txt files."""
@@ -328,7 +439,28 @@ def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test
     held = official_predictions(sorted(set(CLASS_NAMES[test_on]) | set(names)), predictions, names)
     if rt is None:
         rt = _runtime(None)
-    return evaluate(None, dataset_dir, idx_list, test_on, rt=rt, log=log, threshold=threshold, save_curves=save_curves, predictions=held)
+    return evaluate(None, dataset_dir, idx_list, test_on, rt=rt, log=log, threshold=threshold, save_curves=save_curves, predictions=held,
+                    diagnose=diagnose)
+
+
+def add_diagnose_arguments(p):
+    """--diagnose and its two options, for this parser and for detect's."""
+    p.add_argument('--diagnose', action='store_true',
+                   help='sort the errors of every class into kinds and print what fixing each kind would add to its AP (module docstring)')
+    p.add_argument('--diagnose_bg', type=float, default=None, help='--diagnose: the overlap below which a detection is on nothing (default 0.1)')
+    p.add_argument('--diagnose_json', default=None, help='--diagnose: write the summary (counts, AP per fix, dAP, means) to this file')
+
+
+def diagnose_options(p, FLAGS, threshold=0.25):
+    """The `diagnose` dictionary of `evaluate` from parsed flags (None without --diagnose); a parser error where they contradict."""
+    if not FLAGS.diagnose:
+        if FLAGS.diagnose_bg is not None or FLAGS.diagnose_json is not None:
+            p.error('--diagnose_bg / --diagnose_json need --diagnose')
+        return None
+    bg = 0.1 if FLAGS.diagnose_bg is None else FLAGS.diagnose_bg
+    if not 0.0 <= bg < threshold:
+        p.error('--diagnose_bg must lie in [0, %g), below the overlap a true positive needs' % threshold)
+    return {'bg': bg, 'json': FLAGS.diagnose_json}
 
 
 def parser():
@@ -343,21 +475,23 @@ def parser():
     p.add_argument('--threshold', type=float, default=0.25, help='overlap a true positive needs (the script: 0.25)')
     p.add_argument('--save_curves', default=None, help='directory for <class>_pr.npz (precision, recall, isTp, isFp, ...)')
     p.add_argument('--gpu', type=int, default=0)
+    add_diagnose_arguments(p)
     return p
 
 
 def main(argv=None, rt=None, log=print):
     FLAGS, rest = parser().parse_known_args(argv)
+    diagnose = diagnose_options(parser(), FLAGS, FLAGS.threshold)
     if rt is None and torch.cuda.is_available():
         torch.cuda.set_device(FLAGS.gpu)
     if FLAGS.official_eval:
         rest = list(rest) + ['--gpu', str(FLAGS.gpu)]                     # the one flag both parsers have: test_semisup gets it too
         return official_eval_of_test_semisup(rest, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log, threshold=FLAGS.threshold,
-                                             save_curves=FLAGS.save_curves)
+                                             save_curves=FLAGS.save_curves, diagnose=diagnose)
     if rest or not FLAGS.pred_dir:
         parser().error('--pred_dir is required' if not rest else 'unrecognized arguments: %s' % ' '.join(rest))
     return evaluate(FLAGS.pred_dir, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log, threshold=FLAGS.threshold,
-                    save_curves=FLAGS.save_curves)
+                    save_curves=FLAGS.save_curves, diagnose=diagnose)
 
 
 if __name__ == '__main__':
