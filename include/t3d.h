@@ -1629,6 +1629,55 @@ typedef struct {
 #define T3D_V2_SIZE_render_args 192
 int t3d_render(const t3d_render_args* args, t3d_stream_t stream);
 
+/* ---- Label-free consistency of decoded detections (csrc/consistency.hip; consistency.DeviceConsistency, detect --consistency,
+ *      autolabel) ----
+ * A 3-D box that came from a 2-D box has to reproject onto that 2-D box, and it has to sit on the points the network segmented.  One
+ * launch behind t3d_detect_decode, one workgroup of 256 threads per detection b < min(n_valid, B); rows at or past n_valid keep what
+ * they held.  Every arithmetic step is fp64 (the fp32 inputs are widened first); each product and each sum below is its own operation
+ * (no contraction), in the order written, so that a NumPy fp64 transcription gives the same bits.
+ *   Mask             mask[n] = logits[n][1] > logits[n][0] (a tie is background, as in t3d_detect_decode); n_mask = sum mask, which
+ *                    equals the decode's mask_count.
+ *   Point frame      rot_angle != NULL: c = cos(-(double)rot), s = sin(-(double)rot); x' = c*x - s*z, y' = y, z' = s*x + c*z (the way the
+ *                    decode turns the centre).  NULL: the point as it stands, no multiplication.
+ *   In the box       the closed parallelepiped at corner K0 with the edges to corners 1, 3 and 4 (get_3d_box order: w, l, h).
+ *                    q = p' - K0; per edge e = Kj - K0: dv = (q0*e0 + q1*e1) + q2*e2, dd = (e0*e0 + e1*e1) + e2*e2; inside iff
+ *                    0 <= dv && dv <= dd for all three edges (a NaN anywhere: not inside).  n_box counts the points inside, n_both
+ *                    those inside that are also masked, both with multiplicity (the network's draw repeats points).
+ *   Projection       project_upright_camera_to_upright_depth then project_upright_depth_to_image of sunrgbd_data/utils.py.  Per
+ *                    corner (X, Y, Z): d = (X, Z, -Y); t_i = (R[0][i]*d0 + R[1][i]*d1) + R[2][i]*d2 (Rtilt^T d); cam = (t0, -t2, t1);
+ *                    w_i = (K[i][0]*cam0 + K[i][1]*cam1) + K[i][2]*cam2; u = w0/w2, v = w1/w2; the depth is cam2.
+ *   Rectangle        xmin = u of corner 0, then for corners 0..7 in order xmin = u < xmin ? u : xmin; xmax, ymin, ymax likewise.  Where
+ *                    image W > 0 and H > 0, x values are clamped to [0, W-1] and y values to [0, H-1]: x < 0 ? 0 : (x > W-1 ? W-1 : x).
+ *   IoU with box2d   iw = min(xmax_a, xmax_b) - max(xmin_a, xmin_b), ih likewise (min(a, b) = a < b ? a : b, max(a, b) = a > b ? a : b,
+ *                    a the rectangle); inter = (iw > 0 && ih > 0) ? iw*ih : 0; areas (xmax - xmin)*(ymax - ymin);
+ *                    uni = (area_a + area_b) - inter; IoU = uni > 0 ? inter/uni : 0.
+ *   flags            bit 1: some corner has depth <= 0 or a non-finite u or v -- the five reproj values are then 0.
+ *                    bit 2: n_mask == 0.
+ *                    bit 4: calib_index outside [0, n_calib) -- the five reproj values are then 0 and no calibration row is read; the
+ *                    counts are computed all the same.
+ *   calib            rows of 20 fp64: Rtilt row-major (9), K row-major (9), image W, image H (W <= 0 or H <= 0: do not clip).  Several
+ *                    detections may name one row.
+ *   Errors           before any launch: T3D_ERR_SHAPE for B <= 0, N <= 0, n_valid < 0, ld_xyz < 3 or n_calib < 0; T3D_ERR_ARG for a null
+ *                    pointer other than rot_angle, or logits that are not 8-byte aligned.  n_valid == 0: T3D_OK without a launch.
+ * The counts are integer sums over a fixed tree (per thread, 64 lanes by shuffles, four waves in index order).  No atomics, no
+ * allocation, no host synchronisation: equal inputs give equal bytes, whatever B is. */
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_consistency_args) of the caller's header (see T3D_ABI_VERSION) */
+  int B; int N; int n_valid; int ld_xyz;
+  const float* xyz;             /* [B, N, ld_xyz], ld_xyz >= 3: the points the network saw; columns 0..2 are read */
+  const float* logits;          /* [B, N, 2] */
+  const float* corners;         /* [B, 8, 3]: what t3d_detect_decode wrote */
+  const float* rot_angle;       /* [B] or NULL */
+  const double* box2d;          /* [B, 4]: xmin, ymin, xmax, ymax */
+  const int32_t* calib_index;   /* [B] */
+  const double* calib;          /* [n_calib, 20] */
+  int n_calib;
+  int32_t* counts;              /* [B, 4] out: n_mask, n_box, n_both, flags */
+  double* reproj;               /* [B, 5] out: xmin, ymin, xmax, ymax, IoU */
+} t3d_detect_consistency_args;
+#define T3D_V2_SIZE_detect_consistency_args 104
+int t3d_detect_consistency(const t3d_detect_consistency_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -432,6 +432,16 @@ def render_workspace_bytes(pixels):
     return int(pixels) * 12
 
 
+CONSISTENCY_BAD_PROJECTION, CONSISTENCY_EMPTY_MASK, CONSISTENCY_NO_CALIB = 1, 2, 4      # t3d.h t3d_detect_consistency: bits of `flags`
+CONSISTENCY_CALIB_WIDTH = 20          # Rtilt (9), K (9), image W, image H
+
+
+class DetectConsistencyArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('B', i32), ('N', i32), ('n_valid', i32), ('ld_xyz', i32), ('xyz', F), ('logits', F),
+                ('corners', F), ('rot_angle', F), ('box2d', D), ('calib_index', I), ('calib', D), ('n_calib', i32), ('counts', I),
+                ('reproj', D)]
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -544,6 +554,7 @@ ENTRY_POINTS = {
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],
+    't3d_detect_consistency': [C.POINTER(DetectConsistencyArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }
@@ -602,6 +613,10 @@ def iptr(t):
 
 def u8ptr(t):
     return C.cast(C.c_void_p(0 if t is None else t.data_ptr()), U8)
+
+
+def dptr(t):
+    return C.cast(C.c_void_p(0 if t is None else t.data_ptr()), D)
 
 
 def check(rc, what):

@@ -6,6 +6,7 @@
         # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}]]
         [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
+        [--consistency] [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] [--consistency_json FILE]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -26,6 +27,14 @@ kept 3-D boxes in class colours and their 2-D rectangles, beside a bird's-eye pa
 DIR/<id>.json, the legend (there is no text in the pictures).  t3d_render (render.py) paints them from the corners where the decode
 wrote them and from the device copy of the points the extraction made; only the finished panels come back.  --vis_gt adds the label
 boxes in green, --vis_suppressed (with --nms_iou) the boxes NMS dropped in grey.  Nothing else changes with these flags.
+
+--consistency: t3d_detect_consistency (consistency.py) follows every batch's decode and measures, without ground truth, how well each 3-D
+box agrees with what it was predicted from: reproj_iou (its reprojection against its 2-D box; the image size, read from the JPEG's
+header, clips the reprojection), mask_in_box and seg_box_iou (the segmented points against the points inside the box).  Records,
+--vis_dir legends and --consistency_json FILE (one row per detection) carry the numbers.  --min_reproj_iou / --min_mask_in_box /
+--min_seg_box_iou (each implies --consistency) reject a detection below the threshold: it is absent from everything this module hands
+out, and it is rejected BEFORE --nms_iou runs -- it is listed in no NMS group, so a box the filter rejects cannot suppress a good one.
+Without these flags every output is byte for byte what it was.
 """
 import argparse
 import collections
@@ -37,7 +46,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
+from transferable3d_amd import consistency as CS, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -158,23 +167,40 @@ class Vis:
                          'box2d': [float(x) for x in m[3]], 'colour': byte(c), 'kept': kind == 'kept'}
                 if kind == 'suppressed':
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
+                if d.reproj_iou is not None:
+                    entry.update(consistency_fields(d, r, as_lists=True))
+                    if not d.accept[r]:
+                        entry['kind'] = 'rejected'
                 legend['boxes'].append(entry)
         return [cam, bev], legend
+
+
+def consistency_fields(d, i, as_lists=False):
+    """What a record (or a legend / JSON entry: as_lists) says of detection i's consistency measures."""
+    rect = d.reproj_rect[i]
+    return {'reproj_iou': float(d.reproj_iou[i]), 'reproj_rect': [float(v) for v in rect] if as_lists else rect,
+            'mask_in_box': float(d.mask_in_box[i]), 'seg_box_iou': float(d.seg_box_iou[i]), 'flags': int(d.flags[i])}
 
 
 class Detector:
     """The test_semisup inference graph, built once; `detect` runs scenes through it."""
 
     def __init__(self, FLAGS=None, model_path=None, boxpc_model_path=None, rt=None, type_whitelist=SD.TYPE_WHITELIST,
-                 num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, **keywords):
+                 num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
+                 min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.
         nms_iou: None (every detection is reported, as the reference does) or the IoU in (0, 1] above which a box is suppressed by a
         better-ranked kept box of its image and class; nms_metric '3d' (default) / 'bev'; nms_score 'prob' (default: the 2-D
         detection confidence, what the result files and the evaluation rank by) / 'score' (the decoded network score).  log: a
-        function that takes the one line per run on how many detections were kept."""
+        function that takes the one line per run on how many detections were kept.
+        consistency: measure every detection with t3d_detect_consistency (consistency.py); min_reproj_iou / min_mask_in_box /
+        min_seg_box_iou: None, or the value in [0, 1] below which a detection is rejected (any of them implies consistency) -- before
+        the suppression of nms_iou, in whose groups a rejected detection is not listed."""
         self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
+        self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
+        self.consistency = bool(consistency) or any(t is not None for t in self.thresholds)
         self.log = log
         self.FLAGS = FLAGS = FLAGS if FLAGS is not None else flags_from_keywords(**keywords)
         model_path = model_path or FLAGS.model_path
@@ -203,11 +229,12 @@ class Detector:
                 meta.append((s, scene_ids[s], name, np.asarray(box2d, np.float64), float(prob)))
         want_scene = vis is not None and vis.taken < vis.max
         out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene)
+        calib = [CS.calib_row(sc['Rtilt'], sc['K'], sc.get('image_wh')) for sc in scenes] if self.consistency else []
         if out is None:
-            return dict(out=None, keep=[], counts=[], meta=[], n_scenes=len(scenes))
+            return dict(out=None, keep=[], counts=[], meta=[], n_scenes=len(scenes), calib=calib)
         counts = out['count'].cpu().numpy()                          # the one copy back of this launch
         keep = np.nonzero(counts >= MIN_POINTS)[0]
-        part = dict(out=out, keep=keep, counts=counts[keep], meta=[meta[j] for j in keep], n_scenes=len(scenes))
+        part = dict(out=out, keep=keep, counts=counts[keep], meta=[meta[j] for j in keep], n_scenes=len(scenes), calib=calib)
         if want_scene:
             vis.take(self.rt, part, scenes, scene_ids, self.extractor.last_scene)
             self.extractor.last_scene = None
@@ -223,7 +250,8 @@ class Detector:
         return [meta[i] for i in rows], d[rows]
 
     def decode_all(self, parts):
-        """`decode` with every detection in its place: the records say which ones t3d_detect_nms kept (Decoded.keep; None without nms_iou)."""
+        """`decode` with every detection in its place: the records say which ones t3d_detect_nms kept (Decoded.keep; None without nms_iou).
+        With thresholds, Decoded.accept says which ones passed them, and Decoded.keep is False for the others too."""
         FLAGS = self.FLAGS
         meta = [m for p in parts for m in p['meta']]
         if not meta:
@@ -232,16 +260,31 @@ class Detector:
         ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live],
                                           [type2class[m[2]] for m in meta])
         source = DeviceEvalSource(self.ops['graph'], dataset=ds, seed=FLAGS.seed)
+        con = None
+        if self.consistency:
+            rows, index = [], []
+            for p in parts:                              # a part's meta names its scenes by their position in the part
+                index += [len(rows) + m[0] for m in p['meta']]
+                rows += list(p.get('calib', []))
+            con = SI.ConsistencyRequest([m[3] for m in meta], rows, index, *self.thresholds)
         res = SI.inference(self.sess, self.ops, None, None, self.B, prefix=FLAGS.pred_prefix, use_boxpc_fit_prob=FLAGS.use_boxpc_fit_prob,
                            source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False,
                            nms=None if self.nms_iou is None else SI.NmsRequest(
                                self.nms_iou, self.nms_metric, self.nms_score, [m[1] for m in meta], [type2class[m[2]] for m in meta],
-                               [m[4] for m in meta]))
+                               [m[4] for m in meta]), consistency=con)
         d = res.decoded[slice(0, ds.F)]
         self.device_corners = res.device.sec['corners']          # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there)
-        if d.keep is not None and self.log:
+        offered = ds.F
+        if d.accept is not None:
+            if self.log:
+                below = CS.accept_of(d.reproj_iou, d.mask_in_box, d.seg_box_iou, self.thresholds)[1]
+                self.log(CS.log_line(d.accept, below, self.thresholds))
+            if not d.accept.all():                               # a rejected detection is dropped wherever a suppressed one is
+                offered = int(d.accept.sum())
+                d.keep = d.accept.copy() if d.keep is None else d.keep & d.accept
+        if self.nms_iou is not None and self.log:
             self.log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
-                     % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), ds.F))
+                     % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), offered))
         return meta, d
 
     def detect(self, scenes, detections, scene_ids=None, batch_scenes=16, vis_dir=None, vis_max=50, vis_gt=False, vis_suppressed=False):
@@ -252,7 +295,10 @@ class Detector:
         scenes that share a scene id share their groups: give distinct ids.)
         vis_dir: write <id>.png / <id>.json of the first vis_max scenes with a detection there (module docstring); a scene may carry
         'image' (uint8 [H,W,3], RGB) for the camera panel, and 'gt_corners' [g,8,3] (upright camera) / 'gt_classes' for vis_gt.  The
-        records do not depend on it."""
+        records do not depend on it.
+        With `consistency` (or a threshold) the records gain 'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou', 'flags'
+        (consistency.py), and a detection below a threshold has no entry; a scene may carry 'image_wh' = (W, H), to which the
+        reprojected rectangle is then clipped (without it: no clipping)."""
         vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
@@ -278,7 +324,10 @@ class Detector:
 
     @staticmethod
     def record(name, box2d, prob, d, i):
-        return {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
+        r = {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
+        if d.reproj_iou is not None:
+            r.update(consistency_fields(d, i))
+        return r
 
     def predictions(self, meta, d):
         """test_semisup's 14-list of a detection run (the entries it fills for --from_rgb_detection; the rotation angles stayed on the
@@ -303,6 +352,19 @@ def scene_pictures(dataset, idx, with_gt, type_whitelist):
     return out
 
 
+def write_consistency_json(path, meta, d):
+    """One row per detection of a run, in detection order, the rejected and the suppressed ones included."""
+    rows = []
+    for i, m in enumerate(meta):
+        row = {'image': int(m[1]), 'class': m[2], 'box2d': [float(v) for v in m[3]], 'prob': float(m[4]), 'score': float(d.score[i]),
+               'n_mask': int(d.n_mask[i]), 'n_box': int(d.n_box[i]), 'n_both': int(d.n_both[i]), 'accepted': bool(d.accept[i]),
+               'kept': bool(d.keep is None or d.keep[i])}
+        row.update(consistency_fields(d, i, as_lists=True))
+        rows.append(row)
+    with open(path, 'w') as fh:
+        json.dump(rows, fh, indent=1)
+
+
 def parser():
     p = argparse.ArgumentParser(description='3-D detections from SUN-RGBD scenes and 2-D detections, on the device', allow_abbrev=False)
     p.add_argument('--dataset_dir', default='mysunrgbd', help='SUN-RGBD root (<dir>/training/{image,calib,depth,label_dimension})')
@@ -318,6 +380,8 @@ def parser():
     p.add_argument('--vis_max', type=int, default=50, help='how many scenes --vis_dir draws (the first ones with a detection)')
     p.add_argument('--vis_gt', action='store_true', help='--vis_dir: add the label boxes of label_dimension in green')
     p.add_argument('--vis_suppressed', action='store_true', help='--vis_dir: add the boxes --nms_iou dropped, in grey')
+    CS.add_arguments(p)
+    p.add_argument('--consistency_json', default=None, help='write one row per detection (rejected ones included) with its consistency measures here')
     return p
 
 
@@ -336,11 +400,19 @@ def main(argv=None, rt=None, log=print):
     if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
         parser().error('--vis_gt / --vis_suppressed need --vis_dir')
     try:
+        thresholds = CS.check_thresholds(args.min_reproj_iou, args.min_mask_in_box, args.min_seg_box_iou)
+    except ValueError as e:
+        parser().error(str(e))
+    consistency = args.consistency or any(t is not None for t in thresholds)
+    if args.consistency_json and not consistency:
+        parser().error('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
+    try:
         vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None) if args.vis_dir else None
     except ValueError as e:
         parser().error(str(e))
     det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=args.nms_metric,
-                   nms_score=args.nms_score, log=log)
+                   nms_score=args.nms_score, log=log, consistency=consistency, min_reproj_iou=thresholds[0], min_mask_in_box=thresholds[1],
+                   min_seg_box_iou=thresholds[2])
     valid = set(int(line.rstrip()) for line in open(args.idx_path))
     det_id, det_type, det_box2d, det_prob = SD.read_det_folder(args.rgb_detection_path)
     per_scene = collections.OrderedDict()
@@ -352,16 +424,23 @@ def main(argv=None, rt=None, log=print):
     parts = []
     for batch in SD._scenes_in_batches(load, ids, 16, 8):
         scenes = [{'points': depth, 'Rtilt': calib.Rtilt, 'K': calib.K} for _, (calib, depth) in batch]
+        if consistency:
+            for (idx, _), scene in zip(batch, scenes):
+                scene['image_wh'] = CS.image_size(dataset._path('image', idx, 'jpg'))
         if vis is not None and vis.taken < vis.max:
             for (idx, _), scene in zip(batch, scenes):
                 scene.update(scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist))
         parts.append(det.extract(scenes, [per_scene[idx] for idx, _ in batch], [idx for idx, _ in batch], vis=vis))
-    if vis is None:
+    if vis is None and not args.consistency_json:
         meta, d = det.decode(parts)
     else:
         meta, d = det.decode_all(parts)
+        if args.consistency_json:
+            write_consistency_json(args.consistency_json, meta, d)
+            log('consistency measures of %d detections written to %s' % (len(meta), args.consistency_json))
         if d is not None:
-            log('%d scenes drawn to %s' % (len(vis.write(det.rt, parts, d, det.device_corners)), args.vis_dir))
+            if vis is not None:
+                log('%d scenes drawn to %s' % (len(vis.write(det.rt, parts, d, det.device_corners)), args.vis_dir))
             if d.keep is not None:
                 rows = np.nonzero(d.keep)[0]
                 meta, d = [meta[i] for i in rows], d[rows]

@@ -25,6 +25,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transferable3d_amd import abi, nms as NMS, test_semisup as TS       # noqa: E402
 from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
+from transferable3d_amd.consistency import ConsistencyRequest, DeviceConsistency      # noqa: E402
 from transferable3d_amd.constants import type2class                     # noqa: E402
 
 
@@ -67,9 +68,12 @@ class Decoded:
     eval_det.evaluate_predictions read label / corners from it instead of looping over the detections.
     keep [n] bool and suppressed_by [n] (-1: kept; else the row of the better-ranked box that suppressed this one) are what t3d_detect_nms
     answered, or None where no suppression was asked for.  A sliced Decoded carries its rows' values; suppressed_by keeps naming rows of
-    the unsliced run."""
+    the unsliced run.
+    reproj_rect [n,4], reproj_iou, n_mask, n_box, n_both, flags, mask_in_box, seg_box_iou are what t3d_detect_consistency measured
+    (consistency.py) and accept [n] bool whether the detection misses none of the request's thresholds; None where no consistency
+    request was made."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
-    OPTIONAL = ('keep', 'suppressed_by')
+    OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept')
 
     def __init__(self, **fields):
         for k in self.FIELDS:
@@ -104,6 +108,7 @@ class DeviceDecode:
     INTS = ('mask_count', 'heading_cls', 'size_cls')
 
     nms_out = None
+    consistency = None          # what DeviceConsistency.fetch returned for these detections (inference(consistency=...))
 
     def __init__(self, rt, n, num_point, want_seg=False):
         self.rt, self.n, self.N = rt, n, num_point
@@ -127,12 +132,18 @@ class DeviceDecode:
                                  fptr(o['heading_res']), fptr(o['size_res']), fptr(o['label']), fptr(o['corners']))
         abi.check(self.rt.lib.t3d_detect_decode(C.byref(a), self.rt.stream()), 't3d_detect_decode')
 
-    def nms(self, req, total):
+    def nms(self, req, total, rows=None):
         """t3d_detect_nms over the first `total` rows (the rest pad a last batch), on the corners and scores where the decode wrote them;
-        `fetch` then brings keep / suppressed_by back with the records.  -> the DeviceNms that holds them."""
+        `fetch` then brings keep / suppressed_by back with the records.  rows: the detections that take part (default: all); the others
+        are listed in no group, so they suppress nothing and come back as kept.  -> the DeviceNms that holds them."""
         if len(req.image_ids) != total:
             raise ValueError('%d image ids for %d detections' % (len(req.image_ids), total))
-        offsets, members = NMS.groups_of(req.image_ids, req.class_ids)
+        if rows is None:
+            offsets, members = NMS.groups_of(req.image_ids, req.class_ids)
+        else:
+            rows = np.asarray(rows, np.int64)
+            offsets, members = NMS.groups_of(req.image_ids[rows], req.class_ids[rows])
+            members = rows[members].astype(np.int32)
         if req.score == 'prob':
             score = self.rt.zeros(self.n)
             score[:total] = torch.from_numpy(req.prob).to(self.rt.device)
@@ -155,6 +166,8 @@ class DeviceDecode:
         if self.nms_out is not None:
             out['keep'] = self.nms_out.keep[:n].cpu().numpy().astype(bool)
             out['suppressed_by'] = self.nms_out.suppressed_by[:n].cpu().numpy().astype(np.int64)
+        if self.consistency is not None:
+            out.update({k: v for k, v in self.consistency.items() if k in Decoded.OPTIONAL})
         return Decoded(**out), (None if self.seg is None else self.seg.cpu().numpy())
 
 
@@ -177,13 +190,19 @@ def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
 
 
 def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
-              decode='host', want_seg=True, nms=None):
+              decode='host', want_seg=True, nms=None, consistency=None):
     """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
     padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
-    copied back; `.decoded.keep` / `.suppressed_by` hold its answer (None without it).  Nothing is removed here: the callers drop the rows."""
+    copied back; `.decoded.keep` / `.suppressed_by` hold its answer (None without it).  Nothing is removed here: the callers drop the rows.
+    consistency (ConsistencyRequest, decode='device' only): t3d_detect_consistency follows every batch's decode on the points the network
+    read, the logits, the corners just written and the batch's rotation angles; `.decoded.reproj_iou`, `.n_mask`, ... `.accept` hold what
+    it measured.  Its outputs are copied back before the NMS groups are built: a detection below a threshold of the request is listed
+    in no group, so a box the filter rejects cannot suppress a good one (its `keep` stays True; `accept` says it is rejected)."""
     if decode == 'host' and nms is not None:
         raise ValueError("nms runs on the device-decoded boxes: decode='device'")
+    if decode == 'host' and consistency is not None:
+        raise ValueError("the consistency measures are taken on the device-decoded boxes: decode='device'")
     if decode == 'host':
         return TS.inference(sess, ops, pc, one_hot_vec, batch_size, prefix=prefix, use_boxpc_fit_prob=use_boxpc_fit_prob, source=source,
                             n_batches=n_batches, oracle_mask=oracle_mask)
@@ -199,6 +218,12 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     dec = DeviceDecode(rt, n, npts, want_seg=want_seg)
     total = source.ds.F if source is not None else n                 # the frustums past it pad the last batch
     rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
+    con = None
+    if consistency is not None:
+        if len(consistency) != total:
+            raise ValueError('%d detections in the consistency request, %d decoded' % (len(consistency), total))
+        con = DeviceConsistency(rt, n, npts, consistency)
+        xyz = sess.g.inputs.pc                                       # [B * N, ld] where the network read the batch
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
         if source is not None:
@@ -209,9 +234,17 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
             if oracle_mask is not None:
                 feed[ops['y_seg_pl']] = np.asarray(oracle_mask[sl], np.int32)
             sess.run([], feed_dict=feed)
-        dec.launch(sl.start, batch_size, max(0, min(batch_size, total - sl.start)), logits, box, s1, delta, fit, rot)
+        valid = max(0, min(batch_size, total - sl.start))
+        dec.launch(sl.start, batch_size, valid, logits, box, s1, delta, fit, rot)
+        if con is not None:
+            con.launch(sl.start, batch_size, valid, xyz, int(xyz.stride(0)), logits, dec.sec['corners'][sl.start:], rot)
+    rows = None
+    if con is not None:
+        dec.consistency = con.fetch()                                # (the one small copy back in front of the group building)
+        if not dec.consistency['accept'][:total].all():
+            rows = np.nonzero(dec.consistency['accept'][:total])[0]
     if nms is not None:
-        dec.nms(nms, total)
+        dec.nms(nms, total, rows=rows)
     d, seg = dec.fetch()
     res = InferenceResult((None if seg is None else seg.astype(np.int64), d.center, d.heading_cls, d.heading_res, d.size_cls, d.size_res,
                            d.score))
