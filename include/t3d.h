@@ -1678,6 +1678,76 @@ typedef struct {
 #define T3D_V2_SIZE_detect_consistency_args 104
 int t3d_detect_consistency(const t3d_detect_consistency_args* args, t3d_stream_t stream);
 
+/* ---- Box voting: every box t3d_detect_nms kept takes the weighted mean geometry of the boxes it suppressed (csrc/fuse.hip;
+ *      nms.DeviceFuse, detect --nms_iou T --nms_fuse) ----
+ * A 2-D detector reports one object several times, each report becomes a frustum of its own and a 3-D estimate of its own;
+ * t3d_detect_nms keeps the best-ranked one and names, per suppressed box, the kept box that suppressed it.  This entry point runs behind
+ * it on the same stream and the same buffers and leaves the decision who survives alone: it writes, into buffers of its own, the kept
+ * box's geometry fused with that of its cluster (Gidaris & Komodakis, ICCV 2015; weighted box fusion), for oriented 3-D boxes.  The
+ * reference has no such step; it is opt-in.  n, n_groups, group_offsets, members and max_group are those of the t3d_detect_nms call, under
+ * the same contract; keep, suppressed_by and rank are what it wrote (rank is needed here), label and corners what t3d_detect_decode wrote.
+ *   Cluster        of a listed box i with keep[i] != 0: i (the anchor) and every listed box j of its group with keep[j] == 0 and
+ *                  suppressed_by[j] == i.
+ *   Voters         member j != i votes iff all 7 entries of label[j] are finite and IoU(i, j) > vote_threshold, strictly, where the IoU
+ *                  is the fp32 box3d_iou_corners(corners[i], corners[j]) of csrc/boxgeom_dev.h with i as the first argument: the volume
+ *                  IoU for metric T3D_NMS_IOU3D, that of the ground rectangles for T3D_NMS_IOU2D.  A NaN IoU does not vote.  Both
+ *                  boxes are handed over relative to corner 0 of box i (each fp32 coordinate minus that corner's): the IoU does not
+ *                  depend on where the pair lies, its fp32 rounding does, and here the value is a weight, not only a decision.
+ *   Weights        s(x) = x where x is finite and >= 0, else 0.  w_i = s(weight[i]); w_j = s(weight[j]) * IoU(i, j).
+ *   Alignment      a box equals itself turned by pi, and turned by pi/2 with l and w exchanged.  With d = ry_j - ry_i and
+ *                  wrap(x) = x - 2pi * ceil((x - pi) / 2pi) (into (-pi, pi]), the candidates are k = 0, 1, 2, 3: wrap(d + k * pi/2),
+ *                  (l_j, w_j) exchanged for odd k.  The k of the smallest |wrap(d + k * pi/2)| is taken, on a tie the lowest;
+ *                  delta_j is that wrapped difference and (l'_j, w'_j) the dimensions after the exchange.
+ *   Fusion         W = w_i + sum w_j.  cx, cy, cz, l, w, h = the w-weighted means over the anchor and the voters of (tx, ty - h/2, tz),
+ *                  l', w', h: (w_i * x_i + sum w_j * x_j) / W.  ry = ry_i + (sum w_j * delta_j) / W, not wrapped again: it stays
+ *                  continuous with the kept box.  label_out[i] = (h, w, l, cx, cy + h/2, cz, ry).
+ *   Precision      the label entries and weights are widened to fp64, every step above is fp64, the sums run over the voters in
+ *                  ascending rank, the anchor first; the 7 results are rounded to fp32 once.  The IoU is computed in fp32 and widened.
+ *   corners_out    from the fp32 label_out[i] by the fp32 formula of t3d_detect_decode: get_3d_box((l, w, h), ry, (tx, ty - h/2, tz)),
+ *                  corner c: x = (c & 2 ? -l : l) / 2, y = (c < 4 ? h : -h) / 2, z = ((c + 1) & 2 ? -w : w) / 2;
+ *                  ((cos ry * x + sin ry * z) + tx, y + (ty - h/2), (-sin ry * x + cos ry * z) + tz).
+ *   Unchanged      label_out[i] and corners_out[i] are byte copies of label[i] and corners[i] for: a kept box without voters; a kept
+ *                  box with W == 0 or W not finite; a kept box with a non-finite entry in its own label; every listed suppressed box.
+ *   n_votes        the number of voters (0, 1, ...) of a kept box whatever their weights (0 where its own label is not finite: nobody
+ *                  is asked); -1 for a listed suppressed box.
+ *   Unlisted       a box in no group is not visited: none of its three outputs is written.  Neither is a box of a group that breaks
+ *                  the contract of t3d_detect_nms (larger than max_group, or leaving [0, n)).
+ *   Empty input    n == 0, n_groups == 0 or max_group == 0: T3D_OK without a launch.
+ *   Errors         before anything is launched: T3D_ERR_SHAPE for max_group > T3D_DETECT_NMS_MAX_GROUP; T3D_ERR_ARG for n, n_groups or
+ *                  max_group < 0, an unknown metric, a vote_threshold that is NaN or outside [0, 1], a null pointer, a workspace smaller
+ *                  than T3D_DETECT_FUSE_WORKSPACE_BYTES(n) or not 8-byte aligned.
+ *   workspace      per position of the lists an int32 and a 16-byte vote: every group's boxes in rank order, rebuilt from `rank`, and
+ *                  what each suppressed box says of the box that suppressed it (nothing of the workspace of t3d_detect_nms is read,
+ *                  whose layout stays private).
+ * The inputs are never written, the outputs are buffers of their own.  Two launches on `stream`, both one thread per POSITION of the
+ * concatenated lists (a wave covers several whole small groups).  The first writes order[first(g) + rank[box]] = box and, for a
+ * suppressed box, its vote: the IoU with its suppressor, the aligning quarter turn and the heading difference -- one IoU per suppressed
+ * box in all, every lane busy with its own.  In the second the thread of a kept box walks the later ranks of its own group, takes the
+ * votes cast for it and sums them in rank order.  No atomics, no allocation, no host synchronisation: a group's outputs depend on its
+ * own boxes only, and equal inputs give equal bytes. */
+#define T3D_DETECT_FUSE_WORKSPACE_BYTES(n) ((((uint64_t)(n) + 1u) / 2u) * 8u + (uint64_t)(n) * 16u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_fuse_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_groups; int metric;
+  const int32_t* group_offsets;    /* [n_groups + 1], as for t3d_detect_nms */
+  const int32_t* members;          /* [group_offsets[n_groups]] */
+  const uint8_t* keep;             /* [n]: what t3d_detect_nms wrote */
+  const int32_t* suppressed_by;    /* [n]: likewise */
+  const int32_t* rank;             /* [n]: likewise */
+  const float* label;              /* [n,7] (h, w, l, tx, ty, tz, ry), ty the bottom of the box: what t3d_detect_decode wrote */
+  const float* corners;            /* [n,8,3], get_3d_box order: likewise */
+  const float* weight;             /* [n]: what a box's vote counts, usually what ranked it */
+  float vote_threshold;            /* in [0, 1] */
+  int max_group;
+  void* workspace;
+  uint64_t workspace_bytes;
+  float* label_out;                /* [n,7] out */
+  float* corners_out;              /* [n,8,3] out */
+  int32_t* n_votes;                /* [n] out */
+} t3d_detect_fuse_args;
+#define T3D_V2_SIZE_detect_fuse_args 128
+int t3d_detect_fuse(const t3d_detect_fuse_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

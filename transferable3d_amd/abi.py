@@ -442,6 +442,17 @@ class DetectConsistencyArgs(Sized):
                 ('reproj', D)]
 
 
+class DetectFuseArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_groups', i32), ('metric', i32), ('group_offsets', I), ('members', I), ('keep', U8),
+                ('suppressed_by', I), ('rank', I), ('label', F), ('corners', F), ('weight', F), ('vote_threshold', f32), ('max_group', i32),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('label_out', F), ('corners_out', F), ('n_votes', I)]
+
+
+def detect_fuse_workspace_bytes(n):
+    """t3d.h T3D_DETECT_FUSE_WORKSPACE_BYTES"""
+    return (n + 1) // 2 * 8 + n * 16
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -555,6 +566,7 @@ ENTRY_POINTS = {
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],
     't3d_detect_consistency': [C.POINTER(DetectConsistencyArgs), VP],
+    't3d_detect_fuse': [C.POINTER(DetectFuseArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }

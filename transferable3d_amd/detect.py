@@ -4,7 +4,7 @@
     python -m transferable3d_amd.detect --dataset_dir D --idx_path I --rgb_detection_path DETS --model_path M [--boxpc_model_path P] \
         --result_dir R [--official_eval [--diagnose [--diagnose_bg 0.1] [--diagnose_json FILE]]]
         # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
-        [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}]]
+        [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}] [--nms_fuse] [--nms_fuse_iou V]]
         [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
         [--consistency] [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] [--consistency_json FILE]
 
@@ -21,6 +21,13 @@ a part of them does not.
 them as false positives.  With the flag, t3d_detect_nms (nms.py) suppresses, per image and class, every box whose IoU with a
 better-ranked kept box exceeds T, on the decoded corners where they lie; the suppressed detections are absent from everything this
 module hands out.  Without it nothing changes.
+
+--nms_fuse (with --nms_iou): box voting.  The suppressed boxes of a kept box are further estimates of the same object, each from a frustum
+and a point sample of its own; t3d_detect_fuse (nms.DeviceFuse) writes every kept box with the weighted mean geometry of its cluster
+(weights: what ranked, times the IoU with the kept box; headings and the l / w exchange aligned to the kept box first).  Which boxes are
+kept, and every score, stay; a kept box without a suppressed box stays byte for byte.  --nms_fuse_iou V (in [T, 1], implies --nms_fuse)
+lets only the suppressed boxes above IoU V vote.  Records and --vis_dir legends gain 'votes'.  Without --nms_fuse every output is what
+it was, byte for byte.
 
 --vis_dir DIR: for each of the first --vis_max scenes (default 50) with at least one detection, DIR/<id>.png -- the camera image with the
 kept 3-D boxes in class colours and their 2-D rectangles, beside a bird's-eye panel of the scene's points with the same boxes -- and
@@ -167,6 +174,8 @@ class Vis:
                          'box2d': [float(x) for x in m[3]], 'colour': byte(c), 'kept': kind == 'kept'}
                 if kind == 'suppressed':
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
+                if d.n_votes is not None:
+                    entry['votes'] = int(d.n_votes[r])
                 if d.reproj_iou is not None:
                     entry.update(consistency_fields(d, r, as_lists=True))
                     if not d.accept[r]:
@@ -187,7 +196,7 @@ class Detector:
 
     def __init__(self, FLAGS=None, model_path=None, boxpc_model_path=None, rt=None, type_whitelist=SD.TYPE_WHITELIST,
                  num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
-                 min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, **keywords):
+                 min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.
@@ -195,10 +204,14 @@ class Detector:
         better-ranked kept box of its image and class; nms_metric '3d' (default) / 'bev'; nms_score 'prob' (default: the 2-D
         detection confidence, what the result files and the evaluation rank by) / 'score' (the decoded network score).  log: a
         function that takes the one line per run on how many detections were kept.
+        nms_fuse (needs nms_iou): every kept box takes the weighted mean geometry of the boxes it suppressed (t3d_detect_fuse; module
+        docstring); nms_fuse_iou: None (= nms_iou: every suppressed box votes) or the IoU in [nms_iou, 1] above which one votes; it
+        implies nms_fuse.
         consistency: measure every detection with t3d_detect_consistency (consistency.py); min_reproj_iou / min_mask_in_box /
         min_seg_box_iou: None, or the value in [0, 1] below which a detection is rejected (any of them implies consistency) -- before
         the suppression of nms_iou, in whose groups a rejected detection is not listed."""
         self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
+        self.nms_fuse, self.nms_fuse_iou = NMS.check_fuse_options(self.nms_iou, nms_fuse, nms_fuse_iou)
         self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
         self.consistency = bool(consistency) or any(t is not None for t in self.thresholds)
         self.log = log
@@ -271,9 +284,11 @@ class Detector:
                            source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False,
                            nms=None if self.nms_iou is None else SI.NmsRequest(
                                self.nms_iou, self.nms_metric, self.nms_score, [m[1] for m in meta], [type2class[m[2]] for m in meta],
-                               [m[4] for m in meta]), consistency=con)
+                               [m[4] for m in meta], fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou), consistency=con)
         d = res.decoded[slice(0, ds.F)]
-        self.device_corners = res.device.sec['corners']          # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there)
+        # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there); with nms_fuse where t3d_detect_fuse wrote them: the fused
+        # corners of a kept box, and copies of the decode's for every other one (so --vis_suppressed still shows the raw boxes)
+        self.device_corners = res.device.sec['corners'] if res.device.fuse_out is None else res.device.fuse_out.corners
         offered = ds.F
         if d.accept is not None:
             if self.log:
@@ -284,7 +299,7 @@ class Detector:
                 d.keep = d.accept.copy() if d.keep is None else d.keep & d.accept
         if self.nms_iou is not None and self.log:
             self.log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
-                     % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), offered))
+                     % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), offered) + SI.fused_note(d))
         return meta, d
 
     def detect(self, scenes, detections, scene_ids=None, batch_scenes=16, vis_dir=None, vis_max=50, vis_gt=False, vis_suppressed=False):
@@ -298,7 +313,9 @@ class Detector:
         records do not depend on it.
         With `consistency` (or a threshold) the records gain 'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou', 'flags'
         (consistency.py), and a detection below a threshold has no entry; a scene may carry 'image_wh' = (W, H), to which the
-        reprojected rectangle is then clipped (without it: no clipping)."""
+        reprojected rectangle is then clipped (without it: no clipping).
+        With nms_fuse 'label' and 'corners' are the fused box and the records gain 'votes', the number of suppressed boxes that voted
+        (0: the box is what the decode wrote).  The consistency measures of a fused detection are those of its unfused box."""
         vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
@@ -325,6 +342,8 @@ class Detector:
     @staticmethod
     def record(name, box2d, prob, d, i):
         r = {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
+        if d.n_votes is not None:
+            r['votes'] = int(d.n_votes[i])
         if d.reproj_iou is not None:
             r.update(consistency_fields(d, i))
         return r
@@ -391,6 +410,7 @@ def main(argv=None, rt=None, log=print):
     FLAGS = TS.build_flags(list(rest))
     try:
         NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
+        NMS.check_fuse_options(args.nms_iou, args.nms_fuse, args.nms_fuse_iou)
     except ValueError as e:
         parser().error(str(e))
     from transferable3d_amd import evaluate_sunrgbd as ES
@@ -412,7 +432,7 @@ def main(argv=None, rt=None, log=print):
         parser().error(str(e))
     det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=args.nms_metric,
                    nms_score=args.nms_score, log=log, consistency=consistency, min_reproj_iou=thresholds[0], min_mask_in_box=thresholds[1],
-                   min_seg_box_iou=thresholds[2])
+                   min_seg_box_iou=thresholds[2], nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou)
     valid = set(int(line.rstrip()) for line in open(args.idx_path))
     det_id, det_type, det_box2d, det_prob = SD.read_det_folder(args.rgb_detection_path)
     per_scene = collections.OrderedDict()

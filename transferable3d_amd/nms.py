@@ -4,6 +4,9 @@ A 2-D detector hands over several overlapping boxes of one object; each becomes 
 script_3Deval.m credits only the first of them.  `DeviceNms.run` suppresses, inside every (image, class) group, any box that overlaps a
 better-ranked kept box by more than a threshold -- on the corners t3d_detect_decode wrote, which never visit the host in between.
 The reference has no such step: nothing runs it unless it is asked for (detect --nms_iou, semisup_infer --device_decode --nms_iou).
+
+`DeviceFuse.run` (t3d_detect_fuse, csrc/fuse.hip; --nms_fuse) follows it on the same buffers: who is kept stays, and every kept box takes
+the weighted mean geometry of the boxes it suppressed -- several estimates of one object, which the suppression alone throws away.
 """
 import ctypes as C
 
@@ -35,12 +38,30 @@ def check_options(nms_iou, nms_metric=None, nms_score=None):
     return t, metric, score
 
 
+def check_fuse_options(nms_iou, nms_fuse=False, nms_fuse_iou=None):
+    """The two box-voting options of the drivers -> (fuse, vote threshold or None).  nms_fuse_iou implies nms_fuse and defaults to
+    nms_iou; ValueError without nms_iou, and for a vote threshold outside [nms_iou, 1]: every member of a cluster overlaps its kept box
+    by more than nms_iou, so a lower value would silently change nothing."""
+    if not nms_fuse and nms_fuse_iou is None:
+        return False, None
+    if nms_iou is None:
+        raise ValueError('--nms_fuse / --nms_fuse_iou fuse the clusters of --nms_iou: they need --nms_iou')
+    t = float(nms_iou) if nms_fuse_iou is None else float(nms_fuse_iou)
+    if not float(nms_iou) <= t <= 1.0:
+        raise ValueError('--nms_fuse_iou must lie in [--nms_iou, 1] = [%r, 1], got %r' % (nms_iou, nms_fuse_iou))
+    return True, t
+
+
 def add_arguments(parser):
     parser.add_argument('--nms_iou', type=float, default=None,
                         help='suppress, per image and class, a 3-D box that overlaps a better-ranked kept box by more than this IoU (0 < T <= 1; default: no suppression)')
     parser.add_argument('--nms_metric', choices=METRICS, default=None, help="IoU of --nms_iou: '3d' (volume, default) or 'bev' (ground plane)")
     parser.add_argument('--nms_score', choices=SCORES, default=None,
                         help="rank by the 2-D detection confidence ('prob', default: the last column of the result files) or by the decoded network score")
+    parser.add_argument('--nms_fuse', action='store_true',
+                        help='with --nms_iou: every kept box takes the weighted mean geometry of the boxes it suppressed (box voting); which boxes are kept, and every score, stay')
+    parser.add_argument('--nms_fuse_iou', type=float, default=None,
+                        help='a suppressed box votes only above this IoU with its kept box (in [--nms_iou, 1]; default --nms_iou: every suppressed box votes); implies --nms_fuse')
 
 
 def groups_of(image_ids, class_ids):
@@ -104,3 +125,48 @@ class DeviceNms:
     def relaunch(self):
         """The launches of the last `run` again, on the same buffers (tools/bench_detect_nms.py times them alone)."""
         abi.check(self.rt.lib.t3d_detect_nms(C.byref(self._args), self.rt.stream()), 't3d_detect_nms')
+
+
+class DeviceFuse:
+    """Workspace and outputs of t3d_detect_fuse behind a DeviceNms.run: `run` launches on device tensors and owns label_out [n, 7],
+    corners_out [n, 24] and n_votes [n] until its next run."""
+
+    def __init__(self, rt):
+        self.rt = rt
+        self.workspace = self.label = self.corners = self.n_votes = None
+        self._held = ()
+
+    def run(self, nms, label, corners, weight, vote_threshold, fill=None):
+        """nms: the DeviceNms whose last `run` answered for these boxes (its keep / suppressed_by / rank and its lists are read where
+        they lie); label [n, 7], corners [n, 8, 3] / [n, 24], weight [n]: fp32 on the runtime's device, none of them written.
+        -> (label_out, corners_out, n_votes).  Before the launch the outputs hold copies of label and corners and n_votes 0 -- what a box
+        in no group keeps; fill: (label value, corners value, n_votes value) to hold instead."""
+        rt, a = self.rt, nms._args
+        n = int(weight.numel())
+        assert a.n == n and label.numel() == n * 7 and corners.numel() == n * 24
+        assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (label, corners, weight))
+        if self.label is None or self.n_votes.numel() < n:
+            new = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=rt.device)      # (owned here, as DeviceNms's)
+            self.label, self.corners, self.n_votes = new(max(n, 1), 7), new(max(n, 1), 24), new(max(n, 1), dtype=torch.int32)
+        lo, ko, nv = self.label[:n], self.corners[:n], self.n_votes[:n]
+        if fill is None:
+            lo.copy_(label.view(n, 7))
+            ko.copy_(corners.view(n, 24))
+            nv.zero_()
+        else:
+            lo.fill_(fill[0])
+            ko.fill_(fill[1])
+            nv.fill_(fill[2])
+        need = abi.detect_fuse_workspace_bytes(n)
+        if self.workspace is None or self.workspace.numel() * 8 < need:
+            self.workspace = torch.zeros(max(need // 8, 1), dtype=torch.int64, device=rt.device)
+        self._held = (nms, label, corners, weight)            # alive until the launches have run
+        self._args = abi.DetectFuseArgs(n, a.n_groups, a.metric, a.group_offsets, a.members, a.keep, a.suppressed_by, a.rank, fptr(label),
+                                        fptr(corners), fptr(weight), float(vote_threshold), a.max_group,
+                                        C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 8, fptr(lo), fptr(ko), iptr(nv))
+        self.relaunch()
+        return lo, ko, nv
+
+    def relaunch(self):
+        """The launches of the last `run` again, on the same buffers (tools/bench_detect_fuse.py times them)."""
+        abi.check(self.rt.lib.t3d_detect_fuse(C.byref(self._args), self.rt.stream()), 't3d_detect_fuse')

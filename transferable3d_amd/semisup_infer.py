@@ -12,6 +12,8 @@ here hands over to test_semisup's, so nothing that exists changes its numbers.
 
 --nms_iou T (with --from_rgb_detection): before the copy back, t3d_detect_nms (nms.py) suppresses, per image and class, every box that
 overlaps a better-ranked kept box by more than T; the suppressed detections are absent from the 14-list, the result files and --evaluate.
+--nms_fuse [--nms_fuse_iou V] (with --nms_iou): t3d_detect_fuse follows on the same buffers; every kept box is written with the weighted
+mean geometry of the boxes it suppressed (nms.DeviceFuse).  Which boxes are kept, and every score, stay.
 """
 import contextlib
 import ctypes as C
@@ -41,6 +43,7 @@ def build_flags(argv=None):
     FLAGS = TS.build_flags(rest)
     FLAGS.device_decode = device
     FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score = NMS.check_options(nms.nms_iou, nms.nms_metric, nms.nms_score)
+    FLAGS.nms_fuse, FLAGS.nms_fuse_iou = NMS.check_fuse_options(nms.nms_iou, nms.nms_fuse, nms.nms_fuse_iou)
     if FLAGS.nms_iou is not None and not (device and FLAGS.from_rgb_detection):
         raise ValueError('--nms_iou runs on the device-decoded boxes of a detection file: it needs --device_decode and --from_rgb_detection')
     return FLAGS
@@ -49,12 +52,15 @@ def build_flags(argv=None):
 class NmsRequest:
     """What `inference(decode='device', nms=...)` needs to run t3d_detect_nms on its decoded corners: the threshold, the metric ('3d' /
     'bev'), what ranks ('prob': the 2-D detection confidences given here; 'score': the decoded network score) and, per detection, the
-    image id and the class id that make its group."""
+    image id and the class id that make its group.  fuse: t3d_detect_fuse follows (box voting: a kept box takes the weighted mean
+    geometry of the boxes it suppressed); a suppressed box votes above the IoU vote_threshold (default: the threshold, so all of them do)
+    with the weight that ranked it -- `prob`, or exp(score) for score='score' (the decoded score is a sum of logs)."""
 
-    def __init__(self, threshold, metric, score, image_ids, class_ids, prob=None):
+    def __init__(self, threshold, metric, score, image_ids, class_ids, prob=None, fuse=False, vote_threshold=None):
         self.threshold, self.metric, self.score = NMS.check_options(threshold, metric, score)
         if self.threshold is None:
             raise ValueError('an NMS request needs a threshold')
+        self.fuse, self.vote_threshold = NMS.check_fuse_options(self.threshold, fuse, vote_threshold)
         self.image_ids, self.class_ids = np.asarray(image_ids, np.int64), np.asarray(class_ids, np.int64)
         self.prob = None if prob is None else np.asarray(prob, np.float32)
         if self.score == 'prob' and (self.prob is None or len(self.prob) != len(self.image_ids)):
@@ -71,9 +77,14 @@ class Decoded:
     the unsliced run.
     reproj_rect [n,4], reproj_iou, n_mask, n_box, n_both, flags, mask_in_box, seg_box_iou are what t3d_detect_consistency measured
     (consistency.py) and accept [n] bool whether the detection misses none of the request's thresholds; None where no consistency
-    request was made."""
+    request was made.
+    With a fusion (NmsRequest(fuse=True)) label and corners hold what t3d_detect_fuse wrote -- for a kept box with voters the fused
+    geometry, for every other box what the decode wrote -- raw_label / raw_corners what the decode wrote, and n_votes [n] the number of
+    voters of a kept box (-1: suppressed; 0: nothing to fuse, or listed in no group); None without.  center, heading_cls, heading_res,
+    size_cls and size_res are NOT fused: they keep what the decode wrote and describe the raw box."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
-    OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept')
+    OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept',
+                'raw_label', 'raw_corners', 'n_votes')
 
     def __init__(self, **fields):
         for k in self.FIELDS:
@@ -108,6 +119,7 @@ class DeviceDecode:
     INTS = ('mask_count', 'heading_cls', 'size_cls')
 
     nms_out = None
+    fuse_out = None             # the DeviceFuse of `nms` with a request that fuses
     consistency = None          # what DeviceConsistency.fetch returned for these detections (inference(consistency=...))
 
     def __init__(self, rt, n, num_point, want_seg=False):
@@ -135,7 +147,9 @@ class DeviceDecode:
     def nms(self, req, total, rows=None):
         """t3d_detect_nms over the first `total` rows (the rest pad a last batch), on the corners and scores where the decode wrote them;
         `fetch` then brings keep / suppressed_by back with the records.  rows: the detections that take part (default: all); the others
-        are listed in no group, so they suppress nothing and come back as kept.  -> the DeviceNms that holds them."""
+        are listed in no group, so they suppress nothing and come back as kept.  With req.fuse, t3d_detect_fuse follows directly on the
+        same buffers (a row in no group neither votes nor is fused) and `fetch` hands out its label / corners.  -> the DeviceNms that
+        holds them."""
         if len(req.image_ids) != total:
             raise ValueError('%d image ids for %d detections' % (len(req.image_ids), total))
         if rows is None:
@@ -151,6 +165,10 @@ class DeviceDecode:
             score = self.sec['score'].view(-1)
         self.nms_out = NMS.DeviceNms(self.rt)
         self.nms_out.run(self.sec['corners'], score, offsets, members, req.threshold, req.metric)
+        if req.fuse:
+            weight = score if req.score == 'prob' else torch.exp(score)
+            self.fuse_out = NMS.DeviceFuse(self.rt)
+            self.fuse_out.run(self.nms_out, self.sec['label'], self.sec['corners'], weight, req.vote_threshold)
         return self.nms_out
 
     def fetch(self):
@@ -166,6 +184,11 @@ class DeviceDecode:
         if self.nms_out is not None:
             out['keep'] = self.nms_out.keep[:n].cpu().numpy().astype(bool)
             out['suppressed_by'] = self.nms_out.suppressed_by[:n].cpu().numpy().astype(np.int64)
+        if self.fuse_out is not None:
+            out['raw_label'], out['raw_corners'] = out['label'], out['corners']
+            out['label'] = self.fuse_out.label[:n].cpu().numpy().astype(np.float64)
+            out['corners'] = self.fuse_out.corners[:n].cpu().numpy().astype(np.float64).reshape(n, 8, 3)
+            out['n_votes'] = self.fuse_out.n_votes[:n].cpu().numpy().astype(np.int64)
         if self.consistency is not None:
             out.update({k: v for k, v in self.consistency.items() if k in Decoded.OPTIONAL})
         return Decoded(**out), (None if self.seg is None else self.seg.cpu().numpy())
@@ -195,6 +218,7 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
     padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
     copied back; `.decoded.keep` / `.suppressed_by` hold its answer (None without it).  Nothing is removed here: the callers drop the rows.
+    With nms.fuse, t3d_detect_fuse follows it and `.decoded.label` / `.corners` hold the fused boxes (Decoded).
     consistency (ConsistencyRequest, decode='device' only): t3d_detect_consistency follows every batch's decode on the points the network
     read, the logits, the corners just written and the batch's rotation angles; `.decoded.reproj_iou`, `.n_mask`, ... `.accept` hold what
     it measured.  Its outputs are copied back before the NMS groups are built: a detection below a threshold of the request is listed
@@ -269,6 +293,14 @@ def write_detection_results(result_dir, test_classes, predictions, class_names):
         f.close()
 
 
+def fused_note(d):
+    """The tail of the NMS log line of a run that fused: how many kept boxes changed, from how many votes ('' without a fusion)."""
+    if d.n_votes is None:
+        return ''
+    v = d.n_votes[d.n_votes > 0]
+    return ', fused %d boxes from %d votes' % (len(v), int(v.sum()))
+
+
 def kept_predictions(predictions, d):
     """The 14-list and the records `d` of the same detections without the rows t3d_detect_nms suppressed (d.keep)."""
     rows = np.nonzero(d.keep)[0]
@@ -304,12 +336,13 @@ def device_decode_driver(FLAGS):
         req = None
         if getattr(FLAGS, 'nms_iou', None) is not None:
             ds = source.ds
-            req = NmsRequest(FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob)
+            req = NmsRequest(FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob,
+                             fuse=getattr(FLAGS, 'nms_fuse', False), vote_threshold=getattr(FLAGS, 'nms_fuse_iou', None))
         res = inference(sess, ops, pc, one_hot_vec, batch_size, decode='device', want_seg=source is None or bool(FLAGS.output), nms=req, **kw)
         if req is not None:
             log = run.get('log') or print
             log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
-                % (req.metric, req.threshold, req.score, int(res.decoded.keep[:ds.F].sum()), ds.F))
+                % (req.metric, req.threshold, req.score, int(res.decoded.keep[:ds.F].sum()), ds.F) + fused_note(res.decoded[slice(0, ds.F)]))
         run['decoded'] = res.decoded[slice(0, source.ds.F if source is not None else len(res.decoded))]      # without the padding
         seg = res[0] if res[0] is not None else np.full(len(res.decoded), None)      # (no --output: the masks stayed on the device)
         return (seg,) + tuple(res[1:])
