@@ -1748,6 +1748,105 @@ typedef struct {
 #define T3D_V2_SIZE_detect_fuse_args 128
 int t3d_detect_fuse(const t3d_detect_fuse_args* args, t3d_stream_t stream);
 
+/* ---- Threshold sweep, part 1: t3d_detect_nms for many configurations in one call (csrc/nms_sweep.hip; nms.DeviceNmsSweep, detect
+ *      --sweep) ----
+ * Choosing --nms_iou and the --min_* thresholds means scoring a grid of a few hundred configurations, and nothing up to the decoded
+ * boxes depends on them.  n, n_groups, metric, corners, score, group_offsets, members and max_group are those of t3d_detect_nms, under
+ * the same contract; the groups list every candidate box.  A configuration m of the M given is
+ *   config_threshold[m]    an index into thresholds[0 .. n_thresholds-1], or -1: no suppression.  Any other value is no
+ *                          configuration: its keep row and its n_kept are 0;
+ *   listed[m, box] != 0    the boxes that take part in it (rows listed_stride >= n bytes apart); listed == NULL: every box, in every
+ *                          configuration.
+ *   keep[m, 0 .. n)        byte for byte what t3d_detect_nms writes into a zero-filled `keep` when it is called with the threshold
+ *                          thresholds[config_threshold[m]] and every group restricted to its boxes with listed[m, box] != 0 (rows
+ *                          keep_stride >= n bytes apart; the bytes of a row past n are not touched).  The order of a restricted group is
+ *                          the order of the whole group with the other boxes left out, so the order is computed once.  With
+ *                          config_threshold[m] == -1 a listed box of a group gets 1.  A box in no group, or not listed, gets 0.
+ *   n_kept[m]              the number of ones in row m, by integer sums and one integer atomic per wave.
+ * box3d_iou_corners runs once per (earlier, later) pair of a group, whatever M and n_thresholds are, by the call of t3d_detect_nms with
+ * the same argument order: the fp32 value that decides is the same value, so no configuration can differ from the single call by a
+ * rounding.  Per pair one bit in each of n_thresholds bit rows (IoU > thresholds[k], strictly; a NaN IoU sets none).
+ *   Empty input            n == 0, n_groups == 0 or max_group == 0: one launch that zeroes n_kept[0 .. M) and, where keep != NULL, the
+ *                          rows keep[m, 0 .. n): what t3d_detect_nms leaves of a zero-filled keep.  Only n_kept is required then.
+ *   Errors                 before anything is launched: T3D_ERR_SHAPE for max_group > T3D_DETECT_NMS_MAX_GROUP, M outside
+ *                          [1, T3D_SWEEP_MAX_CONFIGS], n_thresholds outside [1, T3D_NMS_SWEEP_MAX_THRESHOLDS]; T3D_ERR_ARG for n,
+ *                          n_groups or max_group < 0, an unknown metric, a NaN among thresholds[0 .. n_thresholds), a null n_kept /
+ *                          corners / score / group_offsets / members / config_threshold / keep / workspace, keep_stride or (with listed)
+ *                          listed_stride < n, a workspace smaller than T3D_DETECT_NMS_SWEEP_WORKSPACE_BYTES(n, max_group, n_thresholds)
+ *                          or not 8-byte aligned.
+ *   workspace              the sorted order of every group and n_thresholds bits per (earlier, later) pair of a group:
+ *                          ceil(max_group / 64) * n_thresholds 64-bit words per box.
+ * Four launches on `stream`: the rows are zeroed; the order (the kernel of t3d_detect_nms); the pair bits, one thread per (box, 64 later
+ * boxes); the walk, one launch for all (configuration, group) pairs with the configuration in the grid's y / z and the lanes of
+ * t3d_detect_nms's sweep per group, so a configuration's work is spread over as many workgroups as the single call's is.  No allocation,
+ * no host synchronisation; the only atomics are integer additions, so equal inputs give equal bytes. */
+#define T3D_NMS_SWEEP_MAX_THRESHOLDS 16
+#define T3D_SWEEP_MAX_CONFIGS 65536
+#define T3D_DETECT_NMS_SWEEP_WORKSPACE_BYTES(n, max_group, n_thresholds) \
+  ((((uint64_t)(n) + 1u) / 2u) * 8u + (uint64_t)(n) * ((((uint64_t)(max_group)) + 63u) / 64u) * (uint64_t)(n_thresholds) * 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_nms_sweep_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_groups; int metric;
+  const float* corners;            /* [n,8,3], as for t3d_detect_nms */
+  const float* score;              /* [n] */
+  const int32_t* group_offsets;    /* [n_groups + 1] */
+  const int32_t* members;          /* [group_offsets[n_groups]] */
+  int max_group;
+  int n_thresholds;                /* K */
+  float thresholds[16];            /* the first K are read (T3D_NMS_SWEEP_MAX_THRESHOLDS entries) */
+  int M;
+  int listed_stride;
+  int keep_stride;
+  const int32_t* config_threshold; /* [M] device: -1 or an index into thresholds */
+  const uint8_t* listed;           /* [M, listed_stride] device, or NULL */
+  void* workspace;
+  uint64_t workspace_bytes;
+  uint8_t* keep;                   /* [M, keep_stride] out */
+  int32_t* n_kept;                 /* [M] out */
+} t3d_detect_nms_sweep_args;
+#define T3D_V2_SIZE_detect_nms_sweep_args 184
+int t3d_detect_nms_sweep(const t3d_detect_nms_sweep_args* args, t3d_stream_t stream);
+
+/* ---- Threshold sweep, part 2: the official evaluation of one class for many subsets of its detections (csrc/sunrgbd_sweep.hip;
+ *      evaluate_sunrgbd.sweep_class, detect --sweep) ----
+ * `eval` is one class's evaluation exactly as t3d_sunrgbd_eval takes it, and every one of its outputs is written with the bytes
+ * t3d_sunrgbd_eval writes for the same input (the entry point calls it); eval->gt_difficult must be NULL.  Configuration m of the M
+ * given is the evaluation of the detections i with mask[m, det_index[i]] != 0 alone, in file order (det_index == NULL: column i; a
+ * column outside [0, mask_stride) selects nothing).  det_index lets one matrix over the detections of all classes -- the `keep` of
+ * t3d_detect_nms_sweep -- serve every class without a gather.  max_overlap and gt_idx of a detection do not depend on the other
+ * detections, and the stable order of a subset is the induced order, so per configuration:
+ *   a selected detection claims box gt_idx - 1 iff gt_idx > 0 and max_overlap >= eval->threshold; it is a true positive iff it also has
+ *   the smallest rank among the selected claimers of that box (an integer minimum, as the evaluation finds its first claimer); every
+ *   other selected detection is a false positive; an unselected detection counts in neither sum.
+ *   ap[m]       by the curve code that computes eval->ap, over the full order, with n_pos = G (integer cumulative sums, recall =
+ *               ctp / G, precision = ctp / (cfp + ctp), the VOC2011 envelope, the same fixed summation tree).  A row of ones therefore
+ *               gives the bytes of eval->ap.  P == 0, G == 0 or an empty row give 0.
+ *   n_det[m], n_tp[m], n_fp[m]   the selected detections, and the true and false positives among them.
+ * workspace: T3D_SUNRGBD_SWEEP_WORKSPACE_BYTES(M, G) bytes, 8-byte aligned, separate from eval->workspace (which is read): the first
+ * claimer's rank per (configuration, box).  Not read when G == 0.
+ * Three launches behind the evaluation's: the claims are cleared, made (one thread per configuration and detection), and the curves
+ * run one workgroup per configuration.  Nothing is allocated or synchronised with the host; the only atomics are integer minima, so
+ * equal inputs give equal bytes.
+ * T3D_ERR_ABI: a struct of another size (either one).  T3D_ERR_ARG: a NULL struct or output array, gt_difficult != NULL, a NULL mask or
+ * a mask_stride < P (< 1 with det_index) when P > 0, a workspace that is missing, too small or misaligned when G > 0, and whatever
+ * t3d_sunrgbd_eval refuses.  T3D_ERR_SHAPE: M outside [1, T3D_SWEEP_MAX_CONFIGS], and eval's shapes.  Nothing is launched then. */
+#define T3D_SUNRGBD_SWEEP_WORKSPACE_BYTES(M, G) ((uint64_t)(M) * (uint64_t)(G) * 4u + 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_sunrgbd_sweep_args) of the caller's header (see T3D_ABI_VERSION) */
+  int M;
+  const uint8_t* mask;             /* [M, mask_stride] device */
+  const int32_t* det_index;        /* [P] device: the column of detection i, or NULL for i */
+  int mask_stride;
+  void* workspace;
+  uint64_t workspace_bytes;
+  double* ap;                      /* [M] out */
+  int32_t* n_det;                  /* [M] out */
+  int32_t* n_tp;                   /* [M] out */
+  int32_t* n_fp;                   /* [M] out */
+} t3d_sunrgbd_sweep_args;
+#define T3D_V2_SIZE_sunrgbd_sweep_args 80
+int t3d_sunrgbd_eval_sweep(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_sweep_args* sweep, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

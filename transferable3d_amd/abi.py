@@ -453,6 +453,32 @@ def detect_fuse_workspace_bytes(n):
     return (n + 1) // 2 * 8 + n * 16
 
 
+NMS_SWEEP_MAX_THRESHOLDS = 16        # t3d.h T3D_NMS_SWEEP_MAX_THRESHOLDS
+SWEEP_MAX_CONFIGS = 65536            # t3d.h T3D_SWEEP_MAX_CONFIGS
+
+
+class DetectNmsSweepArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_groups', i32), ('metric', i32), ('corners', F), ('score', F), ('group_offsets', I),
+                ('members', I), ('max_group', i32), ('n_thresholds', i32), ('thresholds', f32 * NMS_SWEEP_MAX_THRESHOLDS), ('M', i32),
+                ('listed_stride', i32), ('keep_stride', i32), ('config_threshold', I), ('listed', U8), ('workspace', C.c_void_p),
+                ('workspace_bytes', C.c_uint64), ('keep', U8), ('n_kept', I)]
+
+
+def detect_nms_sweep_workspace_bytes(n, max_group, n_thresholds):
+    """t3d.h T3D_DETECT_NMS_SWEEP_WORKSPACE_BYTES"""
+    return (n + 1) // 2 * 8 + n * ((max_group + 63) // 64) * n_thresholds * 8
+
+
+class SunrgbdSweepArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('M', i32), ('mask', U8), ('det_index', I), ('mask_stride', i32), ('workspace', C.c_void_p),
+                ('workspace_bytes', C.c_uint64), ('ap', D), ('n_det', I), ('n_tp', I), ('n_fp', I)]
+
+
+def sunrgbd_sweep_workspace_bytes(M, G):
+    """t3d.h T3D_SUNRGBD_SWEEP_WORKSPACE_BYTES"""
+    return M * G * 4 + 8
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -567,6 +593,8 @@ ENTRY_POINTS = {
     't3d_render': [C.POINTER(RenderArgs), VP],
     't3d_detect_consistency': [C.POINTER(DetectConsistencyArgs), VP],
     't3d_detect_fuse': [C.POINTER(DetectFuseArgs), VP],
+    't3d_detect_nms_sweep': [C.POINTER(DetectNmsSweepArgs), VP],
+    't3d_sunrgbd_eval_sweep': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdSweepArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }

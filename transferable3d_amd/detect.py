@@ -7,6 +7,8 @@
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}] [--nms_fuse] [--nms_fuse_iou V]]
         [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
         [--consistency] [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] [--consistency_json FILE]
+        [--sweep [--sweep_nms_iou V ..] [--sweep_min_reproj_iou V ..] [--sweep_min_mask_in_box V ..] [--sweep_min_seg_box_iou V ..]
+                 [--sweep_json FILE] [--sweep_top N]]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -42,6 +44,15 @@ header, clips the reprojection), mask_in_box and seg_box_iou (the segmented poin
 --min_seg_box_iou (each implies --consistency) reject a detection below the threshold: it is absent from everything this module hands
 out, and it is rejected BEFORE --nms_iou runs -- it is listed in no NMS group, so a box the filter rejects cannot suppress a good one.
 Without these flags every output is byte for byte what it was.
+
+--sweep: which --nms_iou and --min_* to pass.  The pipeline runs once, without thresholds and without suppression (the consistency
+measures are taken iff a --sweep_min_* is given); then every combination of the values given -- numbers the flag of that name accepts, or
+the word off; an omitted flag is off -- is scored by the official AP of --test_on on the device (sweep.py: t3d_detect_nms_sweep computes
+each pair's IoU once for all of them, t3d_sunrgbd_eval_sweep the footprints, ranks and overlaps).  --nms_metric / --nms_score hold for
+every combination.  The log: the size of the grid, the baseline (everything off: the AP --official_eval prints for the plain run), the
+best --sweep_top rows (default 10) by mean AP with their per-class AP and the detections they keep, and `best: <the flags to pass>`;
+--sweep_json FILE takes every row.  No result files, pictures or other reports are written.  Box voting (--nms_fuse) moves the kept
+boxes, so its overlaps differ per combination: it is not swept.
 """
 import argparse
 import collections
@@ -53,7 +64,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
+from transferable3d_amd import consistency as CS, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -289,6 +300,7 @@ class Detector:
         # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there); with nms_fuse where t3d_detect_fuse wrote them: the fused
         # corners of a kept box, and copies of the decode's for every other one (so --vis_suppressed still shows the raw boxes)
         self.device_corners = res.device.sec['corners'] if res.device.fuse_out is None else res.device.fuse_out.corners
+        self.device_score = res.device.sec['score'].view(-1)             # [n] where the decode wrote them (what `sweep` ranks by for nms_score 'score')
         offered = ds.F
         if d.accept is not None:
             if self.log:
@@ -338,6 +350,40 @@ class Detector:
                     out[lo + s].append(self.record(name, box2d, prob, d, i))
                 i += 1
         return out
+
+    def sweep(self, scenes, detections, grid, dataset_dir, idx_list, test_on='AB', scene_ids=None, batch_scenes=16, threshold=0.25):
+        """Which thresholds to use: the scenes go through the pipeline once, as in `detect`, and every configuration of `grid`
+        (sweep.Grid) is scored by the official AP of the class set `test_on` against the label files of dataset_dir for the images
+        idx_list (ids, or the path of an index file) -> sweep.Result.  The detector must have been built without nms_iou and without
+        thresholds, and with consistency=True when the grid sweeps a min_* threshold."""
+        if len(scenes) != len(detections):
+            raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
+        scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
+        parts = [self.extract(scenes[lo:lo + batch_scenes], detections[lo:lo + batch_scenes], scene_ids[lo:lo + batch_scenes])
+                 for lo in range(0, len(scenes), batch_scenes)]
+        return self.sweep_parts(parts, grid, dataset_dir, idx_list, test_on, threshold)
+
+    def sweep_parts(self, parts, grid, dataset_dir, idx_list, test_on='AB', threshold=0.25):
+        """`sweep` on extracted parts (what `main` holds)."""
+        from transferable3d_amd import evaluate_sunrgbd as ES
+        import torch
+        if self.nms_iou is not None or any(t is not None for t in self.thresholds):
+            raise ValueError('a sweep starts from the plain run: the detector has nms_iou or a min_* threshold')
+        if grid.consistency and not self.consistency:
+            raise ValueError('the grid sweeps a min_* threshold: the detector needs consistency=True')
+        meta, d = self.decode_all(parts)
+        if d is None:
+            raise ValueError('no detections to sweep')
+        n, names = len(meta), [m[2] for m in meta]
+        if grid.score == 'prob':
+            score = torch.from_numpy(np.asarray([m[4] for m in meta], np.float32)).to(self.rt.device)
+        else:
+            score = self.device_score[:n]
+        held = ES.official_predictions(sorted(set(ES.CLASS_NAMES[test_on]) | set(names)), self.predictions(meta, d), names)
+        det_index = {c: np.nonzero(np.asarray([x == c for x in names], bool))[0].astype(np.int32) for c in ES.CLASS_NAMES[test_on]}
+        measures = {k: getattr(d, k) for k in CS.MEASURES} if grid.consistency else None
+        return SW.run(self.rt, grid, self.device_corners[:n], score, [m[1] for m in meta], [type2class[m[2]] for m in meta], measures, held,
+                      det_index, dataset_dir, idx_list, test_on, threshold)
 
     @staticmethod
     def record(name, box2d, prob, d, i):
@@ -401,15 +447,39 @@ def parser():
     p.add_argument('--vis_suppressed', action='store_true', help='--vis_dir: add the boxes --nms_iou dropped, in grey')
     CS.add_arguments(p)
     p.add_argument('--consistency_json', default=None, help='write one row per detection (rejected ones included) with its consistency measures here')
+    SW.add_arguments(p)
     return p
+
+
+def sweep_options(p, args):
+    """The sweep.Grid of parsed flags (None without --sweep); a parser error where they contradict."""
+    given = [f for f in SW.FLAGS if getattr(args, 'sweep_' + f) is not None]
+    if not args.sweep:
+        if given or args.sweep_json is not None or args.sweep_top is not None:
+            p.error('--sweep_* flags need --sweep')
+        return None
+    single = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'diagnose') if getattr(args, f)]
+    single += ['nms_fuse_iou'] if args.nms_fuse_iou is not None else []
+    if single:
+        p.error('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
+    if args.vis_dir or args.consistency_json:
+        p.error('--sweep writes no pictures and no per-detection report: it does not go with --vis_dir / --consistency_json')
+    if args.sweep_top is not None and args.sweep_top < 0:
+        p.error('--sweep_top must not be negative')
+    try:
+        return SW.Grid.from_args(args)
+    except ValueError as e:
+        p.error(str(e))
 
 
 def main(argv=None, rt=None, log=print):
     """Every flag this parser does not know is test_semisup's (--seed serves the extraction and the network alike)."""
     args, rest = parser().parse_known_args(argv)
     FLAGS = TS.build_flags(list(rest))
+    grid = sweep_options(parser(), args)
     try:
-        NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
+        if grid is None:
+            NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
         NMS.check_fuse_options(args.nms_iou, args.nms_fuse, args.nms_fuse_iou)
     except ValueError as e:
         parser().error(str(e))
@@ -423,15 +493,15 @@ def main(argv=None, rt=None, log=print):
         thresholds = CS.check_thresholds(args.min_reproj_iou, args.min_mask_in_box, args.min_seg_box_iou)
     except ValueError as e:
         parser().error(str(e))
-    consistency = args.consistency or any(t is not None for t in thresholds)
+    consistency = args.consistency or any(t is not None for t in thresholds) or (grid is not None and grid.consistency)
     if args.consistency_json and not consistency:
         parser().error('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
     try:
         vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None) if args.vis_dir else None
     except ValueError as e:
         parser().error(str(e))
-    det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=args.nms_metric,
-                   nms_score=args.nms_score, log=log, consistency=consistency, min_reproj_iou=thresholds[0], min_mask_in_box=thresholds[1],
+    det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=None if grid is not None else args.nms_metric,
+                   nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=thresholds[0], min_mask_in_box=thresholds[1],
                    min_seg_box_iou=thresholds[2], nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou)
     valid = set(int(line.rstrip()) for line in open(args.idx_path))
     det_id, det_type, det_box2d, det_prob = SD.read_det_folder(args.rgb_detection_path)
@@ -451,6 +521,14 @@ def main(argv=None, rt=None, log=print):
             for (idx, _), scene in zip(batch, scenes):
                 scene.update(scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist))
         parts.append(det.extract(scenes, [per_scene[idx] for idx, _ in batch], [idx for idx, _ in batch], vis=vis))
+    if grid is not None:
+        result = det.sweep_parts(parts, grid, args.dataset_dir, args.idx_path, args.test_on)
+        for line in result.lines(10 if args.sweep_top is None else args.sweep_top):
+            log(line)
+        if args.sweep_json:
+            result.write_json(args.sweep_json)
+            log('sweep of %d configurations written to %s' % (len(grid), args.sweep_json))
+        return result
     if vis is None and not args.consistency_json:
         meta, d = det.decode(parts)
     else:

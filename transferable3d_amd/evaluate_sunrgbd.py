@@ -25,6 +25,10 @@ and two boxes that both have zero volume overlap by 0 (MATLAB: 0 / 0).
 missed box into localised or not, and the AP the class would have if each kind of error were fixed -- the breakdown of Bolya et al.,
 "TIDE" (ECCV 2020) under this protocol's overlap, matching and AP (include/t3d.h has the rules).  Two lines per class follow its AP line
 and one the mean; without the flag nothing changes.
+
+`sweep_class` / `sweep` (t3d_sunrgbd_eval_sweep, csrc/sunrgbd_sweep.hip): the evaluation of one class for many subsets of its detections in
+one call -- footprints, ranks and overlaps once, the claims and the curve per subset -- which `detect --sweep` (sweep.py) scores a grid of
+post-processing thresholds with.
 """
 import argparse
 import ctypes as C
@@ -169,9 +173,11 @@ def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False, other=Non
     return fetch()
 
 
-def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None):
+def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None, sweep=None):
     """_eval_call in its three steps: packs and uploads the inputs (the one copy to the device) -> (launch: the entry point's launches
-    on the runtime's stream, fetch: the one copy back as host arrays).  tools/bench_sunrgbd_diagnose.py times `launch` alone."""
+    on the runtime's stream, fetch: the one copy back as host arrays).  tools/bench_sunrgbd_diagnose.py times `launch` alone.
+    sweep: (mask uint8 [M, stride] on the runtime's device, det_index [P] or None): one t3d_sunrgbd_eval_sweep call instead, and `fetch`
+    copies back its four [M] arrays alone ('ap', 'n_det', 'n_tp', 'n_fp')."""
     rt = _runtime(rt)
     P, G = len(det['confidence']), len(gt['image'])
     gimg = np.asarray(gt['image'], np.int32)
@@ -194,6 +200,10 @@ def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=
         cnt = np.where(hit, (offsets[1:] - offsets[:-1])[np.minimum(k, max(n_img - 1, 0))], 0) if n_img else np.zeros(P, np.int64)
         ov_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
         host_in['overlap_offsets'] = (np.int64, ov_off)
+    if sweep is not None and sweep[1] is not None:
+        if len(sweep[1]) != P:
+            raise ValueError('%d detections, %d columns in det_index' % (P, len(sweep[1])))
+        host_in['det_index'] = (np.int32, sweep[1])
     if other is not None:
         Go = len(other['image'])
         oimg = np.asarray(other['image'], np.int32)
@@ -243,6 +253,32 @@ def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=
     if want_overlaps and int(ov_off[-1]) == 0:
         a.overlaps, a.overlap_gt = None, None
     held = [d_in, d_out, d_ws]                 # what the argument structs point into lives as long as `launch` does
+    if sweep is not None:
+        mask = sweep[0]
+        M = int(mask.shape[0])
+        assert mask.dtype == torch.uint8 and mask.dim() == 2 and (mask.shape[1] <= 1 or mask.stride(1) == 1)
+        sw = _Packed()
+        for name, dt in (('ap', np.float64), ('n_det', np.int32), ('n_tp', np.int32), ('n_fp', np.int32)):
+            sw.add(name, dt, M)
+        d_sw = torch.zeros(max(sw.size, 8), dtype=torch.uint8, device=dev)
+        sws_bytes = abi.sunrgbd_sweep_workspace_bytes(M, G)
+        d_sws = torch.empty((sws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        w_ = lambda n, T: ptr(d_sw, sw, n, T)
+        s = abi.SunrgbdSweepArgs(M, abi.u8ptr(mask), i_('det_index', i32), int(mask.stride(0)) if M > 1 and mask.shape[1] > 0 else int(mask.shape[1]),
+                                 C.c_void_p(d_sws.data_ptr()), sws_bytes, w_('ap', dbl), w_('n_det', i32), w_('n_tp', i32), w_('n_fp', i32))
+        held += [d_sw, d_sws, mask]
+
+        def launch(held=held):
+            abi.check(rt.lib.t3d_sunrgbd_eval_sweep(C.byref(a), C.byref(s), rt.stream()), 't3d_sunrgbd_eval_sweep')
+
+        def fetch(held=held, evaluation=False):
+            host = d_sw.cpu().numpy()                                       # the one copy back (synchronises)
+            res = {name: sw.view(host, name).copy() for name in sw.fields}
+            if evaluation:                                                  # (the tests: what t3d_sunrgbd_eval itself wrote, a second copy)
+                host = d_out.cpu().numpy()
+                res['evaluation'] = {name: out.view(host, name).copy() for name in out.fields}
+            return res
+        return launch, fetch
     if other is None:
         def launch(held=held):
             abi.check(rt.lib.t3d_sunrgbd_eval(C.byref(a), rt.stream()), 't3d_sunrgbd_eval')
@@ -292,6 +328,44 @@ def _pr_curve_result(r, same):
     return {'apScore': float(r['ap'][0]), 'precision': r['precision'], 'recall': r['recall'], 'isTp': r['is_tp'] != 0, 'isFp': r['is_fp'] != 0,
             'isMissed': is_missed, 'gtAssignment': ga, 'maxOverlaps': r['max_overlap'][order], 'numOfgt': int(same.sum()),
             'gtIdxAll': r['gt_idx'][order].astype(np.int64), 'sortIdx': order}
+
+
+def sweep_class(classname, det, gt_all, masks, det_index=None, threshold=0.25, rt=None):
+    """compute_pr_curve_3d(classname, det', gt_all) for M subsets det' of the detections in one t3d_sunrgbd_eval_sweep call
+    (csrc/sunrgbd_sweep.hip): footprints, ranks and overlaps once, then the claims and the curve of every subset.  masks: uint8
+    [M, >= columns], NumPy (uploaded) or a tensor on the runtime's device -- the `keep` matrix of nms.DeviceNmsSweep as it lies;
+    det_index [P]: the column of detection i (None: i).  Subset m holds the detections whose column of row m is not 0, in file order.
+    -> {'ap' float64 [M], 'n_det', 'n_tp', 'n_fp' int32 [M]}: one upload of the class (plus the masks, where they come from the host)
+    and one copy back of the four arrays."""
+    rt = _runtime(rt)
+    same = np.array([c == classname for c in gt_all['classname']], bool) if 'classname' in gt_all else np.ones(len(gt_all['image']), bool)
+    if not torch.is_tensor(masks):
+        masks = torch.from_numpy(np.ascontiguousarray(np.asarray(masks) != 0, np.uint8)).to(rt.device)
+    if masks.dim() != 2 or not 1 <= masks.shape[0] <= abi.SWEEP_MAX_CONFIGS:
+        raise ValueError('masks is [M, columns] with 1 <= M <= %d' % abi.SWEEP_MAX_CONFIGS)
+    launch, fetch = _eval_prepare(det, select_boxes(gt_all, same), None, threshold, rt, sweep=(masks, det_index))
+    launch()
+    return fetch()
+
+
+def sweep(predictions, dataset_dir, idx_list, masks, det_index, test_on='AB', rt=None, threshold=0.25, gt_all=None):
+    """sweep_class over the classes of the set `test_on`: predictions {class: boxes} as `evaluate` takes them, masks [M, columns] shared by
+    all classes, det_index {class: the columns of its detections, or None}.  -> ({class: sweep_class's dictionary}, mean AP float64 [M]:
+    per configuration the mean over the classes, as `evaluate` forms it)."""
+    if test_on not in CLASS_NAMES:
+        raise ValueError("test_on is 'A', 'B' or 'AB'")
+    rt = _runtime(rt)
+    if gt_all is None:
+        gt_all = benchmark_groundtruth(dataset_dir, idx_list)
+    if not torch.is_tensor(masks):
+        masks = torch.from_numpy(np.ascontiguousarray(np.asarray(masks) != 0, np.uint8)).to(rt.device)
+    out = {}
+    for name in CLASS_NAMES[test_on]:
+        if name not in predictions:
+            raise KeyError('no predictions for class %s' % name)
+        out[name] = sweep_class(name, predictions[name], gt_all, masks, det_index.get(name), threshold, rt)
+    ap = np.ascontiguousarray(np.stack([out[c]['ap'] for c in CLASS_NAMES[test_on]], 1))      # [M, classes]: a row's mean is np.mean of its list
+    return out, np.mean(ap, axis=1)
 
 
 GT_STATES = ('claimed', 'localised', 'missed')              # gt_state 1, 2, 3 of t3d_sunrgbd_diagnose

@@ -7,6 +7,9 @@ The reference has no such step: nothing runs it unless it is asked for (detect -
 
 `DeviceFuse.run` (t3d_detect_fuse, csrc/fuse.hip; --nms_fuse) follows it on the same buffers: who is kept stays, and every kept box takes
 the weighted mean geometry of the boxes it suppressed -- several estimates of one object, which the suppression alone throws away.
+
+`DeviceNmsSweep.run` (t3d_detect_nms_sweep, csrc/nms_sweep.hip; detect --sweep) is `DeviceNms.run` for many configurations at once -- a
+threshold out of up to 16 and a subset of the boxes each -- with every pair's IoU computed once (sweep.py chooses thresholds with it).
 """
 import ctypes as C
 
@@ -170,3 +173,72 @@ class DeviceFuse:
     def relaunch(self):
         """The launches of the last `run` again, on the same buffers (tools/bench_detect_fuse.py times them)."""
         abi.check(self.rt.lib.t3d_detect_fuse(C.byref(self._args), self.rt.stream()), 't3d_detect_fuse')
+
+
+class DeviceNmsSweep:
+    """Workspace and outputs of t3d_detect_nms_sweep (csrc/nms_sweep.hip): t3d_detect_nms for M configurations in one call, every pair's
+    IoU computed once.  `run` launches on device tensors and owns keep [M, stride] and n_kept [M] until its next run."""
+
+    def __init__(self, rt):
+        self.rt = rt
+        self.workspace = self.keep = self.n_kept = None
+        self._held = ()
+
+    def run(self, corners, score, group_offsets, members, thresholds, config_threshold, listed=None, metric='3d'):
+        """corners [n, 8, 3] / [n, 24] fp32 and score [n] fp32 on the runtime's device; group_offsets, members: NumPy / lists, as for
+        DeviceNms.run; thresholds: the 1 .. 16 distinct IoU thresholds of the grid; config_threshold [M]: per configuration the index
+        of its threshold, or -1 for no suppression (NumPy / list: uploaded; or an int32 device tensor); listed: None (every box, in every
+        configuration) or a uint8 device tensor [M, >= n] whose row m says which boxes take part in configuration m.
+        -> (keep uint8 [M, n] -- a view of rows `stride` bytes apart, row m what DeviceNms.run answers for configuration m with the
+        unlisted boxes left out of the groups and 0 for a box that is in no group or not listed -- and n_kept int32 [M])."""
+        rt = self.rt
+        n = int(score.numel())
+        assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
+        assert corners.dtype == torch.float32 and score.dtype == torch.float32
+        go, mem = np.ascontiguousarray(group_offsets, np.int32), np.ascontiguousarray(members, np.int32)
+        n_groups = len(go) - 1
+        max_group = int(np.diff(go).max()) if n_groups > 0 else 0
+        if n_groups < 0 or go[0] != 0 or (n_groups > 0 and (np.diff(go).min() < 0 or go[-1] != len(mem))) or len(mem) > n:
+            raise ValueError('group_offsets / members are not the lists of groups_of')
+        if len(mem) and (mem.min() < 0 or mem.max() >= n):
+            raise ValueError('a member is not a box index of [0, %d)' % n)
+        thresholds = [float(t) for t in thresholds]
+        K = len(thresholds)
+        if not 1 <= K <= abi.NMS_SWEEP_MAX_THRESHOLDS:
+            raise ValueError('%d NMS thresholds: one call takes 1 to %d' % (K, abi.NMS_SWEEP_MAX_THRESHOLDS))
+        if torch.is_tensor(config_threshold):
+            d_ct = config_threshold
+            assert d_ct.dtype == torch.int32 and d_ct.is_contiguous()
+        else:
+            d_ct = torch.from_numpy(np.ascontiguousarray(config_threshold, np.int32).reshape(-1)).to(rt.device)
+        M = int(d_ct.numel())
+        if not 1 <= M <= abi.SWEEP_MAX_CONFIGS:
+            raise ValueError('%d configurations: one call takes 1 to %d' % (M, abi.SWEEP_MAX_CONFIGS))
+        listed_stride = 0
+        if listed is not None:
+            assert listed.dtype == torch.uint8 and listed.dim() == 2 and listed.shape[0] == M and listed.shape[1] >= n and listed.stride(1) == 1
+            listed_stride = int(listed.stride(0)) if M > 1 else int(listed.shape[1])
+        stride = max((n + 7) // 8 * 8, 8)                    # rows that start on 8 bytes are zeroed eight bytes at a time
+        if self.keep is None or self.keep.numel() < M * stride:
+            self.keep = torch.zeros(M * stride, dtype=torch.uint8, device=rt.device)      # (owned here, as DeviceNms's)
+        if self.n_kept is None or self.n_kept.numel() < M:
+            self.n_kept = torch.zeros(M, dtype=torch.int32, device=rt.device)
+        need = abi.detect_nms_sweep_workspace_bytes(n, max_group, K)
+        if self.workspace is None or self.workspace.numel() * 8 < need:
+            self.workspace = torch.zeros(max(need // 8, 1), dtype=torch.int64, device=rt.device)
+        d_go, d_mem = torch.from_numpy(go).to(rt.device), torch.from_numpy(mem if len(mem) else np.zeros(1, np.int32)).to(rt.device)
+        self._held = (corners, score, d_go, d_mem, d_ct, listed)            # alive until the launches have run
+        a = abi.DetectNmsSweepArgs(n, n_groups, abi.NMS_METRICS[metric], fptr(corners), fptr(score), iptr(d_go), iptr(d_mem), max_group, K)
+        for k, t in enumerate(thresholds):
+            a.thresholds[k] = t
+        a.M, a.listed_stride, a.keep_stride = M, listed_stride, stride
+        a.config_threshold, a.listed = iptr(d_ct), abi.u8ptr(listed)
+        a.workspace, a.workspace_bytes = C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 8
+        a.keep, a.n_kept = abi.u8ptr(self.keep), iptr(self.n_kept)
+        self._args = a
+        self.relaunch()
+        return self.keep[:M * stride].view(M, stride)[:, :n], self.n_kept[:M]
+
+    def relaunch(self):
+        """The launches of the last `run` again, on the same buffers (tools/bench_detect_sweep.py times them alone)."""
+        abi.check(self.rt.lib.t3d_detect_nms_sweep(C.byref(self._args), self.rt.stream()), 't3d_detect_nms_sweep')
