@@ -1748,6 +1748,76 @@ typedef struct {
 #define T3D_V2_SIZE_detect_fuse_args 128
 int t3d_detect_fuse(const t3d_detect_fuse_args* args, t3d_stream_t stream);
 
+/* ---- Test-time augmentation: the V decoded boxes of every detection -> one fused box and how well the views agree
+ *      (csrc/ensemble.hip; ensemble.DeviceEnsemble, detect --tta K [--tta_flip]) ----
+ * `detect` can send every frustum through the network V times -- each view on a point draw of its own, some mirrored by
+ * t3d_batch_assemble -- and t3d_detect_decode writes a label row per view.  This entry point runs once behind the last decode, before the
+ * consistency filter's rejection, t3d_detect_nms and t3d_detect_fuse: it brings the mirrored views back, measures how far the V boxes
+ * of a detection agree (stability under augmentation, the label-free criterion of semi-supervised detection) and writes their weighted
+ * mean around the view that agrees best with the others.  The reference has no such step; it is opt-in.  Per detection i < n:
+ *   View label     of a view v whose flip_mask bit is clear: label[v][i] as it stands.  Of a mirrored view: the box mirrored back across
+ *                  the vertical plane t3d_batch_assemble's flip used (x -> -x, heading -> pi - heading in the centre view, csrc/data.hip),
+ *                  in fp64 on the widened fp32 entries, every product and sum its own operation: a = rot_angle[i] (0 for NULL),
+ *                  c = cos a, s = sin a; x_c = tx*c - tz*s, z_c = tx*s + tz*c; tx' = -x_c*c + z_c*s, tz' = x_c*s + z_c*c;
+ *                  ry' = wrap((pi - ry) + 2*a) with wrap of t3d_detect_fuse; h, w, l and ty stay.  The three results are rounded to fp32
+ *                  once; everything below reads this fp32 view label (h, w, l, tx', ty, tz', ry').
+ *   Valid views    a view is valid when all 7 entries of its view label are finite (a non-finite entry of label[v][i] leaves at least
+ *                  one, so does a non-finite rot_angle in a mirrored view); m is their number.
+ *   Pair IoUs      for every pair of valid views u < v the fp32 box3d_iou_corners(k_u, k_v) of csrc/boxgeom_dev.h, u the first argument:
+ *                  the volume IoU for metric T3D_NMS_IOU3D, that of the ground rectangles for T3D_NMS_IOU2D.  Both corner sets are
+ *                  built from the view labels by the fp32 corner formula of t3d_detect_decode (quoted under corners_out of
+ *                  t3d_detect_fuse), box u at the translation (0, 0, 0) and box v at the fp32 differences of the two centres
+ *                  (tx_v - tx_u, (ty_v - h_v/2) - (ty_u - h_u/2), tz_v - tz_u): the IoU does not depend on where the pair lies, its fp32
+ *                  rounding does (csrc/fuse.hip), and here the value is a weight and an output.  A NaN IoU counts as 0 everywhere
+ *                  below.  IoU(x, y) below is the value of the pair (min(x, y), max(x, y)).
+ *   agreement      the mean, and min_iou the minimum, of the pair IoUs over all valid pairs: the sum is fp64 over (u, v) in
+ *                  lexicographic order, divided by the number of pairs and rounded to fp32 once.  Both are 0 for m < 2.
+ *   anchor         the medoid: the valid view whose mean IoU with the other valid views (fp64 sum in ascending view order, divided by
+ *                  m - 1) is largest, the lowest view on a tie -- so V = 2 anchors on view 0 whenever view 0 is valid.  The only valid
+ *                  view for m == 1; -1 for m == 0.
+ *   Voters         a valid view v != anchor votes iff IoU(anchor, v) > vote_threshold, strictly; n_votes[i] is their number, whatever
+ *                  their weights.
+ *   Fusion         Weights, Alignment, Fusion and Precision of t3d_detect_fuse with the anchor in the place of the kept box, on the
+ *                  view labels: w_a = s(weight[a][i]), w_v = s(weight[v][i]) * IoU(anchor, v); the quarter turn that aligns a voter is
+ *                  chosen on the view labels' headings; the fp64 sums run anchor first, then the voters in ascending view index; the 7
+ *                  results are rounded to fp32 once and corners_out[i] comes from the rounded label_out[i] by the decode's formula.
+ *   Unchanged      nothing is fused when there is no voter, or W is 0 or not finite.  Then, with the anchor view 0, and for m == 0:
+ *                  label_out[i] and corners_out[i] are byte copies of label[0][i] and corners0[i] (view 0 is never mirrored).  With another
+ *                  anchor: its fp32 view label and the corners the decode's formula builds from it.  So V == 1 is a byte copy with
+ *                  agreement 0, min_iou 0, anchor 0 (-1 for a non-finite label) and n_votes 0.
+ *   Errors         before anything is launched: T3D_ERR_SHAPE for V > T3D_DETECT_ENSEMBLE_MAX_VIEWS; T3D_ERR_ARG for n < 0, V < 1, an
+ *                  unknown metric, bit 0 or a bit at position V or above set in flip_mask, a vote_threshold that is NaN or outside
+ *                  [0, 1], a null pointer among label[0 .. V-1], weight[0 .. V-1], corners0 or the six outputs, a workspace smaller than
+ *                  T3D_DETECT_ENSEMBLE_WORKSPACE_BYTES(n, V) (or null where that is not 0) or not 8-byte aligned.  label[v] and
+ *                  weight[v] for v >= V are not looked at.  n == 0: T3D_OK without a launch, whatever the pointers and the workspace are.
+ *   workspace      one fp32 per (detection, pair), detection-major.
+ * The inputs are never written, the outputs are buffers of their own.  Two launches on `stream`: the first one thread per (detection,
+ * pair) -- every lane busy with one IoU, none walking 28 polygon clips in a row --, the second one thread per detection, which reads its
+ * V(V-1)/2 IoUs, picks the anchor, sums and writes.  No atomics, no allocation, no host synchronisation: a detection's outputs depend
+ * on its own rows only, and equal inputs give equal bytes. */
+#define T3D_DETECT_ENSEMBLE_MAX_VIEWS 8
+#define T3D_DETECT_ENSEMBLE_WORKSPACE_BYTES(n, V) ((((uint64_t)(n) * (uint64_t)((V) * ((V) - 1) / 2) + 1u) / 2u) * 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_ensemble_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int V; int metric;
+  const float* label[T3D_DETECT_ENSEMBLE_MAX_VIEWS];     /* per view [n,7] (h, w, l, tx, ty, tz, ry): what t3d_detect_decode wrote for it */
+  const float* weight[T3D_DETECT_ENSEMBLE_MAX_VIEWS];    /* per view [n]: what the view's vote counts */
+  uint32_t flip_mask;              /* bit v: view v was assembled mirrored; bit 0 clear */
+  float vote_threshold;            /* in [0, 1] */
+  const float* rot_angle;          /* [n] or NULL: the angle t3d_batch_assemble turned the frustum to its centre view by */
+  const float* corners0;           /* [n,8,3]: view 0's decoded corners (read for the byte copies only) */
+  void* workspace;
+  uint64_t workspace_bytes;
+  float* label_out;                /* [n,7] out */
+  float* corners_out;              /* [n,8,3] out */
+  float* agreement;                /* [n] out */
+  float* min_iou;                  /* [n] out */
+  int32_t* anchor;                 /* [n] out */
+  int32_t* n_votes;                /* [n] out */
+} t3d_detect_ensemble_args;
+#define T3D_V2_SIZE_detect_ensemble_args 232
+int t3d_detect_ensemble(const t3d_detect_ensemble_args* args, t3d_stream_t stream);
+
 /* ---- Threshold sweep, part 1: t3d_detect_nms for many configurations in one call (csrc/nms_sweep.hip; nms.DeviceNmsSweep, detect
  *      --sweep) ----
  * Choosing --nms_iou and the --min_* thresholds means scoring a grid of a few hundred configurations, and nothing up to the decoded

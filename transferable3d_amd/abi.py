@@ -453,6 +453,21 @@ def detect_fuse_workspace_bytes(n):
     return (n + 1) // 2 * 8 + n * 16
 
 
+DETECT_ENSEMBLE_MAX_VIEWS = 8        # t3d.h T3D_DETECT_ENSEMBLE_MAX_VIEWS
+
+
+class DetectEnsembleArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('V', i32), ('metric', i32), ('label', F * DETECT_ENSEMBLE_MAX_VIEWS),
+                ('weight', F * DETECT_ENSEMBLE_MAX_VIEWS), ('flip_mask', C.c_uint32), ('vote_threshold', f32), ('rot_angle', F), ('corners0', F),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('label_out', F), ('corners_out', F), ('agreement', F),
+                ('min_iou', F), ('anchor', I), ('n_votes', I)]
+
+
+def detect_ensemble_workspace_bytes(n, V):
+    """t3d.h T3D_DETECT_ENSEMBLE_WORKSPACE_BYTES"""
+    return (n * (V * (V - 1) // 2) + 1) // 2 * 8
+
+
 NMS_SWEEP_MAX_THRESHOLDS = 16        # t3d.h T3D_NMS_SWEEP_MAX_THRESHOLDS
 SWEEP_MAX_CONFIGS = 65536            # t3d.h T3D_SWEEP_MAX_CONFIGS
 
@@ -593,6 +608,7 @@ ENTRY_POINTS = {
     't3d_render': [C.POINTER(RenderArgs), VP],
     't3d_detect_consistency': [C.POINTER(DetectConsistencyArgs), VP],
     't3d_detect_fuse': [C.POINTER(DetectFuseArgs), VP],
+    't3d_detect_ensemble': [C.POINTER(DetectEnsembleArgs), VP],
     't3d_detect_nms_sweep': [C.POINTER(DetectNmsSweepArgs), VP],
     't3d_sunrgbd_eval_sweep': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdSweepArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],

@@ -96,8 +96,10 @@ def accept_of(reproj_iou, mask_in_box, seg_box_iou, thresholds):
     return accept, below
 
 
-def log_line(accept, below, thresholds):
+def log_line(accept, below, thresholds, extra=()):
+    """extra: (measure, threshold, how many lie below it) of further tests that reject where these do (ensemble.py: view_iou)."""
     parts = ['%s < %g: %d' % (m, t, below[name]) for name, m, t in zip(THRESHOLDS, MEASURES, thresholds) if t is not None]
+    parts += ['%s < %g: %d' % e for e in extra]
     return 'consistency: kept %d of %d (%s)' % (int(np.sum(accept)), len(accept), ', '.join(parts) if parts else 'no threshold')
 
 

@@ -491,7 +491,10 @@ class DeviceEvalSource:
     buffers.  `boxpc_perturb` (the BOXPC_* flags): followed by the Box-PC Fit sample generator, as BoxPCFitDataset does for its
     test split (train_boxpc.py:119-124)."""
 
-    def __init__(self, graph, n_frustums=None, seed=0, boxpc_perturb=None, dataset=None):
+    def __init__(self, graph, n_frustums=None, seed=0, boxpc_perturb=None, dataset=None, *, draw_seed=None, flip=False):
+        """draw_seed: the seed of the point draws where it is not `seed` (a further view of the same frustums, ensemble.py); flip: every
+        frustum is mirrored in its centre view -- t3d_batch_assemble's random_flip with an explicit draw of 1 for every slot.  The
+        defaults are the arguments this class always passed."""
         from .engine import Plan
         e = graph.engine
         self.g, self.B = graph, e.B
@@ -499,10 +502,20 @@ class DeviceEvalSource:
         self.ds.perm.copy_(torch.arange(self.ds.F, dtype=torch.int32))      # file order; the walk wraps around past the end
         self.counter = graph.rt.zeros(4)
         self.plan = Plan(graph.rt)
-        self.plan.add('t3d_batch_assemble', self.ds.assemble_args(graph.inputs, self.counter, e.B, e.rpf, e.C, seed=seed, random_flip=False,
-                                                                 random_shift=False))
+        self.seed, self.flip, self.boxpc_perturb = seed, bool(flip), boxpc_perturb
+        extra = {}
+        if flip:
+            aug = graph.rt.zeros(e.B, 3)
+            aug[:, 0] = 1.0
+            extra = dict(aug=aug)
+        self.plan.add('t3d_batch_assemble', self.ds.assemble_args(graph.inputs, self.counter, e.B, e.rpf, e.C, seed=seed if draw_seed is None else draw_seed,
+                                                                 random_flip=bool(flip), random_shift=False, **extra))
         if boxpc_perturb is not None:
             self.plan.add('t3d_boxpc_perturb', boxpc_perturb_args(graph.inputs, self.counter, e.B, boxpc_perturb, seed=seed ^ 0x5bd1e995))
+
+    def view(self, draw_seed, flip=False):
+        """A further view of the same frustums: the same batches on another draw of their points, mirrored or not."""
+        return DeviceEvalSource(self.g, seed=self.seed, boxpc_perturb=self.boxpc_perturb, dataset=self.ds, draw_seed=draw_seed, flip=flip)
 
     def frustums_of(self, i):
         """Indices (file order) of the frustums in batch i."""

@@ -7,6 +7,7 @@
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}] [--nms_fuse] [--nms_fuse_iou V]]
         [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
         [--consistency] [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] [--consistency_json FILE]
+        [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]]
         [--sweep [--sweep_nms_iou V ..] [--sweep_min_reproj_iou V ..] [--sweep_min_mask_in_box V ..] [--sweep_min_seg_box_iou V ..]
                  [--sweep_json FILE] [--sweep_top N]]
 
@@ -45,6 +46,17 @@ header, clips the reprojection), mask_in_box and seg_box_iou (the segmented poin
 out, and it is rejected BEFORE --nms_iou runs -- it is listed in no NMS group, so a box the filter rejects cannot suppress a good one.
 Without these flags every output is byte for byte what it was.
 
+--tta K (2..8): test-time augmentation (ensemble.py).  Every frustum goes through the network K times: view 0 is the run without the
+flag, view v redraws the frustum's points with a seed derived from (--seed, v), and with --tta_flip the odd views are mirrored in the
+centre view.  Behind the last decode one t3d_detect_ensemble call brings the mirrored boxes back, measures how far the K boxes of a
+detection overlap (view_iou: the mean pairwise IoU under --nms_metric, view_min_iou: the smallest) and writes their weighted mean around
+the view that agrees best with the others (weights: exp of a view's score, times its IoU with that anchor view; a view votes above
+--tta_vote_iou, default 0).  --nms_iou, --nms_fuse, the records, the result files and --vis_dir then work on the fused boxes.
+--min_view_iou A rejects a detection whose view_iou lies below A where the --min_* thresholds reject: before the NMS groups are built,
+and counted in the `consistency:` line.  Records, --vis_dir legends and --consistency_json rows gain view_iou, view_min_iou, views_voted
+and anchor_view; score, prob and the consistency measures stay those of view 0.  K views cost K passes of the network.  Without --tta
+every output is byte for byte what it was.  The views are not swept: --tta does not go with --sweep.
+
 --sweep: which --nms_iou and --min_* to pass.  The pipeline runs once, without thresholds and without suppression (the consistency
 measures are taken iff a --sweep_min_* is given); then every combination of the values given -- numbers the flag of that name accepts, or
 the word off; an omitted flag is off -- is scored by the official AP of --test_on on the device (sweep.py: t3d_detect_nms_sweep computes
@@ -64,7 +76,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -187,10 +199,12 @@ class Vis:
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
                 if d.n_votes is not None:
                     entry['votes'] = int(d.n_votes[r])
+                if d.view_iou is not None:
+                    entry.update(view_fields(d, r))
                 if d.reproj_iou is not None:
                     entry.update(consistency_fields(d, r, as_lists=True))
-                    if not d.accept[r]:
-                        entry['kind'] = 'rejected'
+                if d.accept is not None and not d.accept[r]:
+                    entry['kind'] = 'rejected'
                 legend['boxes'].append(entry)
         return [cam, bev], legend
 
@@ -202,12 +216,19 @@ def consistency_fields(d, i, as_lists=False):
             'mask_in_box': float(d.mask_in_box[i]), 'seg_box_iou': float(d.seg_box_iou[i]), 'flags': int(d.flags[i])}
 
 
+def view_fields(d, i):
+    """What a record (or a legend / JSON entry) says of how detection i's views agreed (detect --tta)."""
+    return {'view_iou': float(d.view_iou[i]), 'view_min_iou': float(d.view_min_iou[i]), 'views_voted': int(d.n_views_voted[i]),
+            'anchor_view': int(d.anchor_view[i])}
+
+
 class Detector:
     """The test_semisup inference graph, built once; `detect` runs scenes through it."""
 
     def __init__(self, FLAGS=None, model_path=None, boxpc_model_path=None, rt=None, type_whitelist=SD.TYPE_WHITELIST,
                  num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
-                 min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, **keywords):
+                 min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, tta=None, tta_flip=False,
+                 tta_vote_iou=None, min_view_iou=None, **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.
@@ -220,7 +241,11 @@ class Detector:
         implies nms_fuse.
         consistency: measure every detection with t3d_detect_consistency (consistency.py); min_reproj_iou / min_mask_in_box /
         min_seg_box_iou: None, or the value in [0, 1] below which a detection is rejected (any of them implies consistency) -- before
-        the suppression of nms_iou, in whose groups a rejected detection is not listed."""
+        the suppression of nms_iou, in whose groups a rejected detection is not listed.
+        tta: None, or the number of views 2..8 every frustum is run in (ensemble.py; module docstring); tta_flip: the odd views are
+        mirrored; tta_vote_iou: the IoU with the anchor view above which a view votes (default 0); min_view_iou: None, or the value in
+        [0, 1] below which a detection's view_iou rejects it, as the min_* thresholds do.  The last three need tta."""
+        self.tta, self.tta_flip, self.tta_vote_iou, self.min_view_iou = EN.check_options(tta, tta_flip, tta_vote_iou, min_view_iou)
         self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
         self.nms_fuse, self.nms_fuse_iou = NMS.check_fuse_options(self.nms_iou, nms_fuse, nms_fuse_iou)
         self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
@@ -291,24 +316,31 @@ class Detector:
                 index += [len(rows) + m[0] for m in p['meta']]
                 rows += list(p.get('calib', []))
             con = SI.ConsistencyRequest([m[3] for m in meta], rows, index, *self.thresholds)
+        views = None
+        if self.tta is not None:
+            views = EN.EnsembleRequest(EN.views_of(self.tta, self.tta_flip, FLAGS.seed), self.nms_metric, self.tta_vote_iou, self.min_view_iou)
         res = SI.inference(self.sess, self.ops, None, None, self.B, prefix=FLAGS.pred_prefix, use_boxpc_fit_prob=FLAGS.use_boxpc_fit_prob,
                            source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False,
                            nms=None if self.nms_iou is None else SI.NmsRequest(
                                self.nms_iou, self.nms_metric, self.nms_score, [m[1] for m in meta], [type2class[m[2]] for m in meta],
-                               [m[4] for m in meta], fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou), consistency=con)
+                               [m[4] for m in meta], fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou), consistency=con, views=views)
         d = res.decoded[slice(0, ds.F)]
         # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there); with nms_fuse where t3d_detect_fuse wrote them: the fused
         # corners of a kept box, and copies of the decode's for every other one (so --vis_suppressed still shows the raw boxes)
-        self.device_corners = res.device.sec['corners'] if res.device.fuse_out is None else res.device.fuse_out.corners
+        # (with tta, where t3d_detect_ensemble wrote them, unless a fusion followed)
+        self.device_corners = res.device.boxes()[1] if res.device.fuse_out is None else res.device.fuse_out.corners
         self.device_score = res.device.sec['score'].view(-1)             # [n] where the decode wrote them (what `sweep` ranks by for nms_score 'score')
         offered = ds.F
         if d.accept is not None:
             if self.log:
-                below = CS.accept_of(d.reproj_iou, d.mask_in_box, d.seg_box_iou, self.thresholds)[1]
-                self.log(CS.log_line(d.accept, below, self.thresholds))
+                below = CS.accept_of(d.reproj_iou, d.mask_in_box, d.seg_box_iou, self.thresholds)[1] if d.reproj_iou is not None else {}
+                extra = [] if self.min_view_iou is None else [('view_iou', self.min_view_iou, int((~(d.view_iou >= self.min_view_iou)).sum()))]
+                self.log(CS.log_line(d.accept, below, self.thresholds, extra))
             if not d.accept.all():                               # a rejected detection is dropped wherever a suppressed one is
                 offered = int(d.accept.sum())
                 d.keep = d.accept.copy() if d.keep is None else d.keep & d.accept
+        if views is not None and self.log:
+            self.log(EN.log_line(views, d))
         if self.nms_iou is not None and self.log:
             self.log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
                      % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), offered) + SI.fused_note(d))
@@ -327,7 +359,10 @@ class Detector:
         (consistency.py), and a detection below a threshold has no entry; a scene may carry 'image_wh' = (W, H), to which the
         reprojected rectangle is then clipped (without it: no clipping).
         With nms_fuse 'label' and 'corners' are the fused box and the records gain 'votes', the number of suppressed boxes that voted
-        (0: the box is what the decode wrote).  The consistency measures of a fused detection are those of its unfused box."""
+        (0: the box is what the decode wrote).  The consistency measures of a fused detection are those of its unfused box.
+        With tta 'label' and 'corners' are what t3d_detect_ensemble made of the views (and nms_fuse of that), the records gain
+        'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view', and a detection below min_view_iou has no entry; 'score' and the
+        consistency measures are those of view 0."""
         vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
@@ -369,6 +404,8 @@ class Detector:
         import torch
         if self.nms_iou is not None or any(t is not None for t in self.thresholds):
             raise ValueError('a sweep starts from the plain run: the detector has nms_iou or a min_* threshold')
+        if self.tta is not None:
+            raise ValueError('the views of tta are not swept: the detector has tta')
         if grid.consistency and not self.consistency:
             raise ValueError('the grid sweeps a min_* threshold: the detector needs consistency=True')
         meta, d = self.decode_all(parts)
@@ -390,6 +427,8 @@ class Detector:
         r = {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
         if d.n_votes is not None:
             r['votes'] = int(d.n_votes[i])
+        if d.view_iou is not None:
+            r.update(view_fields(d, i))
         if d.reproj_iou is not None:
             r.update(consistency_fields(d, i))
         return r
@@ -425,6 +464,8 @@ def write_consistency_json(path, meta, d):
                'n_mask': int(d.n_mask[i]), 'n_box': int(d.n_box[i]), 'n_both': int(d.n_both[i]), 'accepted': bool(d.accept[i]),
                'kept': bool(d.keep is None or d.keep[i])}
         row.update(consistency_fields(d, i, as_lists=True))
+        if d.view_iou is not None:
+            row.update(view_fields(d, i))
         rows.append(row)
     with open(path, 'w') as fh:
         json.dump(rows, fh, indent=1)
@@ -447,6 +488,7 @@ def parser():
     p.add_argument('--vis_suppressed', action='store_true', help='--vis_dir: add the boxes --nms_iou dropped, in grey')
     CS.add_arguments(p)
     p.add_argument('--consistency_json', default=None, help='write one row per detection (rejected ones included) with its consistency measures here')
+    EN.add_arguments(p)
     SW.add_arguments(p)
     return p
 
@@ -460,6 +502,7 @@ def sweep_options(p, args):
         return None
     single = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'diagnose') if getattr(args, f)]
     single += ['nms_fuse_iou'] if args.nms_fuse_iou is not None else []
+    single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
     if single:
         p.error('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
     if args.vis_dir or args.consistency_json:
@@ -481,6 +524,7 @@ def main(argv=None, rt=None, log=print):
         if grid is None:
             NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
         NMS.check_fuse_options(args.nms_iou, args.nms_fuse, args.nms_fuse_iou)
+        EN.check_options(args.tta, args.tta_flip, args.tta_vote_iou, args.min_view_iou)
     except ValueError as e:
         parser().error(str(e))
     from transferable3d_amd import evaluate_sunrgbd as ES
@@ -502,7 +546,8 @@ def main(argv=None, rt=None, log=print):
         parser().error(str(e))
     det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=None if grid is not None else args.nms_metric,
                    nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=thresholds[0], min_mask_in_box=thresholds[1],
-                   min_seg_box_iou=thresholds[2], nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou)
+                   min_seg_box_iou=thresholds[2], nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou, tta=args.tta, tta_flip=args.tta_flip,
+                   tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou)
     valid = set(int(line.rstrip()) for line in open(args.idx_path))
     det_id, det_type, det_box2d, det_prob = SD.read_det_folder(args.rgb_detection_path)
     per_scene = collections.OrderedDict()

@@ -81,10 +81,16 @@ class Decoded:
     With a fusion (NmsRequest(fuse=True)) label and corners hold what t3d_detect_fuse wrote -- for a kept box with voters the fused
     geometry, for every other box what the decode wrote -- raw_label / raw_corners what the decode wrote, and n_votes [n] the number of
     voters of a kept box (-1: suppressed; 0: nothing to fuse, or listed in no group); None without.  center, heading_cls, heading_res,
-    size_cls and size_res are NOT fused: they keep what the decode wrote and describe the raw box."""
+    size_cls and size_res are NOT fused: they keep what the decode wrote and describe the raw box.
+    With views (inference(views=...), ensemble.py) label and corners hold what t3d_detect_ensemble wrote (and, with a fusion, what
+    t3d_detect_fuse made of that: raw_label / raw_corners are then the ensemble's output); view_label [V,n,7] and view_score [V,n] what
+    the decode wrote per view, view_iou [n] the mean and view_min_iou [n] the smallest pairwise IoU of a detection's views, anchor_view
+    [n] the view the fused box was built around (-1: no view with a finite label) and n_views_voted [n] the views that voted beside it;
+    None without.  score, mask_count, the heads and the consistency measures stay those of view 0."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
     OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept',
-                'raw_label', 'raw_corners', 'n_votes')
+                'raw_label', 'raw_corners', 'n_votes', 'view_label', 'view_score', 'view_iou', 'view_min_iou', 'anchor_view', 'n_views_voted')
+    VIEW_MAJOR = ('view_label', 'view_score')              # [V, n, ...]: the detection is the second axis
 
     def __init__(self, **fields):
         for k in self.FIELDS:
@@ -98,7 +104,8 @@ class Decoded:
     def __getitem__(self, sel):
         """Rows `sel` (a slice or an index array)."""
         return Decoded(**{k: getattr(self, k)[sel] for k in self.FIELDS},
-                       **{k: getattr(self, k)[sel] for k in self.OPTIONAL if getattr(self, k) is not None})
+                       **{k: getattr(self, k)[:, sel] if k in self.VIEW_MAJOR else getattr(self, k)[sel]
+                          for k in self.OPTIONAL if getattr(self, k) is not None})
 
 
 class Predictions(list):
@@ -121,6 +128,9 @@ class DeviceDecode:
     nms_out = None
     fuse_out = None             # the DeviceFuse of `nms` with a request that fuses
     consistency = None          # what DeviceConsistency.fetch returned for these detections (inference(consistency=...))
+    ens_out = None              # the DeviceEnsemble of a run with views (`ensemble`); view_decodes: the DeviceDecode of every view, this one first
+    view_decodes = None
+    ens_accept = None           # [n] bool: view_iou >= the request's min_view_iou (None without that threshold)
 
     def __init__(self, rt, n, num_point, want_seg=False):
         self.rt, self.n, self.N = rt, n, num_point
@@ -144,8 +154,30 @@ class DeviceDecode:
                                  fptr(o['heading_res']), fptr(o['size_res']), fptr(o['label']), fptr(o['corners']))
         abi.check(self.rt.lib.t3d_detect_decode(C.byref(a), self.rt.stream()), 't3d_detect_decode')
 
+    def boxes(self):
+        """(label [n, 7], corners [n, 24]) on the device as the steps behind the decode read them: the ensemble's where views were run."""
+        if self.ens_out is not None:
+            return self.ens_out.label[:self.n], self.ens_out.corners[:self.n]
+        return self.sec['label'], self.sec['corners']
+
+    def ensemble(self, req, decodes, rot_angle=None):
+        """t3d_detect_ensemble over all rows: `decodes` are the DeviceDecode of the request's views (this one is view 0), a view's weight
+        is exp of its decoded score (what `nms` votes with for score='score'), rot_angle [n] the angle every frustum was turned by.
+        Copies the agreement back -- the one small copy in front of the group building, as the consistency measures' -- and
+        -> accept [n] bool (None without req.min_view_iou)."""
+        from .ensemble import DeviceEnsemble
+        assert decodes[0] is self and len(decodes) == len(req) and all(d.n == self.n for d in decodes)
+        self.view_decodes = list(decodes)
+        self.ens_out = DeviceEnsemble(self.rt)
+        weights = [torch.exp(d.sec['score'].view(-1)) for d in decodes]
+        self.ens_out.run([d.sec['label'] for d in decodes], weights, self.sec['corners'], req.flip_mask, rot_angle, req.vote_threshold, req.metric)
+        if req.min_view_iou is not None:
+            self.ens_accept = self.ens_out.agreement[:self.n].cpu().numpy().astype(np.float64) >= req.min_view_iou
+        return self.ens_accept
+
     def nms(self, req, total, rows=None):
-        """t3d_detect_nms over the first `total` rows (the rest pad a last batch), on the corners and scores where the decode wrote them;
+        """t3d_detect_nms over the first `total` rows (the rest pad a last batch), on the corners and scores where the decode wrote them
+        (the corners of `boxes`: with views, where the ensemble wrote them);
         `fetch` then brings keep / suppressed_by back with the records.  rows: the detections that take part (default: all); the others
         are listed in no group, so they suppress nothing and come back as kept.  With req.fuse, t3d_detect_fuse follows directly on the
         same buffers (a row in no group neither votes nor is fused) and `fetch` hands out its label / corners.  -> the DeviceNms that
@@ -164,11 +196,12 @@ class DeviceDecode:
         else:
             score = self.sec['score'].view(-1)
         self.nms_out = NMS.DeviceNms(self.rt)
-        self.nms_out.run(self.sec['corners'], score, offsets, members, req.threshold, req.metric)
+        label, corners = self.boxes()
+        self.nms_out.run(corners, score, offsets, members, req.threshold, req.metric)
         if req.fuse:
             weight = score if req.score == 'prob' else torch.exp(score)
             self.fuse_out = NMS.DeviceFuse(self.rt)
-            self.fuse_out.run(self.nms_out, self.sec['label'], self.sec['corners'], weight, req.vote_threshold)
+            self.fuse_out.run(self.nms_out, label, corners, weight, req.vote_threshold)
         return self.nms_out
 
     def fetch(self):
@@ -184,6 +217,14 @@ class DeviceDecode:
         if self.nms_out is not None:
             out['keep'] = self.nms_out.keep[:n].cpu().numpy().astype(bool)
             out['suppressed_by'] = self.nms_out.suppressed_by[:n].cpu().numpy().astype(np.int64)
+        if self.ens_out is not None:
+            e = self.ens_out
+            host = lambda t, dtype: t[:n].cpu().numpy().astype(dtype)
+            out['view_label'] = np.stack([host(d.sec['label'], np.float64) for d in self.view_decodes])
+            out['view_score'] = np.stack([host(d.sec['score'].view(-1), np.float64) for d in self.view_decodes])
+            out['label'], out['corners'] = host(e.label, np.float64), host(e.corners, np.float64).reshape(n, 8, 3)
+            out['view_iou'], out['view_min_iou'] = host(e.agreement, np.float64), host(e.min_iou, np.float64)
+            out['anchor_view'], out['n_views_voted'] = host(e.anchor, np.int64), host(e.n_votes, np.int64)
         if self.fuse_out is not None:
             out['raw_label'], out['raw_corners'] = out['label'], out['corners']
             out['label'] = self.fuse_out.label[:n].cpu().numpy().astype(np.float64)
@@ -191,6 +232,8 @@ class DeviceDecode:
             out['n_votes'] = self.fuse_out.n_votes[:n].cpu().numpy().astype(np.int64)
         if self.consistency is not None:
             out.update({k: v for k, v in self.consistency.items() if k in Decoded.OPTIONAL})
+        if self.ens_accept is not None:
+            out['accept'] = self.ens_accept if out.get('accept') is None else out['accept'] & self.ens_accept
         return Decoded(**out), (None if self.seg is None else self.seg.cpu().numpy())
 
 
@@ -213,7 +256,7 @@ def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
 
 
 def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
-              decode='host', want_seg=True, nms=None, consistency=None):
+              decode='host', want_seg=True, nms=None, consistency=None, views=None):
     """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
     padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
@@ -222,11 +265,18 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     consistency (ConsistencyRequest, decode='device' only): t3d_detect_consistency follows every batch's decode on the points the network
     read, the logits, the corners just written and the batch's rotation angles; `.decoded.reproj_iou`, `.n_mask`, ... `.accept` hold what
     it measured.  Its outputs are copied back before the NMS groups are built: a detection below a threshold of the request is listed
-    in no group, so a box the filter rejects cannot suppress a good one (its `keep` stays True; `accept` says it is rejected)."""
+    in no group, so a box the filter rejects cannot suppress a good one (its `keep` stays True; `accept` says it is rejected).
+    views (ensemble.EnsembleRequest, decode='device' with a `source` only): every batch is assembled, run and decoded once per view --
+    view 0 is `source` itself, view v its `source.view(seed, mirrored)` -- each into a DeviceDecode of its own; the consistency kernel
+    still follows view 0's decode.  After the last batch one t3d_detect_ensemble call fuses the views of every detection; the NMS, the
+    box voting and `.decoded.label` / `.corners` then read its output, `.decoded.view_*` / `.anchor_view` / `.n_views_voted` say what
+    it found (Decoded), and a detection whose view_iou lies below views.min_view_iou is rejected as one below a consistency threshold."""
     if decode == 'host' and nms is not None:
         raise ValueError("nms runs on the device-decoded boxes: decode='device'")
     if decode == 'host' and consistency is not None:
         raise ValueError("the consistency measures are taken on the device-decoded boxes: decode='device'")
+    if views is not None and (decode != 'device' or source is None):
+        raise ValueError("views are further draws of a device-resident source: decode='device' and a source")
     if decode == 'host':
         return TS.inference(sess, ops, pc, one_hot_vec, batch_size, prefix=prefix, use_boxpc_fit_prob=use_boxpc_fit_prob, source=source,
                             n_batches=n_batches, oracle_mask=oracle_mask)
@@ -248,8 +298,18 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
             raise ValueError('%d detections in the consistency request, %d decoded' % (len(consistency), total))
         con = DeviceConsistency(rt, n, npts, consistency)
         xyz = sess.g.inputs.pc                                       # [B * N, ld] where the network read the batch
+    decs, sources, rot_all = [dec], [source], None
+    if views is not None:
+        sources += [source.view(seed, flip) for seed, flip in views.views[1:]]
+        decs += [DeviceDecode(rt, n, npts, want_seg=False) for _ in views.views[1:]]
+        rot_all = rt.zeros(n)                                        # every batch's angles: the ensemble mirrors back with them
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
+        valid = max(0, min(batch_size, total - sl.start))
+        for v in range(len(sources) - 1, 0, -1):                     # view 0 last: the consistency kernel reads its points and logits
+            sources[v].load(i, labels=False)
+            sess.run([])
+            decs[v].launch(sl.start, batch_size, valid, logits, box, s1, delta, fit, rot)
         if source is not None:
             source.load(i, labels=False)
             sess.run([])
@@ -258,8 +318,9 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
             if oracle_mask is not None:
                 feed[ops['y_seg_pl']] = np.asarray(oracle_mask[sl], np.int32)
             sess.run([], feed_dict=feed)
-        valid = max(0, min(batch_size, total - sl.start))
         dec.launch(sl.start, batch_size, valid, logits, box, s1, delta, fit, rot)
+        if rot_all is not None:
+            rot_all[sl].copy_(rot.view(-1)[:batch_size])
         if con is not None:
             con.launch(sl.start, batch_size, valid, xyz, int(xyz.stride(0)), logits, dec.sec['corners'][sl.start:], rot)
     rows = None
@@ -267,6 +328,10 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
         dec.consistency = con.fetch()                                # (the one small copy back in front of the group building)
         if not dec.consistency['accept'][:total].all():
             rows = np.nonzero(dec.consistency['accept'][:total])[0]
+    if views is not None:
+        ok = dec.ensemble(views, decs, rot_all)
+        if ok is not None and not ok[:total].all():
+            rows = np.nonzero(ok[:total] if rows is None else ok[:total] & dec.consistency['accept'][:total])[0]
     if nms is not None:
         dec.nms(nms, total, rows=rows)
     d, seg = dec.fetch()
