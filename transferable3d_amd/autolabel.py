@@ -109,6 +109,7 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
         batch_scenes=16, workers=8):
     """The command (module text) with a detect.Detector built by the caller (its thresholds decide).  ids: scene ids, or the path of an
     index file.  -> the dict written to OUT/autolabel.json, plus '_records': one entry per offered object (not written)."""
+    from transferable3d_amd.detect import consistency_fields, scene_batches, view_fields
     if isinstance(ids, str):
         ids = [int(line.rstrip()) for line in open(ids) if line.strip()]
     classes = list(classes)
@@ -118,40 +119,33 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
     dataset = SD.sunrgbd_object(dataset_dir, 'training')
     lines = {}
 
-    def load(idx):
+    def read_lines(idx):
         with open(dataset._path('label_dimension', idx, 'txt')) as fh:
             lines[idx] = [line.rstrip() for line in fh if line.strip()]
-        return dataset.get_calibration(idx), dataset.get_depth(idx)
 
+    image_wh = (lambda path: CS.image_size(path) if os.path.exists(path) else None) if detector.consistency else None
     parts, offered = [], []
-    for batch in SD._scenes_in_batches(load, ids, batch_scenes, workers):
-        scenes, dets = [], []
-        for idx, (calib, depth) in batch:
-            scene = {'points': depth, 'Rtilt': calib.Rtilt, 'K': calib.K}
-            image = dataset._path('image', idx, 'jpg')
-            if detector.consistency and os.path.exists(image):
-                scene['image_wh'] = CS.image_size(image)
-            objs = [(k, SD.SUNObject3d(line)) for k, line in enumerate(lines[idx])]
-            take = [(k, o) for k, o in objs if o.classname in classes]
-            scenes.append(scene)
+    for batch, scenes in scene_batches(dataset, ids, batch_scenes, workers, image_wh=image_wh, also=read_lines):
+        dets = []
+        for idx in batch:
+            take = [(k, o) for k, o in enumerate(SD.SUNObject3d(line) for line in lines[idx]) if o.classname in classes]
             dets.append([(o.classname, o.box2d, 1.0) for _, o in take])
             offered.append((idx, take))
-        parts.append(detector.extract(scenes, dets, [idx for idx, _ in batch]))
+        parts.append(detector.extract(scenes, dets, batch))
     meta, d = detector.decode_all(parts)
     # the detections come back in the order they were offered, without those whose frustum held too few points
     records, i = [], 0
     for idx, take in offered:
         for k, o in take:
-            hit = i < len(meta) and meta[i][1] == idx and meta[i][2] == o.classname and np.array_equal(meta[i][3], o.box2d)
+            hit = i < len(meta) and meta[i].image == idx and meta[i].name == o.classname and np.array_equal(meta[i].box2d, o.box2d)
             r = {'image': idx, 'line': k, 'class': o.classname, 'box2d': o.box2d, 'detected': bool(hit), 'accepted': False}
             if hit:
                 r.update(accepted=bool(d.keep is None or d.keep[i]), label=d.label[i], corners=d.corners[i], row=i)
                 if d.reproj_iou is not None:
-                    r.update(reproj_iou=float(d.reproj_iou[i]), mask_in_box=float(d.mask_in_box[i]), seg_box_iou=float(d.seg_box_iou[i]),
-                             flags=int(d.flags[i]))
+                    fields = consistency_fields(d, i)
+                    r.update((k, fields[k]) for k in CS.MEASURES + ('flags',))
                 if d.view_iou is not None:
-                    r.update(view_iou=float(d.view_iou[i]), view_min_iou=float(d.view_min_iou[i]), views_voted=int(d.n_views_voted[i]),
-                             anchor_view=int(d.anchor_view[i]))
+                    r.update(view_fields(d, i))
                 if score_against_labels:
                     r['label_corners'] = label_corners(o)
                 i += 1
@@ -234,12 +228,13 @@ def parser():
 
 def parse(argv=None):
     """-> (this module's arguments, test_semisup's FLAGS of everything else); a threshold outside [0, 1] is an argument error."""
-    args, rest = parser().parse_known_args(argv)
+    p = parser()
+    args, rest = p.parse_known_args(argv)
     try:
         args.thresholds = CS.check_thresholds(args.min_reproj_iou, args.min_mask_in_box, args.min_seg_box_iou)
         EN.check_options(args.tta, args.tta_flip, args.tta_vote_iou, args.min_view_iou)
     except ValueError as e:
-        parser().error(str(e))
+        p.error(str(e))
     return args, TS.build_flags(list(rest))
 
 

@@ -65,6 +65,13 @@ every combination.  The log: the size of the grid, the baseline (everything off:
 best --sweep_top rows (default 10) by mean AP with their per-class AP and the detections they keep, and `best: <the flags to pass>`;
 --sweep_json FILE takes every row.  No result files, pictures or other reports are written.  Box voting (--nms_fuse) moves the kept
 boxes, so its overlaps differ per combination: it is not swept.
+
+Where things live: the stages behind the decode (views, consistency, the accept rule, NMS, box voting) and their order belong to
+semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
+boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
+`consistency:` / `tta:` / `nms` lines, semisup_infer.kept drops the rows that were not kept.  Here: what the host knows of a detection
+(`Detection`), the extraction, the requests, the records and reports, and `main`, which checks its own flags, lets `Detector` check the
+rest, and turns either's ValueError into an argument error in one place, before a model is built.
 """
 import argparse
 import collections
@@ -82,6 +89,8 @@ from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # no
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
 
 MIN_POINTS = 5
+# what the host knows of a detection: its scene's position in the extraction launch, the image id, the class name, the 2-D box, the confidence
+Detection = collections.namedtuple('Detection', 'scene image name box2d prob')
 
 
 def flags_from_keywords(**kw):
@@ -118,7 +127,7 @@ class Vis:
         if last_scene is None:
             return
         points, offsets = last_scene
-        for s in sorted(set(m[0] for m in part['meta'])):
+        for s in sorted(set(m.scene for m in part['meta'])):
             if self.taken >= self.max:
                 break
             p = points[int(offsets[s]):int(offsets[s + 1])]
@@ -130,14 +139,15 @@ class Vis:
             self.taken += 1
 
     def write(self, rt, parts, d, corners):
-        """parts as Detector.decode_all took them, d its Decoded (every detection in its place), corners the decode's device buffer
-        [n, 24].  -> the scene ids written."""
+        """parts as Detector.decode_all took them, d its Decoded (every detection in its place), corners [n, 24] the boxes on the device
+        after every stage of that run (Detector.stages.corners: with nms_fuse the fused corners of a kept box and copies of the unfused
+        ones for every other, so --vis_suppressed still shows the raw boxes).  -> the scene ids written."""
         os.makedirs(self.dir, exist_ok=True)
         todo, i = [], 0
         for p in parts:
             rows = {}
             for m in p['meta']:
-                rows.setdefault(m[0], []).append((i, m))
+                rows.setdefault(m.scene, []).append((i, m))
                 i += 1
             for s, rec in sorted(p.get('vis', {}).items()):
                 rec['rows'] = rows.get(s, [])
@@ -188,13 +198,13 @@ class Vis:
         for group, kind in ((dropped, 'suppressed'), (kept, 'kept')):              # the kept boxes lie over the suppressed ones
             if not group:
                 continue
-            colours = [RD.SUPPRESSED_COLOUR if kind == 'suppressed' else RD.class_colour(m[2]) for _, m in group]
+            colours = [RD.SUPPRESSED_COLOUR if kind == 'suppressed' else RD.class_colour(m.name) for _, m in group]
             for v in (cam, bev):
                 v.boxes(k3, colours, thickness=1 if kind == 'suppressed' else 2, index=[r for r, _ in group])
-            cam.rects([m[3] for _, m in group], colours, thickness=1)
+            cam.rects([m.box2d for _, m in group], colours, thickness=1)
             for (r, m), c in zip(group, colours):
-                entry = {'kind': kind, 'detection': local[r], 'class': m[2], 'prob': float(m[4]), 'score': float(d.score[r]),
-                         'box2d': [float(x) for x in m[3]], 'colour': byte(c), 'kept': kind == 'kept'}
+                entry = {'kind': kind, 'detection': local[r], 'class': m.name, 'prob': float(m.prob), 'score': float(d.score[r]),
+                         'box2d': [float(x) for x in m.box2d], 'colour': byte(c), 'kept': kind == 'kept'}
                 if kind == 'suppressed':
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
                 if d.n_votes is not None:
@@ -223,7 +233,9 @@ def view_fields(d, i):
 
 
 class Detector:
-    """The test_semisup inference graph, built once; `detect` runs scenes through it."""
+    """The test_semisup inference graph, built once; `detect` runs scenes through it.  `stages`: the semisup_infer.DeviceStages of the
+    last `decode_all` (None where it had no detection)."""
+    stages = None
 
     def __init__(self, FLAGS=None, model_path=None, boxpc_model_path=None, rt=None, type_whitelist=SD.TYPE_WHITELIST,
                  num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
@@ -275,7 +287,7 @@ class Detector:
                 if name not in self.whitelist or (self.classes is not None and name not in self.classes):
                     continue
                 jobs.append({'scene': s, 'box2d': np.asarray(box2d, np.float64), 'box3d': None, 'key': (scene_ids[s], o, 0), 'choice': None})
-                meta.append((s, scene_ids[s], name, np.asarray(box2d, np.float64), float(prob)))
+                meta.append(Detection(s, scene_ids[s], name, np.asarray(box2d, np.float64), float(prob)))
         want_scene = vis is not None and vis.taken < vis.max
         out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene)
         calib = [CS.calib_row(sc['Rtilt'], sc['K'], sc.get('image_wh')) for sc in scenes] if self.consistency else []
@@ -293,57 +305,44 @@ class Detector:
         """The network and t3d_detect_decode over the frustums of `parts` (in order) -> (meta, semisup_infer.Decoded); with nms_iou, of
         the detections t3d_detect_nms kept."""
         meta, d = self.decode_all(parts)
-        if d is None or d.keep is None:
-            return meta, d
-        rows = np.nonzero(d.keep)[0]
-        return [meta[i] for i in rows], d[rows]
+        d, meta = SI.kept(d, meta)
+        return meta, d
 
     def decode_all(self, parts):
         """`decode` with every detection in its place: the records say which ones t3d_detect_nms kept (Decoded.keep; None without nms_iou).
-        With thresholds, Decoded.accept says which ones passed them, and Decoded.keep is False for the others too."""
+        With thresholds, Decoded.accept says which ones passed them, and Decoded.keep is False for the others too.  `self.stages` holds
+        the run's semisup_infer.DeviceStages (None without a detection): its `corners` [n, 24] are the boxes on the device after every
+        stage that ran (what `Vis.write` draws and `sweep_parts` suppresses), its `score` [n] the decoded scores."""
         FLAGS = self.FLAGS
         meta = [m for p in parts for m in p['meta']]
+        self.stages = None
         if not meta:
             return meta, None
         live = [p for p in parts if len(p['keep'])]
-        ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live],
-                                          [type2class[m[2]] for m in meta])
+        classes = [type2class[m.name] for m in meta]
+        ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live], classes)
         source = DeviceEvalSource(self.ops['graph'], dataset=ds, seed=FLAGS.seed)
-        con = None
+        nms = con = views = None
+        if self.nms_iou is not None:
+            nms = SI.NmsRequest(self.nms_iou, self.nms_metric, self.nms_score, [m.image for m in meta], classes, [m.prob for m in meta],
+                                fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou)
         if self.consistency:
             rows, index = [], []
             for p in parts:                              # a part's meta names its scenes by their position in the part
-                index += [len(rows) + m[0] for m in p['meta']]
+                index += [len(rows) + m.scene for m in p['meta']]
                 rows += list(p.get('calib', []))
-            con = SI.ConsistencyRequest([m[3] for m in meta], rows, index, *self.thresholds)
-        views = None
+            con = SI.ConsistencyRequest([m.box2d for m in meta], rows, index, *self.thresholds)
         if self.tta is not None:
             views = EN.EnsembleRequest(EN.views_of(self.tta, self.tta_flip, FLAGS.seed), self.nms_metric, self.tta_vote_iou, self.min_view_iou)
         res = SI.inference(self.sess, self.ops, None, None, self.B, prefix=FLAGS.pred_prefix, use_boxpc_fit_prob=FLAGS.use_boxpc_fit_prob,
-                           source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False,
-                           nms=None if self.nms_iou is None else SI.NmsRequest(
-                               self.nms_iou, self.nms_metric, self.nms_score, [m[1] for m in meta], [type2class[m[2]] for m in meta],
-                               [m[4] for m in meta], fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou), consistency=con, views=views)
+                           source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False, nms=nms, consistency=con,
+                           views=views)
+        self.stages = res.device
         d = res.decoded[slice(0, ds.F)]
-        # [n, 24] where t3d_detect_decode wrote them (Vis.write reads them there); with nms_fuse where t3d_detect_fuse wrote them: the fused
-        # corners of a kept box, and copies of the decode's for every other one (so --vis_suppressed still shows the raw boxes)
-        # (with tta, where t3d_detect_ensemble wrote them, unless a fusion followed)
-        self.device_corners = res.device.boxes()[1] if res.device.fuse_out is None else res.device.fuse_out.corners
-        self.device_score = res.device.sec['score'].view(-1)             # [n] where the decode wrote them (what `sweep` ranks by for nms_score 'score')
-        offered = ds.F
-        if d.accept is not None:
-            if self.log:
-                below = CS.accept_of(d.reproj_iou, d.mask_in_box, d.seg_box_iou, self.thresholds)[1] if d.reproj_iou is not None else {}
-                extra = [] if self.min_view_iou is None else [('view_iou', self.min_view_iou, int((~(d.view_iou >= self.min_view_iou)).sum()))]
-                self.log(CS.log_line(d.accept, below, self.thresholds, extra))
-            if not d.accept.all():                               # a rejected detection is dropped wherever a suppressed one is
-                offered = int(d.accept.sum())
-                d.keep = d.accept.copy() if d.keep is None else d.keep & d.accept
-        if views is not None and self.log:
-            self.log(EN.log_line(views, d))
-        if self.nms_iou is not None and self.log:
-            self.log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
-                     % (self.nms_metric, self.nms_iou, self.nms_score, int(d.keep.sum()), offered) + SI.fused_note(d))
+        if self.log:
+            SI.report(self.log, res.device, d)
+        if d.accept is not None and not d.accept.all():          # a rejected detection is dropped wherever a suppressed one is
+            d.keep = d.accept.copy() if d.keep is None else d.keep & d.accept
         return meta, d
 
     def detect(self, scenes, detections, scene_ids=None, batch_scenes=16, vis_dir=None, vis_max=50, vis_gt=False, vis_suppressed=False):
@@ -377,12 +376,12 @@ class Detector:
         if d is None:
             return out
         if vis is not None:
-            vis.write(self.rt, parts, d, self.device_corners)
+            vis.write(self.rt, parts, d, self.stages.corners)
         i = 0
         for lo, p in zip(first, parts):
-            for s, _, name, box2d, prob in p['meta']:
+            for m in p['meta']:
                 if d.keep is None or d.keep[i]:
-                    out[lo + s].append(self.record(name, box2d, prob, d, i))
+                    out[lo + m.scene].append(self.record(m.name, m.box2d, m.prob, d, i))
                 i += 1
         return out
 
@@ -411,15 +410,15 @@ class Detector:
         meta, d = self.decode_all(parts)
         if d is None:
             raise ValueError('no detections to sweep')
-        n, names = len(meta), [m[2] for m in meta]
+        n, names = len(meta), [m.name for m in meta]
         if grid.score == 'prob':
-            score = torch.from_numpy(np.asarray([m[4] for m in meta], np.float32)).to(self.rt.device)
+            score = torch.from_numpy(np.asarray([m.prob for m in meta], np.float32)).to(self.rt.device)
         else:
-            score = self.device_score[:n]
+            score = self.stages.score[:n]
         held = ES.official_predictions(sorted(set(ES.CLASS_NAMES[test_on]) | set(names)), self.predictions(meta, d), names)
         det_index = {c: np.nonzero(np.asarray([x == c for x in names], bool))[0].astype(np.int32) for c in ES.CLASS_NAMES[test_on]}
         measures = {k: getattr(d, k) for k in CS.MEASURES} if grid.consistency else None
-        return SW.run(self.rt, grid, self.device_corners[:n], score, [m[1] for m in meta], [type2class[m[2]] for m in meta], measures, held,
+        return SW.run(self.rt, grid, self.stages.corners[:n], score, [m.image for m in meta], [type2class[m.name] for m in meta], measures, held,
                       det_index, dataset_dir, idx_list, test_on, threshold)
 
     @staticmethod
@@ -440,8 +439,8 @@ class Detector:
         if d is None:
             return SI.Predictions([None, None, [], [], [], [], [], [], [], [], [], [], [], None])
         p = SI.Predictions([None, None, [None] * n, list(d.center), list(d.heading_cls), list(d.heading_res), list(d.size_cls),
-                            list(d.size_res), [None] * n, [m[4] for m in meta],
-                            [type2class[m[2]] for m in meta], [m[1] for m in meta], [m[3] for m in meta], None])
+                            list(d.size_res), [None] * n, [m.prob for m in meta],
+                            [type2class[m.name] for m in meta], [m.image for m in meta], [m.box2d for m in meta], None])
         p.decoded = d
         return p
 
@@ -460,7 +459,7 @@ def write_consistency_json(path, meta, d):
     """One row per detection of a run, in detection order, the rejected and the suppressed ones included."""
     rows = []
     for i, m in enumerate(meta):
-        row = {'image': int(m[1]), 'class': m[2], 'box2d': [float(v) for v in m[3]], 'prob': float(m[4]), 'score': float(d.score[i]),
+        row = {'image': int(m.image), 'class': m.name, 'box2d': [float(v) for v in m.box2d], 'prob': float(m.prob), 'score': float(d.score[i]),
                'n_mask': int(d.n_mask[i]), 'n_box': int(d.n_box[i]), 'n_both': int(d.n_both[i]), 'accepted': bool(d.accept[i]),
                'kept': bool(d.keep is None or d.keep[i])}
         row.update(consistency_fields(d, i, as_lists=True))
@@ -493,61 +492,71 @@ def parser():
     return p
 
 
-def sweep_options(p, args):
-    """The sweep.Grid of parsed flags (None without --sweep); a parser error where they contradict."""
+def sweep_options(args):
+    """The sweep.Grid of parsed flags (None without --sweep); ValueError where they contradict."""
     given = [f for f in SW.FLAGS if getattr(args, 'sweep_' + f) is not None]
     if not args.sweep:
         if given or args.sweep_json is not None or args.sweep_top is not None:
-            p.error('--sweep_* flags need --sweep')
+            raise ValueError('--sweep_* flags need --sweep')
         return None
     single = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'diagnose') if getattr(args, f)]
     single += ['nms_fuse_iou'] if args.nms_fuse_iou is not None else []
     single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
     if single:
-        p.error('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
+        raise ValueError('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
     if args.vis_dir or args.consistency_json:
-        p.error('--sweep writes no pictures and no per-detection report: it does not go with --vis_dir / --consistency_json')
+        raise ValueError('--sweep writes no pictures and no per-detection report: it does not go with --vis_dir / --consistency_json')
     if args.sweep_top is not None and args.sweep_top < 0:
-        p.error('--sweep_top must not be negative')
-    try:
-        return SW.Grid.from_args(args)
-    except ValueError as e:
-        p.error(str(e))
+        raise ValueError('--sweep_top must not be negative')
+    return SW.Grid.from_args(args)
+
+
+def scene_batches(dataset, ids, batch_scenes=16, workers=8, image_wh=None, pictures=None, also=None):
+    """The scenes `ids` of a sunrgbd_object as `Detector.extract` takes them, loaded by `workers` threads one batch ahead -> per batch,
+    (its ids, [{'points', 'Rtilt', 'K'}]).  image_wh: None, or a function from the path of a scene's JPEG to its (W, H) (None: unknown)
+    for the scenes' 'image_wh'; pictures: None, or a function from a scene's id to what --vis_dir reads of it (`scene_pictures`; {} once
+    enough are drawn), asked as the batch is handed out; also: None, or a function of the id that is called where the scene is loaded."""
+    def load(idx):
+        if also is not None:
+            also(idx)
+        return dataset.get_calibration(idx), dataset.get_depth(idx)
+
+    for batch in SD._scenes_in_batches(load, ids, batch_scenes, workers):
+        scenes = []
+        for idx, (calib, depth) in batch:
+            scene = {'points': depth, 'Rtilt': calib.Rtilt, 'K': calib.K}
+            wh = None if image_wh is None else image_wh(dataset._path('image', idx, 'jpg'))
+            if wh is not None:
+                scene['image_wh'] = wh
+            if pictures is not None:
+                scene.update(pictures(idx))
+            scenes.append(scene)
+        yield [idx for idx, _ in batch], scenes
 
 
 def main(argv=None, rt=None, log=print):
     """Every flag this parser does not know is test_semisup's (--seed serves the extraction and the network alike)."""
-    args, rest = parser().parse_known_args(argv)
-    FLAGS = TS.build_flags(list(rest))
-    grid = sweep_options(parser(), args)
-    try:
-        if grid is None:
-            NMS.check_options(args.nms_iou, args.nms_metric, args.nms_score)
-        NMS.check_fuse_options(args.nms_iou, args.nms_fuse, args.nms_fuse_iou)
-        EN.check_options(args.tta, args.tta_flip, args.tta_vote_iou, args.min_view_iou)
-    except ValueError as e:
-        parser().error(str(e))
     from transferable3d_amd import evaluate_sunrgbd as ES
-    diagnose = ES.diagnose_options(parser(), args)
-    if diagnose is not None and not args.official_eval:
-        parser().error('--diagnose breaks down the score of --official_eval: it needs --official_eval')
-    if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
-        parser().error('--vis_gt / --vis_suppressed need --vis_dir')
-    try:
-        thresholds = CS.check_thresholds(args.min_reproj_iou, args.min_mask_in_box, args.min_seg_box_iou)
-    except ValueError as e:
-        parser().error(str(e))
-    consistency = args.consistency or any(t is not None for t in thresholds) or (grid is not None and grid.consistency)
-    if args.consistency_json and not consistency:
-        parser().error('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
-    try:
+    p = parser()
+    args, rest = p.parse_known_args(argv)
+    FLAGS = TS.build_flags(list(rest))
+    try:                                         # (Detector checks its options before it builds a model)
+        grid = sweep_options(args)
+        diagnose = ES.diagnose_options(p, args)
+        if diagnose is not None and not args.official_eval:
+            raise ValueError('--diagnose breaks down the score of --official_eval: it needs --official_eval')
+        if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
+            raise ValueError('--vis_gt / --vis_suppressed need --vis_dir')
+        consistency = args.consistency or any(getattr(args, t) is not None for t in CS.THRESHOLDS) or (grid is not None and grid.consistency)
+        if args.consistency_json and not consistency:
+            raise ValueError('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
         vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None) if args.vis_dir else None
+        det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=None if grid is not None else args.nms_metric,
+                       nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=args.min_reproj_iou,
+                       min_mask_in_box=args.min_mask_in_box, min_seg_box_iou=args.min_seg_box_iou, nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou,
+                       tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou)
     except ValueError as e:
-        parser().error(str(e))
-    det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=None if grid is not None else args.nms_metric,
-                   nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=thresholds[0], min_mask_in_box=thresholds[1],
-                   min_seg_box_iou=thresholds[2], nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou, tta=args.tta, tta_flip=args.tta_flip,
-                   tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou)
+        p.error(str(e))
     valid = set(int(line.rstrip()) for line in open(args.idx_path))
     det_id, det_type, det_box2d, det_prob = SD.read_det_folder(args.rgb_detection_path)
     per_scene = collections.OrderedDict()
@@ -555,17 +564,9 @@ def main(argv=None, rt=None, log=print):
         per_scene.setdefault(idx, []).append((det_type[d], det_box2d[d], det_prob[d]))
     ids = [i for i in per_scene if i in valid]
     dataset = SD.sunrgbd_object(args.dataset_dir, 'training')
-    load = lambda idx: (dataset.get_calibration(idx), dataset.get_depth(idx))
-    parts = []
-    for batch in SD._scenes_in_batches(load, ids, 16, 8):
-        scenes = [{'points': depth, 'Rtilt': calib.Rtilt, 'K': calib.K} for _, (calib, depth) in batch]
-        if consistency:
-            for (idx, _), scene in zip(batch, scenes):
-                scene['image_wh'] = CS.image_size(dataset._path('image', idx, 'jpg'))
-        if vis is not None and vis.taken < vis.max:
-            for (idx, _), scene in zip(batch, scenes):
-                scene.update(scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist))
-        parts.append(det.extract(scenes, [per_scene[idx] for idx, _ in batch], [idx for idx, _ in batch], vis=vis))
+    pictures = None if vis is None else (lambda idx: scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist) if vis.taken < vis.max else {})
+    parts = [det.extract(scenes, [per_scene[idx] for idx in batch], batch, vis=vis)
+             for batch, scenes in scene_batches(dataset, ids, image_wh=CS.image_size if consistency else None, pictures=pictures)]
     if grid is not None:
         result = det.sweep_parts(parts, grid, args.dataset_dir, args.idx_path, args.test_on)
         for line in result.lines(10 if args.sweep_top is None else args.sweep_top):
@@ -574,21 +575,15 @@ def main(argv=None, rt=None, log=print):
             result.write_json(args.sweep_json)
             log('sweep of %d configurations written to %s' % (len(grid), args.sweep_json))
         return result
-    if vis is None and not args.consistency_json:
-        meta, d = det.decode(parts)
-    else:
-        meta, d = det.decode_all(parts)
-        if args.consistency_json:
-            write_consistency_json(args.consistency_json, meta, d)
-            log('consistency measures of %d detections written to %s' % (len(meta), args.consistency_json))
-        if d is not None:
-            if vis is not None:
-                log('%d scenes drawn to %s' % (len(vis.write(det.rt, parts, d, det.device_corners)), args.vis_dir))
-            if d.keep is not None:
-                rows = np.nonzero(d.keep)[0]
-                meta, d = [meta[i] for i in rows], d[rows]
+    meta, d = det.decode_all(parts)
+    if args.consistency_json:                                    # the two reports that need every row, then the rows go
+        write_consistency_json(args.consistency_json, meta, d)
+        log('consistency measures of %d detections written to %s' % (len(meta), args.consistency_json))
+    if vis is not None and d is not None:
+        log('%d scenes drawn to %s' % (len(vis.write(det.rt, parts, d, det.stages.corners)), args.vis_dir))
+    d, meta = SI.kept(d, meta)
     predictions = det.predictions(meta, d)
-    names = [m[2] for m in meta]
+    names = [m.name for m in meta]
     log('%d detections of %d images' % (len(meta), len(ids)))
     if FLAGS.result_dir:
         SI.write_detection_results(FLAGS.result_dir, det.classes or sorted(set(names)), predictions, names)

@@ -14,6 +14,12 @@ here hands over to test_semisup's, so nothing that exists changes its numbers.
 overlaps a better-ranked kept box by more than T; the suppressed detections are absent from the 14-list, the result files and --evaluate.
 --nms_fuse [--nms_fuse_iou V] (with --nms_iou): t3d_detect_fuse follows on the same buffers; every kept box is written with the weighted
 mean geometry of the boxes it suppressed (nms.DeviceFuse).  Which boxes are kept, and every score, stay.
+
+What runs behind the decode, and in which order, is written down in one place: `DeviceStages`.  `inference` builds one from its requests
+(nms, consistency, views); per batch it decodes every view and then measures the consistency of view 0, after the last batch it runs
+the ensemble of the views, the accept rule, the suppression and the box voting, and fetches everything as one `Decoded`.  It holds the
+boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.  `DeviceDecode` is the buffers of
+t3d_detect_decode alone; `report` writes a run's log lines and `kept` drops the rows that were not kept, for every caller.
 """
 import contextlib
 import ctypes as C
@@ -27,6 +33,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transferable3d_amd import abi, nms as NMS, test_semisup as TS       # noqa: E402
 from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN         # noqa: E402
 from transferable3d_amd.consistency import ConsistencyRequest, DeviceConsistency      # noqa: E402
 from transferable3d_amd.constants import type2class                     # noqa: E402
 
@@ -114,7 +121,8 @@ class Predictions(list):
 
 
 class InferenceResult(tuple):
-    """The 7-tuple of `inference`; `.decoded` as above; `.device` the DeviceDecode whose buffers still hold the records on the device."""
+    """The 7-tuple of `inference`; `.decoded` as above; `.device` the DeviceStages of the run, whose buffers still hold the records on the
+    device: `.device.corners` [n, 24] are the boxes after every stage that ran, `.device.score` [n] the decoded scores."""
     decoded = None
     device = None
 
@@ -124,13 +132,6 @@ class DeviceDecode:
     comes back in two copies) and the launch of one batch of them."""
     WIDTH = (('score', 1), ('center', 3), ('heading_res', 1), ('size_res', 3), ('label', 7), ('corners', 24))
     INTS = ('mask_count', 'heading_cls', 'size_cls')
-
-    nms_out = None
-    fuse_out = None             # the DeviceFuse of `nms` with a request that fuses
-    consistency = None          # what DeviceConsistency.fetch returned for these detections (inference(consistency=...))
-    ens_out = None              # the DeviceEnsemble of a run with views (`ensemble`); view_decodes: the DeviceDecode of every view, this one first
-    view_decodes = None
-    ens_accept = None           # [n] bool: view_iou >= the request's min_view_iou (None without that threshold)
 
     def __init__(self, rt, n, num_point, want_seg=False):
         self.rt, self.n, self.N = rt, n, num_point
@@ -154,56 +155,6 @@ class DeviceDecode:
                                  fptr(o['heading_res']), fptr(o['size_res']), fptr(o['label']), fptr(o['corners']))
         abi.check(self.rt.lib.t3d_detect_decode(C.byref(a), self.rt.stream()), 't3d_detect_decode')
 
-    def boxes(self):
-        """(label [n, 7], corners [n, 24]) on the device as the steps behind the decode read them: the ensemble's where views were run."""
-        if self.ens_out is not None:
-            return self.ens_out.label[:self.n], self.ens_out.corners[:self.n]
-        return self.sec['label'], self.sec['corners']
-
-    def ensemble(self, req, decodes, rot_angle=None):
-        """t3d_detect_ensemble over all rows: `decodes` are the DeviceDecode of the request's views (this one is view 0), a view's weight
-        is exp of its decoded score (what `nms` votes with for score='score'), rot_angle [n] the angle every frustum was turned by.
-        Copies the agreement back -- the one small copy in front of the group building, as the consistency measures' -- and
-        -> accept [n] bool (None without req.min_view_iou)."""
-        from .ensemble import DeviceEnsemble
-        assert decodes[0] is self and len(decodes) == len(req) and all(d.n == self.n for d in decodes)
-        self.view_decodes = list(decodes)
-        self.ens_out = DeviceEnsemble(self.rt)
-        weights = [torch.exp(d.sec['score'].view(-1)) for d in decodes]
-        self.ens_out.run([d.sec['label'] for d in decodes], weights, self.sec['corners'], req.flip_mask, rot_angle, req.vote_threshold, req.metric)
-        if req.min_view_iou is not None:
-            self.ens_accept = self.ens_out.agreement[:self.n].cpu().numpy().astype(np.float64) >= req.min_view_iou
-        return self.ens_accept
-
-    def nms(self, req, total, rows=None):
-        """t3d_detect_nms over the first `total` rows (the rest pad a last batch), on the corners and scores where the decode wrote them
-        (the corners of `boxes`: with views, where the ensemble wrote them);
-        `fetch` then brings keep / suppressed_by back with the records.  rows: the detections that take part (default: all); the others
-        are listed in no group, so they suppress nothing and come back as kept.  With req.fuse, t3d_detect_fuse follows directly on the
-        same buffers (a row in no group neither votes nor is fused) and `fetch` hands out its label / corners.  -> the DeviceNms that
-        holds them."""
-        if len(req.image_ids) != total:
-            raise ValueError('%d image ids for %d detections' % (len(req.image_ids), total))
-        if rows is None:
-            offsets, members = NMS.groups_of(req.image_ids, req.class_ids)
-        else:
-            rows = np.asarray(rows, np.int64)
-            offsets, members = NMS.groups_of(req.image_ids[rows], req.class_ids[rows])
-            members = rows[members].astype(np.int32)
-        if req.score == 'prob':
-            score = self.rt.zeros(self.n)
-            score[:total] = torch.from_numpy(req.prob).to(self.rt.device)
-        else:
-            score = self.sec['score'].view(-1)
-        self.nms_out = NMS.DeviceNms(self.rt)
-        label, corners = self.boxes()
-        self.nms_out.run(corners, score, offsets, members, req.threshold, req.metric)
-        if req.fuse:
-            weight = score if req.score == 'prob' else torch.exp(score)
-            self.fuse_out = NMS.DeviceFuse(self.rt)
-            self.fuse_out.run(self.nms_out, label, corners, weight, req.vote_threshold)
-        return self.nms_out
-
     def fetch(self):
         """-> (Decoded, masks [n, N] uint8 or None): the copies back."""
         f, i = self.f.cpu().numpy().astype(np.float64), self.i.cpu().numpy().astype(np.int64)
@@ -214,27 +165,118 @@ class DeviceDecode:
         out['corners'] = out['corners'].reshape(n, 8, 3)
         for j, k in enumerate(self.INTS):
             out[k] = i[j * n:(j + 1) * n]
-        if self.nms_out is not None:
-            out['keep'] = self.nms_out.keep[:n].cpu().numpy().astype(bool)
-            out['suppressed_by'] = self.nms_out.suppressed_by[:n].cpu().numpy().astype(np.int64)
-        if self.ens_out is not None:
-            e = self.ens_out
-            host = lambda t, dtype: t[:n].cpu().numpy().astype(dtype)
-            out['view_label'] = np.stack([host(d.sec['label'], np.float64) for d in self.view_decodes])
-            out['view_score'] = np.stack([host(d.sec['score'].view(-1), np.float64) for d in self.view_decodes])
-            out['label'], out['corners'] = host(e.label, np.float64), host(e.corners, np.float64).reshape(n, 8, 3)
-            out['view_iou'], out['view_min_iou'] = host(e.agreement, np.float64), host(e.min_iou, np.float64)
-            out['anchor_view'], out['n_views_voted'] = host(e.anchor, np.int64), host(e.n_votes, np.int64)
-        if self.fuse_out is not None:
-            out['raw_label'], out['raw_corners'] = out['label'], out['corners']
-            out['label'] = self.fuse_out.label[:n].cpu().numpy().astype(np.float64)
-            out['corners'] = self.fuse_out.corners[:n].cpu().numpy().astype(np.float64).reshape(n, 8, 3)
-            out['n_votes'] = self.fuse_out.n_votes[:n].cpu().numpy().astype(np.int64)
-        if self.consistency is not None:
-            out.update({k: v for k, v in self.consistency.items() if k in Decoded.OPTIONAL})
-        if self.ens_accept is not None:
-            out['accept'] = self.ens_accept if out.get('accept') is None else out['accept'] & self.ens_accept
         return Decoded(**out), (None if self.seg is None else self.seg.cpu().numpy())
+
+
+class DeviceStages:
+    """The stages behind t3d_detect_decode of one `inference(decode='device')` run over `n` frustums, the first `total` of them real, and
+    the one place that says in which order they run.  Per batch (`launch`): the decode of every view, then -- behind view 0's -- the
+    consistency measures.  After the last batch (`finish`): the ensemble of the views, the accept rows, the suppression, the box
+    voting, and the one fetch of everything as a Decoded.
+
+    label [n, 7], corners [n, 24]: the boxes on the device as the stages so far left them -- a stage that rewrites boxes (the ensemble,
+    the box voting) reads them and puts its output in their place, so neither a later stage nor a caller asks which stage ran; score [n]:
+    where view 0's decode wrote it.  accept [n] bool (None: nothing was asked that could reject): the detections that miss no threshold
+    of the consistency request and do not lie below views.min_view_iou; below: how many of the real detections lie below each of these
+    thresholds (`report`)."""
+
+    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None):
+        if nms is not None and len(nms.image_ids) != total:
+            raise ValueError('%d image ids for %d detections' % (len(nms.image_ids), total))
+        if consistency is not None and len(consistency) != total:
+            raise ValueError('%d detections in the consistency request, %d decoded' % (len(consistency), total))
+        self.rt, self.n, self.total, self.nms_request, self.views = rt, n, total, nms, views
+        self.decodes = [DeviceDecode(rt, n, num_point, want_seg=want_seg and v == 0) for v in range(1 if views is None else len(views))]
+        self.consistency = None if consistency is None else DeviceConsistency(rt, n, num_point, consistency)
+        self.rot_angle = None if views is None else rt.zeros(n)      # every batch's angles: the ensemble mirrors back with them
+        sec = self.decodes[0].sec
+        self.label, self.corners, self.score = sec['label'], sec['corners'], sec['score'].view(-1)
+        self.accept, self.below = None, {}
+        self.measures = self.ensemble_out = self.nms_out = self.fuse_out = None
+
+    def launch(self, view, first, B, n_valid, heads, rot_angle=None, xyz=None):
+        """Behind the graph's run of one view of a batch (a batch's view 0 runs last): t3d_detect_decode on `heads` (`decode_sources`)
+        into the view's rows first .. first + B - 1 and, behind view 0's, t3d_detect_consistency on the points xyz [B * N, ld] the network
+        read, the logits and the corners just written."""
+        self.decodes[view].launch(first, B, n_valid, *heads, rot_angle)
+        if view == 0 and self.rot_angle is not None:
+            self.rot_angle[first:first + B].copy_(rot_angle.view(-1)[:B])
+        if view == 0 and self.consistency is not None:
+            self.consistency.launch(first, B, n_valid, xyz, int(xyz.stride(0)), heads[0], self.corners[first:], rot_angle)
+
+    def finish(self):
+        """After the last batch -> (Decoded, masks [n, N] uint8 or None)."""
+        if self.views is not None:
+            self.ensemble()
+        self.accept_rows()
+        if self.nms_request is not None:
+            self.nms()
+        return self.fetch()
+
+    def ensemble(self):
+        """t3d_detect_ensemble over all rows of the views' decodes: a view's weight is exp of its decoded score (what `nms` votes with
+        for score='score')."""
+        req, self.ensemble_out = self.views, EN.DeviceEnsemble(self.rt)
+        out = self.ensemble_out.run([d.sec['label'] for d in self.decodes], [torch.exp(d.sec['score'].view(-1)) for d in self.decodes],
+                                    self.corners, req.flip_mask, self.rot_angle, req.vote_threshold, req.metric)
+        self.label, self.corners = out[0], out[1]
+
+    def accept_rows(self):
+        """The one accept rule: a detection is rejected where it misses a threshold of the consistency request or its view_iou lies below
+        views.min_view_iou.  Copies the consistency outputs and the agreement back -- the small copies in front of the group building."""
+        total, masks = self.total, []
+        if self.consistency is not None:
+            m = self.measures = self.consistency.fetch()
+            masks.append(m['accept'])
+            # (the counts fetch returns take in the zero rows that pad a last batch; the report counts the real detections)
+            self.below = CS.accept_of(*(m[k][:total] for k in CS.MEASURES), self.consistency.thresholds)[1]
+        if self.views is not None and self.views.min_view_iou is not None:
+            masks.append(self.ensemble_out.agreement[:self.n].cpu().numpy().astype(np.float64) >= self.views.min_view_iou)
+            self.below['view_iou'] = int((~masks[-1][:total]).sum())
+        if masks:
+            self.accept = np.logical_and.reduce(masks)
+
+    def nms(self):
+        """t3d_detect_nms over the real rows, on the current corners.  A rejected detection is listed in no group, so it suppresses
+        nothing and comes back as kept (`accept` says it is rejected).  With a request that fuses, t3d_detect_fuse follows directly on the
+        same buffers (a row in no group neither votes nor is fused) and its output becomes the current boxes."""
+        req, total = self.nms_request, self.total
+        rows = np.arange(total) if self.accept is None else np.nonzero(self.accept[:total])[0]
+        offsets, members = NMS.groups_of(req.image_ids[rows], req.class_ids[rows])
+        score = self.score
+        if req.score == 'prob':
+            score = self.rt.zeros(self.n)
+            score[:total] = torch.from_numpy(req.prob).to(self.rt.device)
+        self.nms_out = NMS.DeviceNms(self.rt)
+        self.nms_out.run(self.corners, score, offsets, rows[members].astype(np.int32), req.threshold, req.metric)
+        if req.fuse:
+            self.fuse_out = NMS.DeviceFuse(self.rt)
+            out = self.fuse_out.run(self.nms_out, self.label, self.corners, score if req.score == 'prob' else torch.exp(score), req.vote_threshold)
+            self.label, self.corners = out[0], out[1]
+
+    def fetch(self):
+        """-> (Decoded, masks): the copies back of the decode's records and of what every stage that ran added to them (Decoded)."""
+        n = self.n
+        d, seg = self.decodes[0].fetch()
+        host = lambda t, dtype=np.float64: t[:n].cpu().numpy().astype(dtype)
+        if self.nms_out is not None:
+            d.keep, d.suppressed_by = host(self.nms_out.keep, bool), host(self.nms_out.suppressed_by, np.int64)
+        if self.ensemble_out is not None:
+            e = self.ensemble_out
+            d.view_label = np.stack([host(v.sec['label']) for v in self.decodes])
+            d.view_score = np.stack([host(v.sec['score'].view(-1)) for v in self.decodes])
+            d.label, d.corners = host(e.label), host(e.corners).reshape(n, 8, 3)
+            d.view_iou, d.view_min_iou = host(e.agreement), host(e.min_iou)
+            d.anchor_view, d.n_views_voted = host(e.anchor, np.int64), host(e.n_votes, np.int64)
+        if self.fuse_out is not None:
+            d.raw_label, d.raw_corners = d.label, d.corners
+            d.label, d.corners = host(self.label), host(self.corners).reshape(n, 8, 3)
+            d.n_votes = host(self.fuse_out.n_votes, np.int64)
+        for k, v in (self.measures or {}).items():
+            if k in Decoded.OPTIONAL:
+                setattr(d, k, v)
+        d.accept = self.accept
+        return d, seg
 
 
 def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
@@ -270,7 +312,8 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     view 0 is `source` itself, view v its `source.view(seed, mirrored)` -- each into a DeviceDecode of its own; the consistency kernel
     still follows view 0's decode.  After the last batch one t3d_detect_ensemble call fuses the views of every detection; the NMS, the
     box voting and `.decoded.label` / `.corners` then read its output, `.decoded.view_*` / `.anchor_view` / `.n_views_voted` say what
-    it found (Decoded), and a detection whose view_iou lies below views.min_view_iou is rejected as one below a consistency threshold."""
+    it found (Decoded), and a detection whose view_iou lies below views.min_view_iou is rejected as one below a consistency threshold.
+    The stages and their order are DeviceStages'; this function loads and runs the graph and says when a view of a batch is ready."""
     if decode == 'host' and nms is not None:
         raise ValueError("nms runs on the device-decoded boxes: decode='device'")
     if decode == 'host' and consistency is not None:
@@ -287,58 +330,29 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     else:
         assert pc.shape[0] % batch_size == 0
         n, npts = pc.shape[0], pc.shape[1]
-    rt = sess.g.rt
-    logits, box, s1, delta, fit = decode_sources(ops, prefix, use_boxpc_fit_prob)
-    dec = DeviceDecode(rt, n, npts, want_seg=want_seg)
+    heads = decode_sources(ops, prefix, use_boxpc_fit_prob)
     total = source.ds.F if source is not None else n                 # the frustums past it pad the last batch
     rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
-    con = None
-    if consistency is not None:
-        if len(consistency) != total:
-            raise ValueError('%d detections in the consistency request, %d decoded' % (len(consistency), total))
-        con = DeviceConsistency(rt, n, npts, consistency)
-        xyz = sess.g.inputs.pc                                       # [B * N, ld] where the network read the batch
-    decs, sources, rot_all = [dec], [source], None
-    if views is not None:
-        sources += [source.view(seed, flip) for seed, flip in views.views[1:]]
-        decs += [DeviceDecode(rt, n, npts, want_seg=False) for _ in views.views[1:]]
-        rot_all = rt.zeros(n)                                        # every batch's angles: the ensemble mirrors back with them
+    xyz = sess.g.inputs.pc if consistency is not None else None      # [B * N, ld] where the network read the batch
+    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views)
+    sources = [source] + ([] if views is None else [source.view(seed, flip) for seed, flip in views.views[1:]])
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
-        valid = max(0, min(batch_size, total - sl.start))
-        for v in range(len(sources) - 1, 0, -1):                     # view 0 last: the consistency kernel reads its points and logits
-            sources[v].load(i, labels=False)
-            sess.run([])
-            decs[v].launch(sl.start, batch_size, valid, logits, box, s1, delta, fit, rot)
-        if source is not None:
-            source.load(i, labels=False)
-            sess.run([])
-        else:
-            feed = {ops['pc_pl']: pc[sl], ops['one_hot_vec_pl']: one_hot_vec[sl]}
-            if oracle_mask is not None:
-                feed[ops['y_seg_pl']] = np.asarray(oracle_mask[sl], np.int32)
-            sess.run([], feed_dict=feed)
-        dec.launch(sl.start, batch_size, valid, logits, box, s1, delta, fit, rot)
-        if rot_all is not None:
-            rot_all[sl].copy_(rot.view(-1)[:batch_size])
-        if con is not None:
-            con.launch(sl.start, batch_size, valid, xyz, int(xyz.stride(0)), logits, dec.sec['corners'][sl.start:], rot)
-    rows = None
-    if con is not None:
-        dec.consistency = con.fetch()                                # (the one small copy back in front of the group building)
-        if not dec.consistency['accept'][:total].all():
-            rows = np.nonzero(dec.consistency['accept'][:total])[0]
-    if views is not None:
-        ok = dec.ensemble(views, decs, rot_all)
-        if ok is not None and not ok[:total].all():
-            rows = np.nonzero(ok[:total] if rows is None else ok[:total] & dec.consistency['accept'][:total])[0]
-    if nms is not None:
-        dec.nms(nms, total, rows=rows)
-    d, seg = dec.fetch()
+        for v in range(len(sources) - 1, -1, -1):                    # view 0 last: the consistency kernel reads its points and logits
+            if sources[v] is not None:
+                sources[v].load(i, labels=False)
+                sess.run([])
+            else:
+                feed = {ops['pc_pl']: pc[sl], ops['one_hot_vec_pl']: one_hot_vec[sl]}
+                if oracle_mask is not None:
+                    feed[ops['y_seg_pl']] = np.asarray(oracle_mask[sl], np.int32)
+                sess.run([], feed_dict=feed)
+            stages.launch(v, sl.start, batch_size, max(0, min(batch_size, total - sl.start)), heads, rot, xyz)
+    d, seg = stages.finish()
     res = InferenceResult((None if seg is None else seg.astype(np.int64), d.center, d.heading_cls, d.heading_res, d.size_cls, d.size_res,
                            d.score))
     res.decoded = d
-    res.device = dec
+    res.device = stages
     return res
 
 
@@ -358,20 +372,33 @@ def write_detection_results(result_dir, test_classes, predictions, class_names):
         f.close()
 
 
-def fused_note(d):
-    """The tail of the NMS log line of a run that fused: how many kept boxes changed, from how many votes ('' without a fusion)."""
-    if d.n_votes is None:
-        return ''
-    v = d.n_votes[d.n_votes > 0]
-    return ', fused %d boxes from %d votes' % (len(v), int(v.sum()))
+def report(log, stages, d):
+    """What a run says of its stages, one line each through `log` and in their order: `consistency:` (how many detections the accept rule
+    kept, how many lie below each threshold), `tta:` (the views) and `nms ...` (how many of the accepted detections were kept and, with
+    a fusion, how many kept boxes changed, from how many votes).  stages: the run's DeviceStages; d: the records of its real detections."""
+    if d.accept is not None:
+        con = stages.consistency
+        extra = [('view_iou', stages.views.min_view_iou, stages.below['view_iou'])] if 'view_iou' in stages.below else []
+        log(CS.log_line(d.accept, stages.below, con.thresholds if con is not None else (None, None, None), extra))
+    if stages.views is not None:
+        log(EN.log_line(stages.views, d))
+    req = stages.nms_request
+    if req is not None:
+        kept, offered = (d.keep, len(d)) if d.accept is None else (d.keep & d.accept, int(d.accept.sum()))
+        line = 'nms (%s IoU > %g, ranked by %s): kept %d of %d detections' % (req.metric, req.threshold, req.score, int(kept.sum()), offered)
+        if d.n_votes is not None:
+            v = d.n_votes[d.n_votes > 0]
+            line += ', fused %d boxes from %d votes' % (len(v), int(v.sum()))
+        log(line)
 
 
-def kept_predictions(predictions, d):
-    """The 14-list and the records `d` of the same detections without the rows t3d_detect_nms suppressed (d.keep)."""
+def kept(d, *lists):
+    """The records `d` (Decoded or None) and the per-detection lists that run beside them (None stays None) without the rows that were
+    not kept (d.keep) -> (d, *lists); as they are where nothing was asked for that drops a row."""
+    if d is None or d.keep is None:
+        return (d,) + lists
     rows = np.nonzero(d.keep)[0]
-    p = Predictions([l if l is None else [l[i] for i in rows] for l in predictions])
-    p.decoded = d[rows]
-    return p
+    return (d[rows],) + tuple(l if l is None else [l[i] for i in rows] for l in lists)
 
 
 @contextlib.contextmanager
@@ -386,15 +413,13 @@ def device_decode_driver(FLAGS):
 
     def attach(predictions):
         d = run.get('decoded')
-        if d is not None and d.keep is not None and len(predictions[3]) == len(d):        # drop what t3d_detect_nms suppressed
-            return kept_predictions(predictions, d)
-        p = Predictions(predictions)
-        p.decoded = d if d is None or d.keep is None else d[np.nonzero(d.keep)[0]]
+        if d is not None and len(predictions[3]) != len(d):       # the rows t3d_detect_nms suppressed are dropped already
+            lists, d = predictions, kept(d)[0]
+        else:
+            d, *lists = kept(d, *predictions)
+        p = Predictions(lists)
+        p.decoded = d
         return p
-
-    def kept_names(names):
-        d = run.get('decoded')
-        return names if d is None or d.keep is None else [names[i] for i in np.nonzero(d.keep)[0]]
 
     def infer(sess, ops, pc, one_hot_vec, batch_size, **kw):
         source = kw.get('source')
@@ -404,11 +429,8 @@ def device_decode_driver(FLAGS):
             req = NmsRequest(FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob,
                              fuse=getattr(FLAGS, 'nms_fuse', False), vote_threshold=getattr(FLAGS, 'nms_fuse_iou', None))
         res = inference(sess, ops, pc, one_hot_vec, batch_size, decode='device', want_seg=source is None or bool(FLAGS.output), nms=req, **kw)
-        if req is not None:
-            log = run.get('log') or print
-            log('nms (%s IoU > %g, ranked by %s): kept %d of %d detections'
-                % (req.metric, req.threshold, req.score, int(res.decoded.keep[:ds.F].sum()), ds.F) + fused_note(res.decoded[slice(0, ds.F)]))
-        run['decoded'] = res.decoded[slice(0, source.ds.F if source is not None else len(res.decoded))]      # without the padding
+        run['decoded'] = res.decoded[slice(0, res.device.total)]                     # without the padding
+        report(run.get('log') or print, res.device, run['decoded'])
         seg = res[0] if res[0] is not None else np.full(len(res.decoded), None)      # (no --output: the masks stayed on the device)
         return (seg,) + tuple(res[1:])
 
@@ -416,7 +438,7 @@ def device_decode_driver(FLAGS):
     saved = (TS.inference, TS.write_detection_results)
     TS.inference = infer
     TS.write_detection_results = lambda d, classes, predictions, names: write_detection_results(d, classes, attach(predictions),
-                                                                                                kept_names(names))
+                                                                                                kept(run.get('decoded'), names)[1])
     eval_det.evaluate_predictions = lambda predictions, *a, **kw: real_evaluate(attach(predictions), *a, **kw)
     attach.run = run
     try:
