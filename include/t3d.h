@@ -1917,6 +1917,76 @@ typedef struct {
 #define T3D_V2_SIZE_sunrgbd_sweep_args 80
 int t3d_sunrgbd_eval_sweep(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_sweep_args* sweep, t3d_stream_t stream);
 
+/* ---- Bootstrap over images, part 1: the resampling weights (csrc/sunrgbd_bootstrap.hip; bootstrap.Weights) ----
+ * weights[r, c], r < R, c < n_images: how often column c is drawn when replicate r draws n_images columns with replacement.  Draw d of
+ * replicate r is, in unsigned 64-bit arithmetic (wrapping),
+ *     key = (((uint64)seed << 32) | (uint64)r) * 0x9E3779B97F4A7C15 + ((uint64)d + 1) * 0xD6E8FEB86659FD93
+ *     u   = mix_u32(key)                     the finaliser of data.hip / frustum.hip:  x ^= x >> 33; x *= 0xff51afd7ed558ccd;
+ *                                            x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33; u = (uint32)(x >> 16)
+ *     column = ((uint64)u * (uint64)n_images) >> 32
+ * The columns n_images .. stride-1 of a row are written 0.  Two launches: the matrix is cleared, then one thread per (replicate, draw)
+ * counts with an integer atomic add -- the only atomics, so equal inputs give equal bytes, and every row sums to n_images.  Nothing is
+ * allocated or synchronised with the host.
+ * T3D_ERR_ABI: a struct of another size.  T3D_ERR_ARG: a NULL struct or matrix, stride < n_images.  T3D_ERR_SHAPE: R outside
+ * [1, T3D_BOOTSTRAP_MAX_REPLICATES], n_images < 1.  Nothing is launched then. */
+#define T3D_BOOTSTRAP_MAX_REPLICATES (1 << 16)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_bootstrap_weights_args) of the caller's header (see T3D_ABI_VERSION) */
+  uint32_t seed;
+  int R;
+  int n_images;
+  int stride;                      /* elements between two rows, >= n_images */
+  int32_t* weights;                /* [R, stride] out, device */
+} t3d_bootstrap_weights_args;
+#define T3D_V2_SIZE_bootstrap_weights_args 32
+int t3d_bootstrap_weights(const t3d_bootstrap_weights_args* args, t3d_stream_t stream);
+
+/* ---- Bootstrap over images, part 2: the official AP of one class on R resampled image lists (csrc/sunrgbd_bootstrap.hip;
+ *      evaluate_sunrgbd.bootstrap_class, --bootstrap) ----
+ * `eval` is one class's evaluation exactly as t3d_sunrgbd_eval takes it, and every one of its outputs is written with the bytes
+ * t3d_sunrgbd_eval writes for the same input (the entry point calls it); eval->gt_difficult must be NULL.  A detection is matched only
+ * against the boxes of its own image, so max_overlap, gt_idx, is_tp and is_fp are the same in every copy of its image: a replicate in
+ * which the image of weight column c occurs weights[r, c] times is the same ranked list with integer weights, and only the curve is new.
+ * det_col[i] / gt_col[g]: the weight column of the image of detection i / of box g; a column outside [0, weight_stride) has weight 0.
+ * Replicate r, with w_i = weights[r, det_col[i]], over the full stable order eval->order:
+ *   detection i adds w_i * is_tp[i] to the true-positive cumulative sum and w_i * is_fp[i] to the false-positive one;
+ *   n_pos[r] = the sum of weights[r, gt_col[g]] over the boxes; n_tp[r], n_fp[r] the two totals; all counts are 64-bit;
+ *   ap[r]    recall = ctp / n_pos, precision = ctp / (cfp + ctp) (0 / 0 is NaN, which the running maximum ignores), the VOC2011
+ *            envelope and the area as the curve code that computes eval->ap forms them, with its chunking (ceil(P / 1024) consecutive
+ *            ranks per thread) and its fixed summation tree for the same P.  A row of ones therefore gives the bytes of eval->ap.
+ *            n_pos[r] == 0 or P == 0 give 0.
+ * This equals the literal evaluation of the resampled data set: every image copy becomes a distinct image, and the copies of a
+ * detection are adjacent in file order.  Inside a block of m copies of a true positive the precision rises.  Inside a block of false
+ * positives it falls and the recall does not move.  So only block ends reach the envelope, and the block contributes
+ * (m / n_pos) * envelope.  (The literal sum adds the block's m steps of 1 / n_pos one by one: the two differ by rounding alone.)
+ * workspace: T3D_SUNRGBD_BOOTSTRAP_WORKSPACE_BYTES(P) bytes, 8-byte aligned, separate from eval->workspace: the rank-ordered stream
+ * det_col << 1 | is_tp per detection, -1 for one that counts in neither sum.  Not read when P == 0.
+ * Two launches behind the evaluation's: the stream is written, then the curves run one workgroup of 1024 threads per replicate, one
+ * replicate per pass over the stream.  The workgroup stages its weight row in LDS when 4 * weight_stride bytes fit beside the scan
+ * scratch in the 160 KiB of a CU, and gathers from global memory otherwise; both paths give the same bytes.  Nothing is allocated or
+ * synchronised with the host and there are no atomics of its own, so equal inputs give equal bytes.
+ * T3D_ERR_ABI: a struct of another size (either one).  T3D_ERR_ARG: a NULL struct, weight matrix or output array, gt_difficult != NULL,
+ * det_col NULL when P > 0, gt_col NULL when G > 0, a workspace that is missing, too small or misaligned when P > 0, and whatever
+ * t3d_sunrgbd_eval refuses.  T3D_ERR_SHAPE: R outside [1, T3D_BOOTSTRAP_MAX_REPLICATES], weight_stride outside [1, 2^30], and eval's
+ * shapes.  Nothing is launched then. */
+#define T3D_SUNRGBD_BOOTSTRAP_WORKSPACE_BYTES(P) ((uint64_t)(P) * 4u + 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_sunrgbd_bootstrap_args) of the caller's header (see T3D_ABI_VERSION) */
+  int R;
+  const int32_t* weights;          /* [R, weight_stride] device */
+  int weight_stride;
+  const int32_t* det_col;          /* [P] device */
+  const int32_t* gt_col;           /* [G] device */
+  void* workspace;
+  uint64_t workspace_bytes;
+  double* ap;                      /* [R] out */
+  int64_t* n_pos;                  /* [R] out */
+  int64_t* n_tp;                   /* [R] out */
+  int64_t* n_fp;                   /* [R] out */
+} t3d_sunrgbd_bootstrap_args;
+#define T3D_V2_SIZE_sunrgbd_bootstrap_args 88
+int t3d_sunrgbd_eval_bootstrap(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_bootstrap_args* boot, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -494,6 +494,23 @@ def sunrgbd_sweep_workspace_bytes(M, G):
     return M * G * 4 + 8
 
 
+BOOTSTRAP_MAX_REPLICATES = 65536     # t3d.h T3D_BOOTSTRAP_MAX_REPLICATES
+
+
+class BootstrapWeightsArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('seed', C.c_uint32), ('R', i32), ('n_images', i32), ('stride', i32), ('weights', I)]
+
+
+class SunrgbdBootstrapArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('R', i32), ('weights', I), ('weight_stride', i32), ('det_col', I), ('gt_col', I),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('ap', D), ('n_pos', L), ('n_tp', L), ('n_fp', L)]
+
+
+def sunrgbd_bootstrap_workspace_bytes(P):
+    """t3d.h T3D_SUNRGBD_BOOTSTRAP_WORKSPACE_BYTES"""
+    return P * 4 + 8
+
+
 def sunrgbd_eval_workspace_bytes(P, G):
     """t3d.h T3D_SUNRGBD_EVAL_WORKSPACE_BYTES"""
     return (P + G) * 92 + 8
@@ -611,6 +628,8 @@ ENTRY_POINTS = {
     't3d_detect_ensemble': [C.POINTER(DetectEnsembleArgs), VP],
     't3d_detect_nms_sweep': [C.POINTER(DetectNmsSweepArgs), VP],
     't3d_sunrgbd_eval_sweep': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdSweepArgs), VP],
+    't3d_bootstrap_weights': [C.POINTER(BootstrapWeightsArgs), VP],
+    't3d_sunrgbd_eval_bootstrap': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdBootstrapArgs), VP],
     't3d_semi_sample': [C.POINTER(SemiSampleArgs), VP],
     't3d_label_subset': [C.POINTER(LabelSubsetArgs), VP],
 }

@@ -10,6 +10,7 @@
         [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]]
         [--sweep [--sweep_nms_iou V ..] [--sweep_min_reproj_iou V ..] [--sweep_min_mask_in_box V ..] [--sweep_min_seg_box_iou V ..]
                  [--sweep_json FILE] [--sweep_top N]]
+        [--bootstrap R [--bootstrap_seed S] [--bootstrap_level L] [--bootstrap_json FILE]]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -66,6 +67,14 @@ best --sweep_top rows (default 10) by mean AP with their per-class AP and the de
 --sweep_json FILE takes every row.  No result files, pictures or other reports are written.  Box voting (--nms_fuse) moves the kept
 boxes, so its overlaps differ per combination: it is not swept.
 
+--bootstrap R [--bootstrap_seed S] [--bootstrap_level L] [--bootstrap_json FILE] (with --official_eval or --sweep; bootstrap.py): how far
+an AP moves when the validation images are redrawn.  R redraws of the image list with replacement are scored on the device
+(t3d_sunrgbd_eval_bootstrap: the matching of the point evaluation, a weighted curve per redraw).  --official_eval gains an `AP interval`
+line behind every AP line and a `Mean AP interval` line; --sweep gains, on each of the --sweep_top rows, the paired interval of the row's
+mean AP minus the baseline's and minus the best row's (the same redraws for every row), a line `indistinguishable from best at 95 %:
+rows ...` behind `best:`, and the intervals in --sweep_json (which is where they go: --bootstrap_json is --official_eval's).  Without
+--bootstrap every output is what it was, byte for byte.
+
 Where things live: the stages behind the decode (views, consistency, the accept rule, NMS, box voting) and their order belong to
 semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
 boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
@@ -83,7 +92,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, ensemble as EN, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
+from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -385,19 +394,22 @@ class Detector:
                 i += 1
         return out
 
-    def sweep(self, scenes, detections, grid, dataset_dir, idx_list, test_on='AB', scene_ids=None, batch_scenes=16, threshold=0.25):
+    def sweep(self, scenes, detections, grid, dataset_dir, idx_list, test_on='AB', scene_ids=None, batch_scenes=16, threshold=0.25,
+              bootstrap=None, top=10):
         """Which thresholds to use: the scenes go through the pipeline once, as in `detect`, and every configuration of `grid`
         (sweep.Grid) is scored by the official AP of the class set `test_on` against the label files of dataset_dir for the images
         idx_list (ids, or the path of an index file) -> sweep.Result.  The detector must have been built without nms_iou and without
-        thresholds, and with consistency=True when the grid sweeps a min_* threshold."""
+        thresholds, and with consistency=True when the grid sweeps a min_* threshold.
+        bootstrap: None, the number of replicates, or {'R', 'seed', 'level'}: the `top` best rows gain the paired bootstrap intervals of
+        their mean AP against the baseline row and against the best row (sweep.Result.bootstrap_rows)."""
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
         parts = [self.extract(scenes[lo:lo + batch_scenes], detections[lo:lo + batch_scenes], scene_ids[lo:lo + batch_scenes])
                  for lo in range(0, len(scenes), batch_scenes)]
-        return self.sweep_parts(parts, grid, dataset_dir, idx_list, test_on, threshold)
+        return self.sweep_parts(parts, grid, dataset_dir, idx_list, test_on, threshold, bootstrap, top)
 
-    def sweep_parts(self, parts, grid, dataset_dir, idx_list, test_on='AB', threshold=0.25):
+    def sweep_parts(self, parts, grid, dataset_dir, idx_list, test_on='AB', threshold=0.25, bootstrap=None, top=10):
         """`sweep` on extracted parts (what `main` holds)."""
         from transferable3d_amd import evaluate_sunrgbd as ES
         import torch
@@ -419,7 +431,8 @@ class Detector:
         det_index = {c: np.nonzero(np.asarray([x == c for x in names], bool))[0].astype(np.int32) for c in ES.CLASS_NAMES[test_on]}
         measures = {k: getattr(d, k) for k in CS.MEASURES} if grid.consistency else None
         return SW.run(self.rt, grid, self.stages.corners[:n], score, [m.image for m in meta], [type2class[m.name] for m in meta], measures, held,
-                      det_index, dataset_dir, idx_list, test_on, threshold)
+                      det_index, dataset_dir, idx_list, test_on, threshold,
+                      bootstrap=({'R': int(bootstrap)} if bootstrap is not None and not isinstance(bootstrap, dict) else bootstrap), top=top)
 
     @staticmethod
     def record(name, box2d, prob, d, i):
@@ -489,6 +502,7 @@ def parser():
     p.add_argument('--consistency_json', default=None, help='write one row per detection (rejected ones included) with its consistency measures here')
     EN.add_arguments(p)
     SW.add_arguments(p)
+    BS.add_arguments(p)                       # with --official_eval or --sweep: intervals behind the APs (bootstrap.py)
     return p
 
 
@@ -545,6 +559,11 @@ def main(argv=None, rt=None, log=print):
         diagnose = ES.diagnose_options(p, args)
         if diagnose is not None and not args.official_eval:
             raise ValueError('--diagnose breaks down the score of --official_eval: it needs --official_eval')
+        bootstrap = BS.options(p, args)
+        if bootstrap is not None and not (args.official_eval or grid is not None):
+            raise ValueError('--bootstrap puts intervals behind the APs of --official_eval or --sweep: it needs one of them')
+        if bootstrap is not None and grid is not None and bootstrap['json']:
+            raise ValueError('--sweep writes its intervals to --sweep_json: it does not go with --bootstrap_json')
         if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
             raise ValueError('--vis_gt / --vis_suppressed need --vis_dir')
         consistency = args.consistency or any(getattr(args, t) is not None for t in CS.THRESHOLDS) or (grid is not None and grid.consistency)
@@ -568,8 +587,9 @@ def main(argv=None, rt=None, log=print):
     parts = [det.extract(scenes, [per_scene[idx] for idx in batch], batch, vis=vis)
              for batch, scenes in scene_batches(dataset, ids, image_wh=CS.image_size if consistency else None, pictures=pictures)]
     if grid is not None:
-        result = det.sweep_parts(parts, grid, args.dataset_dir, args.idx_path, args.test_on)
-        for line in result.lines(10 if args.sweep_top is None else args.sweep_top):
+        top = 10 if args.sweep_top is None else args.sweep_top
+        result = det.sweep_parts(parts, grid, args.dataset_dir, args.idx_path, args.test_on, bootstrap=bootstrap, top=top)
+        for line in result.lines(top):
             log(line)
         if args.sweep_json:
             result.write_json(args.sweep_json)
@@ -590,7 +610,7 @@ def main(argv=None, rt=None, log=print):
         log('detection results written to %s' % FLAGS.result_dir)
     if args.official_eval:
         held = ES.official_predictions(sorted(set(ES.CLASS_NAMES[args.test_on]) | set(names)), predictions, names)
-        ES.evaluate(None, args.dataset_dir, args.idx_path, args.test_on, rt=det.rt, log=log, predictions=held, diagnose=diagnose)
+        ES.evaluate(None, args.dataset_dir, args.idx_path, args.test_on, rt=det.rt, log=log, predictions=held, diagnose=diagnose, bootstrap=bootstrap)
     return predictions
 
 

@@ -29,6 +29,13 @@ and one the mean; without the flag nothing changes.
 `sweep_class` / `sweep` (t3d_sunrgbd_eval_sweep, csrc/sunrgbd_sweep.hip): the evaluation of one class for many subsets of its detections in
 one call -- footprints, ranks and overlaps once, the claims and the curve per subset -- which `detect --sweep` (sweep.py) scores a grid of
 post-processing thresholds with.
+
+--bootstrap R [--bootstrap_seed 0] [--bootstrap_level 0.95] [--bootstrap_json FILE] (either form): how far each AP moves when the image
+list is redrawn -- the percentile bootstrap over images (bootstrap.py).  Per class ONE t3d_sunrgbd_eval_bootstrap call
+(csrc/sunrgbd_bootstrap.hip) in place of the t3d_sunrgbd_eval call: the same evaluation, then the AP of every redraw from the same
+matching with integer weights (`bootstrap_class`).  One `AP interval` line follows each AP line and one `Mean AP interval` line the mean.
+--pred_dir A --compare_pred_dir B --bootstrap R (`compare`) scores two directories with the same redraws and prints, per class and for
+the mean, `dAP for X (B - A): mean [lo, hi], p(≤0) share`.  --diagnose does not go with it; without the flag nothing changes.
 """
 import argparse
 import ctypes as C
@@ -173,11 +180,13 @@ def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False, other=Non
     return fetch()
 
 
-def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None, sweep=None):
+def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None, sweep=None, boot=None):
     """_eval_call in its three steps: packs and uploads the inputs (the one copy to the device) -> (launch: the entry point's launches
     on the runtime's stream, fetch: the one copy back as host arrays).  tools/bench_sunrgbd_diagnose.py times `launch` alone.
     sweep: (mask uint8 [M, stride] on the runtime's device, det_index [P] or None): one t3d_sunrgbd_eval_sweep call instead, and `fetch`
-    copies back its four [M] arrays alone ('ap', 'n_det', 'n_tp', 'n_fp')."""
+    copies back its four [M] arrays alone ('ap', 'n_det', 'n_tp', 'n_fp').
+    boot: (bootstrap.Weights, det_col [P], gt_col [G]): one t3d_sunrgbd_eval_bootstrap call instead, and `fetch` returns the evaluation's
+    arrays plus 'boot': {'ap' float64 [R], 'n_pos', 'n_tp', 'n_fp' int64 [R]} (a second copy back)."""
     rt = _runtime(rt)
     P, G = len(det['confidence']), len(gt['image'])
     gimg = np.asarray(gt['image'], np.int32)
@@ -204,6 +213,10 @@ def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=
         if len(sweep[1]) != P:
             raise ValueError('%d detections, %d columns in det_index' % (P, len(sweep[1])))
         host_in['det_index'] = (np.int32, sweep[1])
+    if boot is not None:
+        if len(boot[1]) != P or len(boot[2]) != G:
+            raise ValueError('%d detections and %d boxes, %d and %d weight columns' % (P, G, len(boot[1]), len(boot[2])))
+        host_in['det_col'], host_in['gt_col'] = (np.int32, boot[1]), (np.int32, boot[2])
     if other is not None:
         Go = len(other['image'])
         oimg = np.asarray(other['image'], np.int32)
@@ -277,6 +290,30 @@ def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=
             if evaluation:                                                  # (the tests: what t3d_sunrgbd_eval itself wrote, a second copy)
                 host = d_out.cpu().numpy()
                 res['evaluation'] = {name: out.view(host, name).copy() for name in out.fields}
+            return res
+        return launch, fetch
+    if boot is not None:
+        weights = boot[0]
+        R = weights.R
+        bo = _Packed()
+        for name, dt in (('ap', np.float64), ('n_pos', np.int64), ('n_tp', np.int64), ('n_fp', np.int64)):
+            bo.add(name, dt, R)
+        d_bo = torch.zeros(bo.size, dtype=torch.uint8, device=dev)
+        bws_bytes = abi.sunrgbd_bootstrap_workspace_bytes(P)
+        d_bws = torch.empty((bws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        b_ = lambda n, T: ptr(d_bo, bo, n, T)
+        b = abi.SunrgbdBootstrapArgs(R, abi.iptr(weights.matrix), weights.stride, i_('det_col', i32), i_('gt_col', i32), C.c_void_p(d_bws.data_ptr()),
+                                     bws_bytes, b_('ap', dbl), b_('n_pos', C.c_int64), b_('n_tp', C.c_int64), b_('n_fp', C.c_int64))
+        held += [d_bo, d_bws, weights]
+
+        def launch(held=held):
+            abi.check(rt.lib.t3d_sunrgbd_eval_bootstrap(C.byref(a), C.byref(b), rt.stream()), 't3d_sunrgbd_eval_bootstrap')
+
+        def fetch(held=held):
+            host = d_out.cpu().numpy()                                      # (synchronises)
+            res = {name: out.view(host, name).copy() for name in out.fields}
+            host = d_bo.cpu().numpy()
+            res['boot'] = {name: bo.view(host, name).copy() for name in bo.fields}
             return res
         return launch, fetch
     if other is None:
@@ -368,6 +405,42 @@ def sweep(predictions, dataset_dir, idx_list, masks, det_index, test_on='AB', rt
     return out, np.mean(ap, axis=1)
 
 
+def _columns(images, idx_list, what):
+    """The position in idx_list of every image id (the first, should an id occur twice); ValueError for an id that is not in the list."""
+    idx = np.asarray(idx_list, np.int64).reshape(-1)
+    images = np.asarray(images, np.int64).reshape(-1)
+    if len(images) == 0:
+        return np.zeros(0, np.int32)
+    if len(idx) == 0:
+        raise ValueError('%s of image %d, and the image list is empty' % (what, images[0]))
+    by = np.argsort(idx, kind='stable')
+    k = np.minimum(np.searchsorted(idx[by], images), len(idx) - 1)
+    bad = idx[by][k] != images
+    if bad.any():
+        raise ValueError('%s of image %d, which is not in the image list: its weight is not defined' % (what, images[bad][0]))
+    return by[k].astype(np.int32)
+
+
+def bootstrap_class(classname, det, gt, weights, idx_list, threshold=0.25, rt=None):
+    """compute_pr_curve_3d(classname, det, gt) -- the point evaluation, its dictionary -- and the AP of the class on every redraw of the
+    image list `idx_list` that `weights` (bootstrap.Weights over len(idx_list) columns) holds, in one t3d_sunrgbd_eval_bootstrap call
+    (csrc/sunrgbd_bootstrap.hip): the matching is that of the point evaluation, only the weighted curve is formed per replicate.
+    Column c of the weights is the image idx_list[c]; a detection or box of an image that is not in the list raises ValueError.
+    -> the dictionary plus 'ap' float64 [R] and 'n_pos', 'n_tp', 'n_fp' int64 [R]."""
+    rt = _runtime(rt)
+    if weights.n_images != len(idx_list):
+        raise ValueError('%d weight columns for %d images' % (weights.n_images, len(idx_list)))
+    same = np.array([c == classname for c in gt['classname']], bool) if 'classname' in gt else np.ones(len(gt['image']), bool)
+    own = select_boxes(gt, same)
+    cols = (weights, _columns(det['image'], idx_list, 'a detection'), _columns(own['image'], idx_list, 'a ground-truth box'))
+    launch, fetch = _eval_prepare(det, own, None, threshold, rt, boot=cols)
+    launch()
+    r = fetch()
+    out = _pr_curve_result(r, same)
+    out.update(r['boot'])
+    return out
+
+
 GT_STATES = ('claimed', 'localised', 'missed')              # gt_state 1, 2, 3 of t3d_sunrgbd_diagnose
 
 
@@ -428,16 +501,30 @@ def num2str(x):
 
 
 def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, threshold=0.25, save_curves=None, predictions=None,
-             diagnose=None):
+             diagnose=None, bootstrap=None):
     """script_3Deval.m:33-60: per class of the set `test_on`, the number of predictions, the AP, and the mean AP, logged as the script
     displays them.  `predictions` ({class: boxes}, e.g. official_predictions of a test_semisup run) stands in for the files of `pred_dir`.
     -> ({class: AP}, mean AP).  save_curves: a directory for <class>_pr.npz.
     diagnose: None, or {'bg': the background overlap t_b (0.1), 'json': a path or None}: diagnose_class per class -- two more lines
     behind each AP line (the detections per kind and the boxes per state; 100 x dAP per fix), one behind the mean (the class means),
-    the summary as JSON at the path, and the per-detection arrays in <class>_pr.npz."""
+    the summary as JSON at the path, and the per-detection arrays in <class>_pr.npz.
+    bootstrap: None, the number of replicates, or {'R', 'seed' (0), 'level' (0.95), 'json' (a path or None), 'weights' (a
+    bootstrap.Weights over the image list, made here when absent)}: bootstrap_class per class -- an `AP interval` line behind each AP
+    line and a `Mean AP interval` line behind the mean (the percentile interval over R redraws of the image list, bootstrap.py) -- and
+    the return value gains a third entry, {'R', 'seed', 'level', 'ap': {class: replicate APs [R]}, 'summary': bootstrap.summary}."""
     if test_on not in CLASS_NAMES:
         raise ValueError("test_on is 'A', 'B' or 'AB'")
     rt = _runtime(rt)
+    if bootstrap is not None:
+        from . import bootstrap as BS
+        if diagnose is not None:
+            raise ValueError('a diagnosis of the replicates is not defined: diagnose and bootstrap exclude each other')
+        bootstrap = dict(bootstrap) if isinstance(bootstrap, dict) else {'R': int(bootstrap)}
+        if isinstance(idx_list, str):
+            idx_list = [int(line.rstrip()) for line in open(idx_list) if line.strip()]
+        idx_list = list(idx_list)
+        weights = bootstrap.get('weights') or BS.Weights(rt, len(idx_list), bootstrap['R'], bootstrap.get('seed', 0))
+        level, boot_ap = bootstrap.get('level', 0.95), {}
     gt_all = benchmark_groundtruth(dataset_dir, idx_list)
     ap, summary = {}, {}
     if save_curves:
@@ -450,12 +537,17 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
         else:
             det = parse_class_predictions(os.path.join(pred_dir, name + '_pred.txt'), name)
         log('Number of predictions for %s: %d' % (name.upper(), len(det['confidence'])))
-        if diagnose is None:
+        if bootstrap is not None:
+            r = bootstrap_class(name, det, gt_all, weights, idx_list, threshold, rt)
+        elif diagnose is None:
             r = compute_pr_curve_3d(name, det, gt_all, None, threshold, rt)
         else:
             r = diagnose_class(name, det, gt_all, threshold, diagnose.get('bg', 0.1), rt, classes=CLASS_NAMES[test_on])
         log('AP Score for %s: [%s]' % (name.upper(), num2str(r['apScore'] * 100.0)))
         ap[name] = r['apScore']
+        if bootstrap is not None:
+            boot_ap[name] = r['ap']
+            log('AP interval for %s: %s' % (name.upper(), BS.interval_text(BS.summary({name: r['ap']}, level)['classes'][name], level, weights.R, num2str)))
         curves = dict(precision=r['precision'], recall=r['recall'], isTp=r['isTp'], isFp=r['isFp'], maxOverlaps=r['maxOverlaps'],
                       gtAssignment=r['gtAssignment'], isMissed=r['isMissed'])
         if diagnose is not None:
@@ -477,7 +569,48 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
             with open(diagnose['json'], 'w') as fh:
                 json.dump({'test_on': test_on, 'threshold': threshold, 'bg_threshold': diagnose.get('bg', 0.1), 'kinds': list(abi.DIAG_KINDS),
                            'fixes': list(abi.DIAG_FIXES), 'classes': summary, 'mean_ap': mean_ap, 'mean_dAP': mean_dap}, fh, indent=1)
+    if bootstrap is not None:
+        boot = {'R': weights.R, 'seed': weights.seed, 'level': level, 'ap': boot_ap, 'summary': BS.summary(boot_ap, level)}
+        log('Mean AP interval: %s' % BS.interval_text(boot['summary']['mean_ap'], level, weights.R, num2str))
+        if bootstrap.get('json'):
+            with open(bootstrap['json'], 'w') as fh:
+                json.dump(bootstrap_json(test_on, threshold, ap, mean_ap, boot), fh, indent=1)
+        return ap, mean_ap, boot
     return ap, mean_ap
+
+
+def bootstrap_json(test_on, threshold, ap, mean_ap, boot):
+    """What --bootstrap_json holds for one evaluation: the point APs, every class's replicate APs and the summaries."""
+    return {'test_on': test_on, 'threshold': threshold, 'R': boot['R'], 'seed': boot['seed'], 'level': boot['level'],
+            'ap': {c: float(v) for c, v in ap.items()}, 'mean_ap': mean_ap, 'replicates': {c: [float(x) for x in v] for c, v in boot['ap'].items()},
+            'summary': boot['summary']}
+
+
+def compare(pred_dir_a, pred_dir_b, dataset_dir, idx_list, test_on='B', rt=None, log=print, threshold=0.25, bootstrap=None):
+    """`evaluate` on two prediction directories against the same ground truth with the SAME bootstrap weights -- the paired bootstrap,
+    each image its own control -- e.g. a run with and one without --nms_fuse.  Both sets of lines are logged, tagged `A: ` and `B: `,
+    then per class and for the mean `dAP for X (B - A): mean [lo, hi], p(≤0) share` (x 100; bootstrap.paired).
+    -> (evaluate's triple for A, for B, bootstrap.paired of the two)."""
+    from . import bootstrap as BS
+    if bootstrap is None:
+        raise ValueError('a comparison needs the bootstrap')
+    rt = _runtime(rt)
+    bootstrap = dict(bootstrap) if isinstance(bootstrap, dict) else {'R': int(bootstrap)}
+    if isinstance(idx_list, str):
+        idx_list = [int(line.rstrip()) for line in open(idx_list) if line.strip()]
+    idx_list = list(idx_list)
+    shared = dict(bootstrap, json=None, weights=bootstrap.get('weights') or BS.Weights(rt, len(idx_list), bootstrap['R'], bootstrap.get('seed', 0)))
+    a = evaluate(pred_dir_a, dataset_dir, idx_list, test_on, rt=rt, log=lambda t: log('A: ' + t), threshold=threshold, bootstrap=shared)
+    b = evaluate(pred_dir_b, dataset_dir, idx_list, test_on, rt=rt, log=lambda t: log('B: ' + t), threshold=threshold, bootstrap=shared)
+    d = BS.paired(a[2]['ap'], b[2]['ap'], a[2]['level'])
+    for name in CLASS_NAMES[test_on]:
+        log('dAP for %s (B - A): %s' % (name.upper(), BS.difference_text(d['classes'][name])))
+    log('Mean dAP (B - A): %s' % BS.difference_text(d['mean_ap']))
+    if bootstrap.get('json'):
+        with open(bootstrap['json'], 'w') as fh:
+            json.dump({'A': bootstrap_json(test_on, threshold, a[0], a[1], a[2]), 'B': bootstrap_json(test_on, threshold, b[0], b[1], b[2]),
+                       'paired': d}, fh, indent=1)
+    return a, b, d
 
 
 def official_predictions(test_classes, predictions, class_names):
@@ -501,7 +634,7 @@ def official_predictions(test_classes, predictions, class_names):
 
 
 def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test_on='AB', rt=None, log=print, threshold=0.25, save_curves=None,
-                                  diagnose=None):
+                                  diagnose=None, bootstrap=None):
     """test_semisup's run (its own command line: a frustum file with --data_path, or its synthetic frustums, whose image ids are their
     indices), then `evaluate` on the predictions it returns.  With --result_dir among its flags the same run also writes the
     <class>_pred.txt files."""
@@ -514,7 +647,7 @@ def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test
     if rt is None:
         rt = _runtime(None)
     return evaluate(None, dataset_dir, idx_list, test_on, rt=rt, log=log, threshold=threshold, save_curves=save_curves, predictions=held,
-                    diagnose=diagnose)
+                    diagnose=diagnose, bootstrap=bootstrap)
 
 
 def add_diagnose_arguments(p):
@@ -550,22 +683,34 @@ def parser():
     p.add_argument('--save_curves', default=None, help='directory for <class>_pr.npz (precision, recall, isTp, isFp, ...)')
     p.add_argument('--gpu', type=int, default=0)
     add_diagnose_arguments(p)
+    from . import bootstrap as BS
+    BS.add_arguments(p)
+    p.add_argument('--compare_pred_dir', default=None,
+                   help='--pred_dir A --compare_pred_dir B --bootstrap R: both directories against the same ground truth with the same redraws, '
+                        'and the paired interval of B - A per class and for the mean')
     return p
 
 
 def main(argv=None, rt=None, log=print):
     FLAGS, rest = parser().parse_known_args(argv)
     diagnose = diagnose_options(parser(), FLAGS, FLAGS.threshold)
+    from . import bootstrap as BS
+    bootstrap = BS.options(parser(), FLAGS)
+    if FLAGS.compare_pred_dir is not None and (bootstrap is None or FLAGS.official_eval or not FLAGS.pred_dir or FLAGS.save_curves):
+        parser().error('--compare_pred_dir needs --pred_dir and --bootstrap (and takes neither --official_eval nor --save_curves)')
     if rt is None and torch.cuda.is_available():
         torch.cuda.set_device(FLAGS.gpu)
     if FLAGS.official_eval:
         rest = list(rest) + ['--gpu', str(FLAGS.gpu)]                     # the one flag both parsers have: test_semisup gets it too
         return official_eval_of_test_semisup(rest, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log, threshold=FLAGS.threshold,
-                                             save_curves=FLAGS.save_curves, diagnose=diagnose)
+                                             save_curves=FLAGS.save_curves, diagnose=diagnose, bootstrap=bootstrap)
     if rest or not FLAGS.pred_dir:
         parser().error('--pred_dir is required' if not rest else 'unrecognized arguments: %s' % ' '.join(rest))
+    if FLAGS.compare_pred_dir is not None:
+        return compare(FLAGS.pred_dir, FLAGS.compare_pred_dir, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log,
+                       threshold=FLAGS.threshold, bootstrap=bootstrap)
     return evaluate(FLAGS.pred_dir, FLAGS.dataset_dir, FLAGS.idx_path, FLAGS.test_on, rt=rt, log=log, threshold=FLAGS.threshold,
-                    save_curves=FLAGS.save_curves, diagnose=diagnose)
+                    save_curves=FLAGS.save_curves, diagnose=diagnose, bootstrap=bootstrap)
 
 
 if __name__ == '__main__':

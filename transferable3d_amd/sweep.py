@@ -127,6 +127,7 @@ class Result:
         self.n_det, self.n_tp, self.n_fp = ({c: per_class[c][k][:M] for c in classes} for k in ('n_det', 'n_tp', 'n_fp'))
         self.mean_ap, self.kept = mean_ap[:M], kept[:M]
         self._table = [self._row(m, self.rows[m], per_class, mean_ap, kept) for m in range(M)]
+        self.bootstrap = None          # set by `bootstrap_rows`
 
     def _row(self, m, row, per_class, mean_ap, kept):
         return {'index': int(m), 'options': dict(zip(FLAGS, row)), 'flags': flags_text(row), 'mean_ap': float(mean_ap[m]),
@@ -152,24 +153,71 @@ class Result:
     def lines(self, top=10):
         out = ['sweep: %d configurations over %d detections of %d classes' % (len(self.rows), self.n_detections, len(self.classes)),
                'baseline: ' + self._text(self.baseline)]
+        boot = self.bootstrap
         for k, m in enumerate(self.ranking(top)):
-            out.append('%3d. %s: %s' % (k + 1, self._table[m]['flags'], self._text(self._table[m])))
+            text = self._text(self._table[m])
+            if boot is not None and m in boot['rows']:
+                from . import bootstrap as BS
+                text += ' | vs baseline %s | vs best %s' % (BS.difference_text(boot['rows'][m]['vs_baseline']), BS.difference_text(boot['rows'][m]['vs_best']))
+            out.append('%3d. %s: %s' % (k + 1, self._table[m]['flags'], text))
         out.append('best: ' + self.best()['flags'])
+        if boot is not None:
+            same = [k + 1 for k, m in enumerate(self.ranking(top)) if k > 0 and m in boot['rows']
+                    and boot['rows'][m]['vs_best']['lo'] <= 0.0 <= boot['rows'][m]['vs_best']['hi']]
+            out.append('indistinguishable from best at %g %%: %s' % (round(100.0 * boot['level'], 10),
+                                                                     'rows ' + ', '.join(str(k) for k in same) if same else 'none'))
         return out
+
+    def bootstrap_rows(self, rt, top, keep, predictions, det_index, gt_all, idx_list, options):
+        """The paired bootstrap of the `top` best rows (options: {'R', 'seed', 'level'}; bootstrap.py): per row, evaluate_sunrgbd.
+        bootstrap_class per class on the detections its row of `keep` selects, with one weight matrix for all rows, so that per
+        replicate the mean AP of two rows can be subtracted.  Every such row of `table()` gains 'bootstrap': {'mean_ap': the summary of
+        its replicate mean APs, 'vs_baseline': the row minus the baseline, 'vs_best': the row minus the best row (mean, se, lo, hi,
+        p_le0)}.  Rows outside the list are not bootstrapped."""
+        from . import bootstrap as BS
+        level = options.get('level', 0.95)
+        weights = options.get('weights') or BS.Weights(rt, len(idx_list), options['R'], options.get('seed', 0))
+        ranked = self.ranking(top)
+        best, base = self.ranking(1)[0], self.baseline['index']
+
+        def replicates(m):
+            row = keep[m].cpu().numpy()
+            ap = {}
+            for c in self.classes:
+                cols = np.arange(len(predictions[c]['confidence'])) if det_index.get(c) is None else np.asarray(det_index[c], np.int64)
+                ok = (cols >= 0) & (cols < len(row))
+                sel = np.zeros(len(cols), bool)
+                sel[ok] = row[cols[ok]] != 0
+                ap[c] = ES.bootstrap_class(c, ES.select_boxes(predictions[c], sel), gt_all, weights, idx_list, self.threshold, rt)['ap']
+            return BS.mean_over_classes(ap)
+        vec = {m: replicates(m) for m in dict.fromkeys(ranked + [best, base])}
+        rows = {m: {'mean_ap': BS.summary({'mean': vec[m]}, level)['mean_ap'], 'vs_baseline': BS.paired_vector(vec[base], vec[m], level),
+                    'vs_best': BS.paired_vector(vec[best], vec[m], level)} for m in ranked}
+        self.bootstrap = {'R': weights.R, 'seed': weights.seed, 'level': level, 'rows': rows, 'replicates': vec}
+        for m, r in rows.items():
+            self._table[m]['bootstrap'] = r
+        return self.bootstrap
 
     def write_json(self, path):
         with open(path, 'w') as fh:
             json.dump({'test_on': self.test_on, 'threshold': self.threshold, 'nms_metric': self.grid.metric, 'nms_score': self.grid.score,
                        'flags': list(FLAGS), 'values': self.grid.values, 'classes': self.classes, 'detections': self.n_detections,
-                       'baseline': self.baseline, 'best': self.best(), 'rows': self._table}, fh, indent=1)
+                       'baseline': self.baseline, 'best': self.best(), 'rows': self._table,
+                       **({} if self.bootstrap is None else {'bootstrap': {k: self.bootstrap[k] for k in ('R', 'seed', 'level')}})}, fh, indent=1)
 
 
 def run(rt, grid, corners, score, image_ids, class_ids, measures, predictions, det_index, dataset_dir, idx_list, test_on='AB', threshold=0.25,
-        gt_all=None):
+        gt_all=None, bootstrap=None, top=10):
     """corners [n, 24] and score [n] fp32 on the runtime's device (what t3d_detect_decode wrote, and what ranks); image_ids, class_ids [n]:
     the groups; measures: {reproj_iou, mask_in_box, seg_box_iou: fp64 [n]} of the run, or None when grid.consistency is False;
     predictions {class: boxes} and det_index {class: the detections of the class among the n, ascending}: what evaluate_sunrgbd.sweep
-    takes.  -> Result."""
+    takes.  bootstrap: None, or {'R', 'seed', 'level'}: Result.bootstrap_rows for the `top` best rows.  -> Result."""
+    if bootstrap is not None:
+        if isinstance(idx_list, str):
+            idx_list = [int(line.rstrip()) for line in open(idx_list) if line.strip()]
+        idx_list = list(idx_list)
+        if gt_all is None:
+            gt_all = ES.benchmark_groundtruth(dataset_dir, idx_list)
     rows = list(grid.rows)
     off = (None,) * len(FLAGS)
     if off in rows:
@@ -187,4 +235,7 @@ def run(rt, grid, corners, score, image_ids, class_ids, measures, predictions, d
     dev = NMS.DeviceNmsSweep(rt)
     keep, n_kept = dev.run(corners, score, offsets, members, thresholds, ct, listed, grid.metric)
     per_class, mean_ap = ES.sweep(predictions, dataset_dir, idx_list, keep, det_index, test_on, rt, threshold, gt_all)
-    return Result(grid, ES.CLASS_NAMES[test_on], per_class, mean_ap, n_kept.cpu().numpy().astype(np.int64), n, base, test_on, threshold)
+    result = Result(grid, ES.CLASS_NAMES[test_on], per_class, mean_ap, n_kept.cpu().numpy().astype(np.int64), n, base, test_on, threshold)
+    if bootstrap is not None:
+        result.bootstrap_rows(rt, top, keep, predictions, det_index, gt_all, idx_list, bootstrap)
+    return result
