@@ -265,7 +265,8 @@ int t3d_pointmlp_wgrad(const t3d_pointmlp_wgrad_args* args, t3d_stream_t stream)
  * latency per layer and lets both kinds of tile share the CUs).  Same arguments and results as the two separate calls;
  * dense dy only (dy.dz != NULL in both), same M, K, N. */
 int t3d_pointmlp_bwd(const t3d_pointmlp_dgrad_args* dgrad, const t3d_pointmlp_wgrad_args* wgrad, t3d_stream_t stream);
-/* Recommended row split (and the tile the launcher will then use) for a K x N weight gradient over M rows. */
+/* Recommended row split (and the tile the launcher will then use) for a K x N weight gradient over M rows.  One exception: a
+ * T3D_BF16 source with K % tile_k != 0 (K = 192, 320, ...) runs 64-row k-tiles, since its loader neither clamps nor masks columns. */
 int t3d_wgrad_plan(int M, int K, int N, int* rows_per_split, int* tile_k, int* tile_n);
 /* Recommended row split for t3d_pointmlp_bwd.  bf16 layers (dtype = T3D_BF16 for dy, the input and the output) with K and N in
  * {64, 128}, or K x N = 256 x 128 / 128 x 256, run ONE-PASS (*one_pass = 1): one workgroup per split walks its 128-row tiles, reads dz, y and the input once, keeps

@@ -4535,9 +4535,13 @@ static int check_wgrad(const t3d_pointmlp_wgrad_args* a) {
 // tile choice: the plan's tile if the caller used t3d_wgrad_plan's split, else by shape
 static void wgrad_tile(const t3d_pointmlp_wgrad_args* a, int* tk, int* tn) {
   int rps = 0;
-  if (a->M % 128 == 0 && t3d_wgrad_plan(a->M, a->K, a->N, &rps, tk, tn) == T3D_OK && rps == a->rows_per_split) return;
-  *tk = a->K > 64 ? 128 : 64;
-  *tn = a->N % 128 == 0 ? 128 : 64;
+  if (!(a->M % 128 == 0 && t3d_wgrad_plan(a->M, a->K, a->N, &rps, tk, tn) == T3D_OK && rps == a->rows_per_split)) {
+    *tk = a->K > 64 ? 128 : 64;
+    *tn = a->N % 128 == 0 ? 128 : 64;
+  }
+  // a bf16 source is staged without column clamp or mask (ActLoaderT::EXACT): whole k-tiles only, as the x3 form asks with K % tk == 0
+  // (K = 192 with 128-row tiles would read x, scale and shift up to 64 elements past column K; check_wgrad gives K % 64 == 0)
+  if (a->a.dtype == T3D_BF16 && a->K % *tk) *tk = 64;
 }
 
 extern "C" int t3d_pointmlp_wgrad(const t3d_pointmlp_wgrad_args* a, t3d_stream_t stream) { return t3d_pointmlp_wgrad_r(a, nullptr, stream); }
