@@ -1240,8 +1240,11 @@ int t3d_pool_bwd_stage1_r(const t3d_pointmlp_gram_args* gram, const t3d_act_cols
 int t3d_pool_bwd_stage2_r(const t3d_pool_wgrad_finish_args* finish, const t3d_pointmlp_dgrad_gram_args* dgrad,
                           const t3d_rider_set* riders, t3d_stream_t stream);
 /* Would the `_r` launcher run a rider set INSIDE the GEMM launch for these arguments (1), or as a launch of its own in front of it
- * (0)?  Answered by the launchers' own dispatch (kernel variant, T3D_X3, tile widths, ...), so a scheduler needs no copy of those
- * rules.  Negative: the arguments would be rejected. */
+ * (0)?  Answered by the launchers' own selection step (kernel variant, T3D_X3, tile widths, ...: what the launcher runs before it
+ * touches a stream), so a scheduler needs no copy of those rules; it launches nothing and reads through no pointer of the structs.
+ * Negative: the arguments would be rejected -- without exception: the launcher refuses with this code whatever the rider set, and
+ * before it runs the set.  (What only the x3 launch step sees -- fragment-order planes `w_x3` of a shape or stride it cannot take,
+ * T3D_ERR_SHAPE -- is refused by the launcher alone, set and GEMM together; the query answers for the variant.) */
 int t3d_pointmlp_fwd_hosts_riders(const t3d_pointmlp_fwd_args* args);
 int t3d_pointmlp_wgrad_hosts_riders(const t3d_pointmlp_wgrad_args* args);
 int t3d_pointmlp_bwd_hosts_riders(const t3d_pointmlp_dgrad_args* dgrad, const t3d_pointmlp_wgrad_args* wgrad);

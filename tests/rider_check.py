@@ -597,12 +597,12 @@ def independent_case(pattern, seed=13):
 # ---- C. the rider-hosting forms -----------------------------------------------------------------------------------------------------------
 # Column-tile rules of csrc/pointmlp.hip, restated once:
 def fwd_wide(M, N):
-    """t3d_pointmlp_fwd_r / t3d_x3_fwd: `a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512`"""
+    """select_fwd / t3d_x3_fwd, csrc/pointmlp.hip `wide_tiles(tiles_m, N)`: `cols % 128 == 0 && (long)tiles_m * (cols / 128) >= 512`"""
     return N % 128 == 0 and (M // 128) * (N // 128) >= 512
 
 
 def dgrad_wide(M, K):
-    """csrc/pointmlp.hip `dgrad_wide`: `a->K % 128 == 0 && (a->M / 128) * (a->K / 128) >= 512` (`dgrad_gram_wide` is the same rule)"""
+    """csrc/pointmlp.hip `dgrad_wide` = `wide_tiles(a->M / 128, a->K)` (`dgrad_gram_wide` is the same rule)"""
     return K % 128 == 0 and (M // 128) * (K // 128) >= 512
 
 

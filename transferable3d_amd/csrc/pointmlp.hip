@@ -3866,6 +3866,31 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_pointmlp_fwd_pool(const t3d
   f.epi_write(n_tiles - 1);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host section.  The environment switches of the dispatch, every one of them read here and nowhere else.
+//   read at EVERY launch (the tests and tools change them inside one process): T3D_X3, T3D_X3_MINKN, T3D_X3_MINKN_BWD,
+//     T3D_X3_BWD_NARROW, T3D_X3_W8 -- the env_x3* functions;
+//   read ONCE per process (a static in the function): all the others.
+// ---------------------------------------------------------------------------------------------
+bool env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }      // on unless the value starts with '0'
+int env_mode(const char* name) { const char* e = getenv(name); return e && e[0] == '0' ? 0 : e && e[0] == '2' ? 2 : 1; }      // '0' off, '2' forced, else on
+bool env_x3() { const char* e = getenv("T3D_X3"); return e ? atoi(e) != 0 : true; }                  // 0: the fp32-MFMA kernels (T3D_ARITH_AUTO launches only)
+long env_x3_minkn() { const char* e = getenv("T3D_X3_MINKN"); return e ? atol(e) : 1L; }             // x3 only for K x N at least this (T3D_ARITH_AUTO only)
+long env_x3_minkn_bwd() { const char* e = getenv("T3D_X3_MINKN_BWD"); return e ? atol(e) : env_x3_minkn(); }
+bool env_x3_bwd_narrow() { const char* e = getenv("T3D_X3_BWD_NARROW"); return e ? atoi(e) != 0 : true; }
+int env_x3_w8() { const char* e = getenv("T3D_X3_W8"); return e ? atoi(e) : 1; }                     // 0: never the eight-wave forward; 2: whenever N % 256 == 0
+bool env_fwd_tinyk() { static const bool v = env_on("T3D_FWD_TINYK"); return v; }                    // 0: first layers take the generic forward
+bool env_fwd_res() { static const bool v = env_on("T3D_FWD_RES"); return v; }                        // 0: no activation-resident bf16 forward
+int env_fwd_res_wgs() { static const int v = []() { const char* e = getenv("T3D_FWD_RES_WGS"); return e ? atoi(e) : 512; }(); return v; }      // its persistent workgroups; 0: one per row tile
+int env_fwd_pool() { static const int v = env_mode("T3D_FWD_POOL"); return v; }                      // 0: no A-resident pooled forward; 2: for K = 256 as well
+long env_wgrad_target() { static const long v = []() { const char* e = getenv("T3D_WGRAD_TARGET"); return e ? atol(e) : 384L; }(); return v; }
+bool env_wgrad_tinyk() { static const bool v = env_on("T3D_WGRAD_TINYK"); return v; }                // 0: first layers take the generic weight gradient
+bool env_bwd1() { static const bool v = env_on("T3D_BWD1"); return v; }                              // 0: no one-pass bf16 backward
+int env_bwd1f() { static const int v = env_mode("T3D_BWD1F"); return v; }                            // 0: no one-pass fp32 backward; 2: whatever the row split
+long env_bwd1_wgs() { static const long v = []() { const char* e = getenv("T3D_BWD1_WGS"); return e ? atol(e) : 256L; }(); return v; }
+bool env_gram1() { static const bool v = env_on("T3D_GRAM1"); return v; }                            // 0: no one-pass Gram forms
+int env_dgram1() { static const int v = []() { const char* e = getenv("T3D_DGRAM1"); return e ? atoi(e) : 1; }(); return v; }                  // see dgram1_ok
+
 // dynamic-LDS launch: two pipeline stages exceed the 64 KB static limit for the 128-wide tiles
 // > 64 KB of dynamic LDS needs the function attribute; set once per kernel and size (a driver call per launch would
 // sit on the host path of every eager launch)
@@ -3880,22 +3905,31 @@ void allow_lds(const void* kernel, size_t lds_bytes) {
   cur = lds_bytes;
 }
 
-template <class Args>
-void launch_lds(void (*kernel)(const Args), dim3 grid, size_t lds_bytes, hipStream_t s, const Args& a) {
-  allow_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
-  T3D_LAUNCH(kernel, grid, dim3(NT), lds_bytes, s, a);
+// THE launch of this file: the arguments are checked against the kernel's own parameter list; the caller follows it with
+// T3D_CHECK_LAUNCH (once per entry point: exactly one launch is taken on every path)
+template <class... Params, class... Args>
+void launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+  if (lds_bytes > 0) allow_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
+  T3D_LAUNCH(kernel, grid, block, lds_bytes, s, args...);
 }
-template <class Args>
-void launch_lds_r(void (*kernel)(const Args, const t3d_rider_set), dim3 grid, size_t lds_bytes, hipStream_t s, const Args& a,
-                  const t3d_rider_set& r) {
-  allow_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
-  T3D_LAUNCH(kernel, grid, dim3(NT), lds_bytes, s, a, r);
+
+// Run-time tile widths -> compile-time constants (the std::integral_constant idiom of static_for): f is a generic callable, called
+// with the one combination that holds.  The launchers instantiate what these two enumerate and nothing else -- 128 / 64 columns, and
+// the four tilings of a weight gradient; square Gram tiles are a width (with_width(gt == 128, ...)), not a tiling.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class T> struct type_c { typedef T type; };      // a kernel's arithmetic path (PathX3 / PathX3P) as a value
+template <class F>
+auto with_width(bool wide, F&& f) { return wide ? f(int_c<128>{}) : f(int_c<64>{}); }
+template <class F>
+auto with_tile(int tk, int tn, F&& f) {
+  if (tk == 128 && tn == 128) return f(int_c<128>{}, int_c<128>{});
+  if (tk == 128) return f(int_c<128>{}, int_c<64>{});
+  if (tn == 128) return f(int_c<64>{}, int_c<128>{});
+  return f(int_c<64>{}, int_c<64>{});
 }
-template <class Args>
-void launch_lds1(void (*kernel)(const Args), dim3 grid, size_t lds_bytes, hipStream_t s, const Args& a) {      // 512-thread kernels
-  allow_lds(reinterpret_cast<const void*>(kernel), lds_bytes);
-  T3D_LAUNCH(kernel, grid, dim3(NT1), lds_bytes, s, a);
-}
+// 128-wide column tiles only when they still give >= 2 workgroups per CU (forward: cols = N; data gradients: cols = K)
+bool wide_tiles(int tiles_m, int cols) { return cols % 128 == 0 && (long)tiles_m * (cols / 128) >= 512; }
+
 constexpr size_t lds_fwd(int bn) { return 2 * (size_t)(128 * LDR + BK * bn) * sizeof(float); }
 constexpr size_t lds_dgrad(int bn) { return 2 * (size_t)(128 * LDR + bn * LDR) * sizeof(float); }
 constexpr size_t lds_wgrad(int bmk, int bn) { return 2 * (size_t)BK * (bmk + bn) * sizeof(float); }
@@ -3927,21 +3961,29 @@ bool dtype_ok(int dt) { return dt == T3D_F32 || dt == T3D_BF16; }
 bool x3_on(int arith) {
   if (arith == T3D_ARITH_FP32_MFMA) return false;
   if (arith == T3D_ARITH_BF16X3) return true;
-  const char* e = getenv("T3D_X3");
-  return e ? atoi(e) != 0 : true;
+  return env_x3();
 }
-long x3_min_kn(int arith) { const char* e = arith == T3D_ARITH_AUTO ? getenv("T3D_X3_MINKN") : nullptr; return e ? atol(e) : 1L; }
-long x3_min_kn_bwd(int arith) { const char* e = arith == T3D_ARITH_AUTO ? getenv("T3D_X3_MINKN_BWD") : nullptr; return e ? atol(e) : x3_min_kn(arith); }
+long x3_min_kn(int arith) { return arith == T3D_ARITH_AUTO ? env_x3_minkn() : 1L; }
+long x3_min_kn_bwd(int arith) { return arith == T3D_ARITH_AUTO ? env_x3_minkn_bwd() : 1L; }
 // (K, N <= T3D_IDENT_MAX: the identity scale / shift tables of ActLoaderE)
 bool x3_layer(int arith, int K, int N) { return x3_on(arith) && (long)K * N >= x3_min_kn(arith) && K <= 4096 && N <= 4096; }            // forward launches
 // backward launches (dense and Gram form).  Until round 5 not the layers with few input and many output channels (64 -> 512, conv6's
 // per-point part: their data gradient is ONE 64-column tile over a long reduction, and the compiler-scheduled x3 loop lost to the
 // fp32-MFMA form, 54.1 vs 50.7 us alone); with the hand-placed iteration the x3 form wins there too (44.0 vs 52.1 us alone at
 // M = 32768, 1.1874 vs 1.1947 ms per step, same box: profiles/r06_narrow_bwd.log).  T3D_X3_BWD_NARROW=0 restores the exclusion.
-bool x3_bwd_narrow() { const char* e = getenv("T3D_X3_BWD_NARROW"); return e ? atoi(e) != 0 : true; }
 bool x3_layer_bwd(int arith, int K, int N) {
-  return x3_on(arith) && (long)K * N >= x3_min_kn_bwd(arith) && (N <= 4 * K || K >= 128 || x3_bwd_narrow()) && K <= 4096 && N <= 4096;
+  return x3_on(arith) && (long)K * N >= x3_min_kn_bwd(arith) && (N <= 4 * K || K >= 128 || env_x3_bwd_narrow()) && K <= 4096 && N <= 4096;
 }
+// The x3 shape rule of each launcher family, stated once: the launchers add the element-type / pointer conditions only they can
+// see, t3d_gemm_arithmetic answers with these alone.  `tk`: the weight-gradient tile's rows (ActLoaderE has neither column clamp
+// nor mask: whole k-tiles of an fp32 source -- K = 192 with 128-row tiles would read x, scale and shift past column K).
+int wgrad_tk_by_shape(int K) { return K > 64 ? 128 : 64; }      // tile rows where rows_per_split is not t3d_wgrad_plan's (wgrad_tile)
+bool x3_fwd_shape(int arith, int K, int N) { return K % BKX == 0 && x3_layer(arith, K, N); }
+bool x3_dgrad_shape(int arith, int K, int N) { return N % BKX == 0 && x3_layer_bwd(arith, K, N); }
+bool x3_wgrad_shape(int arith, int K, int N, int tk) { return K % 64 == 0 && K % tk == 0 && x3_layer_bwd(arith, K, N); }
+bool x3_bwd_shape(int arith, int K, int N, int tk) { return N % BKX == 0 && x3_wgrad_shape(arith, K, N, tk); }
+bool x3_gram_shape(int arith, int K) { return x3_layer_bwd(arith, K, K); }
+bool x3_dgrad_gram_shape(int arith, int K) { return K % BKX == 0 && x3_layer_bwd(arith, K, K); }
 bool act_ok(const t3d_act_src& a, int K) {
   return a.x != nullptr && (a.ldx % 4) == 0 && (a.coff % 4) == 0 && a.coff + (K + 3) / 4 * 4 <= a.ldx &&
          (a.scale == nullptr || a.shift != nullptr) && dtype_ok(a.dtype) && !(a.dtype == T3D_BF16 && a.sub != nullptr) &&
@@ -3963,13 +4005,30 @@ size_t lds_with(size_t lds, const t3d_rider_set* r) { return r && (size_t)r->lds
 // The T3D_X3 kernels are instantiated in a translation unit of their own (csrc/pointmlp_x3.hip = this file with T3D_X3_TU defined:
 // the device templates above, these launch helpers, none of the entry points below): hipcc spends two minutes on this file as it is.
 // ---------------------------------------------------------------------------------------------
+//
+// What a rider-capable entry point launches, chosen from its argument structs alone (select_* below: no stream, no rider set, no HIP
+// call) and handed to the launch step -- and, for the x3 forms, across to the other translation unit.  `hosts`: the variant has a
+// rider form (what t3d_*_hosts_riders answer); `lds`: dynamic LDS bytes before a rider set's own (lds_with).
+enum t3d_form {
+  T3D_FORM_F32,          // fp32-MFMA GEMM kernels
+  T3D_FORM_BF16,         // bf16 GEMM kernels
+  T3D_FORM_X3,           // three-term bf16 kernels (csrc/pointmlp_x3.hip)
+  T3D_FORM_TINYK,        // register kernels of a net's first layer (K <= 4)
+  T3D_FORM_FWD_RES,      // activation-resident bf16 forward
+  T3D_FORM_FWD_POOL,     // A-resident pooled forward without an output tensor
+  T3D_FORM_ONE_PASS,     // 512-thread one-pass forms: k_pointmlp_bwd1 / bwd1f, k_pool_bwd_stage1_h / stage2_h
+};
+struct t3d_fwd_sel { t3d_form form; int bn, n_wg; size_t lds; bool hosts; };                           // bn: column-tile width; n_wg: workgroups before riders
+struct t3d_wgrad_sel { t3d_form form; int tk, tn, n_wg; size_t lds; bool hosts; };
+struct t3d_bwd_sel { t3d_form form; int tk, tn, dbn, n_w, n_d; size_t lds; bool hosts; };               // dbn: data-gradient tile width; one-pass: n_w workgroups, n_d = 0
+struct t3d_stage1_sel { t3d_form form; int gt, n_gram, n_colsum, n_prep; size_t lds; bool hosts; };     // one-pass: n_prep counts PAIRS of prep blocks, n_colsum = 0
+struct t3d_stage2_sel { t3d_form form; int bn, n_finish, n_d; size_t lds; bool hosts; };                // one-pass: n_finish counts PAIRS of finish blocks
 int t3d_x3_fwd(const t3d_pointmlp_fwd_args* a, const t3d_rider_set* r, hipStream_t s);
-int t3d_x3_bwd(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* w, const t3d_rider_set* r, int tk, int tn, bool wide,
-               int n_w, int n_d, hipStream_t s);
+int t3d_x3_bwd(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* w, const t3d_rider_set* r, const t3d_bwd_sel& sel, hipStream_t s);
 int t3d_x3_stage1(const t3d_pointmlp_gram_args* g, const t3d_act_colsum_args* c, const t3d_pool_bwd_prep_args* q, const t3d_rider_set* r,
-                  int gt, int n_gram, int n_colsum, int n_prep, size_t lds_other, hipStream_t s);
-int t3d_x3_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_gram_args* d, const t3d_rider_set* r, bool wide,
-                  int n_finish, int n_d, size_t lds_other, hipStream_t s);
+                  const t3d_stage1_sel& sel, hipStream_t s);
+int t3d_x3_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_gram_args* d, const t3d_rider_set* r, const t3d_stage2_sel& sel,
+                  hipStream_t s);
 int t3d_x3_split(const float* src, void* planes, int64_t n, int64_t plane_stride, hipStream_t s);
 int t3d_x3_split_frag(const float* params, void* pf, void* pd, int64_t stride, const t3d_x3_frag_entry* tab, int n, int n_blocks, hipStream_t s);
 int t3d_x3_step_head(const t3d_pointmlp_fwd_args* a, const float* params, void* pf, void* pd, int64_t stride, const t3d_x3_frag_entry* tab, int n,
@@ -4096,38 +4155,40 @@ int t3d_x3_split(const float* src, void* planes, int64_t n, int64_t plane_stride
 int t3d_x3_dgrad(const t3d_pointmlp_dgrad_args* a, bool wide, hipStream_t s) {
   const int tiles_m = a->M / 128;
   if (a->w_x3 && (a->K % 32 != 0 || a->N % 16 != 0 || a->w_x3_stride < (int64_t)a->K * a->N)) return T3D_ERR_SHAPE;      // (fragment planes: whole blocks)
-  if (a->w_x3 && a->N <= X3_CTAB_MAX_CH) {      // (dy's coefficient table in LDS: 3 N floats)
-    if (wide) launch_lds(k_pointmlp_dgrad<128, false, PathX3P>, dim3(tiles_m * (a->K / 128)), lds_dgrad_x3(128), s, *a);
-    else launch_lds(k_pointmlp_dgrad<64, false, PathX3P>, dim3(tiles_m * (a->K / 64)), lds_dgrad_x3(64), s, *a);
-  } else if (wide) launch_lds(k_pointmlp_dgrad<128, false, PathX3>, dim3(tiles_m * (a->K / 128)), lds_dgrad_x3(128), s, *a);
-  else launch_lds(k_pointmlp_dgrad<64, false, PathX3>, dim3(tiles_m * (a->K / 64)), lds_dgrad_x3(64), s, *a);
+  const auto go = [&](auto path) {
+    with_width(wide, [&](auto bnc) {
+      constexpr int BN = decltype(bnc)::value;
+      launch(k_pointmlp_dgrad<BN, false, typename decltype(path)::type>, dim3(tiles_m * (a->K / BN)), dim3(NT), lds_dgrad_x3(BN), s, *a);
+    });
+  };
+  if (a->w_x3 && a->N <= X3_CTAB_MAX_CH) go(type_c<PathX3P>{});      // (dy's coefficient table in LDS: 3 N floats)
+  else go(type_c<PathX3>{});
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 int t3d_x3_wgrad(const t3d_pointmlp_wgrad_args* a, int tk, int tn, int n_blocks, hipStream_t s) {
-  const dim3 grid(n_blocks);
-#define T3D_WGX(TK, TN_) launch_lds(k_pointmlp_wgrad<TK, TN_, false, false, PathX3, float>, grid, lds_wgrad_x3(TK, TN_), s, *a)
-  if (tk == 128 && tn == 128) T3D_WGX(128, 128);
-  else if (tk == 128) T3D_WGX(128, 64);
-  else if (tn == 128) T3D_WGX(64, 128);
-  else T3D_WGX(64, 64);
-#undef T3D_WGX
+  with_tile(tk, tn, [&](auto tkc, auto tnc) {
+    constexpr int TK = decltype(tkc)::value, TN = decltype(tnc)::value;
+    launch(k_pointmlp_wgrad<TK, TN, false, false, PathX3, float>, dim3(n_blocks), dim3(NT), lds_wgrad_x3(TK, TN), s, *a);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 int t3d_x3_gram(const t3d_pointmlp_gram_args* a, int tk, int n_blocks, hipStream_t s) {
   if (tk != 64) return T3D_ERR_ARG;      // (64 x 64 tiles: the symmetric accumulation keeps three accumulator sets)
-  launch_lds(k_pointmlp_gram<64, 64, PathX3>, dim3(n_blocks), lds_wgrad_x3(64, 64), s, *a);
+  launch(k_pointmlp_gram<64, 64, PathX3>, dim3(n_blocks), dim3(NT), lds_wgrad_x3(64, 64), s, *a);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 int t3d_x3_dgrad_gram(const t3d_pointmlp_dgrad_gram_args* a, bool wide, hipStream_t s) {
   const int tiles_m = a->M / 128;
-  if (wide) launch_lds(k_pointmlp_dgrad_gram<128, PathX3>, dim3(tiles_m * (a->K / 128)), lds_fwd_x3(128), s, *a);
-  else launch_lds(k_pointmlp_dgrad_gram<64, PathX3>, dim3(tiles_m * (a->K / 64)), lds_fwd_x3(64), s, *a);
+  with_width(wide, [&](auto bnc) {
+    constexpr int BN = decltype(bnc)::value;
+    launch(k_pointmlp_dgrad_gram<BN, PathX3>, dim3(tiles_m * (a->K / BN)), dim3(NT), lds_fwd_x3(BN), s, *a);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
@@ -4141,269 +4202,195 @@ int t3d_x3_fwd(const t3d_pointmlp_fwd_args* a, const t3d_rider_set* r, hipStream
   // eight-wave 128 x 256 tiles where a launch has at least two rounds of them (one workgroup per CU: with a single round nothing
   // covers a workgroup's prologue and epilogue, and 512 -> 256 at M = 32768 measured 57.5 us against 56.7; with two or more, 256 -> 512
   // 52.3 against 56.6 and 128 -> 1024 57.3 against 60.5, profiles/r05_w8.log).  T3D_X3_W8=0: never; =2: whenever N % 256 == 0
-  const int w8 = []() { const char* e_ = getenv("T3D_X3_W8"); return e_ ? atoi(e_) : 1; }();
+  const int w8 = env_x3_w8();
   if (w8 && a->N % 256 == 0 && (w8 == 2 || (long)tiles_m * (a->N / 256) >= 512)) {
     const int n_tiles = tiles_m * (a->N / 256);
-    const dim3 grid((n_tiles > T3D_FAIR_CUS ? T3D_FAIR_CUS : n_tiles) + nr);
+    const dim3 grid((n_tiles > T3D_FAIR_CUS ? T3D_FAIR_CUS : n_tiles) + nr), block(2 * NT);
     const size_t lds = lds_with(lds_fwd_x3(256), r);
-    if (r && pre) {
-      auto kern = k_pointmlp_fwd_w8_r<256, PathX3WP>;
-      allow_lds(reinterpret_cast<const void*>(kern), lds);
-      T3D_LAUNCH(kern, grid, dim3(2 * NT), lds, s, *a, *r, n_tiles);
-    } else if (r) {
-      auto kern = k_pointmlp_fwd_w8_r<256, PathX3W>;
-      allow_lds(reinterpret_cast<const void*>(kern), lds);
-      T3D_LAUNCH(kern, grid, dim3(2 * NT), lds, s, *a, *r, n_tiles);
-    } else if (pre) {
-      auto kern = k_pointmlp_fwd_w8<256, PathX3WP>;
-      allow_lds(reinterpret_cast<const void*>(kern), lds);
-      T3D_LAUNCH(kern, grid, dim3(2 * NT), lds, s, *a, n_tiles);
-    } else {
-      auto kern = k_pointmlp_fwd_w8<256, PathX3W>;
-      allow_lds(reinterpret_cast<const void*>(kern), lds);
-      T3D_LAUNCH(kern, grid, dim3(2 * NT), lds, s, *a, n_tiles);
-    }
+    if (r && pre) launch(k_pointmlp_fwd_w8_r<256, PathX3WP>, grid, block, lds, s, *a, *r, n_tiles);
+    else if (r) launch(k_pointmlp_fwd_w8_r<256, PathX3W>, grid, block, lds, s, *a, *r, n_tiles);
+    else if (pre) launch(k_pointmlp_fwd_w8<256, PathX3WP>, grid, block, lds, s, *a, n_tiles);
+    else launch(k_pointmlp_fwd_w8<256, PathX3W>, grid, block, lds, s, *a, n_tiles);
     T3D_CHECK_LAUNCH();
     return T3D_OK;
   }
-  if (a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512) {
-    const dim3 grid(tiles_m * (a->N / 128) + nr);
-    if (r && pre) launch_lds_r(k_pointmlp_fwd_r<128, false, PathX3P>, grid, lds_with(lds_fwd_x3(128), r), s, *a, *r);
-    else if (r) launch_lds_r(k_pointmlp_fwd_r<128, false, PathX3>, grid, lds_with(lds_fwd_x3(128), r), s, *a, *r);
-    else if (pre) launch_lds(k_pointmlp_fwd<128, false, PathX3P, float>, grid, lds_fwd_x3(128), s, *a);
-    else launch_lds(k_pointmlp_fwd<128, false, PathX3, float>, grid, lds_fwd_x3(128), s, *a);
-  } else {
-    const dim3 grid(tiles_m * (a->N / 64) + nr);
-    if (r && pre) launch_lds_r(k_pointmlp_fwd_r<64, false, PathX3P>, grid, lds_with(lds_fwd_x3(64), r), s, *a, *r);
-    else if (r) launch_lds_r(k_pointmlp_fwd_r<64, false, PathX3>, grid, lds_with(lds_fwd_x3(64), r), s, *a, *r);
-    else if (pre) launch_lds(k_pointmlp_fwd<64, false, PathX3P, float>, grid, lds_fwd_x3(64), s, *a);
-    else launch_lds(k_pointmlp_fwd<64, false, PathX3, float>, grid, lds_fwd_x3(64), s, *a);
-  }
+  with_width(wide_tiles(tiles_m, a->N), [&](auto bnc) {
+    constexpr int BN = decltype(bnc)::value;
+    const dim3 grid(tiles_m * (a->N / BN) + nr);
+    const size_t lds = lds_with(lds_fwd_x3(BN), r);
+    if (r && pre) launch(k_pointmlp_fwd_r<BN, false, PathX3P>, grid, dim3(NT), lds, s, *a, *r);
+    else if (r) launch(k_pointmlp_fwd_r<BN, false, PathX3>, grid, dim3(NT), lds, s, *a, *r);
+    else if (pre) launch(k_pointmlp_fwd<BN, false, PathX3P, float>, grid, dim3(NT), lds, s, *a);
+    else launch(k_pointmlp_fwd<BN, false, PathX3, float>, grid, dim3(NT), lds, s, *a);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
-int t3d_x3_bwd(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* w, const t3d_rider_set* r, int tk, int tn, bool wide,
-               int n_w, int n_d, hipStream_t s) {
+int t3d_x3_bwd(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* w, const t3d_rider_set* r, const t3d_bwd_sel& sel, hipStream_t s) {
   if (d->w_x3 && (d->K % 32 != 0 || d->N % 16 != 0 || d->w_x3_stride < (int64_t)d->K * d->N)) return T3D_ERR_SHAPE;
-  const dim3 grid(n_w + n_d + (r ? r->n_wg : 0));
-#define T3D_BWDX_P(DBN, TK, TN_, PR_)                                                             \
-  do {                                                                                             \
-    const size_t lds = lds_max(lds_dgrad_x3(DBN), lds_wgrad_x3(TK, TN_));                          \
-    if (r) {                                                                                       \
-      auto kern = k_pointmlp_bwd_r<DBN, TK, TN_, PR_>;                                             \
-      allow_lds(reinterpret_cast<const void*>(kern), lds_with(lds, r));                            \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds_with(lds, r), s, *d, *w, n_w, *r);                      \
-    } else {                                                                                       \
-      auto kern = k_pointmlp_bwd<DBN, TK, TN_, PR_>;                                               \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                                         \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w);                                       \
-    }                                                                                              \
-  } while (0)
-#define T3D_BWDX(DBN, TK, TN_) do { if (d->w_x3 && d->N <= X3_CTAB_MAX_CH) T3D_BWDX_P(DBN, TK, TN_, PathX3P); else T3D_BWDX_P(DBN, TK, TN_, PathX3); } while (0)
-#define T3D_BWDX_W(DBN)                                  \
-  do {                                                   \
-    if (tk == 128 && tn == 128) T3D_BWDX(DBN, 128, 128); \
-    else if (tk == 128) T3D_BWDX(DBN, 128, 64);          \
-    else if (tn == 128) T3D_BWDX(DBN, 64, 128);          \
-    else T3D_BWDX(DBN, 64, 64);                          \
-  } while (0)
-  if (wide) T3D_BWDX_W(128);
-  else T3D_BWDX_W(64);
-#undef T3D_BWDX_W
-#undef T3D_BWDX
-#undef T3D_BWDX_P
+  const dim3 grid(sel.n_w + sel.n_d + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  const bool pre = d->w_x3 && d->N <= X3_CTAB_MAX_CH;
+  with_width(sel.dbn == 128, [&](auto dc) {
+    with_tile(sel.tk, sel.tn, [&](auto tkc, auto tnc) {
+      constexpr int DBN = decltype(dc)::value, TK = decltype(tkc)::value, TN = decltype(tnc)::value;
+      const auto go = [&](auto path) {
+        typedef typename decltype(path)::type PR;
+        if (r) launch(k_pointmlp_bwd_r<DBN, TK, TN, PR>, grid, dim3(NT), lds, s, *d, *w, sel.n_w, *r);
+        else launch(k_pointmlp_bwd<DBN, TK, TN, PR>, grid, dim3(NT), lds, s, *d, *w, sel.n_w);
+      };
+      if (pre) go(type_c<PathX3P>{});
+      else go(type_c<PathX3>{});
+    });
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 int t3d_x3_stage1(const t3d_pointmlp_gram_args* g, const t3d_act_colsum_args* c, const t3d_pool_bwd_prep_args* q, const t3d_rider_set* r,
-                  int gt, int n_gram, int n_colsum, int n_prep, size_t lds_other, hipStream_t s) {
-  const dim3 grid(n_gram + n_colsum + n_prep + (r ? r->n_wg : 0));
-  const size_t lds = lds_with(lds_max(lds_wgrad_x3(gt, gt), lds_other), r);
-#define T3D_ST1X(GT_)                                                                  \
-  do {                                                                                 \
-    if (r) {                                                                           \
-      auto kern = k_pool_bwd_stage1_r<GT_, PathX3>;                                    \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                             \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *g, *c, *q, n_gram, n_colsum, *r);      \
-    } else {                                                                           \
-      auto kern = k_pool_bwd_stage1<GT_, PathX3>;                                      \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                             \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *g, *c, *q, n_gram, n_colsum);          \
-    }                                                                                  \
-  } while (0)
-  if (gt != 64) return T3D_ERR_ARG;      // (see t3d_x3_gram)
-  T3D_ST1X(64);
-#undef T3D_ST1X
+                  const t3d_stage1_sel& sel, hipStream_t s) {
+  if (sel.gt != 64) return T3D_ERR_ARG;      // (see t3d_x3_gram)
+  const dim3 grid(sel.n_gram + sel.n_colsum + sel.n_prep + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  if (r) launch(k_pool_bwd_stage1_r<64, PathX3>, grid, dim3(NT), lds, s, *g, *c, *q, sel.n_gram, sel.n_colsum, *r);
+  else launch(k_pool_bwd_stage1<64, PathX3>, grid, dim3(NT), lds, s, *g, *c, *q, sel.n_gram, sel.n_colsum);
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
-int t3d_x3_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_gram_args* d, const t3d_rider_set* r, bool wide,
-                  int n_finish, int n_d, size_t lds_other, hipStream_t s) {
-  const dim3 grid(n_finish + n_d + (r ? r->n_wg : 0));
-  const size_t lds = lds_with(lds_max(wide ? lds_fwd_x3(128) : lds_fwd_x3(64), lds_other), r);
-#define T3D_ST2X(BN_)                                                                  \
-  do {                                                                                 \
-    if (r) {                                                                           \
-      auto kern = k_pool_bwd_stage2_r<BN_, PathX3>;                                    \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                             \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *f, *d, n_finish, *r);                  \
-    } else {                                                                           \
-      auto kern = k_pool_bwd_stage2<BN_, PathX3>;                                      \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                             \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *f, *d, n_finish);                      \
-    }                                                                                  \
-  } while (0)
-  if (wide) T3D_ST2X(128); else T3D_ST2X(64);
-#undef T3D_ST2X
+int t3d_x3_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_gram_args* d, const t3d_rider_set* r, const t3d_stage2_sel& sel,
+                  hipStream_t s) {
+  const dim3 grid(sel.n_finish + sel.n_d + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  with_width(sel.bn == 128, [&](auto bnc) {
+    constexpr int BN = decltype(bnc)::value;
+    if (r) launch(k_pool_bwd_stage2_r<BN, PathX3>, grid, dim3(NT), lds, s, *f, *d, sel.n_finish, *r);
+    else launch(k_pool_bwd_stage2<BN, PathX3>, grid, dim3(NT), lds, s, *f, *d, sel.n_finish);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 #else
 
-// "would this launch host a rider set inside the GEMM's grid?" is answered by the launchers themselves (t3d_*_hosts_riders below
-// call them with this pseudo-stream and a dummy set): at every point where the variant is decided they return 1 (rider form) or 0
-// (the set would run as a launch of its own) instead of launching -- the step scheduler needs no mirror of the dispatch rules.
-#define T3D_QUERY_STREAM (reinterpret_cast<t3d_stream_t>(static_cast<intptr_t>(-1)))
-#define T3D_HOSTED(r, stream) do { if ((stream) == T3D_QUERY_STREAM) return (r) ? 1 : 0; } while (0)
-// a launch whose kernel variant has no rider form: the set runs as a launch of its own in front of it
-#define T3D_RIDERS_FIRST(r, stream)                         \
-  do {                                                      \
-    if ((stream) == T3D_QUERY_STREAM) return 0;             \
-    if (r) {                                                \
-      const int rc__ = t3d_run_riders(r, stream);           \
-      if (rc__ != T3D_OK) return rc__;                      \
-    }                                                       \
-  } while (0)
+// Every rider-capable entry point is two steps: select_* chooses the kernel variant from the argument structs (the argument checks,
+// the tile and grid counts, the LDS bytes, `hosts`) without a stream, a rider set or a HIP call; the launcher then runs the set in
+// front where the variant has no rider form, and launches what was selected.  t3d_*_hosts_riders are select_* alone: the step
+// scheduler needs no mirror of the dispatch rules, and nothing that can launch is ever called to answer it.
+static int riders_first(const t3d_rider_set*& r, bool hosts, hipStream_t s) {      // a variant without a rider form: the set is a launch of its own in front
+  if (!r || hosts) return T3D_OK;
+  const t3d_rider_set* set = r;
+  r = nullptr;
+  return t3d_run_riders(set, s);
+}
 
-// an fp32 launch (dtype and a.dtype T3D_F32, checked by the caller) that goes to the fp32 register kernel k_pointmlp_fwd_tinyk: the
-// ONE statement of that rule (t3d_pointmlp_fwd_r's dispatch, t3d_step_head, t3d_step_head_takes)
-static bool fwd_takes_tinyk32(const t3d_pointmlp_fwd_args* a) {
-  static const bool use_tiny32 = []() { const char* e = getenv("T3D_FWD_TINYK"); return !(e && e[0] == '0'); }();
-  return use_tiny32 && a->K <= 4 && a->y && !a->pmax && !a->rowbias && (a->N == 64 || a->N == 128) && a->a.ldx % 4 == 0 &&
-         a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx;
+// a layer that goes to the register kernel k_pointmlp_fwd_tinyk (fp32 source; output type = the launch's dtype): the ONE statement of
+// that rule (select_fwd for both element types, t3d_step_head, t3d_step_head_takes)
+static bool fwd_takes_tinyk(const t3d_pointmlp_fwd_args* a) {
+  return env_fwd_tinyk() && a->a.dtype == T3D_F32 && a->K <= 4 && a->y && !a->pmax && !a->rowbias && (a->N == 64 || a->N == 128) &&
+         a->a.ldx % 4 == 0 && a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx;
+}
+#ifndef T3D_FP_WAVES
+#define T3D_FP_WAVES 8
+#endif
+constexpr size_t lds_fwd_res(int bn, int kt) { return ((size_t)kt * 128 * LDRH + 2 * (size_t)BKH * (bn + 32)) * 2; }
+
+static int select_fwd(const t3d_pointmlp_fwd_args* a, t3d_fwd_sel* o) {
+  if (!a || !a->w || !a->psum || !a->psumsq || !act_ok(a->a, a->K)) return T3D_ERR_ARG;
+  if (a->pmax && (!a->pmin || !a->pamax || !a->pamin)) return T3D_ERR_ARG;
+  if (a->M <= 0 || a->K <= 0 || a->N <= 0 || a->M % T3D_TILE_ROWS || a->rows_per_frustum % T3D_TILE_ROWS ||
+      a->M % a->rows_per_frustum || a->N % 64 || (long)a->M * a->N >= (1L << 30))
+    return T3D_ERR_SHAPE;
+  if (!dtype_ok(a->dtype)) return T3D_ERR_ARG;
+  const int tiles_m = a->M / 128;
+  const bool sub = a->a.sub != nullptr, wide = wide_tiles(tiles_m, a->N);
+  *o = t3d_fwd_sel{T3D_FORM_F32, wide ? 128 : 64, tiles_m * (a->N / (wide ? 128 : 64)), 0, false};
+  if (a->dtype == T3D_BF16) {
+    // bf16 storage + bf16 MFMA (configs[4]); the input is fp32 for the raw point cloud / Box-PC representation, bf16 for a layer output
+    const bool xh = a->a.dtype == T3D_BF16;
+    if (xh && a->K % BKH) return T3D_ERR_SHAPE;      // a bf16 input is a layer output: whole 64-deep k-tiles (the loaders do not mask)
+    if (fwd_takes_tinyk(a)) {      // first layer of a net (xyz [+ 1 channel], fp32 source): the register kernel (T3D_FWD_TINYK=0: the generic one)
+      o->form = T3D_FORM_TINYK, o->n_wg = tiles_m;
+    } else if (env_fwd_res() && xh && !sub && (a->K == 64 || a->K == 128)) {
+      // activation-resident kernel: the input panel is transformed once for all column tiles (T3D_FWD_RES=0: the generic kernel).
+      // K = 256 (a 74 KB panel: one workgroup per CU) measured SLOWER than the generic kernel (256 -> 512: 257 vs 194 us, 256 -> 128:
+      // 82 vs 61 us at M = 262144) and its instantiation was dropped in round 3; K <= 128 keeps two workgroups per CU: 128 -> 1024
+      // 272 -> 219 us, 64 -> 512 144 -> 107 us, 128 -> 256 73 -> 67 us, the small layers unchanged (round 2; round 3: see the kernel).
+      // Persistent workgroups (two per CU) walking the row tiles; T3D_FWD_RES_WGS=0: one workgroup per tile as before
+      const int res_wgs = env_fwd_res_wgs();
+      o->form = T3D_FORM_FWD_RES, o->bn = a->N % 128 == 0 ? 128 : 64, o->n_wg = res_wgs > 0 && tiles_m > res_wgs ? res_wgs : tiles_m;
+      o->lds = lds_fwd_res(o->bn, a->K / 64);
+    } else {
+      o->form = T3D_FORM_BF16, o->lds = lds_fwd_h(o->bn);
+    }
+    return T3D_OK;
+  }
+  if (a->a.dtype != T3D_F32) return T3D_ERR_ARG;
+  if (fwd_takes_tinyk(a)) {      // first layer of a net (xyz [+ 1 channel]): the register kernel (T3D_FWD_TINYK=0: the generic one)
+    o->form = T3D_FORM_TINYK, o->n_wg = tiles_m;
+  } else if (!sub && x3_fwd_shape(a->arith, a->K, a->N)) {      // (ahead of the A-resident fp32 kernel; tiles and grid: t3d_x3_fwd)
+    o->form = T3D_FORM_X3, o->hosts = true;
+  } else if (env_fwd_pool() && !a->y && a->pmax && !sub && a->N % 128 == 0 && a->N >= 256 && (a->K == 128 || (a->K == 256 && env_fwd_pool() == 2))) {
+    // max-pooled layer without an output tensor: the A-resident persistent kernel, 512 threads (T3D_FWD_POOL=0: the generic one).
+    // K = 256 needs 16-deep weight tiles to fit the 133 KB panel next to them and measured slower than the generic kernel
+    // (109 vs 100 us on 256->512); K = 128: 92 vs 100 us on 128->1024, 26 vs 33 us on 128->256.  T3D_FWD_POOL=2 forces it on.
+    o->form = T3D_FORM_FWD_POOL, o->n_wg = tiles_m;
+    o->lds = a->K == 128 ? FwdPool<128, 32, T3D_FP_WAVES>::LDS_BYTES : FwdPool<256, 16, T3D_FP_WAVES>::LDS_BYTES;
+  } else {
+    o->hosts = true, o->lds = lds_fwd(o->bn);
+  }
+  return T3D_OK;
 }
 
 extern "C" int t3d_pointmlp_fwd(const t3d_pointmlp_fwd_args* a, t3d_stream_t stream) { return t3d_pointmlp_fwd_r(a, nullptr, stream); }
 
 extern "C" int t3d_pointmlp_fwd_r(const t3d_pointmlp_fwd_args* a, const t3d_rider_set* r, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_fwd_args, a);
-  if (a && a->struct_size != sizeof(*a)) return T3D_ERR_ABI;
   if (r && !riders_ok(r)) return T3D_ERR_ARG;
-  if (!a || !a->w || !a->psum || !a->psumsq || !act_ok(a->a, a->K)) return T3D_ERR_ARG;
-  if (a->pmax && (!a->pmin || !a->pamax || !a->pamin)) return T3D_ERR_ARG;
-  if (a->M <= 0 || a->K <= 0 || a->N <= 0 || a->M % T3D_TILE_ROWS || a->rows_per_frustum % T3D_TILE_ROWS ||
-      a->M % a->rows_per_frustum || a->N % 64 || (long)a->M * a->N >= (1L << 30))
-    return T3D_ERR_SHAPE;
+  t3d_fwd_sel sel;
+  int rc = select_fwd(a, &sel);
+  if (rc != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int tiles_m = a->M / 128;
-  // 128-wide column tiles only when they still give >= 2 workgroups per CU
-  const bool sub = a->a.sub != nullptr;
-  if (!dtype_ok(a->dtype)) return T3D_ERR_ARG;
-  if (a->dtype == T3D_BF16) {
-    T3D_RIDERS_FIRST(r, stream);
-    // bf16 storage + bf16 MFMA (configs[4]); the input is fp32 for the raw point cloud / Box-PC representation, bf16 for a layer output
-    const bool wide = a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512;
-    const bool xh = a->a.dtype == T3D_BF16;
-    if (xh && a->K % BKH) return T3D_ERR_SHAPE;      // a bf16 input is a layer output: whole 64-deep k-tiles (the loaders do not mask)
-    // first layer of a net (xyz [+ 1 channel], fp32 source): the register kernel (T3D_FWD_TINYK=0: the generic one)
-    static const bool use_tiny = []() { const char* e = getenv("T3D_FWD_TINYK"); return !(e && e[0] == '0'); }();
-    if (use_tiny && !xh && a->K <= 4 && a->y && !a->pmax && !a->rowbias && (a->N == 64 || a->N == 128) && a->a.ldx % 4 == 0 &&
-        a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx) {
-      if (a->N == 64) T3D_LAUNCH(k_pointmlp_fwd_tinyk<64>, dim3(tiles_m), dim3(NT), 0, s, *a);
-      else T3D_LAUNCH(k_pointmlp_fwd_tinyk<128>, dim3(tiles_m), dim3(NT), 0, s, *a);
-      T3D_CHECK_LAUNCH();
-      return T3D_OK;
-    }
-    // activation-resident kernel: the input panel is transformed once for all column tiles (T3D_FWD_RES=0: the generic kernel)
-    static const bool use_res = []() { const char* e = getenv("T3D_FWD_RES"); return !(e && e[0] == '0'); }();
-    // K = 256 (a 74 KB panel: one workgroup per CU) measured SLOWER than the generic kernel (256 -> 512: 257 vs 194 us, 256 -> 128:
-    // 82 vs 61 us at M = 262144) and its instantiation was dropped in round 3; K <= 128 keeps two workgroups per CU: 128 -> 1024
-    // 272 -> 219 us, 64 -> 512 144 -> 107 us, 128 -> 256 73 -> 67 us, the small layers unchanged (round 2; round 3: see the kernel).
-    if (use_res && xh && !sub && (a->K == 64 || a->K == 128)) {
-      // persistent workgroups (two per CU) walking the row tiles; T3D_FWD_RES_WGS=0: one workgroup per tile as before
-      static const int res_wgs = []() { const char* e = getenv("T3D_FWD_RES_WGS"); return e ? atoi(e) : 512; }();
-      const dim3 grid(res_wgs > 0 && tiles_m > res_wgs ? res_wgs : tiles_m);
-#define T3D_FWD_RES(BN_, KT_)                                                                                    \
-  do {                                                                                                          \
-    constexpr size_t lds = ((size_t)KT_ * 128 * LDRH + 2 * (size_t)BKH * (BN_ + 32)) * 2;                        \
-    launch_lds(k_pointmlp_fwd_res<BN_, KT_>, grid, lds, s, *a);                                                 \
-  } while (0)
-      if (a->N % 128 == 0) { if (a->K == 64) T3D_FWD_RES(128, 1); else T3D_FWD_RES(128, 2); }
-      else { if (a->K == 64) T3D_FWD_RES(64, 1); else T3D_FWD_RES(64, 2); }
-#undef T3D_FWD_RES
-      T3D_CHECK_LAUNCH();
-      return T3D_OK;
-    }
-    const dim3 grid(tiles_m * (a->N / (wide ? 128 : 64)));
-    const size_t lds = wide ? lds_fwd_h(128) : lds_fwd_h(64);
-#define T3D_FWD_H(BN_)                                                                                          \
-  do {                                                                                                          \
-    if (sub) launch_lds(k_pointmlp_fwd<BN_, true, PathBF16, float>, grid, lds, s, *a);                          \
-    else if (xh) launch_lds(k_pointmlp_fwd<BN_, false, PathBF16, bf16_t>, grid, lds, s, *a);                    \
-    else launch_lds(k_pointmlp_fwd<BN_, false, PathBF16, float>, grid, lds, s, *a);                             \
-  } while (0)
-    if (wide) T3D_FWD_H(128);
-    else T3D_FWD_H(64);
-#undef T3D_FWD_H
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
-  if (a->a.dtype != T3D_F32) return T3D_ERR_ARG;
-  {   // first layer of a net (xyz [+ 1 channel]): the register kernel (T3D_FWD_TINYK=0: the generic one)
-    if (fwd_takes_tinyk32(a)) {
-      T3D_RIDERS_FIRST(r, stream);
-      if (a->N == 64) T3D_LAUNCH((k_pointmlp_fwd_tinyk<64, float>), dim3(tiles_m), dim3(NT), 0, s, *a);
-      else T3D_LAUNCH((k_pointmlp_fwd_tinyk<128, float>), dim3(tiles_m), dim3(NT), 0, s, *a);
-      T3D_CHECK_LAUNCH();
-      return T3D_OK;
-    }
-  }
-  if (!sub && a->K % BKX == 0 && x3_layer(a->arith, a->K, a->N)) {      // (ahead of the A-resident fp32 kernel)
-    T3D_HOSTED(r, stream);
-    return t3d_x3_fwd(a, r, s);
-  }
-  // max-pooled layer without an output tensor: the A-resident persistent kernel (T3D_FWD_POOL=0: the generic one)
-  static const bool use_pool_kernel = []() { const char* e = getenv("T3D_FWD_POOL"); return !(e && e[0] == '0'); }();
-  // K = 256 needs 16-deep weight tiles to fit the 133 KB panel next to them and measured slower than the generic kernel
-  // (109 vs 100 us on 256->512); K = 128: 92 vs 100 us on 128->1024, 26 vs 33 us on 128->256.  T3D_FWD_POOL=2 forces it on.
-  static const bool fp_k256 = []() { const char* e = getenv("T3D_FWD_POOL"); return e && e[0] == '2'; }();
-  if (use_pool_kernel && !a->y && a->pmax && !sub && a->N % 128 == 0 && a->N >= 256 && (a->K == 128 || (a->K == 256 && fp_k256))) {
-    T3D_RIDERS_FIRST(r, stream);      // (a 512-thread kernel)
-#ifndef T3D_FP_WAVES
-#define T3D_FP_WAVES 8
-#endif
-    if (a->K == 128) {
-      auto kern = k_pointmlp_fwd_pool<128, 32, T3D_FP_WAVES>;
-      constexpr size_t lds = FwdPool<128, 32, T3D_FP_WAVES>::LDS_BYTES;
-      allow_lds(reinterpret_cast<const void*>(kern), lds);
-      T3D_LAUNCH(kern, dim3(tiles_m), dim3(64 * T3D_FP_WAVES), lds, s, *a);
-    } else {
-      auto kern = k_pointmlp_fwd_pool<256, 16, T3D_FP_WAVES>;
-      constexpr size_t lds = FwdPool<256, 16, T3D_FP_WAVES>::LDS_BYTES;
-      allow_lds(reinterpret_cast<const void*>(kern), lds);
-      T3D_LAUNCH(kern, dim3(tiles_m), dim3(64 * T3D_FP_WAVES), lds, s, *a);
-    }
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
-  T3D_HOSTED(r, stream);
-  if (a->N % 128 == 0 && (long)tiles_m * (a->N / 128) >= 512) {
-    const dim3 grid(tiles_m * (a->N / 128) + (r ? r->n_wg : 0));
-    if (r) {
-      if (sub) launch_lds_r(k_pointmlp_fwd_r<128, true>, grid, lds_with(lds_fwd(128), r), s, *a, *r);
-      else launch_lds_r(k_pointmlp_fwd_r<128, false>, grid, lds_with(lds_fwd(128), r), s, *a, *r);
-    } else if (sub) launch_lds(k_pointmlp_fwd<128, true>, grid, lds_fwd(128), s, *a);
-    else launch_lds(k_pointmlp_fwd<128, false>, grid, lds_fwd(128), s, *a);
-  } else {
-    const dim3 grid(tiles_m * (a->N / 64) + (r ? r->n_wg : 0));
-    if (r) {
-      if (sub) launch_lds_r(k_pointmlp_fwd_r<64, true>, grid, lds_with(lds_fwd(64), r), s, *a, *r);
-      else launch_lds_r(k_pointmlp_fwd_r<64, false>, grid, lds_with(lds_fwd(64), r), s, *a, *r);
-    } else if (sub) launch_lds(k_pointmlp_fwd<64, true>, grid, lds_fwd(64), s, *a);
-    else launch_lds(k_pointmlp_fwd<64, false>, grid, lds_fwd(64), s, *a);
+  if ((rc = riders_first(r, sel.hosts, s)) != T3D_OK) return rc;
+  if (sel.form == T3D_FORM_X3) return t3d_x3_fwd(a, r, s);
+  const bool sub = a->a.sub != nullptr, xh = a->a.dtype == T3D_BF16;
+  const dim3 grid(sel.n_wg + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  switch (sel.form) {
+    case T3D_FORM_TINYK:
+      if (a->dtype == T3D_BF16) {
+        if (a->N == 64) launch(k_pointmlp_fwd_tinyk<64>, grid, dim3(NT), 0, s, *a);
+        else launch(k_pointmlp_fwd_tinyk<128>, grid, dim3(NT), 0, s, *a);
+      } else if (a->N == 64) launch(k_pointmlp_fwd_tinyk<64, float>, grid, dim3(NT), 0, s, *a);
+      else launch(k_pointmlp_fwd_tinyk<128, float>, grid, dim3(NT), 0, s, *a);
+      break;
+    case T3D_FORM_FWD_RES:
+      with_width(sel.bn == 128, [&](auto bnc) {
+        constexpr int BN = decltype(bnc)::value;
+        if (a->K == 64) launch(k_pointmlp_fwd_res<BN, 1>, grid, dim3(NT), lds, s, *a);
+        else launch(k_pointmlp_fwd_res<BN, 2>, grid, dim3(NT), lds, s, *a);
+      });
+      break;
+    case T3D_FORM_BF16:
+      with_width(sel.bn == 128, [&](auto bnc) {
+        constexpr int BN = decltype(bnc)::value;
+        if (sub) launch(k_pointmlp_fwd<BN, true, PathBF16, float>, grid, dim3(NT), lds, s, *a);
+        else if (xh) launch(k_pointmlp_fwd<BN, false, PathBF16, bf16_t>, grid, dim3(NT), lds, s, *a);
+        else launch(k_pointmlp_fwd<BN, false, PathBF16, float>, grid, dim3(NT), lds, s, *a);
+      });
+      break;
+    case T3D_FORM_FWD_POOL:
+      if (a->K == 128) launch(k_pointmlp_fwd_pool<128, 32, T3D_FP_WAVES>, grid, dim3(64 * T3D_FP_WAVES), lds, s, *a);
+      else launch(k_pointmlp_fwd_pool<256, 16, T3D_FP_WAVES>, grid, dim3(64 * T3D_FP_WAVES), lds, s, *a);
+      break;
+    default:      // T3D_FORM_F32
+      with_width(sel.bn == 128, [&](auto bnc) {
+        constexpr int BN = decltype(bnc)::value;
+        if (r && sub) launch(k_pointmlp_fwd_r<BN, true>, grid, dim3(NT), lds, s, *a, *r);
+        else if (r) launch(k_pointmlp_fwd_r<BN, false>, grid, dim3(NT), lds, s, *a, *r);
+        else if (sub) launch(k_pointmlp_fwd<BN, true>, grid, dim3(NT), lds, s, *a);
+        else launch(k_pointmlp_fwd<BN, false>, grid, dim3(NT), lds, s, *a);
+      });
   }
   T3D_CHECK_LAUNCH();
   return T3D_OK;
@@ -4420,9 +4407,7 @@ static int check_dgrad(const t3d_pointmlp_dgrad_args* a) {
     return T3D_ERR_SHAPE;
   return T3D_OK;
 }
-static bool dgrad_wide(const t3d_pointmlp_dgrad_args* a) {
-  return a->K % 128 == 0 && (long)(a->M / 128) * (a->K / 128) >= 512;
-}
+static bool dgrad_wide(const t3d_pointmlp_dgrad_args* a) { return wide_tiles(a->M / 128, a->K); }
 
 extern "C" int t3d_pointmlp_dgrad(const t3d_pointmlp_dgrad_args* a, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_dgrad_args, a);
@@ -4430,23 +4415,15 @@ extern "C" int t3d_pointmlp_dgrad(const t3d_pointmlp_dgrad_args* a, t3d_stream_t
   if (rc != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int tiles_m = a->M / 128;
-  const bool pooled = a->dy.dz == nullptr;
-  if (a->dtype == T3D_BF16) {
-    if (dgrad_wide(a)) launch_lds(k_pointmlp_dgrad<128, false, PathBF16>, dim3(tiles_m * (a->K / 128)), lds_dgrad_h(128), s, *a);
-    else launch_lds(k_pointmlp_dgrad<64, false, PathBF16>, dim3(tiles_m * (a->K / 64)), lds_dgrad_h(64), s, *a);
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
-  if (!pooled && a->N % BKX == 0 && x3_layer_bwd(a->arith, a->K, a->N)) return t3d_x3_dgrad(a, dgrad_wide(a), s);
-  if (dgrad_wide(a)) {
-    const dim3 grid(tiles_m * (a->K / 128));
-    if (pooled) launch_lds(k_pointmlp_dgrad<128, true>, grid, lds_dgrad(128), s, *a);
-    else launch_lds(k_pointmlp_dgrad<128, false>, grid, lds_dgrad(128), s, *a);
-  } else {
-    const dim3 grid(tiles_m * (a->K / 64));
-    if (pooled) launch_lds(k_pointmlp_dgrad<64, true>, grid, lds_dgrad(64), s, *a);
-    else launch_lds(k_pointmlp_dgrad<64, false>, grid, lds_dgrad(64), s, *a);
-  }
+  const bool pooled = a->dy.dz == nullptr, bf16 = a->dtype == T3D_BF16;
+  if (!bf16 && !pooled && x3_dgrad_shape(a->arith, a->K, a->N)) return t3d_x3_dgrad(a, dgrad_wide(a), s);
+  with_width(dgrad_wide(a), [&](auto bnc) {
+    constexpr int BN = decltype(bnc)::value;
+    const dim3 grid(tiles_m * (a->K / BN));
+    if (bf16) launch(k_pointmlp_dgrad<BN, false, PathBF16>, grid, dim3(NT), lds_dgrad_h(BN), s, *a);
+    else if (pooled) launch(k_pointmlp_dgrad<BN, true>, grid, dim3(NT), lds_dgrad(BN), s, *a);
+    else launch(k_pointmlp_dgrad<BN, false>, grid, dim3(NT), lds_dgrad(BN), s, *a);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
@@ -4463,7 +4440,7 @@ extern "C" int t3d_wgrad_plan(int M, int K, int N, int* rows_per_split, int* til
   if (cap < 1) cap = 1;
   // number of weight-gradient workgroups aimed at: more splits = shorter workgroups but more slab traffic (every split writes a
   // K x N slab that the slab reducer reads back)
-  static const long target = []() { const char* e = getenv("T3D_WGRAD_TARGET"); return e ? atol(e) : 384L; }();
+  const long target = env_wgrad_target();
   const int cand[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
   int tk = 64, tn = 64;
   long tiles = (long)((K + 63) / 64) * (N / 64);
@@ -4490,24 +4467,21 @@ extern "C" int t3d_wgrad_plan(int M, int K, int N, int* rows_per_split, int* til
 // run of 128-row tiles, one 512-thread workgroup per CU (fewer, longer runs mean fewer K x N slabs) --
 // everything else the split form with t3d_wgrad_plan's row split.
 static bool bwd1_shape(int M, int K, int N, int dtype) {
-  static const bool on = []() { const char* e = getenv("T3D_BWD1"); return !(e && e[0] == '0'); }();
-  static const bool onf = []() { const char* e = getenv("T3D_BWD1F"); return !(e && e[0] == '0'); }();
   const bool narrow = (K == 64 || K == 128) && (N == 64 || N == 128), mid = (K == 256 && N == 128) || (K == 128 && N == 256);
-  if (dtype == T3D_F32) return onf && narrow && M % 128 == 0;
-  return on && dtype == T3D_BF16 && (narrow || mid) && M % 128 == 0;
+  if (dtype == T3D_F32) return env_bwd1f() != 0 && narrow && M % 128 == 0;
+  return env_bwd1() && dtype == T3D_BF16 && (narrow || mid) && M % 128 == 0;
 }
 // fp32: the one-pass form pays from about four 64-row tiles per workgroup (measured per shape on MI355X, DESIGN.md section 4: at
 // B=32 N=1024 -- 256 workgroups of two tiles -- it ties with the split form, its first load and its phase-synchronous tiles exposed);
 // when the rows cannot fill 256 workgroups anyway (M < 32768) the choice does not matter and the one-pass form is taken.
 static bool bwd1_split_ok(int M, int rps, int dtype) {
-  static const bool force = []() { const char* e = getenv("T3D_BWD1F"); return e && e[0] == '2'; }();
-  return dtype != T3D_F32 || force || M / 128 < 256 || rps >= 256;
+  return dtype != T3D_F32 || env_bwd1f() == 2 || M / 128 < 256 || rps >= 256;
 }
 extern "C" int t3d_bwd_plan(int M, int K, int N, int dtype, int* rows_per_split, int* one_pass) {
   if (!rows_per_split || !one_pass) return T3D_ERR_ARG;
   *one_pass = 0;
   if (bwd1_shape(M, K, N, dtype)) {
-    static const long target = []() { const char* e = getenv("T3D_BWD1_WGS"); return e ? atol(e) : 256L; }();
+    const long target = env_bwd1_wgs();
     const int tiles = M / 128;
     int per = 1;
     while (tiles / per > target && tiles % (per * 2) == 0) per *= 2;
@@ -4536,7 +4510,7 @@ static int check_wgrad(const t3d_pointmlp_wgrad_args* a) {
 static void wgrad_tile(const t3d_pointmlp_wgrad_args* a, int* tk, int* tn) {
   int rps = 0;
   if (!(a->M % 128 == 0 && t3d_wgrad_plan(a->M, a->K, a->N, &rps, tk, tn) == T3D_OK && rps == a->rows_per_split)) {
-    *tk = a->K > 64 ? 128 : 64;
+    *tk = wgrad_tk_by_shape(a->K);
     *tn = a->N % 128 == 0 ? 128 : 64;
   }
   // a bf16 source is staged without column clamp or mask (ActLoaderT::EXACT): whole k-tiles only, as the x3 form asks with K % tk == 0
@@ -4544,79 +4518,72 @@ static void wgrad_tile(const t3d_pointmlp_wgrad_args* a, int* tk, int* tn) {
   if (a->a.dtype == T3D_BF16 && a->K % *tk) *tk = 64;
 }
 
+static int select_wgrad(const t3d_pointmlp_wgrad_args* a, t3d_wgrad_sel* o) {
+  const int rc = check_wgrad(a);
+  if (rc != T3D_OK) return rc;
+  const int splits = a->M / a->rows_per_split;
+  int tk = 0, tn = 0;
+  wgrad_tile(a, &tk, &tn);
+  const bool sub = a->a.sub != nullptr, pooled = a->dy.dz == nullptr, f32 = a->dy.dtype != T3D_BF16;
+  *o = t3d_wgrad_sel{T3D_FORM_F32, tk, tn, ((a->K + tk - 1) / tk) * (a->N / tn) * splits, lds_wgrad(tk, tn), false};
+  if (!f32) {
+    o->form = T3D_FORM_BF16, o->lds = lds_wgrad_h(tk, tn);
+  } else if (env_wgrad_tinyk() && !pooled && a->K <= 4 && (a->N == 64 || a->N == 128) && a->a.dtype == T3D_F32 && a->a.ldx % 4 == 0 &&
+             a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx && (a->a.scale == nullptr) == (a->a.shift == nullptr)) {
+    // first layer of a net (K <= 4 raw channels): the register kernel, which has no rider form and beats the generic kernel + a rider;
+    // one workgroup per row split: the slab layout of the generic kernel (T3D_WGRAD_TINYK=0: the generic one)
+    o->form = T3D_FORM_TINYK, o->n_wg = splits, o->lds = 0;
+  } else if (a->a.dtype == T3D_F32 && !sub && !pooled && x3_wgrad_shape(a->arith, a->K, a->N, tk)) {
+    o->form = T3D_FORM_X3;      // (no rider form)
+  } else {
+    o->hosts = tk == 64 && tn == 64 && !pooled;      // rider form: the 64 x 64 tiling only (a first layer's weight gradient, K <= 4 raw channels)
+  }
+  return T3D_OK;
+}
+
 extern "C" int t3d_pointmlp_wgrad(const t3d_pointmlp_wgrad_args* a, t3d_stream_t stream) { return t3d_pointmlp_wgrad_r(a, nullptr, stream); }
 
 extern "C" int t3d_pointmlp_wgrad_r(const t3d_pointmlp_wgrad_args* a, const t3d_rider_set* r, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_wgrad_args, a);
   if (r && !riders_ok(r)) return T3D_ERR_ARG;
-  const int rc = check_wgrad(a);
+  t3d_wgrad_sel sel;
+  int rc = select_wgrad(a, &sel);
   if (rc != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int splits = a->M / a->rows_per_split;
-  int tk = 0, tn = 0;
-  wgrad_tile(a, &tk, &tn);
-  const int tiles_k = (a->K + tk - 1) / tk, tiles_n = a->N / tn;
-  const bool sub = a->a.sub != nullptr, pooled = a->dy.dz == nullptr;
-  // rider form: the 64 x 64 tiling of a first layer's weight gradient (K <= 4 raw channels, fp32) only
-  // x3 form: its activation loader (ActLoaderE) has neither column clamp nor mask -- whole k-tiles of an fp32 source only (K = 192 with
-  // 128-row tiles would read scale / shift / x past column K)
-  const bool x3w = a->dy.dtype != T3D_BF16 && a->a.dtype == T3D_F32 && !sub && !pooled && a->K % tk == 0 && a->K % 64 == 0 &&
-                   x3_layer_bwd(a->arith, a->K, a->N);      // (no rider form)
-  // first layer of a net (K <= 4 raw channels): the register kernel, which has no rider form either and beats the generic kernel + a rider
-  static const bool use_tiny_w = []() { const char* e = getenv("T3D_WGRAD_TINYK"); return !(e && e[0] == '0'); }();
-  const bool tiny_w = use_tiny_w && a->dy.dtype != T3D_BF16 && !pooled && a->K <= 4 && (a->N == 64 || a->N == 128) && a->a.dtype == T3D_F32 &&
-                      a->a.ldx % 4 == 0 && a->a.coff % 4 == 0 && a->a.coff + 4 <= a->a.ldx && (a->a.scale == nullptr) == (a->a.shift == nullptr);
-  const bool host = r && a->dy.dtype != T3D_BF16 && tk == 64 && tn == 64 && !pooled && !x3w && !tiny_w;
-  if (r && !host) { T3D_RIDERS_FIRST(r, stream); r = nullptr; }
-  T3D_HOSTED(r, stream);
-  const dim3 grid(tiles_k * tiles_n * splits + (r ? r->n_wg : 0));
-  if (a->dy.dtype == T3D_BF16) {
-    const bool xh = a->a.dtype == T3D_BF16;
-#define T3D_WGH(TK, TN_)                                                                                                     \
-  do {                                                                                                                       \
-    if (sub) launch_lds(k_pointmlp_wgrad<TK, TN_, true, false, PathBF16, float>, grid, lds_wgrad_h(TK, TN_), s, *a);         \
-    else if (xh) launch_lds(k_pointmlp_wgrad<TK, TN_, false, false, PathBF16, bf16_t>, grid, lds_wgrad_h(TK, TN_), s, *a);   \
-    else launch_lds(k_pointmlp_wgrad<TK, TN_, false, false, PathBF16, float>, grid, lds_wgrad_h(TK, TN_), s, *a);            \
-  } while (0)
-    if (tk == 128 && tn == 128) T3D_WGH(128, 128);
-    else if (tk == 128) T3D_WGH(128, 64);
-    else if (tn == 128) T3D_WGH(64, 128);
-    else T3D_WGH(64, 64);
-#undef T3D_WGH
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
+  if ((rc = riders_first(r, sel.hosts, s)) != T3D_OK) return rc;
+  if (sel.form == T3D_FORM_X3) return t3d_x3_wgrad(a, sel.tk, sel.tn, sel.n_wg, s);
+  const bool sub = a->a.sub != nullptr, pooled = a->dy.dz == nullptr, xh = a->a.dtype == T3D_BF16;
+  const dim3 grid(sel.n_wg + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  if (sel.form == T3D_FORM_BF16) {
+    with_tile(sel.tk, sel.tn, [&](auto tkc, auto tnc) {
+      constexpr int TK = decltype(tkc)::value, TN = decltype(tnc)::value;
+      if (sub) launch(k_pointmlp_wgrad<TK, TN, true, false, PathBF16, float>, grid, dim3(NT), lds, s, *a);
+      else if (xh) launch(k_pointmlp_wgrad<TK, TN, false, false, PathBF16, bf16_t>, grid, dim3(NT), lds, s, *a);
+      else launch(k_pointmlp_wgrad<TK, TN, false, false, PathBF16, float>, grid, dim3(NT), lds, s, *a);
+    });
+  } else if (sel.form == T3D_FORM_TINYK) {
+    if (a->N == 64) { if (sub) launch(k_pointmlp_wgrad_tinyk<64, true>, grid, dim3(NT), 0, s, *a); else launch(k_pointmlp_wgrad_tinyk<64, false>, grid, dim3(NT), 0, s, *a); }
+    else { if (sub) launch(k_pointmlp_wgrad_tinyk<128, true>, grid, dim3(NT), 0, s, *a); else launch(k_pointmlp_wgrad_tinyk<128, false>, grid, dim3(NT), 0, s, *a); }
+  } else if (r) {
+    if (sub) launch(k_pointmlp_wgrad_r<64, 64, true, false>, grid, dim3(NT), lds, s, *a, *r);
+    else launch(k_pointmlp_wgrad_r<64, 64, false, false>, grid, dim3(NT), lds, s, *a, *r);
+  } else {
+    with_tile(sel.tk, sel.tn, [&](auto tkc, auto tnc) {
+      constexpr int TK = decltype(tkc)::value, TN = decltype(tnc)::value;
+      if (sub && pooled) launch(k_pointmlp_wgrad<TK, TN, true, true>, grid, dim3(NT), lds, s, *a);
+      else if (sub) launch(k_pointmlp_wgrad<TK, TN, true, false>, grid, dim3(NT), lds, s, *a);
+      else if (pooled) launch(k_pointmlp_wgrad<TK, TN, false, true>, grid, dim3(NT), lds, s, *a);
+      else launch(k_pointmlp_wgrad<TK, TN, false, false>, grid, dim3(NT), lds, s, *a);
+    });
   }
-#define T3D_WG(TK, TN_)                                                                                   \
-  do {                                                                                                    \
-    if (sub && pooled) launch_lds(k_pointmlp_wgrad<TK, TN_, true, true>, grid, lds_wgrad(TK, TN_), s, *a);        \
-    else if (sub) launch_lds(k_pointmlp_wgrad<TK, TN_, true, false>, grid, lds_wgrad(TK, TN_), s, *a);             \
-    else if (pooled) launch_lds(k_pointmlp_wgrad<TK, TN_, false, true>, grid, lds_wgrad(TK, TN_), s, *a);          \
-    else launch_lds(k_pointmlp_wgrad<TK, TN_, false, false>, grid, lds_wgrad(TK, TN_), s, *a);                     \
-  } while (0)
-  if (tiny_w) {
-    const dim3 gsp(splits);      // one workgroup per row split: the slab layout of the generic kernel
-    if (a->N == 64) { if (sub) T3D_LAUNCH((k_pointmlp_wgrad_tinyk<64, true>), gsp, dim3(NT), 0, s, *a); else T3D_LAUNCH((k_pointmlp_wgrad_tinyk<64, false>), gsp, dim3(NT), 0, s, *a); }
-    else { if (sub) T3D_LAUNCH((k_pointmlp_wgrad_tinyk<128, true>), gsp, dim3(NT), 0, s, *a); else T3D_LAUNCH((k_pointmlp_wgrad_tinyk<128, false>), gsp, dim3(NT), 0, s, *a); }
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
-  if (x3w) return t3d_x3_wgrad(a, tk, tn, tiles_k * tiles_n * splits, s);
-  if (r) {
-    if (sub) launch_lds_r(k_pointmlp_wgrad_r<64, 64, true, false>, grid, lds_with(lds_wgrad(64, 64), r), s, *a, *r);
-    else launch_lds_r(k_pointmlp_wgrad_r<64, 64, false, false>, grid, lds_with(lds_wgrad(64, 64), r), s, *a, *r);
-  } else if (tk == 128 && tn == 128) T3D_WG(128, 128);
-  else if (tk == 128) T3D_WG(128, 64);
-  else if (tn == 128) T3D_WG(64, 128);
-  else T3D_WG(64, 64);
-#undef T3D_WG
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
 
 // One-pass forms of the Gram-form backward (gram1 / dgram1 above): bf16 input with K = 128 or 256 channels.
 static bool gram1_shape(int M, int K, int dtype) {
-  static const bool on = []() { const char* e = getenv("T3D_GRAM1"); return !(e && e[0] == '0'); }();
-  return on && dtype == T3D_BF16 && (K == 128 || K == 256) && M % 128 == 0;
+  return env_gram1() && dtype == T3D_BF16 && (K == 128 || K == 256) && M % 128 == 0;
 }
 static bool act_chunks_ok(const t3d_act_src& a) { return a.dtype == T3D_BF16 && a.ldx % 8 == 0 && a.coff % 8 == 0 && (a.scale == nullptr) == (a.shift == nullptr); }
 extern "C" int t3d_gram_plan(int M, int K, int dtype, int* rows_per_split, int* one_pass) {
@@ -4645,7 +4612,7 @@ static bool dgram1_ok(const t3d_pointmlp_dgrad_gram_args* d) {
   // K = 256 only by default: at K = 128 the split form has a single column tile already (nothing is staged twice) and its 256-thread
   // blocks share the CUs with the dW-assembly blocks of stage 2, whose 24 us of gather latency the 512-thread form leaves exposed
   // (stage 2 at B=128 N=2048: 72 -> 81 us with K = 128, 167 -> 125 us with K = 256).  T3D_DGRAM1=2 takes it for K = 128 as well.
-  static const int mode = []() { const char* e = getenv("T3D_DGRAM1"); return e ? atoi(e) : 1; }();
+  const int mode = env_dgram1();
   if (mode == 0 || (mode == 1 && d->K != 256)) return false;
   return gram1_shape(d->M, d->K, d->dtype) && act_chunks_ok(d->a) && d->a.ldx == d->K && d->a.coff == 0 &&
          (d->prev_y == nullptr || d->prev_y == d->a.x) && (d->add_in == nullptr || d->add_live != nullptr);
@@ -4663,9 +4630,7 @@ static int check_dgrad_gram(const t3d_pointmlp_dgrad_gram_args* a) {
     return T3D_ERR_SHAPE;
   return T3D_OK;
 }
-static bool dgrad_gram_wide(const t3d_pointmlp_dgrad_gram_args* a) {
-  return a->K % 128 == 0 && (long)(a->M / 128) * (a->K / 128) >= 512;
-}
+static bool dgrad_gram_wide(const t3d_pointmlp_dgrad_gram_args* a) { return wide_tiles(a->M / 128, a->K); }
 
 extern "C" int t3d_pointmlp_dgrad_gram(const t3d_pointmlp_dgrad_gram_args* a, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_dgrad_gram_args, a);
@@ -4673,22 +4638,21 @@ extern "C" int t3d_pointmlp_dgrad_gram(const t3d_pointmlp_dgrad_gram_args* a, t3
   if (rc != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int tiles_m = a->M / 128;
+  const bool bf16 = a->dtype == T3D_BF16;
   if (dgram1_ok(a)) {
     const dim3 grid(tiles_m < 256 ? tiles_m : 256);
-    if (a->K == 128) launch_lds1(k_dgram1<128, 128>, grid, lds_dgram1(128, 128), s, *a);
-    else launch_lds1(k_dgram1<256, 64>, grid, lds_dgram1(256, 64), s, *a);
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
-  if (a->dtype == T3D_BF16) {
-    if (dgrad_gram_wide(a)) launch_lds(k_pointmlp_dgrad_gram<128, PathBF16>, dim3(tiles_m * (a->K / 128)), lds_dgram_h(128), s, *a);
-    else launch_lds(k_pointmlp_dgrad_gram<64, PathBF16>, dim3(tiles_m * (a->K / 64)), lds_dgram_h(64), s, *a);
-  } else if (a->K % BKX == 0 && x3_layer_bwd(a->arith, a->K, a->K)) {
+    if (a->K == 128) launch(k_dgram1<128, 128>, grid, dim3(NT1), lds_dgram1(128, 128), s, *a);
+    else launch(k_dgram1<256, 64>, grid, dim3(NT1), lds_dgram1(256, 64), s, *a);
+  } else if (!bf16 && x3_dgrad_gram_shape(a->arith, a->K)) {
     return t3d_x3_dgrad_gram(a, dgrad_gram_wide(a), s);
-  } else if (dgrad_gram_wide(a))
-    launch_lds(k_pointmlp_dgrad_gram<128>, dim3(tiles_m * (a->K / 128)), lds_fwd(128), s, *a);
-  else
-    launch_lds(k_pointmlp_dgrad_gram<64>, dim3(tiles_m * (a->K / 64)), lds_fwd(64), s, *a);
+  } else {
+    with_width(dgrad_gram_wide(a), [&](auto bnc) {
+      constexpr int BN = decltype(bnc)::value;
+      const dim3 grid(tiles_m * (a->K / BN));
+      if (bf16) launch(k_pointmlp_dgrad_gram<BN, PathBF16>, grid, dim3(NT), lds_dgram_h(BN), s, *a);
+      else launch(k_pointmlp_dgrad_gram<BN>, grid, dim3(NT), lds_fwd(BN), s, *a);
+    });
+  }
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
@@ -4711,28 +4675,56 @@ static int gram_tile(const t3d_pointmlp_gram_args* a) {      // square tiles onl
 
 extern "C" int t3d_pointmlp_gram(const t3d_pointmlp_gram_args* a, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_gram_args, a);
-  if (check_gram(a) == T3D_OK && gram1_ok(a)) {
-    const dim3 grid(a->M / a->rows_per_split);
-    if (a->K == 128) launch_lds1(k_gram1<128, 128>, grid, lds_gram1(128, 128), static_cast<hipStream_t>(stream), *a);
-    else launch_lds1(k_gram1<256, 64>, grid, lds_gram1(256, 64), static_cast<hipStream_t>(stream), *a);
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
-  }
   const int rc = check_gram(a);
   if (rc != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int splits = a->M / a->rows_per_split;
-  const bool x3g = a->a.dtype != T3D_BF16 && x3_layer_bwd(a->arith, a->K, a->K);
-  const int tk = x3g ? 64 : gram_tile(a), tn = tk;
-  const dim3 grid((a->K / tk) * (a->K / tn) * splits);
-  if (a->a.dtype == T3D_BF16) {
-    if (tk == 128) launch_lds(k_pointmlp_gram<128, 128, PathBF16>, grid, lds_wgrad_h(128, 128), s, *a);
-    else launch_lds(k_pointmlp_gram<64, 64, PathBF16>, grid, lds_wgrad_h(64, 64), s, *a);
+  const bool bf16 = a->a.dtype == T3D_BF16, x3g = !bf16 && x3_gram_shape(a->arith, a->K);
+  const int gt = x3g ? 64 : gram_tile(a);
+  const int n_blocks = (a->K / gt) * (a->K / gt) * splits;
+  if (gram1_ok(a)) {
+    if (a->K == 128) launch(k_gram1<128, 128>, dim3(splits), dim3(NT1), lds_gram1(128, 128), s, *a);
+    else launch(k_gram1<256, 64>, dim3(splits), dim3(NT1), lds_gram1(256, 64), s, *a);
   } else if (x3g) {
-    return t3d_x3_gram(a, tk, (a->K / tk) * (a->K / tn) * splits, s);
-  } else if (tk == 128) launch_lds(k_pointmlp_gram<128, 128>, grid, lds_wgrad(128, 128), s, *a);
-  else launch_lds(k_pointmlp_gram<64, 64>, grid, lds_wgrad(64, 64), s, *a);
+    return t3d_x3_gram(a, gt, n_blocks, s);
+  } else {
+    with_width(gt == 128, [&](auto gtc) {
+      constexpr int GT = decltype(gtc)::value;
+      if (bf16) launch(k_pointmlp_gram<GT, GT, PathBF16>, dim3(n_blocks), dim3(NT), lds_wgrad_h(GT, GT), s, *a);
+      else launch(k_pointmlp_gram<GT, GT>, dim3(n_blocks), dim3(NT), lds_wgrad(GT, GT), s, *a);
+    });
+  }
   T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+static int select_bwd(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* w, t3d_bwd_sel* o) {
+  int rc = check_dgrad(d);
+  if (rc != T3D_OK) return rc;
+  if ((rc = check_wgrad(w)) != T3D_OK) return rc;
+  // the fused launch covers the dense form only (pooled layers take the Gram path, raw-point layers have no dgrad)
+  if (!d->dy.dz || !w->dy.dz || w->a.sub) return T3D_ERR_ARG;
+  if (d->M != w->M || d->K != w->K || d->N != w->N) return T3D_ERR_SHAPE;
+  if (d->dtype != w->dy.dtype || w->a.dtype != d->dtype) return T3D_ERR_ARG;      // one element type per layer
+  const bool bf16 = d->dtype == T3D_BF16;
+  const int rps = w->rows_per_split, tiles = d->M / 128;
+  // one-pass form: eligible layer and a row split that leaves enough workgroups (t3d_bwd_plan's does).  The epilogue takes the
+  // producer's raw output from the input tile it already holds: prev_y must BE the input tensor
+  const bool own_x = d->prev_y == nullptr || (d->prev_y == w->a.x && w->a.coff == 0 && w->a.ldx == d->K);
+  const int chunk = bf16 ? 8 : 4;      // elements of a 16-byte load of the input
+  if (bwd1_shape(d->M, d->K, d->N, d->dtype) && rps % 128 == 0 && d->M / rps >= (tiles < 256 ? tiles : 256) && own_x &&
+      bwd1_split_ok(d->M, rps, d->dtype) && (w->a.scale == nullptr) == (w->a.shift == nullptr) && w->a.ldx % chunk == 0 && w->a.coff % chunk == 0) {
+    const size_t lds = !bf16 ? lds_bwd1f(d->K, d->N) : lds_bwd1(d->K, d->N, d->K == 256 || d->N == 256 ? 64 : 128);
+    *o = t3d_bwd_sel{T3D_FORM_ONE_PASS, 0, 0, 0, d->M / rps, 0, lds, false};      // (512-thread kernels: no rider form)
+    return T3D_OK;
+  }
+  int tk = 0, tn = 0;
+  wgrad_tile(w, &tk, &tn);
+  const int dbn = dgrad_wide(d) ? 128 : 64;
+  *o = t3d_bwd_sel{T3D_FORM_F32, tk, tn, dbn, ((w->K + tk - 1) / tk) * (w->N / tn) * (w->M / rps), tiles * (d->K / dbn), 0, !bf16};      // both fp32 forms host
+  if (bf16) o->form = T3D_FORM_BF16, o->lds = lds_max(lds_dgrad_h(dbn), lds_wgrad_h(tk, tn));
+  else if (x3_bwd_shape(d->arith, d->K, d->N, tk)) o->form = T3D_FORM_X3, o->lds = lds_max(lds_dgrad_x3(dbn), lds_wgrad_x3(tk, tn));
+  else o->lds = lds_max(lds_dgrad(dbn), lds_wgrad(tk, tn));
   return T3D_OK;
 }
 
@@ -4745,107 +4737,62 @@ extern "C" int t3d_pointmlp_bwd_r(const t3d_pointmlp_dgrad_args* d, const t3d_po
   T3D_ABI_TAKE(pointmlp_dgrad_args, d);
   T3D_ABI_TAKE(pointmlp_wgrad_args, w);
   if (r && !riders_ok(r)) return T3D_ERR_ARG;
-  int rc = check_dgrad(d);
+  t3d_bwd_sel sel;
+  int rc = select_bwd(d, w, &sel);
   if (rc != T3D_OK) return rc;
-  rc = check_wgrad(w);
-  if (rc != T3D_OK) return rc;
-  // the fused launch covers the dense form only (pooled layers take the Gram path, raw-point layers have no dgrad)
-  if (!d->dy.dz || !w->dy.dz || w->a.sub) return T3D_ERR_ARG;
-  if (d->M != w->M || d->K != w->K || d->N != w->N) return T3D_ERR_SHAPE;
-  if (d->dtype != w->dy.dtype || w->a.dtype != d->dtype) return T3D_ERR_ARG;      // one element type per layer
-  const bool bf16 = d->dtype == T3D_BF16;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  {   // one-pass form: eligible layer and a row split that leaves enough workgroups (t3d_bwd_plan's does)
-    const int rps = w->rows_per_split, tiles = d->M / 128;
-    // the epilogue takes the producer's raw output from the input tile it already holds: prev_y must BE the input tensor
-    const bool own_x = d->prev_y == nullptr || (d->prev_y == w->a.x && w->a.coff == 0 && w->a.ldx == d->K);
-    const bool shape1 = bwd1_shape(d->M, d->K, d->N, d->dtype) && rps % 128 == 0 && d->M / rps >= (tiles < 256 ? tiles : 256) && own_x &&
-                        bwd1_split_ok(d->M, rps, d->dtype) &&
-                        (w->a.scale == nullptr) == (w->a.shift == nullptr);
-    if (shape1 && !bf16 && w->a.ldx % 4 == 0 && w->a.coff % 4 == 0) {
-      T3D_RIDERS_FIRST(r, stream);
-      const dim3 grid1(d->M / rps);
-#define T3D_BWD1F(K_, N_)                                                                        \
-  do {                                                                                           \
-    if (d->add_in) {                                                                             \
-      auto kern = k_pointmlp_bwd1f<K_, N_, true>;                                                \
-      allow_lds(reinterpret_cast<const void*>(kern), lds_bwd1f(K_, N_));                         \
-      T3D_LAUNCH(kern, grid1, dim3(NT1), lds_bwd1f(K_, N_), s, *d, *w);                          \
-    } else {                                                                                     \
-      auto kern = k_pointmlp_bwd1f<K_, N_, false>;                                               \
-      allow_lds(reinterpret_cast<const void*>(kern), lds_bwd1f(K_, N_));                         \
-      T3D_LAUNCH(kern, grid1, dim3(NT1), lds_bwd1f(K_, N_), s, *d, *w);                          \
-    }                                                                                            \
-  } while (0)
-      if (d->K == 128 && d->N == 128) T3D_BWD1F(128, 128);
-      else if (d->K == 128) T3D_BWD1F(128, 64);
-      else if (d->N == 128) T3D_BWD1F(64, 128);
-      else T3D_BWD1F(64, 64);
-#undef T3D_BWD1F
-      T3D_CHECK_LAUNCH();
-      return T3D_OK;
-    }
-    if (shape1 && bf16 && w->a.dtype == T3D_BF16 && w->a.ldx % 8 == 0 && w->a.coff % 8 == 0) {
-      T3D_RIDERS_FIRST(r, stream);
-      const dim3 grid1(d->M / rps);
-#define T3D_BWD1(K_, N_, BM_)                                                                    \
-  do {                                                                                           \
-    auto kern = k_pointmlp_bwd1<K_, N_, BM_>;                                                    \
-    allow_lds(reinterpret_cast<const void*>(kern), lds_bwd1(K_, N_, BM_));                       \
-    T3D_LAUNCH(kern, grid1, dim3(NT1), lds_bwd1(K_, N_, BM_), s, *d, *w);                        \
-  } while (0)
-      if (d->K == 256) T3D_BWD1(256, 128, 64);
-      else if (d->N == 256) T3D_BWD1(128, 256, 64);
-      else if (d->K == 128 && d->N == 128) T3D_BWD1(128, 128, 128);
-      else if (d->K == 128) T3D_BWD1(128, 64, 128);
-      else if (d->N == 128) T3D_BWD1(64, 128, 128);
-      else T3D_BWD1(64, 64, 128);
-#undef T3D_BWD1
-      T3D_CHECK_LAUNCH();
-      return T3D_OK;
-    }
-  }
-  int tk = 0, tn = 0;
-  wgrad_tile(w, &tk, &tn);
-  const int n_w = ((w->K + tk - 1) / tk) * (w->N / tn) * (w->M / w->rows_per_split);
-  const bool wide = dgrad_wide(d);
-  const int n_d = (d->M / 128) * (d->K / (wide ? 128 : 64));
-  if (bf16) { T3D_RIDERS_FIRST(r, stream); r = nullptr; }
-  T3D_HOSTED(r, stream);      // (bf16 has left above: both fp32 forms below host the set)
-  if (!bf16 && d->N % BKX == 0 && w->K % 64 == 0 && w->K % tk == 0 && w->a.dtype == T3D_F32 && x3_layer_bwd(d->arith, d->K, d->N)) return t3d_x3_bwd(d, w, r, tk, tn, wide, n_w, n_d, s);
-  const dim3 grid(n_w + n_d + (r ? r->n_wg : 0));
+  if ((rc = riders_first(r, sel.hosts, s)) != T3D_OK) return rc;
+  if (sel.form == T3D_FORM_X3) return t3d_x3_bwd(d, w, r, sel, s);
+  const bool bf16 = d->dtype == T3D_BF16;
   // weight-gradient tiles first: the long wgrad tiles are better started early
-#define T3D_BWD(DBN, TK, TN_)                                                                                      \
-  do {                                                                                                              \
-    if (bf16) {                                                                                                     \
-      const size_t lds = lds_dgrad_h(DBN) > lds_wgrad_h(TK, TN_) ? lds_dgrad_h(DBN) : lds_wgrad_h(TK, TN_);         \
-      auto kern = k_pointmlp_bwd<DBN, TK, TN_, PathBF16>;                                                           \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                                                          \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w);                                                        \
-    } else if (r) {                                                                                                 \
-      const size_t lds = lds_with(lds_dgrad(DBN) > lds_wgrad(TK, TN_) ? lds_dgrad(DBN) : lds_wgrad(TK, TN_), r);    \
-      auto kern = k_pointmlp_bwd_r<DBN, TK, TN_>;                                                                   \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                                                          \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w, *r);                                                    \
-    } else {                                                                                                        \
-      const size_t lds = lds_dgrad(DBN) > lds_wgrad(TK, TN_) ? lds_dgrad(DBN) : lds_wgrad(TK, TN_);                 \
-      auto kern = k_pointmlp_bwd<DBN, TK, TN_>;                                                                     \
-      allow_lds(reinterpret_cast<const void*>(kern), lds);                                                          \
-      T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *d, *w, n_w);                                                        \
-    }                                                                                                               \
-  } while (0)
-#define T3D_BWD_W(DBN)                              \
-  do {                                              \
-    if (tk == 128 && tn == 128) T3D_BWD(DBN, 128, 128); \
-    else if (tk == 128) T3D_BWD(DBN, 128, 64);      \
-    else if (tn == 128) T3D_BWD(DBN, 64, 128);      \
-    else T3D_BWD(DBN, 64, 64);                      \
-  } while (0)
-  if (wide) T3D_BWD_W(128);
-  else T3D_BWD_W(64);
-#undef T3D_BWD_W
-#undef T3D_BWD
+  const dim3 grid(sel.n_w + sel.n_d + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  if (sel.form != T3D_FORM_ONE_PASS) {
+    with_width(sel.dbn == 128, [&](auto dc) {
+      with_tile(sel.tk, sel.tn, [&](auto tkc, auto tnc) {
+        constexpr int DBN = decltype(dc)::value, TK = decltype(tkc)::value, TN = decltype(tnc)::value;
+        if (bf16) launch(k_pointmlp_bwd<DBN, TK, TN, PathBF16>, grid, dim3(NT), lds, s, *d, *w, sel.n_w);
+        else if (r) launch(k_pointmlp_bwd_r<DBN, TK, TN>, grid, dim3(NT), lds, s, *d, *w, sel.n_w, *r);
+        else launch(k_pointmlp_bwd<DBN, TK, TN>, grid, dim3(NT), lds, s, *d, *w, sel.n_w);
+      });
+    });
+  } else if (!bf16) {
+    with_tile(d->K, d->N, [&](auto kc, auto nc) {      // K, N in {64, 128} (bwd1_shape)
+      constexpr int K = decltype(kc)::value, N = decltype(nc)::value;
+      if (d->add_in) launch(k_pointmlp_bwd1f<K, N, true>, grid, dim3(NT1), lds, s, *d, *w);
+      else launch(k_pointmlp_bwd1f<K, N, false>, grid, dim3(NT1), lds, s, *d, *w);
+    });
+  } else if (d->K == 256) {
+    launch(k_pointmlp_bwd1<256, 128, 64>, grid, dim3(NT1), lds, s, *d, *w);
+  } else if (d->N == 256) {
+    launch(k_pointmlp_bwd1<128, 256, 64>, grid, dim3(NT1), lds, s, *d, *w);
+  } else {
+    with_tile(d->K, d->N, [&](auto kc, auto nc) {
+      constexpr int K = decltype(kc)::value, N = decltype(nc)::value;
+      launch(k_pointmlp_bwd1<K, N, 128>, grid, dim3(NT1), lds, s, *d, *w);
+    });
+  }
   T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+static int select_stage1(const t3d_pointmlp_gram_args* g, const t3d_act_colsum_args* c, const t3d_pool_bwd_prep_args* q, t3d_stage1_sel* o) {
+  int rc = check_gram(g);
+  if (rc != T3D_OK) return rc;
+  if ((rc = check_colsum(c)) != T3D_OK) return rc;
+  if ((rc = check_prep(q)) != T3D_OK) return rc;
+  if (c->a.dtype != g->a.dtype) return T3D_ERR_ARG;
+  const int splits = g->M / g->rows_per_split, n_prep = (q->K / 32) * (q->K / 32) * ((q->N + PCH - 1) / PCH);
+  if (gram1_ok(g) && c->M == g->M && c->K == g->K && c->a.x == g->a.x && c->a.ldx == g->a.ldx && c->a.coff == g->a.coff) {
+    const size_t lds = lds_max(g->K == 128 ? lds_gram1(128, 128) : lds_gram1(256, 64), 2 * PREP_LDS);
+    *o = t3d_stage1_sel{T3D_FORM_ONE_PASS, 0, splits, 0, (n_prep + 1) / 2, lds, false};      // (512-thread kernel: no rider form)
+    return T3D_OK;
+  }
+  const bool bf16 = g->a.dtype == T3D_BF16, x3g = !bf16 && x3_gram_shape(g->arith, g->K);
+  const int gt = x3g ? 64 : gram_tile(g);      // (x3: 64 x 64 tiles, see mma_x3)
+  const size_t lds = bf16 ? lds_wgrad_h(gt, gt) : x3g ? lds_wgrad_x3(gt, gt) : lds_wgrad(gt, gt);
+  *o = t3d_stage1_sel{bf16 ? T3D_FORM_BF16 : x3g ? T3D_FORM_X3 : T3D_FORM_F32, gt, (g->K / gt) * (g->K / gt) * splits, c->M / 128, n_prep,
+                      lds_max(lds, lds_max(PREP_LDS, COLSUM_LDS)), !bf16};
   return T3D_OK;
 }
 
@@ -4858,61 +4805,44 @@ extern "C" int t3d_pool_bwd_stage1_r(const t3d_pointmlp_gram_args* g, const t3d_
                                      const t3d_pool_bwd_prep_args* q, const t3d_rider_set* r, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_gram_args, g);
   if (r && !riders_ok(r)) return T3D_ERR_ARG;
-  int rc = check_gram(g);
+  t3d_stage1_sel sel;
+  int rc = select_stage1(g, c, q, &sel);
   if (rc != T3D_OK) return rc;
-  if ((rc = check_colsum(c)) != T3D_OK) return rc;
-  if ((rc = check_prep(q)) != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (c->a.dtype != g->a.dtype) return T3D_ERR_ARG;
-  if (gram1_ok(g) && c->M == g->M && c->K == g->K && c->a.x == g->a.x && c->a.ldx == g->a.ldx && c->a.coff == g->a.coff) {
-    T3D_RIDERS_FIRST(r, stream);
-    const int n_gram1 = g->M / g->rows_per_split, n_prep1 = (q->K / 32) * (q->K / 32) * ((q->N + PCH - 1) / PCH);
-    const dim3 grid1(n_gram1 + (n_prep1 + 1) / 2);
-#define T3D_ST1H(K_, BM_)                                                                                  \
-  do {                                                                                                     \
-    const size_t lds1 = lds_max(lds_gram1(K_, BM_), 2 * PREP_LDS);                                         \
-    auto kern = k_pool_bwd_stage1_h<K_, BM_>;                                                              \
-    allow_lds(reinterpret_cast<const void*>(kern), lds1);                                                  \
-    T3D_LAUNCH(kern, grid1, dim3(NT1), lds1, s, *g, *c, *q, n_gram1);                                      \
-  } while (0)
-    if (g->K == 128) T3D_ST1H(128, 128); else T3D_ST1H(256, 64);
-#undef T3D_ST1H
-    T3D_CHECK_LAUNCH();
+  if ((rc = riders_first(r, sel.hosts, s)) != T3D_OK) return rc;
+  if (sel.form == T3D_FORM_X3) return t3d_x3_stage1(g, c, q, r, sel, s);
+  const dim3 grid(sel.n_gram + sel.n_colsum + sel.n_prep + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  if (sel.form == T3D_FORM_ONE_PASS) {
+    if (g->K == 128) launch(k_pool_bwd_stage1_h<128, 128>, grid, dim3(NT1), lds, s, *g, *c, *q, sel.n_gram);
+    else launch(k_pool_bwd_stage1_h<256, 64>, grid, dim3(NT1), lds, s, *g, *c, *q, sel.n_gram);
+  } else {
+    with_width(sel.gt == 128, [&](auto gtc) {
+      constexpr int GT = decltype(gtc)::value;
+      if (r) launch(k_pool_bwd_stage1_r<GT>, grid, dim3(NT), lds, s, *g, *c, *q, sel.n_gram, sel.n_colsum, *r);
+      else if (sel.form == T3D_FORM_BF16) launch(k_pool_bwd_stage1<GT, PathBF16>, grid, dim3(NT), lds, s, *g, *c, *q, sel.n_gram, sel.n_colsum);
+      else launch(k_pool_bwd_stage1<GT, PathF32>, grid, dim3(NT), lds, s, *g, *c, *q, sel.n_gram, sel.n_colsum);
+    });
+  }
+  T3D_CHECK_LAUNCH();
+  return T3D_OK;
+}
+
+static int select_stage2(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_gram_args* d, t3d_stage2_sel* o) {
+  int rc = check_finish(f);
+  if (rc != T3D_OK) return rc;
+  if ((rc = check_dgrad_gram(d)) != T3D_OK) return rc;
+  if (f->a.dtype != d->a.dtype) return T3D_ERR_ARG;
+  const int n_finish = (f->K / FK) * (f->N / FN), tiles = d->M / 128;
+  if (dgram1_ok(d) && f->K == d->K) {
+    const size_t lds = lds_max(d->K == 128 ? lds_dgram1(128, 128) : lds_dgram1(256, 64), 2 * finish_lds(d->K));
+    *o = t3d_stage2_sel{T3D_FORM_ONE_PASS, 0, (n_finish + 1) / 2, tiles < 256 ? tiles : 256, lds, false};      // (512-thread kernel: no rider form)
     return T3D_OK;
   }
-  const bool x3g = g->a.dtype != T3D_BF16 && x3_layer_bwd(g->arith, g->K, g->K);
-  const int gt = x3g ? 64 : gram_tile(g);      // (x3: 64 x 64 tiles, see mma_x3)
-  const int n_gram = (g->K / gt) * (g->K / gt) * (g->M / g->rows_per_split);
-  const int n_colsum = c->M / 128;
-  const int n_prep = (q->K / 32) * (q->K / 32) * ((q->N + PCH - 1) / PCH);
-  const bool bf16 = g->a.dtype == T3D_BF16;
-  if (c->a.dtype != g->a.dtype) return T3D_ERR_ARG;
-  if (bf16) { T3D_RIDERS_FIRST(r, stream); r = nullptr; }
-  const dim3 grid(n_gram + n_colsum + n_prep + (r ? r->n_wg : 0));
-  size_t lds = bf16 ? lds_wgrad_h(gt, gt) : lds_wgrad(gt, gt);
-  if (PREP_LDS > lds) lds = PREP_LDS;
-  if (COLSUM_LDS > lds) lds = COLSUM_LDS;
-  T3D_HOSTED(r, stream);
-  if (x3g) return t3d_x3_stage1(g, c, q, r, gt, n_gram, n_colsum, n_prep, lds_max(PREP_LDS, COLSUM_LDS), s);
-  lds = lds_with(lds, r);
-#define T3D_ST1(GT_, PR_)                                                              \
-  do {                                                                                 \
-    auto kern = k_pool_bwd_stage1<GT_, PR_>;                                           \
-    allow_lds(reinterpret_cast<const void*>(kern), lds);                               \
-    T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *g, *c, *q, n_gram, n_colsum);            \
-  } while (0)
-#define T3D_ST1R(GT_)                                                                  \
-  do {                                                                                 \
-    auto kern = k_pool_bwd_stage1_r<GT_>;                                              \
-    allow_lds(reinterpret_cast<const void*>(kern), lds);                               \
-    T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *g, *c, *q, n_gram, n_colsum, *r);        \
-  } while (0)
-  if (r) { if (gt == 128) T3D_ST1R(128); else T3D_ST1R(64); }
-  else if (bf16) { if (gt == 128) T3D_ST1(128, PathBF16); else T3D_ST1(64, PathBF16); }
-  else { if (gt == 128) T3D_ST1(128, PathF32); else T3D_ST1(64, PathF32); }
-#undef T3D_ST1R
-#undef T3D_ST1
-  T3D_CHECK_LAUNCH();
+  const bool bf16 = d->dtype == T3D_BF16, x3 = !bf16 && x3_dgrad_gram_shape(d->arith, d->K);
+  const int bn = dgrad_gram_wide(d) ? 128 : 64;
+  const size_t lds = bf16 ? lds_dgram_h(bn) : x3 ? lds_fwd_x3(bn) : lds_fwd(bn);
+  *o = t3d_stage2_sel{bf16 ? T3D_FORM_BF16 : x3 ? T3D_FORM_X3 : T3D_FORM_F32, bn, n_finish, tiles * (d->K / bn), lds_max(lds, finish_lds(f->K)), !bf16};
   return T3D_OK;
 }
 
@@ -4925,57 +4855,26 @@ extern "C" int t3d_pool_bwd_stage2_r(const t3d_pool_wgrad_finish_args* f, const 
                                      const t3d_rider_set* r, t3d_stream_t stream) {
   T3D_ABI_TAKE(pointmlp_dgrad_gram_args, d);
   if (r && !riders_ok(r)) return T3D_ERR_ARG;
-  int rc = check_finish(f);
+  t3d_stage2_sel sel;
+  int rc = select_stage2(f, d, &sel);
   if (rc != T3D_OK) return rc;
-  if ((rc = check_dgrad_gram(d)) != T3D_OK) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int n_finish = (f->K / FK) * (f->N / FN);
-  if (f->a.dtype != d->a.dtype) return T3D_ERR_ARG;
-  if (dgram1_ok(d) && f->K == d->K) {
-    T3D_RIDERS_FIRST(r, stream);
-    const int n_fin2 = (n_finish + 1) / 2, tiles = d->M / 128;
-    const dim3 grid2(n_fin2 + (tiles < 256 ? tiles : 256));
+  if ((rc = riders_first(r, sel.hosts, s)) != T3D_OK) return rc;
+  if (sel.form == T3D_FORM_X3) return t3d_x3_stage2(f, d, r, sel, s);
+  const dim3 grid(sel.n_finish + sel.n_d + (r ? r->n_wg : 0));
+  const size_t lds = lds_with(sel.lds, r);
+  if (sel.form == T3D_FORM_ONE_PASS) {
     const int fin_floats = (int)(finish_lds(f->K) / sizeof(float));
-#define T3D_ST2H(K_, BM_)                                                                                  \
-  do {                                                                                                     \
-    const size_t lds2 = lds_max(lds_dgram1(K_, BM_), 2 * finish_lds(K_));                                  \
-    auto kern = k_pool_bwd_stage2_h<K_, BM_>;                                                              \
-    allow_lds(reinterpret_cast<const void*>(kern), lds2);                                                  \
-    T3D_LAUNCH(kern, grid2, dim3(NT1), lds2, s, *f, *d, n_fin2, fin_floats);                               \
-  } while (0)
-    if (d->K == 128) T3D_ST2H(128, 128); else T3D_ST2H(256, 64);
-#undef T3D_ST2H
-    T3D_CHECK_LAUNCH();
-    return T3D_OK;
+    if (d->K == 128) launch(k_pool_bwd_stage2_h<128, 128>, grid, dim3(NT1), lds, s, *f, *d, sel.n_finish, fin_floats);
+    else launch(k_pool_bwd_stage2_h<256, 64>, grid, dim3(NT1), lds, s, *f, *d, sel.n_finish, fin_floats);
+  } else {
+    with_width(sel.bn == 128, [&](auto bnc) {
+      constexpr int BN = decltype(bnc)::value;
+      if (r) launch(k_pool_bwd_stage2_r<BN>, grid, dim3(NT), lds, s, *f, *d, sel.n_finish, *r);
+      else if (sel.form == T3D_FORM_BF16) launch(k_pool_bwd_stage2<BN, PathBF16>, grid, dim3(NT), lds, s, *f, *d, sel.n_finish);
+      else launch(k_pool_bwd_stage2<BN, PathF32>, grid, dim3(NT), lds, s, *f, *d, sel.n_finish);
+    });
   }
-  const bool wide = dgrad_gram_wide(d);
-  const int n_d = (d->M / 128) * (d->K / (wide ? 128 : 64));
-  const bool bf16 = d->dtype == T3D_BF16;
-  if (f->a.dtype != d->a.dtype) return T3D_ERR_ARG;
-  if (bf16) { T3D_RIDERS_FIRST(r, stream); r = nullptr; }
-  const dim3 grid(n_finish + n_d + (r ? r->n_wg : 0));
-  size_t lds = bf16 ? (wide ? lds_dgram_h(128) : lds_dgram_h(64)) : (wide ? lds_fwd(128) : lds_fwd(64));
-  if (finish_lds(f->K) > lds) lds = finish_lds(f->K);
-  T3D_HOSTED(r, stream);
-  if (!bf16 && d->K % BKX == 0 && x3_layer_bwd(d->arith, d->K, d->K)) return t3d_x3_stage2(f, d, r, wide, n_finish, n_d, finish_lds(f->K), s);
-  lds = lds_with(lds, r);
-#define T3D_ST2(BN_, PR_)                                                              \
-  do {                                                                                 \
-    auto kern = k_pool_bwd_stage2<BN_, PR_>;                                           \
-    allow_lds(reinterpret_cast<const void*>(kern), lds);                               \
-    T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *f, *d, n_finish);                        \
-  } while (0)
-#define T3D_ST2R(BN_)                                                                  \
-  do {                                                                                 \
-    auto kern = k_pool_bwd_stage2_r<BN_>;                                              \
-    allow_lds(reinterpret_cast<const void*>(kern), lds);                               \
-    T3D_LAUNCH(kern, grid, dim3(NT), lds, s, *f, *d, n_finish, *r);                    \
-  } while (0)
-  if (r) { if (wide) T3D_ST2R(128); else T3D_ST2R(64); }
-  else if (bf16) { if (wide) T3D_ST2(128, PathBF16); else T3D_ST2(64, PathBF16); }
-  else { if (wide) T3D_ST2(128, PathF32); else T3D_ST2(64, PathF32); }
-#undef T3D_ST2R
-#undef T3D_ST2
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }
@@ -5003,7 +4902,7 @@ static int step_head_fwd_check(const t3d_pointmlp_fwd_args* a) {
     return T3D_ERR_SHAPE;
   // only the layer t3d_pointmlp_fwd gives to the fp32 register kernel, on a raw input: beside the input, the fp32 weights and the
   // bias that kernel then reads nothing -- no `hyper`, no planes, no scale / shift / per-frustum offset another launch could write
-  if (a->dtype != T3D_F32 || a->a.dtype != T3D_F32 || !fwd_takes_tinyk32(a) || a->a.scale || a->a.shift || a->a.sub) return T3D_ERR_ARG;
+  if (a->dtype != T3D_F32 || a->a.dtype != T3D_F32 || !fwd_takes_tinyk(a) || a->a.scale || a->a.shift || a->a.sub) return T3D_ERR_ARG;
   return T3D_OK;
 }
 
@@ -5026,35 +4925,53 @@ extern "C" int t3d_step_head(const t3d_pointmlp_fwd_args* a, const float* params
   return t3d_x3_step_head(a, params, planes_fwd, planes_dgrad, plane_stride, table, n_entries, n_blocks, hyper, sched, static_cast<hipStream_t>(stream));
 }
 
-// ---- does the `_r` launcher host a rider set for these arguments? (1 / 0; negative: the arguments are rejected) ----
-static const t3d_rider_set* query_set() {
-  static const t3d_rider_set q = []() { t3d_rider_set r{}; r.n_ops = 1; r.n_wg = 1; r.sync = reinterpret_cast<unsigned*>(16); return r; }();
-  return &q;
-}
 extern "C" int t3d_gemm_arithmetic(int arith, int dtype, int K, int N, int kind) {
   if (dtype == T3D_BF16) return T3D_ARITH_BF16;
   bool x3 = false;
   switch (kind) {      // each launcher's own shape rule (the element-type / pointer conditions of a launch are the caller's to know)
-    case T3D_GEMM_FWD: x3 = K % BKX == 0 && x3_layer(arith, K, N); break;                                                   // t3d_pointmlp_fwd[_r]
-    case T3D_GEMM_BWD: x3 = N % BKX == 0 && K % 64 == 0 && (K <= 64 || K % 128 == 0) && x3_layer_bwd(arith, K, N); break;    // t3d_pointmlp_bwd[_r]: both tile kinds
-    case T3D_GEMM_DGRAD: x3 = N % BKX == 0 && x3_layer_bwd(arith, K, N); break;                                             // t3d_pointmlp_dgrad (dense dy)
-    case T3D_GEMM_WGRAD: x3 = K % 64 == 0 && (K <= 64 || K % 128 == 0) && x3_layer_bwd(arith, K, N); break;                  // t3d_pointmlp_wgrad[_r]: whole k-tiles of an fp32 source
-    case T3D_GEMM_GRAM: x3 = x3_layer_bwd(arith, K, K); break;                                                              // t3d_pointmlp_gram, t3d_pool_bwd_stage1 (N ignored)
-    case T3D_GEMM_DGRAD_GRAM: x3 = K % BKX == 0 && x3_layer_bwd(arith, K, K); break;                                        // t3d_pointmlp_dgrad_gram, t3d_pool_bwd_stage2
+    case T3D_GEMM_FWD: x3 = x3_fwd_shape(arith, K, N); break;                                  // t3d_pointmlp_fwd[_r]
+    case T3D_GEMM_BWD: x3 = x3_bwd_shape(arith, K, N, wgrad_tk_by_shape(K)); break;            // t3d_pointmlp_bwd[_r]: both tile kinds
+    case T3D_GEMM_DGRAD: x3 = x3_dgrad_shape(arith, K, N); break;                              // t3d_pointmlp_dgrad (dense dy)
+    case T3D_GEMM_WGRAD: x3 = x3_wgrad_shape(arith, K, N, wgrad_tk_by_shape(K)); break;        // t3d_pointmlp_wgrad[_r]: whole k-tiles of an fp32 source
+    case T3D_GEMM_GRAM: x3 = x3_gram_shape(arith, K); break;                                   // t3d_pointmlp_gram, t3d_pool_bwd_stage1 (N ignored)
+    case T3D_GEMM_DGRAD_GRAM: x3 = x3_dgrad_gram_shape(arith, K); break;                       // t3d_pointmlp_dgrad_gram, t3d_pool_bwd_stage2
     default: return T3D_ERR_ARG;
   }
   return x3 ? T3D_ARITH_BF16X3 : T3D_ARITH_FP32_MFMA;
 }
-extern "C" int t3d_pointmlp_fwd_hosts_riders(const t3d_pointmlp_fwd_args* a) { return t3d_pointmlp_fwd_r(a, query_set(), T3D_QUERY_STREAM); }
-extern "C" int t3d_pointmlp_wgrad_hosts_riders(const t3d_pointmlp_wgrad_args* a) { return t3d_pointmlp_wgrad_r(a, query_set(), T3D_QUERY_STREAM); }
+
+// ---- does the `_r` launcher host a rider set for these arguments? (1 / 0; negative: the arguments would be rejected) ----
+// The launcher's own selection step, without a stream or a set: nothing here can launch.
+extern "C" int t3d_pointmlp_fwd_hosts_riders(const t3d_pointmlp_fwd_args* a) {
+  T3D_ABI_TAKE(pointmlp_fwd_args, a);
+  t3d_fwd_sel sel;
+  const int rc = select_fwd(a, &sel);
+  return rc != T3D_OK ? rc : sel.hosts;
+}
+extern "C" int t3d_pointmlp_wgrad_hosts_riders(const t3d_pointmlp_wgrad_args* a) {
+  T3D_ABI_TAKE(pointmlp_wgrad_args, a);
+  t3d_wgrad_sel sel;
+  const int rc = select_wgrad(a, &sel);
+  return rc != T3D_OK ? rc : sel.hosts;
+}
 extern "C" int t3d_pointmlp_bwd_hosts_riders(const t3d_pointmlp_dgrad_args* d, const t3d_pointmlp_wgrad_args* w) {
-  return t3d_pointmlp_bwd_r(d, w, query_set(), T3D_QUERY_STREAM);
+  T3D_ABI_TAKE(pointmlp_dgrad_args, d);
+  T3D_ABI_TAKE(pointmlp_wgrad_args, w);
+  t3d_bwd_sel sel;
+  const int rc = select_bwd(d, w, &sel);
+  return rc != T3D_OK ? rc : sel.hosts;
 }
 extern "C" int t3d_pool_bwd_stage1_hosts_riders(const t3d_pointmlp_gram_args* g, const t3d_act_colsum_args* c, const t3d_pool_bwd_prep_args* q) {
-  return t3d_pool_bwd_stage1_r(g, c, q, query_set(), T3D_QUERY_STREAM);
+  T3D_ABI_TAKE(pointmlp_gram_args, g);
+  t3d_stage1_sel sel;
+  const int rc = select_stage1(g, c, q, &sel);
+  return rc != T3D_OK ? rc : sel.hosts;
 }
 extern "C" int t3d_pool_bwd_stage2_hosts_riders(const t3d_pool_wgrad_finish_args* f, const t3d_pointmlp_dgrad_gram_args* d) {
-  return t3d_pool_bwd_stage2_r(f, d, query_set(), T3D_QUERY_STREAM);
+  T3D_ABI_TAKE(pointmlp_dgrad_gram_args, d);
+  t3d_stage2_sel sel;
+  const int rc = select_stage2(f, d, &sel);
+  return rc != T3D_OK ? rc : sel.hosts;
 }
 
 #ifdef T3D_TRACE
