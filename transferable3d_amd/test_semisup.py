@@ -21,6 +21,7 @@ from transferable3d_amd.config import make_parser                        # noqa:
 from transferable3d_amd.constants import NUM_HEADING_BIN, NUM_SIZE_CLUSTER   # noqa: E402
 from transferable3d_amd.synthetic import make_batch                      # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                  # noqa: E402
+from transferable3d_amd.train_common import add_point_arguments, boxes_from_labels, finish_flags      # noqa: E402
 
 
 def build_flags(argv=None):
@@ -36,7 +37,6 @@ def build_flags(argv=None):
     cfg.add_argument('--pred_prefix', default='F2_')
     cfg.add_argument('--refine', default=None)
     cfg.add_argument('--output', default=None)
-    cfg.add_argument('--no_rgb', action='store_true')
     cfg.add_argument('--mask_pc_for_boxpc', action='store_true', help='Mask the PC before giving to BoxPC network.')
     cfg.add_argument('--use_oracle_mask', action='store_true', help='ground-truth segmentation instead of the seg net\'s (use_oracle_mask of the reference\'s get_model / test)')
     cfg.add_argument('--use_boxpc_fit_prob', action='store_true')
@@ -47,13 +47,9 @@ def build_flags(argv=None):
     cfg.add_argument('--result_dir', default=None, help='write <class>_pred.txt files for the MATLAB evaluation')
     cfg.add_argument('--gt_path', default=None, help='frustum file with the 3-D labels to evaluate detections against (evaluate.py --gt_path)')
     cfg.add_argument('--data_path', default=None, help='frustum file of the reference (frustums/*.zip.pickle); classes: --SUNRGBD_SEMI_TEST_CLS')
-    cfg.add_argument('--num_channels', type=int, default=None)
     cfg.add_argument('--num_frustums', type=int, default=64)
-    cfg.add_argument('--seed', type=int, default=0)
-    cfg.add_argument('--dtype', default='f32', choices=['f32', 'bf16'],
-                     help='element type of the per-point layer tensors and GEMM operands (bf16: BASELINE configs[4]; weights, statistics, heads, losses and Adam stay fp32)')
-    FLAGS = cfg.parse_special_args(argv)
-    FLAGS.NUM_CHANNELS = FLAGS.num_channels if FLAGS.num_channels else (3 if FLAGS.no_rgb else 6)
+    add_point_arguments(cfg)           # --no_rgb --num_channels --seed --dtype
+    FLAGS = finish_flags(cfg.parse_special_args(argv))
     FLAGS.SEMI_MODEL = FLAGS.semi_type
     return FLAGS
 
@@ -158,14 +154,11 @@ def test(FLAGS, rt=None, log=print):
                    list(scores), list(np.argmax(oh, 1)), list(range(n)), None, None]
     if FLAGS.evaluate:
         # evaluate.py:27-76 against the label boxes of the same frustums (the reference builds them from the SUN-RGBD label files)
-        from transferable3d_amd.constants import MEAN_DIMS_ARR, class2type
-        from transferable3d_amd.eval_det import evaluate_predictions, get_3d_box, get_ap_info
+        from transferable3d_amd.constants import class2type
+        from transferable3d_amd.eval_det import evaluate_predictions, get_ap_info
         classes = [class2type[i] for i in range(10)]
         lab = {k: np.concatenate([b[k] for b in batches]) for k in ('y_center', 'y_orient_cls', 'y_orient_reg', 'y_dims_cls', 'y_dims_reg')}
-        gt_all = {i: [(classes[int(np.argmax(oh[i]))],
-                       get_3d_box(MEAN_DIMS_ARR[int(lab['y_dims_cls'][i])] + lab['y_dims_reg'][i],
-                                  int(lab['y_orient_cls'][i]) * (2 * np.pi / NUM_HEADING_BIN) + float(lab['y_orient_reg'][i]), lab['y_center'][i]))]
-                  for i in range(n)}
+        gt_all = {i: [gt] for i, gt in enumerate(boxes_from_labels(dict(lab, one_hot_vec=oh)))}
         _, _, ap, mean_ap = evaluate_predictions(predictions, gt_all, classes, rt=sess.g.rt)
         log(get_ap_info(ap, mean_ap))
     if FLAGS.output:

@@ -10,11 +10,10 @@ with the label box before / after the predicted deltas; `--eval_batches n` adds 
   python -m transferable3d_amd.train_boxpc --BOX_PC_MASK_REPRESENTATION A --BOXPC_WEIGHT_DELTA 4 --num_point 1024 \
       --num_channels 4 --max_epoch 1 --steps_per_epoch 100
 """
+import argparse
 import os
 import sys
 import time
-
-import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,11 +23,12 @@ from transferable3d_amd import dataset as _dataset                      # noqa: 
 from transferable3d_amd.dataset import _checked_prob, reference_drop_subset      # noqa: E402
 from transferable3d_amd.synthetic import make_batch                     # noqa: E402
 from transferable3d_amd.tf_checkpoint import Saver, restore_model  # noqa: E402
+from transferable3d_amd.train_common import add_training_arguments, eval_seed, finish_flags, run_epochs, start      # noqa: E402
 
 
 def build_flags(argv=None):
     cfg = make_parser()
-    cfg.add_argument('--train_data', type=str, default='synthetic')
+    add_training_arguments(cfg, log_dir='log_boxpc', steps_per_epoch=None, model='boxpc_sunrgbd')
     cfg.add_argument('--classes_to_drop_prob', type=float, default=None,
                      help='every frustum of the classes without 3-D labels (SUNRGBD_SEMI_TEST_CLS) is left out of the data set with this '
                           'probability; 1 drops them all [default: 1 for --frustum_file; synthetic data (--device_data) has always held all ten '
@@ -38,34 +38,7 @@ def build_flags(argv=None):
     cfg.add_argument('--use_mini', action='store_true', help='(accepted: the data comes from --frustum_file / --device_data)')
     cfg.add_argument('--train_all', action='store_true', help='TRAIN_CLS = TEST_CLS = all 10 classes (train_boxpc.py:73-75): every class is then a class to drop, so pass '
                           '--classes_to_drop_prob below 1 with it (at 1 nothing is left, as in the reference)')
-    cfg.add_argument('--gpu', type=int, default=0)
-    cfg.add_argument('--model', default='boxpc_sunrgbd')
-    cfg.add_argument('--log_dir', default='log_boxpc')
-    cfg.add_argument('--num_point', type=int, default=2048)
-    cfg.add_argument('--max_epoch', type=int, default=31)
-    cfg.add_argument('--batch_size', type=int, default=32)
-    cfg.add_argument('--learning_rate', type=float, default=0.001)
-    cfg.add_argument('--momentum', type=float, default=0.9)
-    cfg.add_argument('--optimizer', default='adam', help='adam or momentum [default: adam]')
-    cfg.add_argument('--decay_step', type=int, default=800000)
-    cfg.add_argument('--decay_rate', type=float, default=0.5)
-    cfg.add_argument('--use_one_hot', action='store_true')
-    cfg.add_argument('--no_rgb', action='store_true')
-    cfg.add_argument('--restore_model_path', default=None)
-    cfg.add_argument('--ckpt_format', default='npz', choices=['npz', 'tf'], help='tf: TensorFlow Saver bundle')
-    cfg.add_argument('--synthetic', action='store_true')
-    cfg.add_argument('--num_channels', type=int, default=None)
-    cfg.add_argument('--steps_per_epoch', type=int, default=None, help='[default: one pass over the data set; 100 for --synthetic batches]')
-    cfg.add_argument('--seed', type=int, default=0)
-    cfg.add_argument('--dtype', default='f32', choices=['f32', 'bf16'],
-                     help='element type of the per-point layer tensors and GEMM operands (bf16: BASELINE configs[4]; weights, statistics, heads, losses and Adam stay fp32)')
-    cfg.add_argument('--eval_file', default=None, help='held-out frustum file of the reference for eval_one_epoch (with --frustum_file / --device_data)')
-    cfg.add_argument('--frustum_file', default=None, help='train from a frustum file of the reference (frustums/*.zip.pickle) held in HBM')
-    cfg.add_argument('--eval_batches', type=int, default=0, help='held-out synthetic batches evaluated after every epoch (eval_one_epoch)')
-    cfg.add_argument('--device_data', type=int, default=0, metavar='F',
-                     help='F > 0: F synthetic frustums resident in HBM; batches and the perturbed-box samples are made on the device')
-    FLAGS = cfg.parse_special_args(argv)
-    FLAGS.NUM_CHANNELS = FLAGS.num_channels if FLAGS.num_channels else (3 if FLAGS.no_rgb else 6)
+    FLAGS = finish_flags(cfg.parse_special_args(argv))
     # the synthetic source has always trained on every class: there the flag counts only when it was given
     FLAGS.classes_to_drop_prob_given = FLAGS.classes_to_drop_prob is not None
     FLAGS.classes_to_drop_prob = _checked_prob('classes_to_drop_prob', 1.0 if FLAGS.classes_to_drop_prob is None else FLAGS.classes_to_drop_prob)
@@ -101,11 +74,8 @@ def open_boxpc_training_set(rt, FLAGS, C, seed, log=print):
 
 def train(FLAGS, rt=None, log=print):
     # data parallel: one process per GPU, own samples per replica, one all-reduce of the gradients per step; rank 0 logs
-    world, rank, pg = api.init_data_parallel(rt, FLAGS.gpu)
-    if rank != 0:
-        log = lambda *a, **k: None
+    world, rank, pg, log = start(FLAGS, rt, log)
     B, N, C = FLAGS.batch_size, FLAGS.num_point, FLAGS.NUM_CHANNELS
-    os.makedirs(FLAGS.log_dir, exist_ok=True)
     with api.Graph(rt=rt, seed=FLAGS.seed, dtype=FLAGS.dtype).as_default() as g:
         pls = MODEL.placeholder_inputs(B, N, C)
         pc_pl, one_hot_vec_pl, y_seg_pl, x_center_pl, x_orient_cls_pl, x_orient_reg_pl, x_dims_cls_pl, x_dims_reg_pl, \
@@ -120,7 +90,6 @@ def train(FLAGS, rt=None, log=print):
         saver = Saver(max_to_keep=5)      # train_boxpc.py:261
         if FLAGS.restore_model_path:
             restore_model(g, FLAGS.restore_model_path)
-        step, mean_loss = 0, 0.0
         from transferable3d_amd.boxpc_stats import ALL_CLASSES, BoxDeltaIOUStats, ClassificationStats, record_batch
         fit_lo = float(FLAGS.BOXPC_FIT_BOUNDS[0])
         fetch_stats = [loss, end_points['pred_boxpc_fit'], end_points['boxpc_delta_center'], end_points['boxpc_delta_size'],
@@ -147,7 +116,7 @@ def train(FLAGS, rt=None, log=print):
                     eval_source.load(i)
                     feed = {}
                 else:
-                    feed = feed_of(make_batch(B, N, C, seed=FLAGS.seed * 1000003 + 900000 + i, boxpc=True))
+                    feed = feed_of(make_batch(B, N, C, seed=eval_seed(FLAGS, i), boxpc=True))
                 feed[is_training_pl] = False
                 out = sess.run(fetch_stats, feed_dict=feed)
                 record_batch(stats[0], stats[1], stats[2], fit_lo, out[0], out[1], out[2:5], g.inputs)
@@ -163,64 +132,43 @@ def train(FLAGS, rt=None, log=print):
         ds = open_boxpc_training_set(g.rt, FLAGS, C, FLAGS.seed + 17 * rank, log)
         if ds is not None:
             api.assert_ranks_agree(pg, world, ds.n_active, 'the length of the Box-PC data set')
-            if FLAGS.eval_batches > 0 or FLAGS.eval_file:
+            if FLAGS.eval_batches > 0 or FLAGS.eval_file:      # as found: opened before training, also for an --eval_file that is never evaluated
                 eval_source = open_eval_source(g, FLAGS, classes=list(FLAGS.SUNRGBD_SEMI_TRAIN_CLS), boxpc_perturb=FLAGS)
             # BOXPC_SAMPLING_METHOD 'SAMPLE': class-balanced batches with probability BOXPC_SAMPLE_EQUAL_CLASS_WITH_PROB
             # (train_boxpc.py:323-328); 'BATCH': the epoch permutation
             eq = float(FLAGS.BOXPC_SAMPLE_EQUAL_CLASS_WITH_PROB) if FLAGS.BOXPC_SAMPLING_METHOD == 'SAMPLE' else 0.0
             g.use_device_dataset(ds, seed=FLAGS.seed * 7919 + rank, boxpc_perturb=FLAGS, equal_class_prob=eq)
+            # as found: class-balanced sampling never partitions (100 steps unless --steps_per_epoch says otherwise)
             if eq == 0.0:            # 'BATCH': an epoch is at most one pass over the data set (whole batches, train_boxpc.py:316-321)
                 FLAGS.steps_per_epoch = ds.partition(rank, world, B, FLAGS.steps_per_epoch)
         if not FLAGS.steps_per_epoch:
             FLAGS.steps_per_epoch = 100
-        for epoch in range(FLAGS.max_epoch):
-            t0, loss_sum = time.time(), 0.0
-            if ds is not None:
-                # box_pc_fit_dataset.py 'BATCH' sampling: an epoch permutation; the loss is fetched every 10th step only
-                ds.shuffle(FLAGS.seed * 1000003 + epoch)
-                n_logged = 0
-                stats = new_stats()
-                for it in range(FLAGS.steps_per_epoch):
-                    if it % 10 == 9 or it == FLAGS.steps_per_epoch - 1:
-                        out = sess.run(fetch_stats + [train_op])
-                        record_batch(stats[0], stats[1], stats[2], fit_lo, out[0], out[1], out[2:5], g.inputs)
-                        loss_sum += float(out[0])
-                        n_logged += 1
-                    else:
-                        sess.run([train_op])
-                    step += 1
-                mean_loss = loss_sum / n_logged
-                log('**** EPOCH %03d ****  mean loss: %f  (%.1f frustums/s, samples made on the device)' % (
-                    epoch, mean_loss, FLAGS.steps_per_epoch * B / (time.time() - t0)))
-                report('train (every 10th step)', stats)
-                if FLAGS.eval_batches > 0 and rank == 0:
-                    eval_one_epoch(epoch)
-                if epoch % 5 == 0 and rank == 0:
-                    sess.check_riders()      # never checkpoint weights a timed-out rider barrier may have corrupted
-                    log('Model saved in file: %s' % saver.save(FLAGS.log_dir, epoch, g, FLAGS.ckpt_format))
-                continue
-            stats = new_stats()
-            for _ in range(FLAGS.steps_per_epoch):
-                feed = feed_of(make_batch(B, N, C, seed=FLAGS.seed * 1000003 + step * world + rank, boxpc=True))
-                feed[is_training_pl] = True
-                out = sess.run(fetch_stats + [train_op], feed_dict=feed)
-                record_batch(stats[0], stats[1], stats[2], fit_lo, out[0], out[1], out[2:5], g.inputs)
-                loss_sum += float(out[0])
-                step += 1
-            mean_loss = loss_sum / FLAGS.steps_per_epoch
-            log('**** EPOCH %03d ****  mean loss: %f  (%.1f frustums/s incl. host batch synthesis)' % (
-                epoch, mean_loss, FLAGS.steps_per_epoch * B / (time.time() - t0)))
-            report('train', stats)
-            if FLAGS.eval_batches > 0 and rank == 0:
+        acc = argparse.Namespace(mean_loss=0.0)
+
+        def begin_epoch():
+            acc.stats, acc.loss_sum = new_stats(), 0.0
+
+        def record(out):
+            record_batch(acc.stats[0], acc.stats[1], acc.stats[2], fit_lo, out[0], out[1], out[2:5], g.inputs)
+            acc.loss_sum += float(out[0])
+
+        def epoch_lines(epoch, n_fetched, n_steps, t0):
+            acc.mean_loss = acc.loss_sum / n_fetched
+            log('**** EPOCH %03d ****  mean loss: %f  (%.1f frustums/s%s)' % (
+                epoch, acc.mean_loss, n_steps * B / (time.time() - t0),       # as found: the rate of one replica, not times `world`
+                ', samples made on the device' if ds is not None else ' incl. host batch synthesis'))
+            report('train (every 10th step)' if ds is not None else 'train', acc.stats)
+
+        def evaluate(epoch):
+            if FLAGS.eval_batches > 0:      # as found: --eval_file alone opens the eval source (above) and evaluates nothing
                 eval_one_epoch(epoch)
-            if epoch % 5 == 0 and rank == 0:
-                sess.check_riders()      # never checkpoint weights a timed-out rider barrier may have corrupted
-                path = saver.save(FLAGS.log_dir, epoch, g, FLAGS.ckpt_format)
-                log('Model saved in file: %s' % path)
-        sess.check_riders()
-        final = g.vars.state_dict()
-    api.finish_data_parallel(world)
-    return final, mean_loss
+
+        final = run_epochs(
+            FLAGS, sess, saver, world, rank, log, ds, is_training_pl, fetches=fetch_stats + [train_op], train_op=train_op,
+            fetch_on=lambda it, n_steps: it % 10 == 9 or it == n_steps - 1,      # as found: every 10th step and the last
+            host_feed=lambda seed, it, step: feed_of(make_batch(B, N, C, seed=seed, boxpc=True)),
+            begin_epoch=begin_epoch, record=record, epoch_lines=epoch_lines, evaluate=evaluate)
+    return final, acc.mean_loss
 
 
 if __name__ == '__main__':
