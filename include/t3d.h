@@ -1991,6 +1991,74 @@ typedef struct {
 #define T3D_V2_SIZE_sunrgbd_bootstrap_args 88
 int t3d_sunrgbd_eval_bootstrap(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_bootstrap_args* boot, t3d_stream_t stream);
 
+/* ---- Soft-NMS: a box that overlaps a better one keeps its place and loses confidence (Bodla et al., ICCV 2017; csrc/soft_nms.hip;
+ *      nms.DeviceSoftNms, detect --soft_nms) ----
+ * t3d_detect_nms makes one decision per pair, so a threshold low enough to remove a duplicate report also removes a true neighbour
+ * (chairs in a row).  Here the confidence of an overlapped box is multiplied down by a function of the IoU: the duplicate moves to the
+ * tail of the ranked list, the neighbour with moderate overlap keeps most of its confidence.  The reference has no such step; it is
+ * opt-in.  n, n_groups, metric, corners, score, group_offsets, members and max_group are those of t3d_detect_nms, under the same contract
+ * and with the same leading layout; the IoU is the same box3d_iou_corners.  Per group:
+ *   1 Working score   every box starts with its input score.  A listed box whose score is not a finite number above 0 takes no part:
+ *                     it decays nothing and is never decayed, and comes back kept -- keep 1, suppressed_by -1, score_out the input
+ *                     bits, n_decays 0.  The others are live.
+ *   2 Selection       until no box is live: the live box with the largest working score is selected; on equal scores the lower box
+ *                     index wins, as in t3d_detect_nms.  It is kept (keep 1, suppressed_by -1), is live no longer, and its score_out is
+ *                     its working score at that moment.
+ *   3 Decay           for every box j still live, IoU(selected, j) under `metric`, THE SELECTED BOX AS THE FIRST ARGUMENT (both boxes
+ *                     and their order are the group's own: nothing outside the group enters).  A NaN IoU decays nothing.
+ *                       T3D_SOFT_NMS_GAUSSIAN   if IoU > 0:          score *= exp(-IoU^2 / sigma)
+ *                       T3D_SOFT_NMS_LINEAR     if IoU > threshold:  score *= 1 - IoU
+ *                     in fp32 (expf).  Two boxes whose centres lie farther apart than their half diagonals add up to cannot touch:
+ *                     their IoU is 0 and is not computed.  Both boxes are handed to box3d_iou_corners with x and z relative to the
+ *                     selected box's first corner: far from the origin the function's rectangle areas lose digits (1e-4 of the
+ *                     ground-plane IoU at 45 m), which a decayed score would carry; t3d_detect_nms passes them as they come.
+ *   4 Prune           a box whose working score falls below min_score (strictly) by a decay leaves the group: keep 0, suppressed_by =
+ *                     the selected box whose decay took it below the floor, score_out the value it fell to.  Only a decayed box is
+ *                     pruned: a box nothing overlapped keeps its score bits, whatever they are.
+ *   5 n_decays        n_decays[j] = the number of selected boxes that decayed j.
+ *   6 Unlisted boxes  a box in no group is not visited: its four outputs keep what they held, as in t3d_detect_nms.
+ * Consequences: with LINEAR, threshold T and a min_score above every score, every decayed box is pruned at its first decay, and keep /
+ * suppressed_by are those of t3d_detect_nms at T and the same metric, byte for byte, for every box that takes part (where no IoU lies
+ * within the rounding of the two calls, a few 1e-5, of T); and a group's outputs are a function of its own boxes only, wherever they
+ * sit in the call.
+ *   Errors            as t3d_detect_nms (T3D_ERR_SHAPE for max_group > T3D_DETECT_NMS_MAX_GROUP; T3D_ERR_ARG for n, n_groups or max_group
+ *                     < 0, an unknown metric, a null corners / score / group_offsets / members / score_out / keep / suppressed_by /
+ *                     n_decays on a call that is not empty), and T3D_ERR_ARG for an unknown method, for sigma not a finite number above
+ *                     0 with GAUSSIAN, for min_score NaN or negative, and for a workspace smaller than
+ *                     T3D_DETECT_SOFT_NMS_WORKSPACE_BYTES(n, max_group) or, where that is not 0, null or misaligned.  Nothing is
+ *                     launched then.  n == 0, n_groups == 0 or max_group == 0: T3D_OK without a launch.
+ * One launch on `stream`: a group has LPG lanes, the power of two >= max_group / 4, at most 64, so 64 / LPG groups share a wave and walk
+ * their selections in lockstep; a lane owns the boxes at list positions lane, lane + LPG, ... of its group (up to 4 where max_group <=
+ * 256, at most 16) and keeps their live bits in a register; the working scores live in score_out.  Per step each lane finds its best live box, a butterfly of shuffles
+ * finds the group's, every lane reads the winner's corners (one address: a broadcast) and decays its own boxes.  No workspace (the
+ * macro is 0 and `workspace` may be NULL; the fields are there for a form that stores IoUs), no LDS, no atomics, no allocation, no
+ * host synchronisation: equal inputs give equal bytes. */
+#define T3D_SOFT_NMS_GAUSSIAN 0
+#define T3D_SOFT_NMS_LINEAR 1
+#define T3D_DETECT_SOFT_NMS_WORKSPACE_BYTES(n, max_group) ((uint64_t)0 * ((uint64_t)(n) + (uint64_t)(max_group)))
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_soft_nms_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_groups; int metric;
+  const float* corners;            /* [n,8,3], as for t3d_detect_nms */
+  const float* score;              /* [n] */
+  const int32_t* group_offsets;    /* [n_groups + 1] */
+  const int32_t* members;          /* [group_offsets[n_groups]] */
+  float threshold;                 /* LINEAR: the IoU above which a box is decayed; GAUSSIAN: not read */
+  int max_group;
+  int method;                      /* T3D_SOFT_NMS_* */
+  float sigma;                     /* GAUSSIAN: > 0; LINEAR: not read */
+  float min_score;                 /* >= 0: the floor below which a decayed box is pruned */
+  int reserved;                    /* 0 */
+  void* workspace;
+  uint64_t workspace_bytes;
+  float* score_out;                /* [n] out: the working score a box was selected or pruned with */
+  uint8_t* keep;                   /* [n] out: 0 for a pruned box */
+  int32_t* suppressed_by;          /* [n] out: -1, or the selected box whose decay pruned this one */
+  int32_t* n_decays;               /* [n] out */
+} t3d_detect_soft_nms_args;
+#define T3D_V2_SIZE_detect_soft_nms_args 120
+int t3d_detect_soft_nms(const t3d_detect_soft_nms_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -398,6 +398,21 @@ def detect_nms_workspace_bytes(n, max_group):
     return (n + 1) // 2 * 8 + n * ((max_group + 63) // 64) * 8
 
 
+SOFT_NMS_GAUSSIAN, SOFT_NMS_LINEAR = 0, 1       # t3d.h T3D_SOFT_NMS_*
+SOFT_NMS_METHODS = {'gaussian': SOFT_NMS_GAUSSIAN, 'linear': SOFT_NMS_LINEAR}
+
+
+class DetectSoftNmsArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_groups', i32), ('metric', i32), ('corners', F), ('score', F), ('group_offsets', I),
+                ('members', I), ('threshold', f32), ('max_group', i32), ('method', i32), ('sigma', f32), ('min_score', f32), ('reserved', i32),
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('score_out', F), ('keep', U8), ('suppressed_by', I), ('n_decays', I)]
+
+
+def detect_soft_nms_workspace_bytes(n, max_group):
+    """t3d.h T3D_DETECT_SOFT_NMS_WORKSPACE_BYTES"""
+    return 0
+
+
 RENDER_RGB, RENDER_LABEL, RENDER_FLAT = 0, 1, 2      # t3d.h T3D_RENDER_*
 
 
@@ -627,6 +642,7 @@ ENTRY_POINTS = {
     't3d_detect_fuse': [C.POINTER(DetectFuseArgs), VP],
     't3d_detect_ensemble': [C.POINTER(DetectEnsembleArgs), VP],
     't3d_detect_nms_sweep': [C.POINTER(DetectNmsSweepArgs), VP],
+    't3d_detect_soft_nms': [C.POINTER(DetectSoftNmsArgs), VP],
     't3d_sunrgbd_eval_sweep': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdSweepArgs), VP],
     't3d_bootstrap_weights': [C.POINTER(BootstrapWeightsArgs), VP],
     't3d_sunrgbd_eval_bootstrap': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdBootstrapArgs), VP],

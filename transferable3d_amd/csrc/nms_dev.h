@@ -1,5 +1,6 @@
 // Device code that t3d_detect_nms (nms.hip) and t3d_detect_nms_sweep (nms_sweep.hip) share: the group of a list position, a box's key and
 // the order of every group by counting.  The sweep ranks its boxes with the very kernel the single suppression ranks them with.
+// t3d_detect_soft_nms (soft_nms.hip) takes NMS_THREADS, nms_group_at and nms_box_ok from here: it has no fixed order to share.
 #pragma once
 #include "common.h"
 
@@ -9,8 +10,19 @@ constexpr int NMS_THREADS = 256;
 
 struct NmsGroup { int first, size; };      // size < 0: no group (past the lists, or a list that breaks the contract)
 
+// Group g of the lists, as the caller declared them: {first, size}, or size < 0 for a g past the lists and for offsets that break the
+// contract (descending, leaving [0, n], a group larger than max_group).  An empty group has size 0.
+template <class Args>      // t3d_detect_nms_args, or a struct with its leading fields (t3d_detect_soft_nms_args)
+__device__ __forceinline__ NmsGroup nms_group_at(const Args& a, int g) {
+  if (g < 0 || g >= a.n_groups) return {0, -1};
+  const int f = a.group_offsets[g], e = a.group_offsets[g + 1];
+  if (f < 0 || e < f || e > a.n || e - f > a.max_group) return {0, -1};
+  return {f, e - f};
+}
+
 // The group that holds position p of the concatenated lists: the first g with group_offsets[g + 1] > p (empty groups are stepped over).
-__device__ __forceinline__ NmsGroup nms_group_of(const t3d_detect_nms_args& a, int p) {
+template <class Args>
+__device__ __forceinline__ NmsGroup nms_group_of(const Args& a, int p) {
   int lo = 0, hi = a.n_groups;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -22,13 +34,15 @@ __device__ __forceinline__ NmsGroup nms_group_of(const t3d_detect_nms_args& a, i
   return {f, e - f};
 }
 
-__device__ __forceinline__ bool nms_box_ok(const t3d_detect_nms_args& a, int box) { return (unsigned)box < (unsigned)a.n; }
+template <class Args>      // t3d_detect_nms_args, or a struct with its leading fields (t3d_detect_soft_nms_args)
+__device__ __forceinline__ bool nms_box_ok(const Args& a, int box) { return (unsigned)box < (unsigned)a.n; }
 
 __device__ __forceinline__ float nms_key(const t3d_detect_nms_args& a, int box) {
   const float s = nms_box_ok(a, box) ? a.score[box] : 0.f;
   return s != s ? -__builtin_inff() : s;
 }
 
+#ifndef NMS_DEV_NO_ORDER      // (a unit that ranks nothing defines it: soft_nms.hip)
 __global__ __launch_bounds__(NMS_THREADS) void k_nms_order(const t3d_detect_nms_args a, int32_t* order) {
   const int p = blockIdx.x * NMS_THREADS + threadIdx.x;
   if (p >= a.n) return;
@@ -46,5 +60,6 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms_order(const t3d_detect_nms_
   order[g.first + r] = box;
   if (a.rank && nms_box_ok(a, box)) a.rank[box] = r;
 }
+#endif
 
 }  // namespace

@@ -5,6 +5,7 @@
         --result_dir R [--official_eval [--diagnose [--diagnose_bg 0.1] [--diagnose_json FILE]]]
         # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}] [--nms_fuse] [--nms_fuse_iou V]]
+        [--soft_nms gaussian [--soft_nms_sigma S] | --soft_nms linear --nms_iou T] [--soft_nms_min_prob F] [--nms_metric {3d,bev}]
         [--vis_dir DIR [--vis_max N] [--vis_gt] [--vis_suppressed]]
         [--consistency] [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] [--consistency_json FILE]
         [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]]
@@ -33,11 +34,19 @@ kept, and every score, stay; a kept box without a suppressed box stays byte for 
 lets only the suppressed boxes above IoU V vote.  Records and --vis_dir legends gain 'votes'.  Without --nms_fuse every output is what
 it was, byte for byte.
 
+--soft_nms {gaussian,linear}: Soft-NMS in place of the suppression (t3d_detect_soft_nms, nms.DeviceSoftNms; Bodla et al., ICCV 2017).
+Neighbouring true objects overlap in 3-D, so a threshold that removes duplicates removes neighbours; here a box that overlaps a better
+one of its image and class keeps its place and its confidence is multiplied by exp(-IoU^2 / sigma) (gaussian; --soft_nms_sigma, default
+0.5) or, above --nms_iou T, by 1 - IoU (linear).  The decayed confidence is what the result files' last column, --official_eval and the
+14-list carry; in records, legends and --consistency_json rows 'prob' stays the 2-D detector's and 'soft_prob' / 'decays' say what
+became of it.  A detection that falls below --soft_nms_min_prob (default 0.001) is dropped like a suppressed one.  It does not go with
+--nms_score score, --nms_fuse or --sweep.  Without the flag every output is what it was, byte for byte.
+
 --vis_dir DIR: for each of the first --vis_max scenes (default 50) with at least one detection, DIR/<id>.png -- the camera image with the
 kept 3-D boxes in class colours and their 2-D rectangles, beside a bird's-eye panel of the scene's points with the same boxes -- and
 DIR/<id>.json, the legend (there is no text in the pictures).  t3d_render (render.py) paints them from the corners where the decode
 wrote them and from the device copy of the points the extraction made; only the finished panels come back.  --vis_gt adds the label
-boxes in green, --vis_suppressed (with --nms_iou) the boxes NMS dropped in grey.  Nothing else changes with these flags.
+boxes in green, --vis_suppressed (with --nms_iou or --soft_nms) the boxes that were dropped in grey.  Nothing else changes with these flags.
 
 --consistency: t3d_detect_consistency (consistency.py) follows every batch's decode and measures, without ground truth, how well each 3-D
 box agrees with what it was predicted from: reproj_iou (its reprojection against its 2-D box; the image size, read from the JPEG's
@@ -121,7 +130,7 @@ class Vis:
 
     def __init__(self, vis_dir, vis_max=50, vis_gt=False, vis_suppressed=False, nms=False):
         if vis_suppressed and not nms:
-            raise ValueError('--vis_suppressed shows what --nms_iou dropped: it needs --nms_iou')
+            raise ValueError('--vis_suppressed shows what --nms_iou / --soft_nms dropped: it needs one of them')
         if int(vis_max) < 0:
             raise ValueError('--vis_max must not be negative')
         self.dir, self.max, self.gt, self.suppressed = vis_dir, int(vis_max), bool(vis_gt), bool(vis_suppressed)
@@ -218,6 +227,8 @@ class Vis:
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
                 if d.n_votes is not None:
                     entry['votes'] = int(d.n_votes[r])
+                if d.soft_prob is not None:
+                    entry.update(soft_fields(d, r))
                 if d.view_iou is not None:
                     entry.update(view_fields(d, r))
                 if d.reproj_iou is not None:
@@ -235,6 +246,11 @@ def consistency_fields(d, i, as_lists=False):
             'mask_in_box': float(d.mask_in_box[i]), 'seg_box_iou': float(d.seg_box_iou[i]), 'flags': int(d.flags[i])}
 
 
+def soft_fields(d, i):
+    """What a record (or a legend / JSON entry) says of what Soft-NMS left of detection i's confidence ('prob' stays the 2-D detector's)."""
+    return {'soft_prob': float(d.soft_prob[i]), 'decays': int(d.n_decays[i])}
+
+
 def view_fields(d, i):
     """What a record (or a legend / JSON entry) says of how detection i's views agreed (detect --tta)."""
     return {'view_iou': float(d.view_iou[i]), 'view_min_iou': float(d.view_min_iou[i]), 'views_voted': int(d.n_views_voted[i]),
@@ -249,7 +265,7 @@ class Detector:
     def __init__(self, FLAGS=None, model_path=None, boxpc_model_path=None, rt=None, type_whitelist=SD.TYPE_WHITELIST,
                  num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
                  min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, tta=None, tta_flip=False,
-                 tta_vote_iou=None, min_view_iou=None, **keywords):
+                 tta_vote_iou=None, min_view_iou=None, soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.
@@ -265,10 +281,18 @@ class Detector:
         the suppression of nms_iou, in whose groups a rejected detection is not listed.
         tta: None, or the number of views 2..8 every frustum is run in (ensemble.py; module docstring); tta_flip: the odd views are
         mirrored; tta_vote_iou: the IoU with the anchor view above which a view votes (default 0); min_view_iou: None, or the value in
-        [0, 1] below which a detection's view_iou rejects it, as the min_* thresholds do.  The last three need tta."""
+        [0, 1] below which a detection's view_iou rejects it, as the min_* thresholds do.  The last three need tta.
+        soft_nms: None, 'gaussian' or 'linear' -- Soft-NMS in place of the suppression (t3d_detect_soft_nms; module docstring): the
+        confidence of a box that overlaps a better one of its image and class is multiplied by exp(-IoU^2 / soft_nms_sigma) (default
+        0.5), or by 1 - IoU above nms_iou ('linear' needs it, 'gaussian' refuses it); a detection whose confidence falls below
+        soft_nms_min_prob (in [0, 1), default 0.001) is dropped.  nms_metric applies; nms_score 'score' and nms_fuse do not go with it."""
         self.tta, self.tta_flip, self.tta_vote_iou, self.min_view_iou = EN.check_options(tta, tta_flip, tta_vote_iou, min_view_iou)
-        self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
-        self.nms_fuse, self.nms_fuse_iou = NMS.check_fuse_options(self.nms_iou, nms_fuse, nms_fuse_iou)
+        self.soft_nms = NMS.check_soft_options(soft_nms, soft_nms_sigma, soft_nms_min_prob, nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou)
+        if self.soft_nms is not None:            # (the threshold and the metric travel in the options; the views still read nms_metric)
+            self.nms_iou, self.nms_metric, self.nms_score, self.nms_fuse, self.nms_fuse_iou = None, self.soft_nms.metric, 'prob', False, None
+        else:
+            self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
+            self.nms_fuse, self.nms_fuse_iou = NMS.check_fuse_options(self.nms_iou, nms_fuse, nms_fuse_iou)
         self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
         self.consistency = bool(consistency) or any(t is not None for t in self.thresholds)
         self.log = log
@@ -332,7 +356,11 @@ class Detector:
         ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live], classes)
         source = DeviceEvalSource(self.ops['graph'], dataset=ds, seed=FLAGS.seed)
         nms = con = views = None
-        if self.nms_iou is not None:
+        if self.soft_nms is not None:
+            o = self.soft_nms
+            nms = SI.NmsRequest(o.threshold, o.metric, None, [m.image for m in meta], classes, [m.prob for m in meta], soft=o.method,
+                                sigma=o.sigma if o.method == 'gaussian' else None, min_prob=o.min_prob)
+        elif self.nms_iou is not None:
             nms = SI.NmsRequest(self.nms_iou, self.nms_metric, self.nms_score, [m.image for m in meta], classes, [m.prob for m in meta],
                                 fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou)
         if self.consistency:
@@ -370,8 +398,10 @@ class Detector:
         (0: the box is what the decode wrote).  The consistency measures of a fused detection are those of its unfused box.
         With tta 'label' and 'corners' are what t3d_detect_ensemble made of the views (and nms_fuse of that), the records gain
         'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view', and a detection below min_view_iou has no entry; 'score' and the
-        consistency measures are those of view 0."""
-        vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None)
+        consistency measures are those of view 0.
+        With soft_nms the records gain 'soft_prob', the confidence Soft-NMS left ('prob' stays the 2-D detector's), and 'decays', the
+        number of better boxes that decayed it; a detection whose confidence fell below soft_nms_min_prob has no entry."""
+        vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None or self.soft_nms is not None)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
@@ -413,8 +443,8 @@ class Detector:
         """`sweep` on extracted parts (what `main` holds)."""
         from transferable3d_amd import evaluate_sunrgbd as ES
         import torch
-        if self.nms_iou is not None or any(t is not None for t in self.thresholds):
-            raise ValueError('a sweep starts from the plain run: the detector has nms_iou or a min_* threshold')
+        if self.nms_iou is not None or self.soft_nms is not None or any(t is not None for t in self.thresholds):
+            raise ValueError('a sweep starts from the plain run: the detector has nms_iou, soft_nms or a min_* threshold')
         if self.tta is not None:
             raise ValueError('the views of tta are not swept: the detector has tta')
         if grid.consistency and not self.consistency:
@@ -439,6 +469,8 @@ class Detector:
         r = {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
         if d.n_votes is not None:
             r['votes'] = int(d.n_votes[i])
+        if d.soft_prob is not None:
+            r.update(soft_fields(d, i))
         if d.view_iou is not None:
             r.update(view_fields(d, i))
         if d.reproj_iou is not None:
@@ -447,12 +479,14 @@ class Detector:
 
     def predictions(self, meta, d):
         """test_semisup's 14-list of a detection run (the entries it fills for --from_rgb_detection; the rotation angles stayed on the
-        device, the label rows carry them) with the decoded records attached."""
+        device, the label rows carry them) with the decoded records attached.  Its confidence entry -- what the result files write and
+        the evaluation ranks by -- is what Soft-NMS left of it, where that ran."""
         n = len(meta)
         if d is None:
             return SI.Predictions([None, None, [], [], [], [], [], [], [], [], [], [], [], None])
         p = SI.Predictions([None, None, [None] * n, list(d.center), list(d.heading_cls), list(d.heading_res), list(d.size_cls),
-                            list(d.size_res), [None] * n, [m.prob for m in meta],
+                            list(d.size_res), [None] * n,
+                            [m.prob for m in meta] if d.soft_prob is None else [float(v) for v in d.soft_prob],
                             [type2class[m.name] for m in meta], [m.image for m in meta], [m.box2d for m in meta], None])
         p.decoded = d
         return p
@@ -476,6 +510,8 @@ def write_consistency_json(path, meta, d):
                'n_mask': int(d.n_mask[i]), 'n_box': int(d.n_box[i]), 'n_both': int(d.n_both[i]), 'accepted': bool(d.accept[i]),
                'kept': bool(d.keep is None or d.keep[i])}
         row.update(consistency_fields(d, i, as_lists=True))
+        if d.soft_prob is not None:
+            row.update(soft_fields(d, i))
         if d.view_iou is not None:
             row.update(view_fields(d, i))
         rows.append(row)
@@ -497,7 +533,7 @@ def parser():
     p.add_argument('--vis_dir', default=None, help='write <id>.png (camera image + bird\'s-eye panel with the 3-D boxes) and <id>.json (legend) of detected scenes here')
     p.add_argument('--vis_max', type=int, default=50, help='how many scenes --vis_dir draws (the first ones with a detection)')
     p.add_argument('--vis_gt', action='store_true', help='--vis_dir: add the label boxes of label_dimension in green')
-    p.add_argument('--vis_suppressed', action='store_true', help='--vis_dir: add the boxes --nms_iou dropped, in grey')
+    p.add_argument('--vis_suppressed', action='store_true', help='--vis_dir: add the boxes --nms_iou (or --soft_nms) dropped, in grey')
     CS.add_arguments(p)
     p.add_argument('--consistency_json', default=None, help='write one row per detection (rejected ones included) with its consistency measures here')
     EN.add_arguments(p)
@@ -515,6 +551,7 @@ def sweep_options(args):
         return None
     single = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'diagnose') if getattr(args, f)]
     single += ['nms_fuse_iou'] if args.nms_fuse_iou is not None else []
+    single += ['soft_nms'] if args.soft_nms is not None else []      # (the scores differ per configuration: ranks cannot be shared)
     single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
     if single:
         raise ValueError('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
@@ -569,11 +606,12 @@ def main(argv=None, rt=None, log=print):
         consistency = args.consistency or any(getattr(args, t) is not None for t in CS.THRESHOLDS) or (grid is not None and grid.consistency)
         if args.consistency_json and not consistency:
             raise ValueError('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
-        vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None) if args.vis_dir else None
+        vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None or args.soft_nms is not None) if args.vis_dir else None
         det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=None if grid is not None else args.nms_metric,
                        nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=args.min_reproj_iou,
                        min_mask_in_box=args.min_mask_in_box, min_seg_box_iou=args.min_seg_box_iou, nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou,
-                       tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou)
+                       tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou,
+                       soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_min_prob=args.soft_nms_min_prob)
     except ValueError as e:
         p.error(str(e))
     valid = set(int(line.rstrip()) for line in open(args.idx_path))

@@ -10,7 +10,12 @@ the weighted mean geometry of the boxes it suppressed -- several estimates of on
 
 `DeviceNmsSweep.run` (t3d_detect_nms_sweep, csrc/nms_sweep.hip; detect --sweep) is `DeviceNms.run` for many configurations at once -- a
 threshold out of up to 16 and a subset of the boxes each -- with every pair's IoU computed once (sweep.py chooses thresholds with it).
+
+`DeviceSoftNms.run` (t3d_detect_soft_nms, csrc/soft_nms.hip; --soft_nms) is the alternative to `DeviceNms.run` where true neighbours overlap
+(chairs in a row): a box that overlaps a better one is not dropped, its confidence is multiplied down by a function of the IoU (Soft-NMS,
+Bodla et al., ICCV 2017), so a duplicate sinks to the tail of the ranked list while a neighbour keeps most of its confidence.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -21,6 +26,7 @@ from .abi import fptr, iptr
 
 METRICS = tuple(abi.NMS_METRICS)          # '3d': volume IoU, 'bev': IoU of the ground-plane rectangles
 SCORES = ('prob', 'score')                # rank by the 2-D detection confidence / by the decoded network score
+SOFT_METHODS = ('gaussian', 'linear')     # Soft-NMS: score *= exp(-IoU^2 / sigma) for IoU > 0 / score *= 1 - IoU for IoU > threshold
 
 
 def check_options(nms_iou, nms_metric=None, nms_score=None):
@@ -55,7 +61,53 @@ def check_fuse_options(nms_iou, nms_fuse=False, nms_fuse_iou=None):
     return True, t
 
 
+SoftOptions = collections.namedtuple('SoftOptions', 'method threshold sigma min_prob metric')
+
+
+def check_soft_options(soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, nms_iou=None, nms_metric=None, nms_score=None, nms_fuse=False,
+                       nms_fuse_iou=None):
+    """The Soft-NMS options of the drivers beside the ones they share with the hard suppression -> None without soft_nms, else
+    SoftOptions(method, threshold or None, sigma, min_prob, metric name).  'gaussian' decays every overlapping box by exp(-IoU^2 /
+    sigma) and takes no threshold; 'linear' decays a box above the IoU nms_iou by 1 - IoU and needs it.  ValueError for an unknown method,
+    sigma not a finite number above 0, min_prob outside [0, 1), a threshold with 'gaussian' or none with 'linear', for what cannot go with
+    a decay -- ranking by the decoded score (the decay acts on the confidence the evaluation ranks by) and box voting (there are no
+    clusters) -- and for a soft_nms_* option without soft_nms."""
+    if soft_nms is None:
+        if soft_nms_sigma is not None or soft_nms_min_prob is not None:
+            raise ValueError('--soft_nms_sigma / --soft_nms_min_prob need --soft_nms')
+        return None
+    if soft_nms not in SOFT_METHODS:
+        raise ValueError('--soft_nms is one of %s, got %r' % (SOFT_METHODS, soft_nms))
+    if nms_score not in (None, 'prob'):
+        raise ValueError('--soft_nms decays the 2-D detection confidence, which the evaluation ranks by: it does not go with --nms_score %s' % nms_score)
+    if nms_fuse or nms_fuse_iou is not None:
+        raise ValueError('--soft_nms suppresses nothing into clusters: it does not go with --nms_fuse / --nms_fuse_iou')
+    metric = nms_metric or '3d'
+    if metric not in METRICS:
+        raise ValueError('--nms_metric is one of %s, got %r' % (METRICS, metric))
+    sigma = 0.5 if soft_nms_sigma is None else float(soft_nms_sigma)
+    floor = 0.001 if soft_nms_min_prob is None else float(soft_nms_min_prob)
+    if not (0.0 < sigma < float('inf')):
+        raise ValueError('--soft_nms_sigma must be a finite number above 0, got %r' % (soft_nms_sigma,))
+    if not 0.0 <= floor < 1.0:
+        raise ValueError('--soft_nms_min_prob must lie in [0, 1), got %r' % (soft_nms_min_prob,))
+    if soft_nms == 'gaussian':
+        if nms_iou is not None:
+            raise ValueError('--soft_nms gaussian decays every overlapping box and has no threshold: it does not go with --nms_iou')
+        return SoftOptions('gaussian', None, sigma, floor, metric)
+    if soft_nms_sigma is not None:
+        raise ValueError('--soft_nms_sigma is the width of --soft_nms gaussian: it does not go with --soft_nms linear')
+    if nms_iou is None:
+        raise ValueError('--soft_nms linear decays the boxes above an IoU threshold: it needs --nms_iou')
+    return SoftOptions('linear', check_options(nms_iou)[0], sigma, floor, metric)
+
+
 def add_arguments(parser):
+    parser.add_argument('--soft_nms', choices=SOFT_METHODS, default=None,
+                        help="Soft-NMS: per image and class, a box that overlaps a better one keeps its place and its confidence is multiplied down -- 'gaussian': by exp(-IoU^2 / sigma); 'linear': by 1 - IoU above --nms_iou (which it needs); decayed confidences below --soft_nms_min_prob are dropped")
+    parser.add_argument('--soft_nms_sigma', type=float, default=None, help='--soft_nms gaussian: the width sigma (> 0; default 0.5)')
+    parser.add_argument('--soft_nms_min_prob', type=float, default=None,
+                        help='--soft_nms: a detection whose decayed confidence falls below this is dropped (in [0, 1); default 0.001)')
     parser.add_argument('--nms_iou', type=float, default=None,
                         help='suppress, per image and class, a 3-D box that overlaps a better-ranked kept box by more than this IoU (0 < T <= 1; default: no suppression)')
     parser.add_argument('--nms_metric', choices=METRICS, default=None, help="IoU of --nms_iou: '3d' (volume, default) or 'bev' (ground plane)")
@@ -128,6 +180,61 @@ class DeviceNms:
     def relaunch(self):
         """The launches of the last `run` again, on the same buffers (tools/bench_detect_nms.py times them alone)."""
         abi.check(self.rt.lib.t3d_detect_nms(C.byref(self._args), self.rt.stream()), 't3d_detect_nms')
+
+
+class DeviceSoftNms:
+    """Outputs of t3d_detect_soft_nms; `run` launches on device tensors.  The buffers grow as needed and are reused."""
+
+    def __init__(self, rt):
+        self.rt = rt
+        self.score_out = self.keep = self.suppressed_by = self.n_decays = None
+        self._held = ()
+
+    def run(self, corners, score, group_offsets, members, method, threshold=None, sigma=0.5, min_score=0.001, metric='3d', fill=None):
+        """corners [n, 8, 3] / [n, 24] fp32 and score [n] fp32 on the runtime's device; group_offsets, members: NumPy / lists, as for
+        DeviceNms.run; method 'gaussian' (sigma) or 'linear' (threshold); min_score: the floor below which a decayed box is pruned.
+        -> (score_out fp32 [n], keep uint8 [n], suppressed_by int32 [n], n_decays int32 [n]) device tensors, owned by this object until
+        the next run.  fill: (score_out, keep, suppressed_by, n_decays) values the outputs hold before the launch (what a box in no
+        group keeps; default: its input score, 1, -1, 0: an unlisted box is a kept one that nothing decayed)."""
+        rt = self.rt
+        n = int(score.numel())
+        assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
+        assert corners.dtype == torch.float32 and score.dtype == torch.float32
+        if method not in SOFT_METHODS:
+            raise ValueError('method is one of %s, got %r' % (SOFT_METHODS, method))
+        if method == 'linear' and threshold is None:
+            raise ValueError("method 'linear' needs a threshold")
+        go, mem = np.ascontiguousarray(group_offsets, np.int32), np.ascontiguousarray(members, np.int32)
+        n_groups = len(go) - 1
+        max_group = int(np.diff(go).max()) if n_groups > 0 else 0
+        if n_groups < 0 or go[0] != 0 or (n_groups > 0 and (np.diff(go).min() < 0 or go[-1] != len(mem))) or len(mem) > n:
+            raise ValueError('group_offsets / members are not the lists of groups_of')
+        if len(mem) and (mem.min() < 0 or mem.max() >= n):
+            raise ValueError('a member is not a box index of [0, %d)' % n)
+        if self.keep is None or self.keep.numel() < n:
+            new = lambda dtype: torch.zeros(max(n, 1), dtype=dtype, device=rt.device)      # (owned here, as DeviceNms's)
+            self.score_out, self.keep, self.suppressed_by, self.n_decays = new(torch.float32), new(torch.uint8), new(torch.int32), new(torch.int32)
+        out, keep, sup, dec = self.score_out[:n], self.keep[:n], self.suppressed_by[:n], self.n_decays[:n]
+        if fill is None:
+            out.copy_(score.view(-1))
+        else:
+            out.fill_(fill[0])
+        fk, fs, fd = (1, -1, 0) if fill is None else fill[1:]
+        keep.fill_(fk)
+        sup.fill_(fs)
+        dec.fill_(fd)
+        d_go, d_mem = torch.from_numpy(go).to(rt.device), torch.from_numpy(mem if len(mem) else np.zeros(1, np.int32)).to(rt.device)
+        self._held = (corners, score, d_go, d_mem)            # alive until the launch has run
+        self._args = abi.DetectSoftNmsArgs(n, n_groups, abi.NMS_METRICS[metric], fptr(corners), fptr(score), iptr(d_go), iptr(d_mem),
+                                           0.0 if threshold is None else float(threshold), max_group, abi.SOFT_NMS_METHODS[method], float(sigma),
+                                           float(min_score), 0, None, 0, fptr(out), abi.u8ptr(keep), iptr(sup), iptr(dec))
+        self.relaunch()
+        return out, keep, sup, dec
+
+    def relaunch(self):
+        """The launch of the last `run` again, on the same buffers and on the working scores the last launch left: every listed box
+        starts again from its input score (tools/bench_detect_soft_nms.py times it alone)."""
+        abi.check(self.rt.lib.t3d_detect_soft_nms(C.byref(self._args), self.rt.stream()), 't3d_detect_soft_nms')
 
 
 class DeviceFuse:

@@ -14,6 +14,9 @@ here hands over to test_semisup's, so nothing that exists changes its numbers.
 overlaps a better-ranked kept box by more than T; the suppressed detections are absent from the 14-list, the result files and --evaluate.
 --nms_fuse [--nms_fuse_iou V] (with --nms_iou): t3d_detect_fuse follows on the same buffers; every kept box is written with the weighted
 mean geometry of the boxes it suppressed (nms.DeviceFuse).  Which boxes are kept, and every score, stay.
+--soft_nms {gaussian,linear} (with --from_rgb_detection): t3d_detect_soft_nms (nms.DeviceSoftNms) runs in place of t3d_detect_nms; the
+confidence of a box that overlaps a better one is decayed and is what the 14-list, the result files and --evaluate then carry; a
+detection whose confidence falls below --soft_nms_min_prob is absent like a suppressed one.
 
 What runs behind the decode, and in which order, is written down in one place: `DeviceStages`.  `inference` builds one from its requests
 (nms, consistency, views); per batch it decodes every view and then measures the consistency of view 0, after the last batch it runs
@@ -49,6 +52,13 @@ def build_flags(argv=None):
     nms, rest = own.parse_known_args([a for a in argv if a != '--device_decode'])
     FLAGS = TS.build_flags(rest)
     FLAGS.device_decode = device
+    FLAGS.soft_nms = NMS.check_soft_options(nms.soft_nms, nms.soft_nms_sigma, nms.soft_nms_min_prob, nms.nms_iou, nms.nms_metric, nms.nms_score,
+                                            nms.nms_fuse, nms.nms_fuse_iou)
+    if FLAGS.soft_nms is not None:               # (its threshold travels in the options; nms_metric is its metric, as in detect.Detector; the hard suppression stays off)
+        FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, FLAGS.nms_fuse, FLAGS.nms_fuse_iou = None, FLAGS.soft_nms.metric, 'prob', False, None
+        if not (device and FLAGS.from_rgb_detection):
+            raise ValueError('--soft_nms runs on the device-decoded boxes of a detection file: it needs --device_decode and --from_rgb_detection')
+        return FLAGS
     FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score = NMS.check_options(nms.nms_iou, nms.nms_metric, nms.nms_score)
     FLAGS.nms_fuse, FLAGS.nms_fuse_iou = NMS.check_fuse_options(nms.nms_iou, nms.nms_fuse, nms.nms_fuse_iou)
     if FLAGS.nms_iou is not None and not (device and FLAGS.from_rgb_detection):
@@ -61,13 +71,21 @@ class NmsRequest:
     'bev'), what ranks ('prob': the 2-D detection confidences given here; 'score': the decoded network score) and, per detection, the
     image id and the class id that make its group.  fuse: t3d_detect_fuse follows (box voting: a kept box takes the weighted mean
     geometry of the boxes it suppressed); a suppressed box votes above the IoU vote_threshold (default: the threshold, so all of them do)
-    with the weight that ranked it -- `prob`, or exp(score) for score='score' (the decoded score is a sum of logs)."""
+    with the weight that ranked it -- `prob`, or exp(score) for score='score' (the decoded score is a sum of logs).
+    soft ('gaussian' / 'linear'; sigma, min_prob): t3d_detect_soft_nms runs in place of t3d_detect_nms (nms.check_soft_options: 'linear'
+    takes the threshold, 'gaussian' none; the confidences `prob` are decayed, nothing is fused)."""
+    soft = None
 
-    def __init__(self, threshold, metric, score, image_ids, class_ids, prob=None, fuse=False, vote_threshold=None):
-        self.threshold, self.metric, self.score = NMS.check_options(threshold, metric, score)
-        if self.threshold is None:
-            raise ValueError('an NMS request needs a threshold')
-        self.fuse, self.vote_threshold = NMS.check_fuse_options(self.threshold, fuse, vote_threshold)
+    def __init__(self, threshold, metric, score, image_ids, class_ids, prob=None, fuse=False, vote_threshold=None, soft=None, sigma=None,
+                 min_prob=None):
+        self.soft = NMS.check_soft_options(soft, sigma, min_prob, threshold, metric, score, fuse, vote_threshold)
+        if self.soft is not None:
+            self.threshold, self.metric, self.score, self.fuse, self.vote_threshold = self.soft.threshold, self.soft.metric, 'prob', False, None
+        else:
+            self.threshold, self.metric, self.score = NMS.check_options(threshold, metric, score)
+            if self.threshold is None:
+                raise ValueError('an NMS request needs a threshold')
+            self.fuse, self.vote_threshold = NMS.check_fuse_options(self.threshold, fuse, vote_threshold)
         self.image_ids, self.class_ids = np.asarray(image_ids, np.int64), np.asarray(class_ids, np.int64)
         self.prob = None if prob is None else np.asarray(prob, np.float32)
         if self.score == 'prob' and (self.prob is None or len(self.prob) != len(self.image_ids)):
@@ -93,10 +111,14 @@ class Decoded:
     t3d_detect_fuse made of that: raw_label / raw_corners are then the ensemble's output); view_label [V,n,7] and view_score [V,n] what
     the decode wrote per view, view_iou [n] the mean and view_min_iou [n] the smallest pairwise IoU of a detection's views, anchor_view
     [n] the view the fused box was built around (-1: no view with a finite label) and n_views_voted [n] the views that voted beside it;
-    None without.  score, mask_count, the heads and the consistency measures stay those of view 0."""
+    None without.  score, mask_count, the heads and the consistency measures stay those of view 0.
+    With Soft-NMS (NmsRequest(soft=...)) soft_prob [n] is the confidence t3d_detect_soft_nms left of every detection -- the 2-D
+    detector's where nothing decayed it -- and n_decays [n] the number of better boxes that decayed it; keep is False for a detection
+    whose confidence fell below the floor and suppressed_by names the box whose decay took it there; None without."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
     OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept',
-                'raw_label', 'raw_corners', 'n_votes', 'view_label', 'view_score', 'view_iou', 'view_min_iou', 'anchor_view', 'n_views_voted')
+                'raw_label', 'raw_corners', 'n_votes', 'view_label', 'view_score', 'view_iou', 'view_min_iou', 'anchor_view', 'n_views_voted',
+                'soft_prob', 'n_decays')
     VIEW_MAJOR = ('view_label', 'view_score')              # [V, n, ...]: the detection is the second axis
 
     def __init__(self, **fields):
@@ -239,7 +261,8 @@ class DeviceStages:
     def nms(self):
         """t3d_detect_nms over the real rows, on the current corners.  A rejected detection is listed in no group, so it suppresses
         nothing and comes back as kept (`accept` says it is rejected).  With a request that fuses, t3d_detect_fuse follows directly on the
-        same buffers (a row in no group neither votes nor is fused) and its output becomes the current boxes."""
+        same buffers (a row in no group neither votes nor is fused) and its output becomes the current boxes.  With a soft request
+        t3d_detect_soft_nms runs in its place, on the same groups: a row in no group keeps its confidence."""
         req, total = self.nms_request, self.total
         rows = np.arange(total) if self.accept is None else np.nonzero(self.accept[:total])[0]
         offsets, members = NMS.groups_of(req.image_ids[rows], req.class_ids[rows])
@@ -247,6 +270,11 @@ class DeviceStages:
         if req.score == 'prob':
             score = self.rt.zeros(self.n)
             score[:total] = torch.from_numpy(req.prob).to(self.rt.device)
+        if req.soft is not None:
+            self.nms_out = NMS.DeviceSoftNms(self.rt)
+            self.nms_out.run(self.corners, score, offsets, rows[members].astype(np.int32), req.soft.method, req.soft.threshold, req.soft.sigma,
+                             req.soft.min_prob, req.soft.metric)
+            return
         self.nms_out = NMS.DeviceNms(self.rt)
         self.nms_out.run(self.corners, score, offsets, rows[members].astype(np.int32), req.threshold, req.metric)
         if req.fuse:
@@ -261,6 +289,8 @@ class DeviceStages:
         host = lambda t, dtype=np.float64: t[:n].cpu().numpy().astype(dtype)
         if self.nms_out is not None:
             d.keep, d.suppressed_by = host(self.nms_out.keep, bool), host(self.nms_out.suppressed_by, np.int64)
+            if self.nms_request.soft is not None:
+                d.soft_prob, d.n_decays = host(self.nms_out.score_out), host(self.nms_out.n_decays, np.int64)
         if self.ensemble_out is not None:
             e = self.ensemble_out
             d.view_label = np.stack([host(v.sec['label']) for v in self.decodes])
@@ -385,6 +415,12 @@ def report(log, stages, d):
     req = stages.nms_request
     if req is not None:
         kept, offered = (d.keep, len(d)) if d.accept is None else (d.keep & d.accept, int(d.accept.sum()))
+        if req.soft is not None:
+            o = req.soft
+            how = 'sigma %g' % o.sigma if o.method == 'gaussian' else 'IoU > %g' % o.threshold
+            log('soft-nms (%s, %s, %s IoU, floor %g): kept %d of %d detections, decayed %d'
+                % (o.method, how, o.metric, o.min_prob, int(kept.sum()), offered, int((d.n_decays > 0).sum())))
+            return
         line = 'nms (%s IoU > %g, ranked by %s): kept %d of %d detections' % (req.metric, req.threshold, req.score, int(kept.sum()), offered)
         if d.n_votes is not None:
             v = d.n_votes[d.n_votes > 0]
@@ -418,13 +454,20 @@ def device_decode_driver(FLAGS):
         else:
             d, *lists = kept(d, *predictions)
         p = Predictions(lists)
+        if d is not None and d.soft_prob is not None:            # the confidence the files and the evaluation rank by
+            p[9] = [float(v) for v in d.soft_prob]
         p.decoded = d
         return p
 
     def infer(sess, ops, pc, one_hot_vec, batch_size, **kw):
         source = kw.get('source')
         req = None
-        if getattr(FLAGS, 'nms_iou', None) is not None:
+        soft = getattr(FLAGS, 'soft_nms', None)
+        if soft is not None:
+            ds = source.ds
+            req = NmsRequest(soft.threshold, soft.metric, None, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob,
+                             soft=soft.method, sigma=soft.sigma if soft.method == 'gaussian' else None, min_prob=soft.min_prob)
+        elif getattr(FLAGS, 'nms_iou', None) is not None:
             ds = source.ds
             req = NmsRequest(FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob,
                              fuse=getattr(FLAGS, 'nms_fuse', False), vote_threshold=getattr(FLAGS, 'nms_fuse_iou', None))
