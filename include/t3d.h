@@ -2059,6 +2059,66 @@ typedef struct {
 #define T3D_V2_SIZE_detect_soft_nms_args 120
 int t3d_detect_soft_nms(const t3d_detect_soft_nms_args* args, t3d_stream_t stream);
 
+/* ---- Localisation errors split into centre, size and heading (csrc/sunrgbd_locparts.hip; evaluate_sunrgbd.py
+ *      diagnose_class(parts=True), --diagnose_parts) ----
+ * T3D_DIAG_LOC says a detection sits on its own box but too loosely (t_b <= overlap < t_f).  This call says which parameter group of
+ * the box is to blame: TIDE's idea one level down, after the true-positive metrics of nuScenes (translation, scale, orientation error),
+ * restated for this protocol's prism overlap, its matching and its VOC2011 AP.
+ * It first calls t3d_sunrgbd_diagnose(eval, diag, stream): every output of both structs has the bytes that call writes, and whatever it
+ * refuses is refused here.  Then, for upright boxes (what both parsers produce), per detection i with g = gt_idx[i] - 1 >= 0 -- the
+ * detection is A, its arg-max box is B:
+ *   Rows        the vertical row of a box is the basis row with the largest |z component|, the first on ties; the other two, in row
+ *               order, are its horizontal rows a0, a1 (of B: b0, b1).  A row's size is |coeff|.
+ *   Pairing     on the xy components p = |a0 . b0|, q = |a0 . b1|: p >= q pairs a0 with b0 and a1 with b1, otherwise a0 with b1 and a1
+ *               with b0 (a box equals itself turned by pi/2 with l and w exchanged).  The vertical rows pair with each other.
+ *   loc_error   [i][0] hypot(Ax - Bx, Ay - By); [1] Az - Bz, signed; [2..4] log(size of the partner row of A / size) for b0, b1 and the
+ *               vertical row of B, signed (l, w, h for ground truth from label files); [5] the heading error atan2(min(p, q),
+ *               max(p, q)) in [0, pi/4].
+ *   Counterfactual boxes, one per part:
+ *     T3D_LOCPART_XY       A with B's x and y;
+ *     T3D_LOCPART_Z        A with B's z;
+ *     T3D_LOCPART_CENTRE   A with B's centroid;
+ *     T3D_LOCPART_SIZE     A's centroid and basis, each row's size replaced by its partner's;
+ *     T3D_LOCPART_HEADING  A's centroid and B's basis, each row of B carrying the size of its partner row of A.
+ *   part_overlap[i][f]     the evaluation's own overlap (ev_overlap of the ev_footprints) of counterfactual box f with B; a box of
+ *                          zero volume overlaps nothing, here as there.
+ *   Where gt_idx[i] == 0 the five overlaps are 0 and the six errors NaN.
+ * A LOC detection is REPAIRED BY f iff part_overlap[i][f] >= t_f.  ap_part[f] is the AP of that variant, by the curve code and the
+ * summation tree of `ap` and `ap_fixed`: true positives stay; per box in state 2 the best-ranked repaired detection that chose it
+ * becomes a true positive (an integer minimum over ranks); every other repaired detection -- one on a claimed box included -- is
+ * removed and counts in neither sum; unrepaired LOC detections and all other false positives stay false positives; n_pos = G.
+ * part_counts[f]: the repaired LOC detections; part_boxes[f]: the boxes that gain a true positive.
+ * P == 0 or G == 0: all zeros, as ap_fixed.  A part that repairs nothing has the bytes of `ap`; one that repairs every LOC detection
+ * those of ap_fixed[T3D_DIAG_FIX_LOC].
+ * THE PARTS DO NOT ADD UP: a box off in xy and in z may be repaired by either fix alone, or only by CENTRE; a detection may be repaired
+ * by several parts or by none, so neither the counts nor the AP gains sum to those of T3D_DIAG_FIX_LOC.
+ * workspace: T3D_SUNRGBD_LOCPARTS_WORKSPACE_BYTES(P, G) bytes (five int32[G] arrays of ranks), separate from the other two.
+ * Three launches behind the diagnosis': the rank arrays; one thread per (detection, part), so that a lane clips once; six workgroups,
+ * five curves and the counts.  Everything is fp64.  Nothing is allocated or synchronised with the host; the only atomics are integer
+ * minima, so equal inputs give equal bytes.
+ * T3D_ERR_ABI: a struct of another size (any of the three).  T3D_ERR_ARG: a NULL struct or output, reserved != 0, a workspace that is
+ * NULL or too small where G > 0, and whatever t3d_sunrgbd_diagnose refuses; T3D_ERR_SHAPE: its shapes.  Nothing is launched then. */
+#define T3D_LOCPART_XY 0
+#define T3D_LOCPART_Z 1
+#define T3D_LOCPART_CENTRE 2
+#define T3D_LOCPART_SIZE 3
+#define T3D_LOCPART_HEADING 4
+#define T3D_SUNRGBD_LOCPARTS_WORKSPACE_BYTES(P, G) ((uint64_t)(G) * 20u + (uint64_t)(P) * 0u + 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_sunrgbd_locparts_args) of the caller's header (see T3D_ABI_VERSION) */
+  int reserved;                        /* 0 */
+  void* workspace;
+  uint64_t workspace_bytes;
+  double* part_overlap;                /* [P,5] out, file order: T3D_LOCPART_* */
+  double* loc_error;                   /* [P,6] out, file order */
+  int32_t* part_counts;                /* [5] out */
+  int32_t* part_boxes;                 /* [5] out */
+  double* ap_part;                     /* [5] out */
+} t3d_sunrgbd_locparts_args;
+#define T3D_V2_SIZE_sunrgbd_locparts_args 64
+int t3d_sunrgbd_locparts(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_diagnose_args* diag,
+                         const t3d_sunrgbd_locparts_args* parts, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

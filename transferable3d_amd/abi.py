@@ -354,6 +354,15 @@ class SunrgbdDiagnoseArgs(Sized):
                 ('other_gt', I), ('kind', U8), ('gt_state', U8), ('counts', I), ('gt_counts', I), ('ap_fixed', D)]
 
 
+LOC_PARTS = ('xy', 'z', 'centre', 'size', 'heading')                             # t3d.h T3D_LOCPART_*: part_overlap[i][5], ap_part[5]
+LOC_ERRORS = ('xy', 'z', 'l', 'w', 'h', 'heading')                               # loc_error[i][6]
+
+
+class SunrgbdLocPartsArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('reserved', i32), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64),
+                ('part_overlap', D), ('loc_error', D), ('part_counts', I), ('part_boxes', I), ('ap_part', D)]
+
+
 SEMI_BATCH, SEMI_ALTERNATE_BATCH, SEMI_MIXED_BATCH = 0, 1, 2          # t3d.h T3D_SEMI_*
 SEMI_METHODS = {'BATCH': SEMI_BATCH, 'ALTERNATE_BATCH': SEMI_ALTERNATE_BATCH, 'MIXED_BATCH': SEMI_MIXED_BATCH}
 SEMI_SAMPLE_MAX_B = 256
@@ -536,6 +545,11 @@ def sunrgbd_diagnose_workspace_bytes(P, G, Go):
     return Go * 88 + G * 4 + 8
 
 
+def sunrgbd_locparts_workspace_bytes(P, G):
+    """t3d.h T3D_SUNRGBD_LOCPARTS_WORKSPACE_BYTES"""
+    return G * 20 + 8
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -635,6 +649,7 @@ ENTRY_POINTS = {
     't3d_frustum_extract': [C.POINTER(FrustumExtractArgs), VP],
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
     't3d_sunrgbd_diagnose': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdDiagnoseArgs), VP],
+    't3d_sunrgbd_locparts': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdDiagnoseArgs), C.POINTER(SunrgbdLocPartsArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],

@@ -2,7 +2,7 @@
 """Scenes and 2-D detections in, 3-D boxes out, in one process and without a frustum file.
 
     python -m transferable3d_amd.detect --dataset_dir D --idx_path I --rgb_detection_path DETS --model_path M [--boxpc_model_path P] \
-        --result_dir R [--official_eval [--diagnose [--diagnose_bg 0.1] [--diagnose_json FILE]]]
+        --result_dir R [--official_eval [--diagnose [--diagnose_bg 0.1] [--diagnose_json FILE] [--diagnose_parts]]]
         # + test_semisup's model flags (--semi_type, --refine, --pred_prefix, --num_point, ...)
         [--nms_iou T [--nms_metric {3d,bev}] [--nms_score {prob,score}] [--nms_fuse] [--nms_fuse_iou V]]
         [--soft_nms gaussian [--soft_nms_sigma S] | --soft_nms linear --nms_iou T] [--soft_nms_min_prob F] [--nms_metric {3d,bev}]

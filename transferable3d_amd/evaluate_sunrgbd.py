@@ -26,6 +26,12 @@ missed box into localised or not, and the AP the class would have if each kind o
 "TIDE" (ECCV 2020) under this protocol's overlap, matching and AP (include/t3d.h has the rules).  Two lines per class follow its AP line
 and one the mean; without the flag nothing changes.
 
+--diagnose --diagnose_parts: which part of a loose box is loose.  Per class ONE t3d_sunrgbd_locparts call (csrc/sunrgbd_locparts.hip) in
+place of the t3d_sunrgbd_diagnose call: the same diagnosis, then per detection the overlap with its box once its xy, its z, its centre,
+its size or its heading is the box's own, the six errors behind them (centre distance, dz, log size ratios, heading), and the AP the
+class would have if every LOC detection that one part repairs were repaired.  Two more lines per class (`Localisation for X:`, `dAP(loc)
+for X:`) and `Mean dAP(loc):`.  The parts do not add up: a detection may be repaired by several parts, or only by the centre as a whole.
+
 `sweep_class` / `sweep` (t3d_sunrgbd_eval_sweep, csrc/sunrgbd_sweep.hip): the evaluation of one class for many subsets of its detections in
 one call -- footprints, ranks and overlaps once, the claims and the curve per subset -- which `detect --sweep` (sweep.py) scores a grid of
 post-processing thresholds with.
@@ -171,23 +177,27 @@ def _by_image(img):
     return ids, np.concatenate([first, [len(img)]]).astype(np.int32), lst
 
 
-def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None):
+def _eval_call(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None, parts=False):
     """One t3d_sunrgbd_eval call on one class -> host arrays of every output.  other (boxes of the other evaluated classes) and
-    bg_threshold: one t3d_sunrgbd_diagnose call instead, the diagnosis' outputs beside the evaluation's.  Either way one copy to the
-    device and one copy back."""
-    launch, fetch = _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps, other, bg_threshold)
+    bg_threshold: one t3d_sunrgbd_diagnose call instead, the diagnosis' outputs beside the evaluation's; with parts one
+    t3d_sunrgbd_locparts call, the split of the localisation errors beside both.  Either way one copy to the device and one copy back."""
+    launch, fetch = _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps, other, bg_threshold, parts=parts)
     launch()
     return fetch()
 
 
-def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None, sweep=None, boot=None):
+def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=None, bg_threshold=None, sweep=None, boot=None, parts=False):
     """_eval_call in its three steps: packs and uploads the inputs (the one copy to the device) -> (launch: the entry point's launches
     on the runtime's stream, fetch: the one copy back as host arrays).  tools/bench_sunrgbd_diagnose.py times `launch` alone.
     sweep: (mask uint8 [M, stride] on the runtime's device, det_index [P] or None): one t3d_sunrgbd_eval_sweep call instead, and `fetch`
     copies back its four [M] arrays alone ('ap', 'n_det', 'n_tp', 'n_fp').
     boot: (bootstrap.Weights, det_col [P], gt_col [G]): one t3d_sunrgbd_eval_bootstrap call instead, and `fetch` returns the evaluation's
-    arrays plus 'boot': {'ap' float64 [R], 'n_pos', 'n_tp', 'n_fp' int64 [R]} (a second copy back)."""
+    arrays plus 'boot': {'ap' float64 [R], 'n_pos', 'n_tp', 'n_fp' int64 [R]} (a second copy back).
+    parts (with other): one t3d_sunrgbd_locparts call instead of the t3d_sunrgbd_diagnose call, and `fetch` returns 'part_overlap' [P * 5],
+    'loc_error' [P * 6], 'ap_part', 'part_counts' and 'part_boxes' [5] as well."""
     rt = _runtime(rt)
+    if parts and other is None:
+        raise ValueError('the split of the localisation errors belongs to a diagnosis: parts needs other')
     P, G = len(det['confidence']), len(gt['image'])
     gimg = np.asarray(gt['image'], np.int32)
     image_ids, offsets, image_gt = _by_image(gimg)
@@ -237,6 +247,11 @@ def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=
     if other is not None:
         for name, dt, n in (('other_overlap', np.float64, P), ('ap_fixed', np.float64, len(abi.DIAG_FIXES)), ('other_gt', np.int32, P),
                             ('counts', np.int32, len(abi.DIAG_KINDS)), ('gt_counts', np.int32, 3), ('kind', np.uint8, P), ('gt_state', np.uint8, G)):
+            out.add(name, dt, n)
+    if parts:
+        for name, dt, n in (('part_overlap', np.float64, P * len(abi.LOC_PARTS)), ('loc_error', np.float64, P * len(abi.LOC_ERRORS)),
+                            ('ap_part', np.float64, len(abi.LOC_PARTS)), ('part_counts', np.int32, len(abi.LOC_PARTS)),
+                            ('part_boxes', np.int32, len(abi.LOC_PARTS))):
             out.add(name, dt, n)
     if want_overlaps:
         n_ov = int(ov_off[-1])
@@ -327,9 +342,18 @@ def _eval_prepare(det, gt, difficult, threshold, rt, want_overlaps=False, other=
                                     float(bg_threshold), C.c_void_p(d_dws.data_ptr()), dws_bytes, o_('other_overlap', dbl), o_('other_gt', i32),
                                     o_('kind', u8), o_('gt_state', u8), o_('counts', i32), o_('gt_counts', i32), o_('ap_fixed', dbl))
         held.append(d_dws)
+        if parts:
+            pws_bytes = abi.sunrgbd_locparts_workspace_bytes(P, G)
+            d_pws = torch.empty((pws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+            q = abi.SunrgbdLocPartsArgs(0, C.c_void_p(d_pws.data_ptr()), pws_bytes, o_('part_overlap', dbl), o_('loc_error', dbl),
+                                        o_('part_counts', i32), o_('part_boxes', i32), o_('ap_part', dbl))
+            held.append(d_pws)
 
-        def launch(held=held):
-            abi.check(rt.lib.t3d_sunrgbd_diagnose(C.byref(a), C.byref(d), rt.stream()), 't3d_sunrgbd_diagnose')
+            def launch(held=held):
+                abi.check(rt.lib.t3d_sunrgbd_locparts(C.byref(a), C.byref(d), C.byref(q), rt.stream()), 't3d_sunrgbd_locparts')
+        else:
+            def launch(held=held):
+                abi.check(rt.lib.t3d_sunrgbd_diagnose(C.byref(a), C.byref(d), rt.stream()), 't3d_sunrgbd_diagnose')
 
     def fetch(held=held):
         host = d_out.cpu().numpy()                                          # the one copy back (synchronises)
@@ -444,18 +468,38 @@ def bootstrap_class(classname, det, gt, weights, idx_list, threshold=0.25, rt=No
 GT_STATES = ('claimed', 'localised', 'missed')              # gt_state 1, 2, 3 of t3d_sunrgbd_diagnose
 
 
-def diagnose_class(classname, det, gt_all, threshold=0.25, bg_threshold=0.1, rt=None, classes=None):
+def loc_summary(kind, loc_error):
+    """The host's summary of loc_error [P,6], separately over the true positives and over the LOC detections: {'tp' | 'loc': {'n',
+    and per abi.LOC_ERRORS column the median of its finite values (NaN when there is none: n == 0, or a box without volume)}}."""
+    out = {}
+    for group in ('tp', 'loc'):
+        rows = np.asarray(loc_error, np.float64).reshape(-1, len(abi.LOC_ERRORS))[np.asarray(kind) == abi.DIAG_KINDS.index(group)]
+        s = {'n': int(len(rows))}
+        for k, name in enumerate(abi.LOC_ERRORS):
+            v = rows[:, k][np.isfinite(rows[:, k])]
+            s[name] = float(np.median(v)) if len(v) else float('nan')
+        out[group] = s
+    return out
+
+
+def diagnose_class(classname, det, gt_all, threshold=0.25, bg_threshold=0.1, rt=None, classes=None, parts=False):
     """compute_pr_curve_3d(classname, det, gt_all) and the diagnosis of its errors (t3d_sunrgbd_diagnose, include/t3d.h), one call.
     gt_all holds the ground truth of every class ('classname' per box); classes: the evaluated set (default: every class of gt_all) --
     the boxes of its other members are what a detection can be confused with.  -> compute_pr_curve_3d's dictionary plus, in file
     order, kind (abi.DIAG_KINDS), otherOverlap, otherGt (1-based into gt_all, 0 = none); gtState over gt_all (1 claimed, 2 missed but
     localised, 3 missed; 0 for the boxes of other classes); counts {tp cls loc both dup bkg}, gtCounts {claimed localised missed},
-    apFixed and dAP = apFixed - apScore {cls loc both dup bkg missed fp fn}."""
+    apFixed and dAP = apFixed - apScore {cls loc both dup bkg missed fp fn}.
+    parts: one t3d_sunrgbd_locparts call in place of the diagnose call -- which parameter group makes a LOC detection loose.  The
+    dictionary gains, in file order, partOverlap [P,5] (the overlap with its box once the detection's xy / z / centre / size / heading is
+    the box's: abi.LOC_PARTS) and locError [P,6] (abi.LOC_ERRORS: centre distance in xy, dz, log size ratios l w h, heading in
+    radians); partCounts (LOC detections each part repairs), partBoxes (boxes that gain a true positive), apPart and dAPPart = apPart -
+    apScore, keyed by abi.LOC_PARTS; locSummary (`loc_summary`).  The parts do not add up: a detection may be repaired by several."""
     names = gt_all['classname']
     same = np.array([c == classname for c in names], bool)
     others = np.array([c != classname and (classes is None or c in classes) for c in names], bool)
     osel = np.nonzero(others)[0]
-    r = _eval_call(det, select_boxes(gt_all, same), None, threshold, rt, other=select_boxes(gt_all, others), bg_threshold=bg_threshold)
+    r = _eval_call(det, select_boxes(gt_all, same), None, threshold, rt, other=select_boxes(gt_all, others), bg_threshold=bg_threshold,
+                   parts=parts)
     out = _pr_curve_result(r, same)
     og = r['other_gt'].astype(np.int64)
     og[og > 0] = osel[og[og > 0] - 1] + 1
@@ -465,12 +509,32 @@ def diagnose_class(classname, det, gt_all, threshold=0.25, bg_threshold=0.1, rt=
     out.update(kind=r['kind'], otherOverlap=r['other_overlap'], otherGt=og, gtState=state,
                counts={k: int(v) for k, v in zip(abi.DIAG_KINDS, r['counts'])}, gtCounts={k: int(v) for k, v in zip(GT_STATES, r['gt_counts'])},
                apFixed=ap_fixed, dAP={k: v - out['apScore'] for k, v in ap_fixed.items()})
+    if parts:
+        ap_part = {k: float(v) for k, v in zip(abi.LOC_PARTS, r['ap_part'])}
+        loc_error = r['loc_error'].reshape(-1, len(abi.LOC_ERRORS))
+        out.update(partOverlap=r['part_overlap'].reshape(-1, len(abi.LOC_PARTS)), locError=loc_error,
+                   partCounts={k: int(v) for k, v in zip(abi.LOC_PARTS, r['part_counts'])},
+                   partBoxes={k: int(v) for k, v in zip(abi.LOC_PARTS, r['part_boxes'])}, apPart=ap_part,
+                   dAPPart={k: v - out['apScore'] for k, v in ap_part.items()}, locSummary=loc_summary(r['kind'], loc_error))
     return out
 
 
 def _dap_text(dap):
     v = ['%s %.2f' % (k, 100.0 * dap[k]) for k in abi.DIAG_FIXES]
     return ' '.join(v[:6]) + ' | ' + ' '.join(v[6:])
+
+
+def _loc_text(s):
+    """`loc n 5 | xy 0.41 z +0.02 | l +35% w -3% h +1% | heading 12.0 deg` of one group of loc_summary; `-` for a value there is none of."""
+    val = lambda k, fmt, f=lambda v: v: fmt % f(s[k]) if math.isfinite(s[k]) else '-'
+    pct = lambda v: 100.0 * (math.exp(v) - 1.0)
+    return 'loc n %d | xy %s z %s | l %s w %s h %s | heading %s deg' % (
+        s['n'], val('xy', '%.2f'), val('z', '%+.2f'), val('l', '%+.0f%%', pct), val('w', '%+.0f%%', pct), val('h', '%+.0f%%', pct),
+        val('heading', '%.1f', math.degrees))
+
+
+def _dap_parts_text(dap):
+    return ' '.join('%s %.2f' % (k, 100.0 * dap[k]) for k in abi.LOC_PARTS)
 
 
 def bb3d_overlap_close_form(bb1, bb2, rt=None):
@@ -507,7 +571,11 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
     -> ({class: AP}, mean AP).  save_curves: a directory for <class>_pr.npz.
     diagnose: None, or {'bg': the background overlap t_b (0.1), 'json': a path or None}: diagnose_class per class -- two more lines
     behind each AP line (the detections per kind and the boxes per state; 100 x dAP per fix), one behind the mean (the class means),
-    the summary as JSON at the path, and the per-detection arrays in <class>_pr.npz.
+    the summary as JSON at the path, and the per-detection arrays in <class>_pr.npz.  With 'parts': True (diagnose_class(parts=True))
+    two more lines behind each `dAP for` line -- `Localisation for X:` (the medians of the six errors over the LOC detections, sizes
+    as 100 (exp(median log ratio) - 1) per cent) and `dAP(loc) for X:` (100 x dAPPart per part, beside the loc fix, and the detections
+    each part repairs) -- and `Mean dAP(loc):` behind `Mean dAP:`; the JSON gains `parts` and `locSummary` per class, `loc_parts` and
+    `mean_dAP_parts`; the .npz gains partOverlap and locError.
     bootstrap: None, the number of replicates, or {'R', 'seed' (0), 'level' (0.95), 'json' (a path or None), 'weights' (a
     bootstrap.Weights over the image list, made here when absent)}: bootstrap_class per class -- an `AP interval` line behind each AP
     line and a `Mean AP interval` line behind the mean (the percentile interval over R redraws of the image list, bootstrap.py) -- and
@@ -527,6 +595,7 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
         level, boot_ap = bootstrap.get('level', 0.95), {}
     gt_all = benchmark_groundtruth(dataset_dir, idx_list)
     ap, summary = {}, {}
+    parts = bool(diagnose is not None and diagnose.get('parts'))
     if save_curves:
         os.makedirs(save_curves, exist_ok=True)
     for name in CLASS_NAMES[test_on]:
@@ -542,7 +611,7 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
         elif diagnose is None:
             r = compute_pr_curve_3d(name, det, gt_all, None, threshold, rt)
         else:
-            r = diagnose_class(name, det, gt_all, threshold, diagnose.get('bg', 0.1), rt, classes=CLASS_NAMES[test_on])
+            r = diagnose_class(name, det, gt_all, threshold, diagnose.get('bg', 0.1), rt, classes=CLASS_NAMES[test_on], parts=parts)
         log('AP Score for %s: [%s]' % (name.upper(), num2str(r['apScore'] * 100.0)))
         ap[name] = r['apScore']
         if bootstrap is not None:
@@ -558,6 +627,13 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
             summary[name] = {'ap': r['apScore'], 'predictions': len(det['confidence']), 'boxes': r['numOfgt'], 'counts': c, 'gtCounts': g,
                              'apFixed': r['apFixed'], 'dAP': r['dAP']}
             curves.update(kind=r['kind'], otherOverlap=r['otherOverlap'], otherGt=r['otherGt'], gtState=r['gtState'])
+            if parts:
+                log('Localisation for %s: %s' % (name.upper(), _loc_text(r['locSummary']['loc'])))
+                log('dAP(loc) for %s: %s | of loc %.2f | repaired %s of %d' % (name.upper(), _dap_parts_text(r['dAPPart']), 100.0 * r['dAP']['loc'],
+                                                                             ' '.join('%d' % r['partCounts'][k] for k in abi.LOC_PARTS), c['loc']))
+                summary[name].update(parts={'apPart': r['apPart'], 'dAPPart': r['dAPPart'], 'partCounts': r['partCounts'], 'partBoxes': r['partBoxes']},
+                                     locSummary=r['locSummary'])
+                curves.update(partOverlap=r['partOverlap'], locError=r['locError'])
         if save_curves:
             np.savez(os.path.join(save_curves, name + '_pr.npz'), **curves)
     mean_ap = float(np.mean([ap[c] for c in CLASS_NAMES[test_on]]))
@@ -565,10 +641,15 @@ def evaluate(pred_dir, dataset_dir, idx_list, test_on='B', rt=None, log=print, t
     if diagnose is not None:
         mean_dap = {k: float(np.mean([summary[c]['dAP'][k] for c in CLASS_NAMES[test_on]])) for k in abi.DIAG_FIXES}
         log('Mean dAP: %s' % _dap_text(mean_dap))
+        doc = {'test_on': test_on, 'threshold': threshold, 'bg_threshold': diagnose.get('bg', 0.1), 'kinds': list(abi.DIAG_KINDS),
+               'fixes': list(abi.DIAG_FIXES), 'classes': summary, 'mean_ap': mean_ap, 'mean_dAP': mean_dap}
+        if parts:
+            mean_parts = {k: float(np.mean([summary[c]['parts']['dAPPart'][k] for c in CLASS_NAMES[test_on]])) for k in abi.LOC_PARTS}
+            log('Mean dAP(loc): %s' % _dap_parts_text(mean_parts))
+            doc.update(loc_parts=list(abi.LOC_PARTS), mean_dAP_parts=mean_parts)
         if diagnose.get('json'):
             with open(diagnose['json'], 'w') as fh:
-                json.dump({'test_on': test_on, 'threshold': threshold, 'bg_threshold': diagnose.get('bg', 0.1), 'kinds': list(abi.DIAG_KINDS),
-                           'fixes': list(abi.DIAG_FIXES), 'classes': summary, 'mean_ap': mean_ap, 'mean_dAP': mean_dap}, fh, indent=1)
+                json.dump(doc, fh, indent=1)
     if bootstrap is not None:
         boot = {'R': weights.R, 'seed': weights.seed, 'level': level, 'ap': boot_ap, 'summary': BS.summary(boot_ap, level)}
         log('Mean AP interval: %s' % BS.interval_text(boot['summary']['mean_ap'], level, weights.R, num2str))
@@ -651,23 +732,25 @@ def official_eval_of_test_semisup(test_semisup_argv, dataset_dir, idx_list, test
 
 
 def add_diagnose_arguments(p):
-    """--diagnose and its two options, for this parser and for detect's."""
+    """--diagnose and its three options, for this parser and for detect's."""
     p.add_argument('--diagnose', action='store_true',
                    help='sort the errors of every class into kinds and print what fixing each kind would add to its AP (module docstring)')
     p.add_argument('--diagnose_bg', type=float, default=None, help='--diagnose: the overlap below which a detection is on nothing (default 0.1)')
     p.add_argument('--diagnose_json', default=None, help='--diagnose: write the summary (counts, AP per fix, dAP, means) to this file')
+    p.add_argument('--diagnose_parts', action='store_true',
+                   help='--diagnose: split the localisation errors into xy, z, centre, size and heading -- what each costs and repairs')
 
 
 def diagnose_options(p, FLAGS, threshold=0.25):
     """The `diagnose` dictionary of `evaluate` from parsed flags (None without --diagnose); a parser error where they contradict."""
     if not FLAGS.diagnose:
-        if FLAGS.diagnose_bg is not None or FLAGS.diagnose_json is not None:
-            p.error('--diagnose_bg / --diagnose_json need --diagnose')
+        if FLAGS.diagnose_bg is not None or FLAGS.diagnose_json is not None or FLAGS.diagnose_parts:
+            p.error('--diagnose_bg / --diagnose_json / --diagnose_parts need --diagnose')
         return None
     bg = 0.1 if FLAGS.diagnose_bg is None else FLAGS.diagnose_bg
     if not 0.0 <= bg < threshold:
         p.error('--diagnose_bg must lie in [0, %g), below the overlap a true positive needs' % threshold)
-    return {'bg': bg, 'json': FLAGS.diagnose_json}
+    return {'bg': bg, 'json': FLAGS.diagnose_json, 'parts': bool(FLAGS.diagnose_parts)}
 
 
 def parser():
