@@ -2119,6 +2119,146 @@ typedef struct {
 int t3d_sunrgbd_locparts(const t3d_sunrgbd_eval_args* eval, const t3d_sunrgbd_diagnose_args* diag,
                          const t3d_sunrgbd_locparts_args* parts, t3d_stream_t stream);
 
+/* ---- Rescoring: one confidence from the label-free measures of a detection (csrc/rescore.hip; transferable3d_amd/rescore.py) ----
+ * The decode, t3d_detect_consistency and t3d_detect_ensemble each say something about a finished 3-D box; the confidence the result
+ * files carry is still the 2-D detector's.  These three calls turn the measures into one number: a feature matrix built from the stage
+ * buffers where they lie, an L2-regularised logistic regression fitted on the detections whose class has 3-D labels (y: what
+ * t3d_sunrgbd_eval says about them), and the model applied to every detection.  The reference has no such step; it is opt-in.
+ * Everything is fp64.  No floating-point atomics (none at all), no allocation, no host synchronisation: equal inputs give equal bytes.
+ *
+ * t3d_rescore_features -- X[i][k], row stride ld, k counting the set bits of feature_mask in ascending bit order.  Per detection i < n,
+ * every operation below its own fp64 operation (no contraction):
+ *   bit 0 logit_prob   p = (double)prob[i]; p = p < 1e-6 ? 1e-6 : p; p = p > 1 - 1e-6 ? 1 - 1e-6 : p (a NaN stays);  log(p / (1 - p))
+ *   bit 1 score        (double)score[i]
+ *   bit 2 reproj_iou   reproj[i][4]                                            (t3d_detect_consistency's `reproj`, [n,5])
+ *   bit 3 mask_in_box  n_mask > 0 ? (double)n_both / (double)n_mask : 0        (its `counts` [n,4]: n_mask, n_box, n_both, flags)
+ *   bit 4 seg_box_iou  u = n_mask + n_box - n_both (64-bit integer);  u > 0 ? (double)n_both / (double)u : 0
+ *   bit 5 log_mask     log1p((double)n_mask)
+ *   bit 6 view_iou     (double)view_iou[i]                                     (t3d_detect_ensemble's `agreement`)
+ * Columns 1, 2, 3, 4 and 6 have the bits a NumPy transcription gives.  Columns 0 and 5 go through log / log1p of two libraries, each
+ * within 1 ulp of the true value: within 2 ulps of each other.  Columns k >= popcount(feature_mask) of a row are not written.
+ * T3D_ERR_ARG: a NULL struct or X, feature_mask 0 or with a bit above 6, a NULL input that a selected feature reads (view_iou selected
+ * and NULL included); T3D_ERR_SHAPE: n < 0, ld < popcount(feature_mask).  n == 0: T3D_OK without a launch.
+ *
+ * t3d_rescore_fit -- minimises over (w [F], b), on the rows with r[i] > 0 (a row with r[i] == 0, or a NaN weight, takes no part whatever
+ * it holds), W = sum r:
+ *     J(w, b) = (1/W) sum_i r_i ( log(1 + exp(z_i)) - y_i z_i ) + lambda/2 |w|^2,   z_i = b + sum_j w_j xs_ij,   y_i = (y[i] != 0)
+ * on the standardised columns xs_ij = (X[i][j] - mean_j) * (1 / scale_j).  The intercept b is not penalised (lambda enters the
+ * gradient and the diagonal of the Hessian for the F feature coefficients only).
+ *   Standardisation  one kernel: per slice the weighted sum, then the weighted squared deviations from the slice's own mean (the slice
+ *                    is read twice by the workgroup that holds it), the minimum and the maximum of every column; the slices are
+ *                    merged in slice order by the pairwise update of Chan, Golub and LeVeque.  mean_j is the weighted mean, scale_j
+ *                    the square root of (weighted squared deviations / W).  A column with minimum == maximum (or a deviation that is
+ *                    not above 0) gets scale 1 -- and, where minimum == maximum, that value as its mean, so its standardised column
+ *                    is exactly 0 -- and sets T3D_RESCORE_CONSTANT_COLUMN.
+ *   Start            w = 0, b = log(Wy / (W - Wy)), Wy = sum r_i y_i.
+ *   Iteration        max_iter evaluations are enqueued (0: the default 30), each a launch over the slices and a one-workgroup launch.
+ *                    An evaluation at the trial point gives J, the gradient and the Hessian  (1/W) Xs^T diag(r p (1-p)) Xs + lambda I_F.
+ *                    The first evaluation, and every one whose J is <= the J of the last accepted point, is ACCEPTED: J is appended to
+ *                    `loss`, the point becomes the accepted point, and -- unless |gradient|_inf <= gtol (0: the default 1e-9), which
+ *                    ends the fit -- the next trial point is accepted + step, step = -Hessian^-1 gradient by Cholesky.  Otherwise
+ *                    (J larger, or not a number) the step is halved and the next trial point is accepted + step; after
+ *                    T3D_RESCORE_MAX_HALVINGS halvings in a row the fit ends unconverged.  So loss[0 .. n_iter-1] never increases.
+ *                    A Hessian that Cholesky refuses ends the fit unconverged too.  Once the fit has ended the remaining launches
+ *                    return at their first instruction; the host never reads the flag.
+ *   Reduction        a workgroup of 256 threads owns one slice of T3D_RESCORE_SLICE consecutive rows -- the cuts depend on n alone,
+ *                    never on the number of CUs -- and writes the slice's sums to the workspace; the one-workgroup launch adds the
+ *                    slices in slice order.  The Gram matrix of a slice is accumulated by v_mfma_f64_16x16x4_f64, four rows at a
+ *                    time per wave, the four waves' matrices added in wave order.
+ *   Outputs          coef_std [F+1]: w then b on the standardised columns, at the last accepted point; coef [F+1]: the same model in
+ *                    raw feature units, coef[j] = w_j * (1 / scale_j) and coef[F] = b - sum_j coef[j] mean_j (ascending j), what
+ *                    t3d_rescore_apply reads; mean [F], scale [F]; loss [max_iter]: the accepted J's, NaN behind them; n_iter: how
+ *                    many were accepted; n_rows, n_pos: the rows with r > 0 and those of them with y != 0; status: T3D_RESCORE_* bits.
+ *   T3D_RESCORE_NO_ROWS          W is not above 0.  mean 0, scale 1, every coefficient 0.  (T3D_OK: the call itself succeeded.)
+ *   T3D_RESCORE_ONE_CLASS        n_pos == 0 or n_pos == n_rows.  No iteration runs; w = 0 and b = logit((Wy + 0.5) / (W + 1)).
+ *   T3D_RESCORE_CONSTANT_COLUMN  above.  The fit runs; the column's coefficient is 0 (its standardised column is 0, the ridge does the rest).
+ *   T3D_RESCORE_NOT_CONVERGED    the enqueued evaluations ran out, the halvings did, or Cholesky refused.
+ *   T3D_RESCORE_NONFINITE        a row with r > 0 holds a NaN or an Inf in one of its F columns or in r.  No iteration runs and the
+ *                                coefficients are 0: the result is not to be used.
+ *   Equal bytes      two calls on equal inputs give equal bytes.  The SAME weighted rows interleaved with zero-weight rows in a larger
+ *                    call fall into other slices, so the sums are formed in another order: the coefficients then agree within the
+ *                    rounding of the sums (the tests bound it), not byte for byte.
+ *   workspace        T3D_RESCORE_FIT_WORKSPACE_BYTES(n) bytes, 8-byte aligned; its content means nothing before or after the call.
+ * T3D_ERR_ARG: a NULL struct, reserved != 0, lambda not above 0 (NaN included), gtol < 0 or NaN, max_iter < 0 or > 1000, a NULL output, a NULL
+ * X, y or r where n > 0, a workspace that is NULL, misaligned or too small.  T3D_ERR_SHAPE: n < 0, F < 1, F > T3D_RESCORE_MAX_FEATURES,
+ * ld < F.  n == 0 is a fit without rows: T3D_RESCORE_NO_ROWS.
+ *
+ * t3d_rescore_apply -- per row i < n_valid:  z = coef[F];  z = z + coef[j] * X[i][j] for j = 0 .. F-1 in this order, the product and
+ * the sum each rounded (no fused multiply-add);  out[i] = 1 / (1 + exp(-z)).  exp is within 1 ulp of the true value here and in the
+ * NumPy transcription, so the two differ by at most 4 u in exp, 6 u in the sum and 8 u = 2^-50 relative in out (u = 2^-53).
+ * out32[i] = (float)out[i] where out32 is not NULL: the ranking the suppression stages read.  Rows n_valid .. n-1 keep what they held.
+ * coef is device memory (what the fit wrote).  T3D_ERR_ARG: a NULL struct, X, coef or out, reserved != 0; T3D_ERR_SHAPE: n < 0,
+ * n_valid < 0 or > n, F < 1 or > T3D_RESCORE_MAX_FEATURES, ld < F.  n_valid == 0: T3D_OK without a launch. */
+#define T3D_RESCORE_MAX_FEATURES 15
+#define T3D_RESCORE_SLICE 2048
+#define T3D_RESCORE_MAX_HALVINGS 30
+#define T3D_RESCORE_N_FEATURES 7         /* the named features: bits 0 .. 6 of feature_mask */
+#define T3D_RESCORE_F_LOGIT_PROB 1u
+#define T3D_RESCORE_F_SCORE 2u
+#define T3D_RESCORE_F_REPROJ_IOU 4u
+#define T3D_RESCORE_F_MASK_IN_BOX 8u
+#define T3D_RESCORE_F_SEG_BOX_IOU 16u
+#define T3D_RESCORE_F_LOG_MASK 32u
+#define T3D_RESCORE_F_VIEW_IOU 64u
+#define T3D_RESCORE_NO_ROWS 1u
+#define T3D_RESCORE_ONE_CLASS 2u
+#define T3D_RESCORE_CONSTANT_COLUMN 4u
+#define T3D_RESCORE_NOT_CONVERGED 8u
+#define T3D_RESCORE_NONFINITE 16u
+#define T3D_RESCORE_SLICES(n) (((uint64_t)(n) + T3D_RESCORE_SLICE - 1u) / T3D_RESCORE_SLICE)
+/* 128 doubles of state, and per slice 80 doubles of column statistics and 288 of one evaluation's sums */
+#define T3D_RESCORE_FIT_WORKSPACE_BYTES(n) ((128u + T3D_RESCORE_SLICES(n) * 368u) * 8u)
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_rescore_features_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int ld;
+  uint32_t feature_mask;               /* T3D_RESCORE_F_* */
+  const float* prob;                   /* [n] the 2-D detector's confidence */
+  const float* score;                  /* [n] what t3d_detect_decode wrote */
+  const double* reproj;                /* [n,5] what t3d_detect_consistency wrote */
+  const int32_t* counts;               /* [n,4] what t3d_detect_consistency wrote */
+  const float* view_iou;               /* [n] t3d_detect_ensemble's agreement, or NULL */
+  double* X;                           /* [n,ld] out */
+} t3d_rescore_features_args;
+#define T3D_V2_SIZE_rescore_features_args 64
+int t3d_rescore_features(const t3d_rescore_features_args* args, t3d_stream_t stream);
+
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_rescore_fit_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int F; int ld;
+  int max_iter;                        /* evaluations to enqueue; 0: 30 */
+  int reserved;                        /* 0 */
+  const double* X;                     /* [n,ld] */
+  const uint8_t* y;                    /* [n] */
+  const double* r;                     /* [n] row weights, >= 0 */
+  double lambda;                       /* > 0 */
+  double gtol;                         /* 0: 1e-9 */
+  void* workspace;
+  uint64_t workspace_bytes;
+  double* coef;                        /* [F+1] out: raw units, the intercept last */
+  double* coef_std;                    /* [F+1] out: standardised units, the intercept last */
+  double* mean;                        /* [F] out */
+  double* scale;                       /* [F] out */
+  double* loss;                        /* [max_iter] out */
+  int32_t* n_iter;                     /* [1] out */
+  uint32_t* status;                    /* [1] out */
+  int64_t* n_rows;                     /* [1] out */
+  int64_t* n_pos;                      /* [1] out */
+} t3d_rescore_fit_args;
+#define T3D_V2_SIZE_rescore_fit_args 152
+int t3d_rescore_fit(const t3d_rescore_fit_args* args, t3d_stream_t stream);
+
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_rescore_apply_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_valid; int F; int ld;
+  int reserved;                        /* 0 */
+  const double* X;                     /* [n,ld] */
+  const double* coef;                  /* [F+1] device memory: raw units, the intercept last */
+  double* out;                         /* [n] out */
+  float* out32;                        /* [n] out, or NULL */
+} t3d_rescore_apply_args;
+#define T3D_V2_SIZE_rescore_apply_args 56
+int t3d_rescore_apply(const t3d_rescore_apply_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -363,6 +363,31 @@ class SunrgbdLocPartsArgs(Sized):
                 ('part_overlap', D), ('loc_error', D), ('part_counts', I), ('part_boxes', I), ('ap_part', D)]
 
 
+# t3d.h T3D_RESCORE_*: the named features (bit k of feature_mask is RESCORE_FEATURES[k]), the limits and the status bits of the fit
+RESCORE_FEATURES = ('logit_prob', 'score', 'reproj_iou', 'mask_in_box', 'seg_box_iou', 'log_mask', 'view_iou')
+RESCORE_MAX_FEATURES, RESCORE_SLICE, RESCORE_MAX_HALVINGS = 15, 2048, 30
+RESCORE_NO_ROWS, RESCORE_ONE_CLASS, RESCORE_CONSTANT_COLUMN, RESCORE_NOT_CONVERGED, RESCORE_NONFINITE = 1, 2, 4, 8, 16
+RESCORE_STATUS = {RESCORE_NO_ROWS: 'no_rows', RESCORE_ONE_CLASS: 'one_class', RESCORE_CONSTANT_COLUMN: 'constant_column',
+                  RESCORE_NOT_CONVERGED: 'not_converged', RESCORE_NONFINITE: 'nonfinite'}
+
+
+class RescoreFeaturesArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('ld', i32), ('feature_mask', C.c_uint32), ('prob', F), ('score', F), ('reproj', D),
+                ('counts', I), ('view_iou', F), ('X', D)]
+
+
+class RescoreFitArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('F', i32), ('ld', i32), ('max_iter', i32), ('reserved', i32), ('X', D), ('y', U8),
+                ('r', D), ('lambda_', C.c_double), ('gtol', C.c_double), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64),
+                ('coef', D), ('coef_std', D), ('mean', D), ('scale', D), ('loss', D), ('n_iter', I), ('status', C.POINTER(C.c_uint32)),
+                ('n_rows', L), ('n_pos', L)]
+
+
+class RescoreApplyArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_valid', i32), ('F', i32), ('ld', i32), ('reserved', i32), ('X', D), ('coef', D),
+                ('out', D), ('out32', F)]
+
+
 SEMI_BATCH, SEMI_ALTERNATE_BATCH, SEMI_MIXED_BATCH = 0, 1, 2          # t3d.h T3D_SEMI_*
 SEMI_METHODS = {'BATCH': SEMI_BATCH, 'ALTERNATE_BATCH': SEMI_ALTERNATE_BATCH, 'MIXED_BATCH': SEMI_MIXED_BATCH}
 SEMI_SAMPLE_MAX_B = 256
@@ -550,6 +575,16 @@ def sunrgbd_locparts_workspace_bytes(P, G):
     return G * 20 + 8
 
 
+def rescore_slices(n):
+    """t3d.h T3D_RESCORE_SLICES"""
+    return (n + RESCORE_SLICE - 1) // RESCORE_SLICE
+
+
+def rescore_fit_workspace_bytes(n):
+    """t3d.h T3D_RESCORE_FIT_WORKSPACE_BYTES"""
+    return (128 + rescore_slices(n) * 368) * 8
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -650,6 +685,9 @@ ENTRY_POINTS = {
     't3d_sunrgbd_eval': [C.POINTER(SunrgbdEvalArgs), VP],
     't3d_sunrgbd_diagnose': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdDiagnoseArgs), VP],
     't3d_sunrgbd_locparts': [C.POINTER(SunrgbdEvalArgs), C.POINTER(SunrgbdDiagnoseArgs), C.POINTER(SunrgbdLocPartsArgs), VP],
+    't3d_rescore_features': [C.POINTER(RescoreFeaturesArgs), VP],
+    't3d_rescore_fit': [C.POINTER(RescoreFitArgs), VP],
+    't3d_rescore_apply': [C.POINTER(RescoreApplyArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],

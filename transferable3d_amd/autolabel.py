@@ -3,7 +3,8 @@
 
     python -m transferable3d_amd.autolabel --dataset_dir D --idx_path I --classes table sofa dresser night_stand bookshelf \
         --model_path M [test_semisup's model flags] --out_dir OUT [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] \
-        [--keep_other_classes] [--link_inputs] [--score_against_labels] [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]]
+        [--keep_other_classes] [--link_inputs] [--score_against_labels] [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]] \
+        [--rescore MODEL.json [--min_rescore P]]
 
 Of every object of --classes in D/training/label_dimension/*.txt only the class and the 2-D box are used.  detect.Detector runs on that
 box (with prob 1); t3d_detect_consistency (consistency.py) measures the 3-D box it predicts against the 2-D box and the segmented points,
@@ -22,6 +23,11 @@ views, the label line is written from their fused box, and --min_view_iou reject
 -- stability under augmentation, the one test here that does not compare the box with its own frustum.  --score_against_labels then
 reports the accepted and the rejected boxes of that test alone as well.
 
+--rescore MODEL.json [--min_rescore P]: detect's rescoring (rescore.py).  A model fitted by `detect --rescore_fit` on the classes with 3-D
+labels gives every box one confidence from its measures, and --min_rescore rejects a box below P: one calibrated accept rule in the
+place of three cut-offs picked by hand (they still combine).  Every object is offered with prob 1, so a model's logit_prob column is
+constant here.  --score_against_labels reports the boxes that test alone accepts and rejects as well.
+
 A label line, from a decoded label row (h, w, l, tx, ty, tz, ry) (`label_line`): the 2-D box as x, y, w, h; the centroid (tx, tz,
 -(ty - h/2)) in upright depth coordinates; the half sizes (w/2, l/2, h/2); the basis (cos ry, -sin ry, sin ry, cos ry); the orientation
 (cos ry, -sin ry).  sunrgbd_data.SUNObject3d + compute_box_3d read such a line back as the decode's corner set, to the six decimals of %f.
@@ -36,7 +42,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, ensemble as EN, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, rescore as RS, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
 
 LINE = '%s %d %d %d %d %f %f %f %f %f %f %f %f %f %f %f %f'
 IOU_HIT = 0.25
@@ -57,19 +63,24 @@ def label_corners(obj):
     return get_3d_box((2.0 * obj.l, 2.0 * obj.w, 2.0 * obj.h), obj.heading_angle, (obj.centroid[0], -obj.centroid[2], obj.centroid[1]))
 
 
-def new_counts(thresholds, min_view_iou=None):
+# the tests beside the consistency thresholds: (flag, the record's measure)
+EXTRA_TESTS = (('min_view_iou', 'view_iou'), ('min_rescore', 'rescore_prob'))
+
+
+def new_counts(thresholds, min_view_iou=None, min_rescore=None):
     c = collections.OrderedDict(offered=0, too_few_points=0, accepted=0, rejected=0)
     c['rejected_by'] = collections.OrderedDict((name, 0) for name, t in zip(CS.THRESHOLDS, thresholds) if t is not None)
-    if min_view_iou is not None:
-        c['rejected_by']['min_view_iou'] = 0
+    for (flag, _), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
+        if t is not None:
+            c['rejected_by'][flag] = 0
     return c
 
 
-def count(records, classes, thresholds, min_view_iou=None):
+def count(records, classes, thresholds, min_view_iou=None, min_rescore=None):
     """records: [{'class', 'detected' (False: its frustum held too few points), 'accepted', 'reproj_iou', 'mask_in_box', 'seg_box_iou'}] ->
     {class: offered, too_few_points, accepted, rejected, rejected_by {threshold: n}} (a box may fail several tests).  min_view_iou: the
-    records carry 'view_iou' and the boxes below it are counted too."""
-    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou)) for c in classes)
+    records carry 'view_iou' and the boxes below it are counted too; min_rescore: the same for 'rescore_prob'."""
+    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou, min_rescore)) for c in classes)
     for r in records:
         c = out[r['class']]
         c['offered'] += 1
@@ -80,14 +91,16 @@ def count(records, classes, thresholds, min_view_iou=None):
         for name, measure, t in zip(CS.THRESHOLDS, CS.MEASURES, thresholds):
             if t is not None and not r[measure] >= t:
                 c['rejected_by'][name] += 1
-        if min_view_iou is not None and not r['view_iou'] >= min_view_iou:
-            c['rejected_by']['min_view_iou'] += 1
+        for (flag, measure), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
+            if t is not None and not r[measure] >= t:
+                c['rejected_by'][flag] += 1
     return out
 
 
-def score(records, classes, rt, min_view_iou=None):
+def score(records, classes, rt, min_view_iou=None, min_rescore=None):
     """--score_against_labels: per class, for the accepted and the rejected boxes, how many, their mean 3-D IoU with the label's own box
-    and the share at IoU >= 0.25.  min_view_iou: also under 'min_view_iou' for the boxes that test alone accepts and rejects."""
+    and the share at IoU >= 0.25.  min_view_iou: also under 'min_view_iou' for the boxes that test alone accepts and rejects; min_rescore: the
+    same under 'min_rescore'."""
     from transferable3d_amd.eval_det import box3d_iou_batch
     rows = [r for r in records if r['detected']]
     iou = box3d_iou_batch(np.stack([r['corners'] for r in rows]), np.stack([r['label_corners'] for r in rows]), rt)[0] if rows else []
@@ -98,10 +111,11 @@ def score(records, classes, rt, min_view_iou=None):
         out[c] = {}
         for kind in ('accepted', 'rejected'):
             out[c][kind] = stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c and r['accepted'] == (kind == 'accepted')]))
-        if min_view_iou is not None:
-            out[c]['min_view_iou'] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
-                                                            and bool(r['view_iou'] >= min_view_iou) == (kind == 'accepted')]))
-                                      for kind in ('accepted', 'rejected')}
+        for (flag, measure), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
+            if t is not None:
+                out[c][flag] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
+                                                      and bool(r[measure] >= t) == (kind == 'accepted')]))
+                                for kind in ('accepted', 'rejected')}
     return out
 
 
@@ -146,6 +160,8 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
                     r.update((k, fields[k]) for k in CS.MEASURES + ('flags',))
                 if d.view_iou is not None:
                     r.update(view_fields(d, i))
+                if d.rescore_prob is not None:
+                    r['rescore_prob'] = float(d.rescore_prob[i])
                 if score_against_labels:
                     r['label_corners'] = label_corners(o)
                 i += 1
@@ -153,12 +169,15 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
     assert i == len(meta), 'a detection matches no offered object'
     thresholds = detector.thresholds if detector.consistency else (None, None, None)
     min_view_iou = getattr(detector, 'min_view_iou', None)
-    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou), thresholds=dict(zip(CS.THRESHOLDS, thresholds)),
-                                      scenes=len(ids))
+    min_rescore = getattr(detector, 'min_rescore', None)
+    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou, min_rescore),
+                                      thresholds=dict(zip(CS.THRESHOLDS, thresholds)), scenes=len(ids))
     if getattr(detector, 'tta', None) is not None:
         summary['tta'] = dict(views=detector.tta, flip=detector.tta_flip, vote_iou=detector.tta_vote_iou, min_view_iou=min_view_iou)
+    if getattr(detector, 'rescore', None) is not None:
+        summary['rescore'] = dict(features=detector.rescore.features, min_rescore=min_rescore)
     if score_against_labels:
-        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou)
+        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou, min_rescore)
     written = write_labels(out_dir, ids, lines, records, classes, keep_other_classes)
     summary['scenes_written'] = len(written)
     if link_inputs:
@@ -171,7 +190,7 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
             ''.join(' (%s: %d)' % kv for kv in n['rejected_by'].items())))
         if score_against_labels:
             by = summary['score_against_labels'][c]
-            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --min_view_iou' % k, v) for k, v in by.get('min_view_iou', {}).items()]:
+            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag, _ in EXTRA_TESTS for k, v in by.get(flag, {}).items()]:
                 if v['n']:
                     log('  %s %d: mean 3-D IoU with the label %.3f, at IoU >= %g %.1f %%' % (kind, v['n'], v['mean_iou3d'], IOU_HIT,
                                                                                             100.0 * v['share_iou_ge_0.25']))
@@ -223,6 +242,7 @@ def parser():
     p.add_argument('--link_inputs', action='store_true', help='link image, calib and depth of the data set into <out_dir>/training')
     p.add_argument('--score_against_labels', action='store_true', help='report the 3-D IoU of accepted and rejected boxes with the 3-D boxes of the label lines')
     EN.add_arguments(p)
+    RS.add_arguments(p)
     return p
 
 
@@ -233,6 +253,8 @@ def parse(argv=None):
     try:
         args.thresholds = CS.check_thresholds(args.min_reproj_iou, args.min_mask_in_box, args.min_seg_box_iou)
         EN.check_options(args.tta, args.tta_flip, args.tta_vote_iou, args.min_view_iou)
+        if RS.check_min_rescore(args.min_rescore) is not None and args.rescore is None:
+            raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
     except ValueError as e:
         p.error(str(e))
     return args, TS.build_flags(list(rest))
@@ -245,7 +267,7 @@ def main(argv=None, rt=None, log=print):
         FLAGS.SUNRGBD_SEMI_TEST_CLS = list(args.classes)
     det = Detector(FLAGS, rt=rt, log=log, consistency=True, min_reproj_iou=args.thresholds[0], min_mask_in_box=args.thresholds[1],
                    min_seg_box_iou=args.thresholds[2], tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou,
-                   min_view_iou=args.min_view_iou)
+                   min_view_iou=args.min_view_iou, rescore=args.rescore, min_rescore=args.min_rescore)
     return run(det, args.dataset_dir, args.idx_path, args.classes, args.out_dir, keep_other_classes=args.keep_other_classes,
                link_inputs=args.link_inputs, score_against_labels=args.score_against_labels, log=log)
 

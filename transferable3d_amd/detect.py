@@ -12,6 +12,9 @@
         [--sweep [--sweep_nms_iou V ..] [--sweep_min_reproj_iou V ..] [--sweep_min_mask_in_box V ..] [--sweep_min_seg_box_iou V ..]
                  [--sweep_json FILE] [--sweep_top N]]
         [--bootstrap R [--bootstrap_seed S] [--bootstrap_level L] [--bootstrap_json FILE]]
+        [--rescore MODEL.json [--min_rescore P]]
+        [--rescore_fit MODEL.json [--rescore_classes C ..] [--rescore_target {overlap,tp}] [--rescore_lambda L] [--rescore_holdout H]
+                       [--rescore_features NAME ..]]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -84,6 +87,15 @@ mean AP minus the baseline's and minus the best row's (the same redraws for ever
 rows ...` behind `best:`, and the intervals in --sweep_json (which is where they go: --bootstrap_json is --official_eval's).  Without
 --bootstrap every output is what it was, byte for byte.
 
+--rescore MODEL.json [--min_rescore P]: one confidence per detection from its label-free measures (rescore.py: t3d_rescore_features and
+t3d_rescore_apply behind the ensemble, in front of the accept rule).  The records, the legends of --vis_dir and the rows of
+--consistency_json gain rescore_prob ('prob' stays the 2-D detector's); the suppression ranks by it where it ranks by 'prob', and the
+last column of the result files, --official_eval, --diagnose and --bootstrap use it (with --soft_nms: what Soft-NMS leaves of it);
+--min_rescore rejects a detection below P as the min_* thresholds do.  It implies --consistency; a model that reads view_iou needs --tta.
+--rescore_fit MODEL.json fits such a model (rescore.fit_parts): the pipeline runs once as for --sweep, the classes with ground truth are
+evaluated on the device, the images are split by --seed, and the held-out part reports the AP by prob against the AP by rescore_prob.
+It does not go with --rescore, --sweep, a suppression or a threshold.  Without these flags every output is what it was, byte for byte.
+
 Where things live: the stages behind the decode (views, consistency, the accept rule, NMS, box voting) and their order belong to
 semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
 boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
@@ -101,7 +113,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, nms as NMS, render as RD, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
+from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, nms as NMS, render as RD, rescore as RS, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -227,6 +239,8 @@ class Vis:
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
                 if d.n_votes is not None:
                     entry['votes'] = int(d.n_votes[r])
+                if d.rescore_prob is not None:
+                    entry['rescore_prob'] = float(d.rescore_prob[r])
                 if d.soft_prob is not None:
                     entry.update(soft_fields(d, r))
                 if d.view_iou is not None:
@@ -265,7 +279,8 @@ class Detector:
     def __init__(self, FLAGS=None, model_path=None, boxpc_model_path=None, rt=None, type_whitelist=SD.TYPE_WHITELIST,
                  num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
                  min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, tta=None, tta_flip=False,
-                 tta_vote_iou=None, min_view_iou=None, soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, **keywords):
+                 tta_vote_iou=None, min_view_iou=None, soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, rescore=None, min_rescore=None,
+                 **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.
@@ -285,7 +300,15 @@ class Detector:
         soft_nms: None, 'gaussian' or 'linear' -- Soft-NMS in place of the suppression (t3d_detect_soft_nms; module docstring): the
         confidence of a box that overlaps a better one of its image and class is multiplied by exp(-IoU^2 / soft_nms_sigma) (default
         0.5), or by 1 - IoU above nms_iou ('linear' needs it, 'gaussian' refuses it); a detection whose confidence falls below
-        soft_nms_min_prob (in [0, 1), default 0.001) is dropped.  nms_metric applies; nms_score 'score' and nms_fuse do not go with it."""
+        soft_nms_min_prob (in [0, 1), default 0.001) is dropped.  nms_metric applies; nms_score 'score' and nms_fuse do not go with it.
+        rescore: None, a rescore.Model or the path of one (rescore.py; module docstring): every detection gets `rescore_prob`, the
+        model's confidence from its measures, which the suppression, the result files and the evaluation then rank by in the place of
+        the 2-D detector's; it implies consistency, and a model that reads view_iou needs tta.  min_rescore: None, or the value in
+        [0, 1] below which a detection's rescore_prob rejects it, as the min_* thresholds do; it needs rescore."""
+        self.min_rescore = RS.check_min_rescore(min_rescore)
+        if self.min_rescore is not None and rescore is None:
+            raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
+        self.rescore = None if rescore is None else RS.Model.of(rescore)
         self.tta, self.tta_flip, self.tta_vote_iou, self.min_view_iou = EN.check_options(tta, tta_flip, tta_vote_iou, min_view_iou)
         self.soft_nms = NMS.check_soft_options(soft_nms, soft_nms_sigma, soft_nms_min_prob, nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou)
         if self.soft_nms is not None:            # (the threshold and the metric travel in the options; the views still read nms_metric)
@@ -294,7 +317,9 @@ class Detector:
             self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
             self.nms_fuse, self.nms_fuse_iou = NMS.check_fuse_options(self.nms_iou, nms_fuse, nms_fuse_iou)
         self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
-        self.consistency = bool(consistency) or any(t is not None for t in self.thresholds)
+        self.consistency = bool(consistency) or any(t is not None for t in self.thresholds) or self.rescore is not None
+        if self.rescore is not None and 'view_iou' in self.rescore.features and self.tta is None:
+            raise ValueError('the rescoring model reads view_iou, the agreement of the augmented views: it needs --tta')
         self.log = log
         self.FLAGS = FLAGS = FLAGS if FLAGS is not None else flags_from_keywords(**keywords)
         model_path = model_path or FLAGS.model_path
@@ -355,7 +380,9 @@ class Detector:
         classes = [type2class[m.name] for m in meta]
         ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live], classes)
         source = DeviceEvalSource(self.ops['graph'], dataset=ds, seed=FLAGS.seed)
-        nms = con = views = None
+        nms = con = views = rescore = None
+        if self.rescore is not None:
+            rescore = RS.RescoreRequest(self.rescore, [m.prob for m in meta], self.min_rescore)
         if self.soft_nms is not None:
             o = self.soft_nms
             nms = SI.NmsRequest(o.threshold, o.metric, None, [m.image for m in meta], classes, [m.prob for m in meta], soft=o.method,
@@ -373,7 +400,7 @@ class Detector:
             views = EN.EnsembleRequest(EN.views_of(self.tta, self.tta_flip, FLAGS.seed), self.nms_metric, self.tta_vote_iou, self.min_view_iou)
         res = SI.inference(self.sess, self.ops, None, None, self.B, prefix=FLAGS.pred_prefix, use_boxpc_fit_prob=FLAGS.use_boxpc_fit_prob,
                            source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False, nms=nms, consistency=con,
-                           views=views)
+                           views=views, rescore=rescore)
         self.stages = res.device
         d = res.decoded[slice(0, ds.F)]
         if self.log:
@@ -400,7 +427,9 @@ class Detector:
         'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view', and a detection below min_view_iou has no entry; 'score' and the
         consistency measures are those of view 0.
         With soft_nms the records gain 'soft_prob', the confidence Soft-NMS left ('prob' stays the 2-D detector's), and 'decays', the
-        number of better boxes that decayed it; a detection whose confidence fell below soft_nms_min_prob has no entry."""
+        number of better boxes that decayed it; a detection whose confidence fell below soft_nms_min_prob has no entry.
+        With rescore the records gain 'rescore_prob' ('prob' stays the 2-D detector's; soft_nms then decays rescore_prob), and a
+        detection below min_rescore has no entry."""
         vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None or self.soft_nms is not None)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
@@ -447,6 +476,8 @@ class Detector:
             raise ValueError('a sweep starts from the plain run: the detector has nms_iou, soft_nms or a min_* threshold')
         if self.tta is not None:
             raise ValueError('the views of tta are not swept: the detector has tta')
+        if self.rescore is not None:
+            raise ValueError('a sweep starts from the plain run: the detector has a rescoring model')
         if grid.consistency and not self.consistency:
             raise ValueError('the grid sweeps a min_* threshold: the detector needs consistency=True')
         meta, d = self.decode_all(parts)
@@ -469,6 +500,8 @@ class Detector:
         r = {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
         if d.n_votes is not None:
             r['votes'] = int(d.n_votes[i])
+        if d.rescore_prob is not None:
+            r['rescore_prob'] = float(d.rescore_prob[i])
         if d.soft_prob is not None:
             r.update(soft_fields(d, i))
         if d.view_iou is not None:
@@ -480,13 +513,14 @@ class Detector:
     def predictions(self, meta, d):
         """test_semisup's 14-list of a detection run (the entries it fills for --from_rgb_detection; the rotation angles stayed on the
         device, the label rows carry them) with the decoded records attached.  Its confidence entry -- what the result files write and
-        the evaluation ranks by -- is what Soft-NMS left of it, where that ran."""
+        the evaluation ranks by -- is the rescored confidence where a model rescored, and what Soft-NMS left of it where that ran."""
         n = len(meta)
         if d is None:
             return SI.Predictions([None, None, [], [], [], [], [], [], [], [], [], [], [], None])
         p = SI.Predictions([None, None, [None] * n, list(d.center), list(d.heading_cls), list(d.heading_res), list(d.size_cls),
                             list(d.size_res), [None] * n,
-                            [m.prob for m in meta] if d.soft_prob is None else [float(v) for v in d.soft_prob],
+                            [float(v) for v in d.soft_prob] if d.soft_prob is not None else
+                            [float(v) for v in d.rescore_prob] if d.rescore_prob is not None else [m.prob for m in meta],
                             [type2class[m.name] for m in meta], [m.image for m in meta], [m.box2d for m in meta], None])
         p.decoded = d
         return p
@@ -510,6 +544,8 @@ def write_consistency_json(path, meta, d):
                'n_mask': int(d.n_mask[i]), 'n_box': int(d.n_box[i]), 'n_both': int(d.n_both[i]), 'accepted': bool(d.accept[i]),
                'kept': bool(d.keep is None or d.keep[i])}
         row.update(consistency_fields(d, i, as_lists=True))
+        if d.rescore_prob is not None:
+            row['rescore_prob'] = float(d.rescore_prob[i])
         if d.soft_prob is not None:
             row.update(soft_fields(d, i))
         if d.view_iou is not None:
@@ -539,6 +575,8 @@ def parser():
     EN.add_arguments(p)
     SW.add_arguments(p)
     BS.add_arguments(p)                       # with --official_eval or --sweep: intervals behind the APs (bootstrap.py)
+    RS.add_arguments(p)
+    RS.add_fit_arguments(p)
     return p
 
 
@@ -553,6 +591,7 @@ def sweep_options(args):
     single += ['nms_fuse_iou'] if args.nms_fuse_iou is not None else []
     single += ['soft_nms'] if args.soft_nms is not None else []      # (the scores differ per configuration: ranks cannot be shared)
     single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
+    single += [f for f in ('rescore', 'min_rescore', 'rescore_fit') if getattr(args, f) is not None]
     if single:
         raise ValueError('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
     if args.vis_dir or args.consistency_json:
@@ -601,9 +640,20 @@ def main(argv=None, rt=None, log=print):
             raise ValueError('--bootstrap puts intervals behind the APs of --official_eval or --sweep: it needs one of them')
         if bootstrap is not None and grid is not None and bootstrap['json']:
             raise ValueError('--sweep writes its intervals to --sweep_json: it does not go with --bootstrap_json')
+        fit = RS.fit_options(args)
+        if args.min_rescore is not None and args.rescore is None:
+            raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
+        if fit is not None and fit['features'] is not None and 'view_iou' in fit['features'] and args.tta is None:
+            raise ValueError('the feature view_iou is the agreement of the augmented views: it needs --tta')
+        if fit is not None:
+            other = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'official_eval') if getattr(args, f)]
+            other += [f for f in ('nms_fuse_iou', 'soft_nms', 'min_view_iou', 'vis_dir', 'consistency_json') if getattr(args, f) is not None]
+            if other:
+                raise ValueError('--rescore_fit starts from the plain run, as --sweep does: it does not go with %s' % ' '.join('--' + f for f in other))
         if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
             raise ValueError('--vis_gt / --vis_suppressed need --vis_dir')
         consistency = args.consistency or any(getattr(args, t) is not None for t in CS.THRESHOLDS) or (grid is not None and grid.consistency)
+        consistency = consistency or args.rescore is not None or fit is not None
         if args.consistency_json and not consistency:
             raise ValueError('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
         vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None or args.soft_nms is not None) if args.vis_dir else None
@@ -611,7 +661,8 @@ def main(argv=None, rt=None, log=print):
                        nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=args.min_reproj_iou,
                        min_mask_in_box=args.min_mask_in_box, min_seg_box_iou=args.min_seg_box_iou, nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou,
                        tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou,
-                       soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_min_prob=args.soft_nms_min_prob)
+                       soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_min_prob=args.soft_nms_min_prob,
+                       rescore=args.rescore, min_rescore=args.min_rescore)
     except ValueError as e:
         p.error(str(e))
     valid = set(int(line.rstrip()) for line in open(args.idx_path))
@@ -624,6 +675,8 @@ def main(argv=None, rt=None, log=print):
     pictures = None if vis is None else (lambda idx: scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist) if vis.taken < vis.max else {})
     parts = [det.extract(scenes, [per_scene[idx] for idx in batch], batch, vis=vis)
              for batch, scenes in scene_batches(dataset, ids, image_wh=CS.image_size if consistency else None, pictures=pictures)]
+    if fit is not None:
+        return RS.fit_parts(det, parts, args.dataset_dir, args.idx_path, args.test_on, seed=FLAGS.seed, log=log, **fit)
     if grid is not None:
         top = 10 if args.sweep_top is None else args.sweep_top
         result = det.sweep_parts(parts, grid, args.dataset_dir, args.idx_path, args.test_on, bootstrap=bootstrap, top=top)

@@ -20,9 +20,10 @@ detection whose confidence falls below --soft_nms_min_prob is absent like a supp
 
 What runs behind the decode, and in which order, is written down in one place: `DeviceStages`.  `inference` builds one from its requests
 (nms, consistency, views); per batch it decodes every view and then measures the consistency of view 0, after the last batch it runs
-the ensemble of the views, the accept rule, the suppression and the box voting, and fetches everything as one `Decoded`.  It holds the
-boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.  `DeviceDecode` is the buffers of
-t3d_detect_decode alone; `report` writes a run's log lines and `kept` drops the rows that were not kept, for every caller.
+the ensemble of the views, the rescoring, the accept rule, the suppression and the box voting, and fetches everything as one
+`Decoded`.  It holds the boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.
+`DeviceDecode` is the buffers of t3d_detect_decode alone; `report` writes a run's log lines and `kept` drops the rows that were not
+kept, for every caller.
 """
 import contextlib
 import ctypes as C
@@ -36,7 +37,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transferable3d_amd import abi, nms as NMS, test_semisup as TS       # noqa: E402
 from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
-from transferable3d_amd import consistency as CS, ensemble as EN         # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, rescore as RS      # noqa: E402
 from transferable3d_amd.consistency import ConsistencyRequest, DeviceConsistency      # noqa: E402
 from transferable3d_amd.constants import type2class                     # noqa: E402
 
@@ -114,11 +115,14 @@ class Decoded:
     None without.  score, mask_count, the heads and the consistency measures stay those of view 0.
     With Soft-NMS (NmsRequest(soft=...)) soft_prob [n] is the confidence t3d_detect_soft_nms left of every detection -- the 2-D
     detector's where nothing decayed it -- and n_decays [n] the number of better boxes that decayed it; keep is False for a detection
-    whose confidence fell below the floor and suppressed_by names the box whose decay took it there; None without."""
+    whose confidence fell below the floor and suppressed_by names the box whose decay took it there; None without.
+    With a rescoring model (RescoreRequest, rescore.py) rescore_prob [n] is the confidence t3d_rescore_apply gave every detection from
+    its measures; the suppression stages then rank by it where they rank by 'prob' (and soft_prob is what Soft-NMS left of it); None
+    without."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
     OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept',
                 'raw_label', 'raw_corners', 'n_votes', 'view_label', 'view_score', 'view_iou', 'view_min_iou', 'anchor_view', 'n_views_voted',
-                'soft_prob', 'n_decays')
+                'soft_prob', 'n_decays', 'rescore_prob')
     VIEW_MAJOR = ('view_label', 'view_score')              # [V, n, ...]: the detection is the second axis
 
     def __init__(self, **fields):
@@ -193,21 +197,31 @@ class DeviceDecode:
 class DeviceStages:
     """The stages behind t3d_detect_decode of one `inference(decode='device')` run over `n` frustums, the first `total` of them real, and
     the one place that says in which order they run.  Per batch (`launch`): the decode of every view, then -- behind view 0's -- the
-    consistency measures.  After the last batch (`finish`): the ensemble of the views, the accept rows, the suppression, the box
-    voting, and the one fetch of everything as a Decoded.
+    consistency measures.  After the last batch (`finish`): the ensemble of the views, the rescoring, the accept rows, the suppression,
+    the box voting, and the one fetch of everything as a Decoded.
 
     label [n, 7], corners [n, 24]: the boxes on the device as the stages so far left them -- a stage that rewrites boxes (the ensemble,
     the box voting) reads them and puts its output in their place, so neither a later stage nor a caller asks which stage ran; score [n]:
     where view 0's decode wrote it.  accept [n] bool (None: nothing was asked that could reject): the detections that miss no threshold
-    of the consistency request and do not lie below views.min_view_iou; below: how many of the real detections lie below each of these
-    thresholds (`report`)."""
+    of the consistency request and do not lie below views.min_view_iou or rescore.min_rescore; below: how many of the real detections
+    lie below each of these thresholds (`report`).  rescore_out (rescore.DeviceRescore, None without a request): its out32 [n] is the
+    rescored confidence on the device, which `nms` ranks by in the place of the request's `prob`."""
 
-    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None):
+    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None, rescore=None):
         if nms is not None and len(nms.image_ids) != total:
             raise ValueError('%d image ids for %d detections' % (len(nms.image_ids), total))
         if consistency is not None and len(consistency) != total:
             raise ValueError('%d detections in the consistency request, %d decoded' % (len(consistency), total))
+        if rescore is not None:
+            if len(rescore) != total:
+                raise ValueError('%d confidences in the rescore request, %d decoded' % (len(rescore), total))
+            names = rescore.model.features
+            if 'view_iou' in names and views is None:
+                raise ValueError('the rescoring model reads view_iou, the agreement of the augmented views: it needs --tta')
+            if consistency is None and any(k in names for k in ('reproj_iou', 'mask_in_box', 'seg_box_iou', 'log_mask')):
+                raise ValueError('the rescoring model reads the consistency measures: it needs a consistency request')
         self.rt, self.n, self.total, self.nms_request, self.views = rt, n, total, nms, views
+        self.rescore_request, self.rescore_out = rescore, None
         self.decodes = [DeviceDecode(rt, n, num_point, want_seg=want_seg and v == 0) for v in range(1 if views is None else len(views))]
         self.consistency = None if consistency is None else DeviceConsistency(rt, n, num_point, consistency)
         self.rot_angle = None if views is None else rt.zeros(n)      # every batch's angles: the ensemble mirrors back with them
@@ -230,6 +244,8 @@ class DeviceStages:
         """After the last batch -> (Decoded, masks [n, N] uint8 or None)."""
         if self.views is not None:
             self.ensemble()
+        if self.rescore_request is not None:
+            self.rescore()
         self.accept_rows()
         if self.nms_request is not None:
             self.nms()
@@ -243,9 +259,23 @@ class DeviceStages:
                                     self.corners, req.flip_mask, self.rot_angle, req.vote_threshold, req.metric)
         self.label, self.corners = out[0], out[1]
 
+    def rescore(self):
+        """t3d_rescore_features on the buffers the stages so far wrote -- the 2-D confidences, view 0's decoded score, the consistency
+        kernel's rectangle and counts, the ensemble's agreement -- and t3d_rescore_apply of the request's model over the real rows."""
+        req, total = self.rescore_request, self.total
+        out = self.rescore_out = RS.DeviceRescore(self.rt, self.n, req.model.features)
+        prob = self.rt.zeros(self.n)
+        prob[:total] = torch.from_numpy(req.prob).to(self.rt.device)
+        con, ens = self.consistency, self.ensemble_out
+        out.features(prob, self.score, None if con is None else con.reproj, None if con is None else con.counts,
+                     None if ens is None else ens.agreement)
+        out.load(req.model)
+        out.apply(n_valid=total)
+
     def accept_rows(self):
-        """The one accept rule: a detection is rejected where it misses a threshold of the consistency request or its view_iou lies below
-        views.min_view_iou.  Copies the consistency outputs and the agreement back -- the small copies in front of the group building."""
+        """The one accept rule: a detection is rejected where it misses a threshold of the consistency request, its view_iou lies below
+        views.min_view_iou or its rescored confidence below rescore.min_rescore.  Copies the consistency outputs, the agreement and the
+        rescored confidence back -- the small copies in front of the group building."""
         total, masks = self.total, []
         if self.consistency is not None:
             m = self.measures = self.consistency.fetch()
@@ -255,6 +285,11 @@ class DeviceStages:
         if self.views is not None and self.views.min_view_iou is not None:
             masks.append(self.ensemble_out.agreement[:self.n].cpu().numpy().astype(np.float64) >= self.views.min_view_iou)
             self.below['view_iou'] = int((~masks[-1][:total]).sum())
+        if self.rescore_request is not None and self.rescore_request.min_rescore is not None:
+            ok = self.rescore_out.out[:self.n].cpu().numpy() >= self.rescore_request.min_rescore
+            self.below['rescore_prob'] = int((~ok[:total]).sum())
+            ok[total:] = True                                     # (the rows that pad a last batch are no detections)
+            masks.append(ok)
         if masks:
             self.accept = np.logical_and.reduce(masks)
 
@@ -262,12 +297,15 @@ class DeviceStages:
         """t3d_detect_nms over the real rows, on the current corners.  A rejected detection is listed in no group, so it suppresses
         nothing and comes back as kept (`accept` says it is rejected).  With a request that fuses, t3d_detect_fuse follows directly on the
         same buffers (a row in no group neither votes nor is fused) and its output becomes the current boxes.  With a soft request
-        t3d_detect_soft_nms runs in its place, on the same groups: a row in no group keeps its confidence."""
+        t3d_detect_soft_nms runs in its place, on the same groups: a row in no group keeps its confidence.  Where the rescoring stage
+        ran, 'prob' is the confidence it left on the device, not the request's."""
         req, total = self.nms_request, self.total
         rows = np.arange(total) if self.accept is None else np.nonzero(self.accept[:total])[0]
         offsets, members = NMS.groups_of(req.image_ids[rows], req.class_ids[rows])
         score = self.score
-        if req.score == 'prob':
+        if req.score == 'prob' and self.rescore_out is not None:
+            score = self.rescore_out.out32                        # the rescored confidence, where the stage wrote it
+        elif req.score == 'prob':
             score = self.rt.zeros(self.n)
             score[:total] = torch.from_numpy(req.prob).to(self.rt.device)
         if req.soft is not None:
@@ -305,6 +343,8 @@ class DeviceStages:
         for k, v in (self.measures or {}).items():
             if k in Decoded.OPTIONAL:
                 setattr(d, k, v)
+        if self.rescore_out is not None:
+            d.rescore_prob = host(self.rescore_out.out)
         d.accept = self.accept
         return d, seg
 
@@ -328,7 +368,7 @@ def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
 
 
 def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
-              decode='host', want_seg=True, nms=None, consistency=None, views=None):
+              decode='host', want_seg=True, nms=None, consistency=None, views=None, rescore=None):
     """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
     padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
@@ -343,11 +383,16 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     still follows view 0's decode.  After the last batch one t3d_detect_ensemble call fuses the views of every detection; the NMS, the
     box voting and `.decoded.label` / `.corners` then read its output, `.decoded.view_*` / `.anchor_view` / `.n_views_voted` say what
     it found (Decoded), and a detection whose view_iou lies below views.min_view_iou is rejected as one below a consistency threshold.
+    rescore (rescore.RescoreRequest, decode='device' only): behind the ensemble, t3d_rescore_features and t3d_rescore_apply give every
+    detection one confidence from its measures (`.decoded.rescore_prob`); a detection below rescore.min_rescore is rejected like one below
+    a consistency threshold, and an nms request that ranks by 'prob' ranks by the rescored confidence.
     The stages and their order are DeviceStages'; this function loads and runs the graph and says when a view of a batch is ready."""
     if decode == 'host' and nms is not None:
         raise ValueError("nms runs on the device-decoded boxes: decode='device'")
     if decode == 'host' and consistency is not None:
         raise ValueError("the consistency measures are taken on the device-decoded boxes: decode='device'")
+    if decode == 'host' and rescore is not None:
+        raise ValueError("the rescoring reads the device-decoded records: decode='device'")
     if views is not None and (decode != 'device' or source is None):
         raise ValueError("views are further draws of a device-resident source: decode='device' and a source")
     if decode == 'host':
@@ -364,7 +409,7 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     total = source.ds.F if source is not None else n                 # the frustums past it pad the last batch
     rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
     xyz = sess.g.inputs.pc if consistency is not None else None      # [B * N, ld] where the network read the batch
-    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views)
+    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views, rescore=rescore)
     sources = [source] + ([] if views is None else [source.view(seed, flip) for seed, flip in views.views[1:]])
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
@@ -409,6 +454,8 @@ def report(log, stages, d):
     if d.accept is not None:
         con = stages.consistency
         extra = [('view_iou', stages.views.min_view_iou, stages.below['view_iou'])] if 'view_iou' in stages.below else []
+        if 'rescore_prob' in stages.below:
+            extra.append(('rescore_prob', stages.rescore_request.min_rescore, stages.below['rescore_prob']))
         log(CS.log_line(d.accept, stages.below, con.thresholds if con is not None else (None, None, None), extra))
     if stages.views is not None:
         log(EN.log_line(stages.views, d))
