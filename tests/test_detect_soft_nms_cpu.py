@@ -247,7 +247,8 @@ def test_flag_errors(tmp_path):
     with pytest.raises(ValueError):
         SI.inference(None, None, None, None, 4, decode='host', nms=req)
     with pytest.raises(ValueError, match='soft_nms'):
-        DT.Detector.sweep_parts(type('D', (), dict(nms_iou=None, soft_nms=req.soft, thresholds=(None,) * 3, tta=None))(), [], None, None, None)
+        DT.Detector.sweep_parts(type('D', (), dict(nms_iou=None, soft_nms=req.soft, suppression=NMS.suppression('gaussian', 0.3, nms_metric='bev'),
+                                                   thresholds=(None,) * 3, tta=None))(), [], None, None, None)
 
 
 # ---- the flow --------------------------------------------------------------------------------------------------------------------------

@@ -763,6 +763,16 @@ def dptr(t):
     return C.cast(C.c_void_p(0 if t is None else t.data_ptr()), D)
 
 
+def grown(t, n, dtype, device, *width):
+    """A wrapper's output or workspace of at least n rows [*width] of `dtype` on `device` (a workspace of 8-byte words: int64 rows): `t`
+    where it holds that many already, else a new zeroed tensor of max(n, 1) rows.  The wrapper object keeps what this returns; such
+    buffers are not the runtime's, because they are replaced as they grow."""
+    import torch
+    if t is not None and t.shape[0] >= n:
+        return t
+    return torch.zeros(max(n, 1), *width, dtype=dtype, device=device)
+
+
 def check(rc, what):
     if rc != 0:
         raise T3DError('%s failed: %s' % (what, ERRORS.get(rc, rc)))

@@ -100,8 +100,9 @@ Where things live: the stages behind the decode (views, consistency, the accept 
 semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
 boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
 `consistency:` / `tta:` / `nms` lines, semisup_infer.kept drops the rows that were not kept.  Here: what the host knows of a detection
-(`Detection`), the extraction, the requests, the records and reports, and `main`, which checks its own flags, lets `Detector` check the
-rest, and turns either's ValueError into an argument error in one place, before a model is built.
+(`Detection`), the extraction, the requests, the records and reports with the fields every stage adds to them (`FIELD_GROUPS`), and
+`main`, which checks its own flags, lets `Detector` check the rest (`STAGE_KEYWORDS`), and turns either's ValueError into an argument
+error in one place, before a model is built.
 """
 import argparse
 import collections
@@ -237,16 +238,7 @@ class Vis:
                          'box2d': [float(x) for x in m.box2d], 'colour': byte(c), 'kept': kind == 'kept'}
                 if kind == 'suppressed':
                     entry['suppressed_by'] = local.get(int(d.suppressed_by[r]), None)
-                if d.n_votes is not None:
-                    entry['votes'] = int(d.n_votes[r])
-                if d.rescore_prob is not None:
-                    entry['rescore_prob'] = float(d.rescore_prob[r])
-                if d.soft_prob is not None:
-                    entry.update(soft_fields(d, r))
-                if d.view_iou is not None:
-                    entry.update(view_fields(d, r))
-                if d.reproj_iou is not None:
-                    entry.update(consistency_fields(d, r, as_lists=True))
+                entry.update(fields_of(d, r, RECORD_GROUPS, as_lists=True))
                 if d.accept is not None and not d.accept[r]:
                     entry['kind'] = 'rejected'
                 legend['boxes'].append(entry)
@@ -260,15 +252,40 @@ def consistency_fields(d, i, as_lists=False):
             'mask_in_box': float(d.mask_in_box[i]), 'seg_box_iou': float(d.seg_box_iou[i]), 'flags': int(d.flags[i])}
 
 
-def soft_fields(d, i):
+def soft_fields(d, i, as_lists=False):
     """What a record (or a legend / JSON entry) says of what Soft-NMS left of detection i's confidence ('prob' stays the 2-D detector's)."""
     return {'soft_prob': float(d.soft_prob[i]), 'decays': int(d.n_decays[i])}
 
 
-def view_fields(d, i):
+def view_fields(d, i, as_lists=False):
     """What a record (or a legend / JSON entry) says of how detection i's views agreed (detect --tta)."""
     return {'view_iou': float(d.view_iou[i]), 'view_min_iou': float(d.view_min_iou[i]), 'views_voted': int(d.n_views_voted[i]),
             'anchor_view': int(d.anchor_view[i])}
+
+
+# The optional fields of a detection, one group per stage that adds some: the Decoded attribute that says the stage ran, and the fields
+# it contributes to a record (as_lists: to a legend entry or a JSON row).  A writer names the groups it carries, in its own order.
+FIELD_GROUPS = {
+    'votes': ('n_votes', lambda d, i, as_lists=False: {'votes': int(d.n_votes[i])}),
+    'rescore': ('rescore_prob', lambda d, i, as_lists=False: {'rescore_prob': float(d.rescore_prob[i])}),
+    'soft': ('soft_prob', soft_fields),
+    'views': ('view_iou', view_fields),
+    'consistency': ('reproj_iou', consistency_fields),
+}
+RECORD_GROUPS = ('votes', 'rescore', 'soft', 'views', 'consistency')       # the records of `Detector.detect` and the legends of --vis_dir
+ROW_GROUPS = ('consistency', 'rescore', 'soft', 'views')                   # the rows of --consistency_json
+# the options of the stages as `Detector` takes them, under the names of the flags (the module docstring describes them)
+STAGE_KEYWORDS = ('nms_iou', 'nms_metric', 'nms_score', 'nms_fuse', 'nms_fuse_iou', 'soft_nms', 'soft_nms_sigma', 'soft_nms_min_prob', 'consistency',
+                  'min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou', 'tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou', 'rescore', 'min_rescore')
+
+
+def fields_of(d, i, groups, as_lists=False):
+    """The fields the stages that ran (Decoded `d`) add for detection i, of the groups named, in that order."""
+    out = {}
+    for present, fields in (FIELD_GROUPS[g] for g in groups):
+        if getattr(d, present) is not None:
+            out.update(fields(d, i, as_lists))
+    return out
 
 
 class Detector:
@@ -283,39 +300,21 @@ class Detector:
                  **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
-        frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.
-        nms_iou: None (every detection is reported, as the reference does) or the IoU in (0, 1] above which a box is suppressed by a
-        better-ranked kept box of its image and class; nms_metric '3d' (default) / 'bev'; nms_score 'prob' (default: the 2-D
-        detection confidence, what the result files and the evaluation rank by) / 'score' (the decoded network score).  log: a
-        function that takes the one line per run on how many detections were kept.
-        nms_fuse (needs nms_iou): every kept box takes the weighted mean geometry of the boxes it suppressed (t3d_detect_fuse; module
-        docstring); nms_fuse_iou: None (= nms_iou: every suppressed box votes) or the IoU in [nms_iou, 1] above which one votes; it
-        implies nms_fuse.
-        consistency: measure every detection with t3d_detect_consistency (consistency.py); min_reproj_iou / min_mask_in_box /
-        min_seg_box_iou: None, or the value in [0, 1] below which a detection is rejected (any of them implies consistency) -- before
-        the suppression of nms_iou, in whose groups a rejected detection is not listed.
-        tta: None, or the number of views 2..8 every frustum is run in (ensemble.py; module docstring); tta_flip: the odd views are
-        mirrored; tta_vote_iou: the IoU with the anchor view above which a view votes (default 0); min_view_iou: None, or the value in
-        [0, 1] below which a detection's view_iou rejects it, as the min_* thresholds do.  The last three need tta.
-        soft_nms: None, 'gaussian' or 'linear' -- Soft-NMS in place of the suppression (t3d_detect_soft_nms; module docstring): the
-        confidence of a box that overlaps a better one of its image and class is multiplied by exp(-IoU^2 / soft_nms_sigma) (default
-        0.5), or by 1 - IoU above nms_iou ('linear' needs it, 'gaussian' refuses it); a detection whose confidence falls below
-        soft_nms_min_prob (in [0, 1), default 0.001) is dropped.  nms_metric applies; nms_score 'score' and nms_fuse do not go with it.
-        rescore: None, a rescore.Model or the path of one (rescore.py; module docstring): every detection gets `rescore_prob`, the
-        model's confidence from its measures, which the suppression, the result files and the evaluation then rank by in the place of
-        the 2-D detector's; it implies consistency, and a model that reads view_iou needs tta.  min_rescore: None, or the value in
-        [0, 1] below which a detection's rescore_prob rejects it, as the min_* thresholds do; it needs rescore."""
+        frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.  log: a
+        function that takes the lines a run says of its stages (semisup_infer.report).
+        The options of the stages (STAGE_KEYWORDS) carry the names, the values and the defaults of the flags the module docstring
+        describes, None or False where a flag is not given; consistency: measure every detection (a threshold and rescore imply it);
+        rescore: a rescore.Model or the path of one.  They are checked here, before a model is built, and kept under their names:
+        nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou and soft_nms (its nms.SoftOptions) as `suppression` (nms.Suppression)
+        holds them -- with soft_nms, nms_iou is None -- thresholds, consistency, tta, tta_flip, tta_vote_iou, min_view_iou, rescore (the
+        Model), min_rescore."""
         self.min_rescore = RS.check_min_rescore(min_rescore)
         if self.min_rescore is not None and rescore is None:
             raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
         self.rescore = None if rescore is None else RS.Model.of(rescore)
         self.tta, self.tta_flip, self.tta_vote_iou, self.min_view_iou = EN.check_options(tta, tta_flip, tta_vote_iou, min_view_iou)
-        self.soft_nms = NMS.check_soft_options(soft_nms, soft_nms_sigma, soft_nms_min_prob, nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou)
-        if self.soft_nms is not None:            # (the threshold and the metric travel in the options; the views still read nms_metric)
-            self.nms_iou, self.nms_metric, self.nms_score, self.nms_fuse, self.nms_fuse_iou = None, self.soft_nms.metric, 'prob', False, None
-        else:
-            self.nms_iou, self.nms_metric, self.nms_score = NMS.check_options(nms_iou, nms_metric, nms_score)
-            self.nms_fuse, self.nms_fuse_iou = NMS.check_fuse_options(self.nms_iou, nms_fuse, nms_fuse_iou)
+        self.suppression = NMS.suppression(soft_nms, soft_nms_sigma, soft_nms_min_prob, nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou)
+        self.nms_iou, self.nms_metric, self.nms_score, self.nms_fuse, self.nms_fuse_iou, self.soft_nms = self.suppression
         self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
         self.consistency = bool(consistency) or any(t is not None for t in self.thresholds) or self.rescore is not None
         if self.rescore is not None and 'view_iou' in self.rescore.features and self.tta is None:
@@ -383,13 +382,8 @@ class Detector:
         nms = con = views = rescore = None
         if self.rescore is not None:
             rescore = RS.RescoreRequest(self.rescore, [m.prob for m in meta], self.min_rescore)
-        if self.soft_nms is not None:
-            o = self.soft_nms
-            nms = SI.NmsRequest(o.threshold, o.metric, None, [m.image for m in meta], classes, [m.prob for m in meta], soft=o.method,
-                                sigma=o.sigma if o.method == 'gaussian' else None, min_prob=o.min_prob)
-        elif self.nms_iou is not None:
-            nms = SI.NmsRequest(self.nms_iou, self.nms_metric, self.nms_score, [m.image for m in meta], classes, [m.prob for m in meta],
-                                fuse=self.nms_fuse, vote_threshold=self.nms_fuse_iou)
+        if self.suppression.on:
+            nms = SI.NmsRequest.of(self.suppression, [m.image for m in meta], classes, [m.prob for m in meta])
         if self.consistency:
             rows, index = [], []
             for p in parts:                              # a part's meta names its scenes by their position in the part
@@ -418,19 +412,15 @@ class Detector:
         vis_dir: write <id>.png / <id>.json of the first vis_max scenes with a detection there (module docstring); a scene may carry
         'image' (uint8 [H,W,3], RGB) for the camera panel, and 'gt_corners' [g,8,3] (upright camera) / 'gt_classes' for vis_gt.  The
         records do not depend on it.
-        With `consistency` (or a threshold) the records gain 'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou', 'flags'
-        (consistency.py), and a detection below a threshold has no entry; a scene may carry 'image_wh' = (W, H), to which the
-        reprojected rectangle is then clipped (without it: no clipping).
-        With nms_fuse 'label' and 'corners' are the fused box and the records gain 'votes', the number of suppressed boxes that voted
-        (0: the box is what the decode wrote).  The consistency measures of a fused detection are those of its unfused box.
-        With tta 'label' and 'corners' are what t3d_detect_ensemble made of the views (and nms_fuse of that), the records gain
-        'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view', and a detection below min_view_iou has no entry; 'score' and the
-        consistency measures are those of view 0.
-        With soft_nms the records gain 'soft_prob', the confidence Soft-NMS left ('prob' stays the 2-D detector's), and 'decays', the
-        number of better boxes that decayed it; a detection whose confidence fell below soft_nms_min_prob has no entry.
-        With rescore the records gain 'rescore_prob' ('prob' stays the 2-D detector's; soft_nms then decays rescore_prob), and a
-        detection below min_rescore has no entry."""
-        vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.nms_iou is not None or self.soft_nms is not None)
+        A stage that ran adds its fields to the records (FIELD_GROUPS, in the order of RECORD_GROUPS; the module docstring says what they
+        mean): nms_fuse 'votes', the number of suppressed boxes that voted (0: the box is what the decode wrote); rescore
+        'rescore_prob'; soft_nms 'soft_prob' and 'decays'; tta 'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view'; consistency
+        'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou' and 'flags'.  'prob' stays the 2-D detector's.  'label' and
+        'corners' are the box after every stage that ran: what t3d_detect_ensemble made of the views, and nms_fuse of that; 'score'
+        and the consistency measures stay those of view 0's unfused box.  A detection that a threshold rejected, or whose confidence
+        Soft-NMS took below soft_nms_min_prob, has no entry.  With consistency a scene may carry 'image_wh' = (W, H), to which the
+        reprojected rectangle is then clipped (without it: no clipping)."""
+        vis = None if vis_dir is None else Vis(vis_dir, vis_max, vis_gt, vis_suppressed, nms=self.suppression.on)
         if len(scenes) != len(detections):
             raise ValueError('%d scenes, detections of %d' % (len(scenes), len(detections)))
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
@@ -472,7 +462,7 @@ class Detector:
         """`sweep` on extracted parts (what `main` holds)."""
         from transferable3d_amd import evaluate_sunrgbd as ES
         import torch
-        if self.nms_iou is not None or self.soft_nms is not None or any(t is not None for t in self.thresholds):
+        if self.suppression.on or any(t is not None for t in self.thresholds):
             raise ValueError('a sweep starts from the plain run: the detector has nms_iou, soft_nms or a min_* threshold')
         if self.tta is not None:
             raise ValueError('the views of tta are not swept: the detector has tta')
@@ -498,30 +488,18 @@ class Detector:
     @staticmethod
     def record(name, box2d, prob, d, i):
         r = {'class': name, 'box2d': box2d, 'prob': prob, 'score': float(d.score[i]), 'label': d.label[i], 'corners': d.corners[i]}
-        if d.n_votes is not None:
-            r['votes'] = int(d.n_votes[i])
-        if d.rescore_prob is not None:
-            r['rescore_prob'] = float(d.rescore_prob[i])
-        if d.soft_prob is not None:
-            r.update(soft_fields(d, i))
-        if d.view_iou is not None:
-            r.update(view_fields(d, i))
-        if d.reproj_iou is not None:
-            r.update(consistency_fields(d, i))
+        r.update(fields_of(d, i, RECORD_GROUPS))
         return r
 
     def predictions(self, meta, d):
         """test_semisup's 14-list of a detection run (the entries it fills for --from_rgb_detection; the rotation angles stayed on the
         device, the label rows carry them) with the decoded records attached.  Its confidence entry -- what the result files write and
-        the evaluation ranks by -- is the rescored confidence where a model rescored, and what Soft-NMS left of it where that ran."""
+        the evaluation ranks by -- is semisup_infer.Decoded.confidence."""
         n = len(meta)
         if d is None:
             return SI.Predictions([None, None, [], [], [], [], [], [], [], [], [], [], [], None])
         p = SI.Predictions([None, None, [None] * n, list(d.center), list(d.heading_cls), list(d.heading_res), list(d.size_cls),
-                            list(d.size_res), [None] * n,
-                            [float(v) for v in d.soft_prob] if d.soft_prob is not None else
-                            [float(v) for v in d.rescore_prob] if d.rescore_prob is not None else [m.prob for m in meta],
-                            [type2class[m.name] for m in meta], [m.image for m in meta], [m.box2d for m in meta], None])
+                            list(d.size_res), [None] * n, d.confidence([m.prob for m in meta]), [type2class[m.name] for m in meta], [m.image for m in meta], [m.box2d for m in meta], None])
         p.decoded = d
         return p
 
@@ -543,13 +521,7 @@ def write_consistency_json(path, meta, d):
         row = {'image': int(m.image), 'class': m.name, 'box2d': [float(v) for v in m.box2d], 'prob': float(m.prob), 'score': float(d.score[i]),
                'n_mask': int(d.n_mask[i]), 'n_box': int(d.n_box[i]), 'n_both': int(d.n_both[i]), 'accepted': bool(d.accept[i]),
                'kept': bool(d.keep is None or d.keep[i])}
-        row.update(consistency_fields(d, i, as_lists=True))
-        if d.rescore_prob is not None:
-            row['rescore_prob'] = float(d.rescore_prob[i])
-        if d.soft_prob is not None:
-            row.update(soft_fields(d, i))
-        if d.view_iou is not None:
-            row.update(view_fields(d, i))
+        row.update(fields_of(d, i, ROW_GROUPS, as_lists=True))
         rows.append(row)
     with open(path, 'w') as fh:
         json.dump(rows, fh, indent=1)
@@ -641,8 +613,9 @@ def main(argv=None, rt=None, log=print):
         if bootstrap is not None and grid is not None and bootstrap['json']:
             raise ValueError('--sweep writes its intervals to --sweep_json: it does not go with --bootstrap_json')
         fit = RS.fit_options(args)
-        if args.min_rescore is not None and args.rescore is None:
+        if args.min_rescore is not None and args.rescore is None:                # (Detector's own check would come behind the ones below)
             raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
+        # (of the features to fit: Detector checks the ones a model of --rescore reads)
         if fit is not None and fit['features'] is not None and 'view_iou' in fit['features'] and args.tta is None:
             raise ValueError('the feature view_iou is the agreement of the augmented views: it needs --tta')
         if fit is not None:
@@ -656,13 +629,12 @@ def main(argv=None, rt=None, log=print):
         consistency = consistency or args.rescore is not None or fit is not None
         if args.consistency_json and not consistency:
             raise ValueError('--consistency_json writes the consistency measures: it needs --consistency or a --min_* threshold')
+        # (the flags as given, not Detector.suppression.on: an error of --vis_* is reported before one of the options Detector checks)
         vis = Vis(args.vis_dir, args.vis_max, args.vis_gt, args.vis_suppressed, nms=args.nms_iou is not None or args.soft_nms is not None) if args.vis_dir else None
-        det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, nms_iou=args.nms_iou, nms_metric=None if grid is not None else args.nms_metric,
-                       nms_score=None if grid is not None else args.nms_score, log=log, consistency=consistency, min_reproj_iou=args.min_reproj_iou,
-                       min_mask_in_box=args.min_mask_in_box, min_seg_box_iou=args.min_seg_box_iou, nms_fuse=args.nms_fuse, nms_fuse_iou=args.nms_fuse_iou,
-                       tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou, min_view_iou=args.min_view_iou,
-                       soft_nms=args.soft_nms, soft_nms_sigma=args.soft_nms_sigma, soft_nms_min_prob=args.soft_nms_min_prob,
-                       rescore=args.rescore, min_rescore=args.min_rescore)
+        stage = dict({k: getattr(args, k) for k in STAGE_KEYWORDS}, consistency=consistency)
+        if grid is not None:                     # (--nms_metric / --nms_score hold for every combination of the sweep, not for its plain run)
+            stage.update(nms_metric=None, nms_score=None)
+        det = Detector(FLAGS, rt=rt, type_whitelist=args.type_whitelist, log=log, **stage)
     except ValueError as e:
         p.error(str(e))
     valid = set(int(line.rstrip()) for line in open(args.idx_path))

@@ -118,18 +118,14 @@ class DeviceEnsemble:
         assert all(t.is_contiguous() and t.dtype == torch.float32 for t in held)
         if V > MAX_VIEWS:
             raise abi.T3DError('t3d_detect_ensemble: T3D_ERR_SHAPE (%d views, at most %d)' % (V, MAX_VIEWS))
-        if self.label is None or self.n_votes.numel() < n:
-            new = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=rt.device)      # (owned here, as DeviceFuse's)
-            m = max(n, 1)
-            self.label, self.corners, self.agreement, self.min_iou = new(m, 7), new(m, 24), new(m), new(m)
-            self.anchor, self.n_votes = new(m, dtype=torch.int32), new(m, dtype=torch.int32)
+        self.label, self.corners = abi.grown(self.label, n, torch.float32, rt.device, 7), abi.grown(self.corners, n, torch.float32, rt.device, 24)
+        self.agreement, self.min_iou = (abi.grown(t, n, torch.float32, rt.device) for t in (self.agreement, self.min_iou))
+        self.anchor, self.n_votes = (abi.grown(t, n, torch.int32, rt.device) for t in (self.anchor, self.n_votes))
         out = (self.label[:n], self.corners[:n], self.agreement[:n], self.min_iou[:n], self.anchor[:n], self.n_votes[:n])
         if fill is not None:
             for t, v in zip(out, fill):
                 t.fill_(v)
-        need = abi.detect_ensemble_workspace_bytes(n, V)
-        if self.workspace is None or self.workspace.numel() * 8 < need:
-            self.workspace = torch.zeros(max(need // 8, 1), dtype=torch.int64, device=rt.device)
+        self.workspace = abi.grown(self.workspace, (abi.detect_ensemble_workspace_bytes(n, V) + 7) // 8, torch.int64, rt.device)
         self._held = held                                     # alive until the launches have run
         a = abi.DetectEnsembleArgs(n=n, V=V, metric=abi.NMS_METRICS[metric], flip_mask=int(flip_mask), vote_threshold=float(vote_threshold),
                                    rot_angle=fptr(rot_angle), corners0=fptr(corners0), workspace=C.c_void_p(self.workspace.data_ptr()),

@@ -102,6 +102,30 @@ def check_soft_options(soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=Non
     return SoftOptions('linear', check_options(nms_iou)[0], sigma, floor, metric)
 
 
+class Suppression(collections.namedtuple('Suppression', 'nms_iou nms_metric nms_score nms_fuse nms_fuse_iou soft')):
+    """The suppression options of the drivers, checked and with their defaults (`suppression`): the threshold of the hard suppression or
+    None, the metric name, the score name, whether the kept boxes are fused, the IoU above which a suppressed box votes (or None), and
+    `soft`, the SoftOptions of Soft-NMS or None.  With `soft` the hard suppression stays off -- nms_iou None, no fusion, ranked by
+    'prob' -- the threshold of 'linear' travels in `soft`, and nms_metric is its metric (the views of --tta read it there)."""
+    __slots__ = ()
+
+    @property
+    def on(self):
+        """Whether a suppression, hard or soft, was asked for."""
+        return self.nms_iou is not None or self.soft is not None
+
+
+def suppression(soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, nms_iou=None, nms_metric=None, nms_score=None, nms_fuse=False,
+                nms_fuse_iou=None):
+    """The eight suppression options of the drivers -> Suppression; ValueError as check_soft_options, check_options and
+    check_fuse_options raise it, in that order."""
+    soft = check_soft_options(soft_nms, soft_nms_sigma, soft_nms_min_prob, nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou)
+    if soft is not None:
+        return Suppression(None, soft.metric, 'prob', False, None, soft)
+    t, metric, score = check_options(nms_iou, nms_metric, nms_score)
+    return Suppression(t, metric, score, *check_fuse_options(t, nms_fuse, nms_fuse_iou), None)
+
+
 def add_arguments(parser):
     parser.add_argument('--soft_nms', choices=SOFT_METHODS, default=None,
                         help="Soft-NMS: per image and class, a box that overlaps a better one keeps its place and its confidence is multiplied down -- 'gaussian': by exp(-IoU^2 / sigma); 'linear': by 1 - IoU above --nms_iou (which it needs); decayed confidences below --soft_nms_min_prob are dropped")
@@ -134,8 +158,22 @@ def groups_of(image_ids, class_ids):
     return np.concatenate([starts, [n]]).astype(np.int32), members.astype(np.int32)
 
 
+def _lists(rt, group_offsets, members, n):
+    """The lists of groups_of over n boxes, checked and uploaded -> (n_groups, max_group, and the two lists as int32 device
+    tensors; an empty member list as one zero)."""
+    go, mem = np.ascontiguousarray(group_offsets, np.int32), np.ascontiguousarray(members, np.int32)
+    n_groups = len(go) - 1
+    max_group = int(np.diff(go).max()) if n_groups > 0 else 0
+    if n_groups < 0 or go[0] != 0 or (n_groups > 0 and (np.diff(go).min() < 0 or go[-1] != len(mem))) or len(mem) > n:
+        raise ValueError('group_offsets / members are not the lists of groups_of')
+    if len(mem) and (mem.min() < 0 or mem.max() >= n):
+        raise ValueError('a member is not a box index of [0, %d)' % n)
+    d_go, d_mem = torch.from_numpy(go).to(rt.device), torch.from_numpy(mem if len(mem) else np.zeros(1, np.int32)).to(rt.device)
+    return n_groups, max_group, d_go, d_mem
+
+
 class DeviceNms:
-    """Workspace and outputs of t3d_detect_nms; `run` launches on device tensors.  The buffers grow as needed and are reused."""
+    """Workspace and outputs of t3d_detect_nms; `run` launches on device tensors.  The buffers grow as needed and are reused (abi.grown)."""
 
     def __init__(self, rt):
         self.rt = rt
@@ -151,25 +189,16 @@ class DeviceNms:
         n = int(score.numel())
         assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
         assert corners.dtype == torch.float32 and score.dtype == torch.float32
-        go, mem = np.ascontiguousarray(group_offsets, np.int32), np.ascontiguousarray(members, np.int32)
-        n_groups = len(go) - 1
-        max_group = int(np.diff(go).max()) if n_groups > 0 else 0
-        if n_groups < 0 or go[0] != 0 or (n_groups > 0 and (np.diff(go).min() < 0 or go[-1] != len(mem))) or len(mem) > n:
-            raise ValueError('group_offsets / members are not the lists of groups_of')
-        if len(mem) and (mem.min() < 0 or mem.max() >= n):
-            raise ValueError('a member is not a box index of [0, %d)' % n)
+        n_groups, max_group, d_go, d_mem = _lists(rt, group_offsets, members, n)
         fk, fs, fr = (1, -1, -1) if fill is None else fill
-        if self.keep is None or self.keep.numel() < n:
-            new = lambda dtype: torch.zeros(max(n, 1), dtype=dtype, device=rt.device)      # (owned here, not by the runtime: they are replaced as they grow)
-            self.keep, self.suppressed_by, self.rank = new(torch.uint8), new(torch.int32), new(torch.int32)
+        self.keep = abi.grown(self.keep, n, torch.uint8, rt.device)
+        self.suppressed_by, self.rank = (abi.grown(t, n, torch.int32, rt.device) for t in (self.suppressed_by, self.rank))
         keep, sup, rank = self.keep[:n], self.suppressed_by[:n], self.rank[:n]
         keep.fill_(fk)
         sup.fill_(fs)
         rank.fill_(fr)
         need = abi.detect_nms_workspace_bytes(n, max_group)
-        if self.workspace is None or self.workspace.numel() * 8 < need:
-            self.workspace = torch.zeros(max(need // 8, 1), dtype=torch.int64, device=rt.device)
-        d_go, d_mem = torch.from_numpy(go).to(rt.device), torch.from_numpy(mem if len(mem) else np.zeros(1, np.int32)).to(rt.device)
+        self.workspace = abi.grown(self.workspace, (need + 7) // 8, torch.int64, rt.device)
         self._held = (corners, score, d_go, d_mem)            # alive until the launches have run
         a = abi.DetectNmsArgs(n, n_groups, abi.NMS_METRICS[metric], fptr(corners), fptr(score), iptr(d_go), iptr(d_mem), float(threshold),
                               max_group, C.c_void_p(self.workspace.data_ptr()), self.workspace.numel() * 8, abi.u8ptr(keep), iptr(sup), iptr(rank))
@@ -204,16 +233,9 @@ class DeviceSoftNms:
             raise ValueError('method is one of %s, got %r' % (SOFT_METHODS, method))
         if method == 'linear' and threshold is None:
             raise ValueError("method 'linear' needs a threshold")
-        go, mem = np.ascontiguousarray(group_offsets, np.int32), np.ascontiguousarray(members, np.int32)
-        n_groups = len(go) - 1
-        max_group = int(np.diff(go).max()) if n_groups > 0 else 0
-        if n_groups < 0 or go[0] != 0 or (n_groups > 0 and (np.diff(go).min() < 0 or go[-1] != len(mem))) or len(mem) > n:
-            raise ValueError('group_offsets / members are not the lists of groups_of')
-        if len(mem) and (mem.min() < 0 or mem.max() >= n):
-            raise ValueError('a member is not a box index of [0, %d)' % n)
-        if self.keep is None or self.keep.numel() < n:
-            new = lambda dtype: torch.zeros(max(n, 1), dtype=dtype, device=rt.device)      # (owned here, as DeviceNms's)
-            self.score_out, self.keep, self.suppressed_by, self.n_decays = new(torch.float32), new(torch.uint8), new(torch.int32), new(torch.int32)
+        n_groups, max_group, d_go, d_mem = _lists(rt, group_offsets, members, n)
+        self.score_out, self.keep = abi.grown(self.score_out, n, torch.float32, rt.device), abi.grown(self.keep, n, torch.uint8, rt.device)
+        self.suppressed_by, self.n_decays = (abi.grown(t, n, torch.int32, rt.device) for t in (self.suppressed_by, self.n_decays))
         out, keep, sup, dec = self.score_out[:n], self.keep[:n], self.suppressed_by[:n], self.n_decays[:n]
         if fill is None:
             out.copy_(score.view(-1))
@@ -223,7 +245,6 @@ class DeviceSoftNms:
         keep.fill_(fk)
         sup.fill_(fs)
         dec.fill_(fd)
-        d_go, d_mem = torch.from_numpy(go).to(rt.device), torch.from_numpy(mem if len(mem) else np.zeros(1, np.int32)).to(rt.device)
         self._held = (corners, score, d_go, d_mem)            # alive until the launch has run
         self._args = abi.DetectSoftNmsArgs(n, n_groups, abi.NMS_METRICS[metric], fptr(corners), fptr(score), iptr(d_go), iptr(d_mem),
                                            0.0 if threshold is None else float(threshold), max_group, abi.SOFT_NMS_METHODS[method], float(sigma),
@@ -255,9 +276,8 @@ class DeviceFuse:
         n = int(weight.numel())
         assert a.n == n and label.numel() == n * 7 and corners.numel() == n * 24
         assert all(t.is_contiguous() and t.dtype == torch.float32 for t in (label, corners, weight))
-        if self.label is None or self.n_votes.numel() < n:
-            new = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=rt.device)      # (owned here, as DeviceNms's)
-            self.label, self.corners, self.n_votes = new(max(n, 1), 7), new(max(n, 1), 24), new(max(n, 1), dtype=torch.int32)
+        self.label, self.corners = abi.grown(self.label, n, torch.float32, rt.device, 7), abi.grown(self.corners, n, torch.float32, rt.device, 24)
+        self.n_votes = abi.grown(self.n_votes, n, torch.int32, rt.device)
         lo, ko, nv = self.label[:n], self.corners[:n], self.n_votes[:n]
         if fill is None:
             lo.copy_(label.view(n, 7))
@@ -267,9 +287,7 @@ class DeviceFuse:
             lo.fill_(fill[0])
             ko.fill_(fill[1])
             nv.fill_(fill[2])
-        need = abi.detect_fuse_workspace_bytes(n)
-        if self.workspace is None or self.workspace.numel() * 8 < need:
-            self.workspace = torch.zeros(max(need // 8, 1), dtype=torch.int64, device=rt.device)
+        self.workspace = abi.grown(self.workspace, (abi.detect_fuse_workspace_bytes(n) + 7) // 8, torch.int64, rt.device)
         self._held = (nms, label, corners, weight)            # alive until the launches have run
         self._args = abi.DetectFuseArgs(n, a.n_groups, a.metric, a.group_offsets, a.members, a.keep, a.suppressed_by, a.rank, fptr(label),
                                         fptr(corners), fptr(weight), float(vote_threshold), a.max_group,
@@ -302,13 +320,7 @@ class DeviceNmsSweep:
         n = int(score.numel())
         assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
         assert corners.dtype == torch.float32 and score.dtype == torch.float32
-        go, mem = np.ascontiguousarray(group_offsets, np.int32), np.ascontiguousarray(members, np.int32)
-        n_groups = len(go) - 1
-        max_group = int(np.diff(go).max()) if n_groups > 0 else 0
-        if n_groups < 0 or go[0] != 0 or (n_groups > 0 and (np.diff(go).min() < 0 or go[-1] != len(mem))) or len(mem) > n:
-            raise ValueError('group_offsets / members are not the lists of groups_of')
-        if len(mem) and (mem.min() < 0 or mem.max() >= n):
-            raise ValueError('a member is not a box index of [0, %d)' % n)
+        n_groups, max_group, d_go, d_mem = _lists(rt, group_offsets, members, n)
         thresholds = [float(t) for t in thresholds]
         K = len(thresholds)
         if not 1 <= K <= abi.NMS_SWEEP_MAX_THRESHOLDS:
@@ -326,14 +338,9 @@ class DeviceNmsSweep:
             assert listed.dtype == torch.uint8 and listed.dim() == 2 and listed.shape[0] == M and listed.shape[1] >= n and listed.stride(1) == 1
             listed_stride = int(listed.stride(0)) if M > 1 else int(listed.shape[1])
         stride = max((n + 7) // 8 * 8, 8)                    # rows that start on 8 bytes are zeroed eight bytes at a time
-        if self.keep is None or self.keep.numel() < M * stride:
-            self.keep = torch.zeros(M * stride, dtype=torch.uint8, device=rt.device)      # (owned here, as DeviceNms's)
-        if self.n_kept is None or self.n_kept.numel() < M:
-            self.n_kept = torch.zeros(M, dtype=torch.int32, device=rt.device)
+        self.keep, self.n_kept = abi.grown(self.keep, M * stride, torch.uint8, rt.device), abi.grown(self.n_kept, M, torch.int32, rt.device)
         need = abi.detect_nms_sweep_workspace_bytes(n, max_group, K)
-        if self.workspace is None or self.workspace.numel() * 8 < need:
-            self.workspace = torch.zeros(max(need // 8, 1), dtype=torch.int64, device=rt.device)
-        d_go, d_mem = torch.from_numpy(go).to(rt.device), torch.from_numpy(mem if len(mem) else np.zeros(1, np.int32)).to(rt.device)
+        self.workspace = abi.grown(self.workspace, (need + 7) // 8, torch.int64, rt.device)
         self._held = (corners, score, d_go, d_mem, d_ct, listed)            # alive until the launches have run
         a = abi.DetectNmsSweepArgs(n, n_groups, abi.NMS_METRICS[metric], fptr(corners), fptr(score), iptr(d_go), iptr(d_mem), max_group, K)
         for k, t in enumerate(thresholds):

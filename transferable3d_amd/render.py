@@ -203,9 +203,7 @@ class Renderer:
             total_pixels = sum(vt[i].H * vt[i].W for i in range(nv))
         if total_point_items is None:
             total_point_items = sum(rg[i].count for i in range(nr))
-        need = abi.render_workspace_bytes(max(total_pixels, 0))
-        if self.workspace is None or self.workspace.numel() * 8 < need:
-            self.workspace = torch.zeros(max((need + 7) // 8, 1), dtype=torch.int64, device=rt.device)
+        self.workspace = abi.grown(self.workspace, (abi.render_workspace_bytes(max(total_pixels, 0)) + 7) // 8, torch.int64, rt.device)
         up = lambda t, n: torch.from_numpy(_bytes_of(t, n)).to(rt.device)
         d_views, d_ranges, d_boxes, d_rects = up(vt, nv), up(rg, nr), up(bx, nb), up(rc, nc)
         ptr = lambda t: C.c_void_p(0 if t is None else t.data_ptr())

@@ -53,17 +53,11 @@ def build_flags(argv=None):
     nms, rest = own.parse_known_args([a for a in argv if a != '--device_decode'])
     FLAGS = TS.build_flags(rest)
     FLAGS.device_decode = device
-    FLAGS.soft_nms = NMS.check_soft_options(nms.soft_nms, nms.soft_nms_sigma, nms.soft_nms_min_prob, nms.nms_iou, nms.nms_metric, nms.nms_score,
-                                            nms.nms_fuse, nms.nms_fuse_iou)
-    if FLAGS.soft_nms is not None:               # (its threshold travels in the options; nms_metric is its metric, as in detect.Detector; the hard suppression stays off)
-        FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, FLAGS.nms_fuse, FLAGS.nms_fuse_iou = None, FLAGS.soft_nms.metric, 'prob', False, None
-        if not (device and FLAGS.from_rgb_detection):
-            raise ValueError('--soft_nms runs on the device-decoded boxes of a detection file: it needs --device_decode and --from_rgb_detection')
-        return FLAGS
-    FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score = NMS.check_options(nms.nms_iou, nms.nms_metric, nms.nms_score)
-    FLAGS.nms_fuse, FLAGS.nms_fuse_iou = NMS.check_fuse_options(nms.nms_iou, nms.nms_fuse, nms.nms_fuse_iou)
-    if FLAGS.nms_iou is not None and not (device and FLAGS.from_rgb_detection):
-        raise ValueError('--nms_iou runs on the device-decoded boxes of a detection file: it needs --device_decode and --from_rgb_detection')
+    FLAGS.suppression = s = NMS.suppression(**vars(nms))
+    FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, FLAGS.nms_fuse, FLAGS.nms_fuse_iou, FLAGS.soft_nms = s
+    if s.on and not (device and FLAGS.from_rgb_detection):
+        raise ValueError('--%s runs on the device-decoded boxes of a detection file: it needs --device_decode and --from_rgb_detection'
+                         % ('nms_iou' if s.soft is None else 'soft_nms'))
     return FLAGS
 
 
@@ -73,20 +67,26 @@ class NmsRequest:
     image id and the class id that make its group.  fuse: t3d_detect_fuse follows (box voting: a kept box takes the weighted mean
     geometry of the boxes it suppressed); a suppressed box votes above the IoU vote_threshold (default: the threshold, so all of them do)
     with the weight that ranked it -- `prob`, or exp(score) for score='score' (the decoded score is a sum of logs).
-    soft ('gaussian' / 'linear'; sigma, min_prob): t3d_detect_soft_nms runs in place of t3d_detect_nms (nms.check_soft_options: 'linear'
-    takes the threshold, 'gaussian' none; the confidences `prob` are decayed, nothing is fused)."""
+    soft ('gaussian' / 'linear'; sigma, min_prob): t3d_detect_soft_nms runs in place of t3d_detect_nms (nms.suppression checks them all: 'linear'
+    takes the threshold, 'gaussian' none; the confidences `prob` are decayed, nothing is fused).  `of` takes the checked options as they are."""
     soft = None
 
     def __init__(self, threshold, metric, score, image_ids, class_ids, prob=None, fuse=False, vote_threshold=None, soft=None, sigma=None,
                  min_prob=None):
-        self.soft = NMS.check_soft_options(soft, sigma, min_prob, threshold, metric, score, fuse, vote_threshold)
-        if self.soft is not None:
-            self.threshold, self.metric, self.score, self.fuse, self.vote_threshold = self.soft.threshold, self.soft.metric, 'prob', False, None
-        else:
-            self.threshold, self.metric, self.score = NMS.check_options(threshold, metric, score)
-            if self.threshold is None:
-                raise ValueError('an NMS request needs a threshold')
-            self.fuse, self.vote_threshold = NMS.check_fuse_options(self.threshold, fuse, vote_threshold)
+        self._set(NMS.suppression(soft, sigma, min_prob, threshold, metric, score, fuse, vote_threshold), image_ids, class_ids, prob)
+
+    @classmethod
+    def of(cls, suppression, image_ids, class_ids, prob):
+        """The request of a nms.Suppression that is on, as the drivers hold it."""
+        req = cls.__new__(cls)
+        req._set(suppression, image_ids, class_ids, prob)
+        return req
+
+    def _set(self, s, image_ids, class_ids, prob):
+        if not s.on:
+            raise ValueError('an NMS request needs a threshold')
+        self.soft, self.threshold = s.soft, s.nms_iou if s.soft is None else s.soft.threshold
+        self.metric, self.score, self.fuse, self.vote_threshold = s.nms_metric, s.nms_score, s.nms_fuse, s.nms_fuse_iou
         self.image_ids, self.class_ids = np.asarray(image_ids, np.int64), np.asarray(class_ids, np.int64)
         self.prob = None if prob is None else np.asarray(prob, np.float32)
         if self.score == 'prob' and (self.prob is None or len(self.prob) != len(self.image_ids)):
@@ -139,6 +139,12 @@ class Decoded:
         return Decoded(**{k: getattr(self, k)[sel] for k in self.FIELDS},
                        **{k: getattr(self, k)[:, sel] if k in self.VIEW_MAJOR else getattr(self, k)[sel]
                           for k in self.OPTIONAL if getattr(self, k) is not None})
+
+    def confidence(self, prob):
+        """What the result files write and the evaluation rank by, per detection: what Soft-NMS left where it ran, else the rescored
+        confidence (either as Python floats), else `prob`, the 2-D detector's, as it is."""
+        best = self.soft_prob if self.soft_prob is not None else self.rescore_prob
+        return prob if best is None else [float(v) for v in best]
 
 
 class Predictions(list):
@@ -501,23 +507,17 @@ def device_decode_driver(FLAGS):
         else:
             d, *lists = kept(d, *predictions)
         p = Predictions(lists)
-        if d is not None and d.soft_prob is not None:            # the confidence the files and the evaluation rank by
-            p[9] = [float(v) for v in d.soft_prob]
+        if d is not None:                                         # the confidence the files and the evaluation rank by
+            p[9] = d.confidence(p[9])
         p.decoded = d
         return p
 
     def infer(sess, ops, pc, one_hot_vec, batch_size, **kw):
         source = kw.get('source')
+        s = getattr(FLAGS, 'suppression', None)                   # (FLAGS of test_semisup.build_flags have none)
         req = None
-        soft = getattr(FLAGS, 'soft_nms', None)
-        if soft is not None:
-            ds = source.ds
-            req = NmsRequest(soft.threshold, soft.metric, None, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob,
-                             soft=soft.method, sigma=soft.sigma if soft.method == 'gaussian' else None, min_prob=soft.min_prob)
-        elif getattr(FLAGS, 'nms_iou', None) is not None:
-            ds = source.ds
-            req = NmsRequest(FLAGS.nms_iou, FLAGS.nms_metric, FLAGS.nms_score, ds.image_ids, [type2class[t] for t in ds.class_names], ds.prob,
-                             fuse=getattr(FLAGS, 'nms_fuse', False), vote_threshold=getattr(FLAGS, 'nms_fuse_iou', None))
+        if s is not None and s.on:
+            req = NmsRequest.of(s, source.ds.image_ids, [type2class[t] for t in source.ds.class_names], source.ds.prob)
         res = inference(sess, ops, pc, one_hot_vec, batch_size, decode='device', want_seg=source is None or bool(FLAGS.output), nms=req, **kw)
         run['decoded'] = res.decoded[slice(0, res.device.total)]                     # without the padding
         report(run.get('log') or print, res.device, run['decoded'])
