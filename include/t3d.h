@@ -2259,6 +2259,122 @@ typedef struct {
 #define T3D_V2_SIZE_rescore_apply_args 56
 int t3d_rescore_apply(const t3d_rescore_apply_args* args, t3d_stream_t stream);
 
+/* ---- Scene synthesis: depth points, image and visibility of box scenes by ray casting (csrc/scene_synth.hip;
+ *      transferable3d_amd/synth_scenes.py) ----
+ * t3d_scene_raycast casts one ray per pixel of an H x W image against the oriented boxes ("parts") of each scene of a batch and the
+ * axis-aligned room around them, and writes what a depth camera at the origin would see: which surface every pixel shows, a shaded
+ * image, and the compacted rows `x y z r g b` of the strided pixels in upright depth coordinates -- the layout of a SUN-RGBD depth file,
+ * the exact inverse of the projection t3d_frustum_extract applies.  Everything is fp64, no operation is contracted into a fused
+ * multiply-add, every random number is a counter-based hash of (seed, scene id, pixel): a scene's outputs are a function of its inputs
+ * and its scene id, never of the batch it is cast in or of the order of anything.  Three launches, no host synchronisation, no
+ * floating-point atomic (the integer minima, maxima and counts of `vis_box` / `visible` do not depend on order).
+ *
+ *   Scene s < n_scenes   rtilt[s][9], K[s][9] row-major;  scene_id[s];  room[s][6] = x0, x1, y0, y1, z0, z1 with lo < 0 < hi on every
+ *                        axis (the camera is the origin, strictly inside);  its parts are part_offsets[s] .. part_offsets[s+1]-1 of
+ *                        `parts`, at most T3D_SCENE_MAX_PARTS of them, staged in LDS once per workgroup;  n_objects_host[s] <=
+ *                        T3D_SCENE_MAX_OBJECTS.  A part index below is the index within the scene.
+ *   Part                 centre, half (half-extents along its own axes), cos_r and sin_r of its rotation r about the up axis z (its own
+ *                        x axis is (cos_r, sin_r, 0) in the scene), colour[3] in [0, 255], owner: the ordinal of the object it belongs
+ *                        to; an owner outside [0, T3D_SCENE_MAX_OBJECTS) belongs to nothing (it is seen, and counted for nobody).
+ *   Ray of pixel (u, v)  cx = (u - K[2]) / K[0];  cy = (v - K[5]) / K[4];  q = (cx, 1, -cy);
+ *                        d[i] = (rtilt[3i] * q[0] + rtilt[3i+1] * q[1]) + rtilt[3i+2] * q[2].  d is not normalised: the parameter t of
+ *                        the point t * d is the depth along the camera's forward axis.  dd = (d0*d0 + d1*d1) + d2*d2.
+ *   Hit of a part        the origin and the direction in the part's frame:
+ *                          o = (cos_r * -centre[0] + sin_r * -centre[1],  cos_r * -centre[1] - sin_r * -centre[0],  -centre[2])
+ *                          e = (cos_r * d0 + sin_r * d1,                  cos_r * d1 - sin_r * d0,                  d2)
+ *                        t_in = -DBL_MAX, t_out = DBL_MAX (compared, never computed with).  Per axis k = 0, 1, 2 in this order:
+ *                          e[k] == 0:  a miss if o[k] < -half[k] or o[k] > half[k], no constraint otherwise (nothing is divided);
+ *                          else  ta = (-half[k] - o[k]) / e[k],  tb = (half[k] - o[k]) / e[k];  the near one tn = e[k] > 0 ? ta : tb
+ *                                and the far one tf the other;  tn > t_in: t_in = tn, the entered face is (k, sign = e[k] > 0 ? -1 : +1);
+ *                                tf < t_out: t_out = tf.
+ *                        A hit: t_in > 0 and t_in <= t_out.  (A part that contains the camera has t_in <= 0: it is ignored, and so is
+ *                        one wholly behind the camera.)  nd = e[k] of the entered face's axis.
+ *   Room                 per axis k in order with d[k] != 0: tw = (d[k] > 0 ? hi[k] : lo[k]) / d[k];  tw < t_room: t_room = tw, the wall
+ *                        is (k, sign = d[k] > 0 ? +1 : -1), nd = d[k].  (No axis with d[k] != 0: the pixel is invalid.)
+ *   Choice               over the parts in ascending index the first hit with the smallest t_in (a later part replaces an earlier one
+ *                        only when its t_in is smaller: on equal t the lower index wins);  it is the surface if t_in <= t_room, else
+ *                        the wall is;  t = that t_in or t_room.  The pixel is valid iff t <= max_range and nd * nd >= min_cos2 * dd
+ *                        (min_cos2: the squared cosine between ray and normal below which a sensor sees nothing).
+ *   hit [S,H,W]          the part index, T3D_SCENE_HIT_ROOM (-1) or T3D_SCENE_HIT_INVALID (-2).  Being comparisons of + - * / results
+ *                        in a stated order, it equals a NumPy transcription bit for bit; so do image, scene_offsets, visible, vis_box.
+ *   image [S,H,W,3]      noise-free uint8:  x = colour[c] * T3D_SCENE_SHADES[2k + (sign > 0)] + 0.5, clamped to [0, 255], truncated;  the
+ *                        room's colour is T3D_SCENE_ROOM_COLOUR on every channel;  an invalid pixel is 0 0 0.
+ *   Random numbers       base = ((uint64)seed << 32) ^ ((uint64)(uint32)scene_id * 0x9E3779B97F4A7C15)
+ *                               ^ ((uint64)(v * W + u + 1) * 0xC2B2AE3D27D4EB4F);
+ *                        U_j = ((double)mix((base ^ 0x94D049BB133111EB) + (uint64)(j + 1) * 0xBF58476D1CE4E5B9) + 0.5) * 2^-32, mix the
+ *                        finaliser of t3d_frustum_extract's hash (x ^= x >> 33, x *= 0xff51afd7ed558ccd, x ^= x >> 33,
+ *                        x *= 0xc4ceb9fe1a85ec53, x ^= x >> 33, bits 16..47).  0 < U_j < 1.
+ *   points               a pixel is EMITTED iff u % stride == 0, v % stride == 0, it is valid and not U_0 < p_drop.  Its row:
+ *                          noise_a == 0:  m = t  (no transcendental is evaluated)
+ *                          else           g = sqrt(-2 * log(U_1)) * cos(6.283185307179586 * U_2);   m = t + ((noise_a * (t * t)) * g)
+ *                          x y z = d[i] * m;   r g b = (its image bytes) / 255.0
+ *                        Rows are compacted in (scene, v, u) order: a count per workgroup, one scan, a scatter -- the position of a row
+ *                        is its rank, whatever ran first.  scene_offsets[S+1] (int64) is written on the device; point_pixel (NULL: not
+ *                        wanted) receives v * W + u of every row.  points_capacity >= S * ceil(H/stride) * ceil(W/stride) rows.
+ *                        With noise_a == 0 the rows equal the NumPy transcription bit for bit.  With noise, the two sides call two
+ *                        libraries: log within 1 ulp on both (2 between them, 1 after the square root halves it), sqrt correctly
+ *                        rounded on both (0.5 + 0.5), cos within 2 ulps on the device and 1 on the host (3), the product 0.5 + 0.5:
+ *                        g differs by at most 6 ulps, bounded as 8 * 2^-52 * |g| with the second-order terms.  m then differs by
+ *                        that times noise_a * t * t plus one ulp of m for its two roundings, and a coordinate by one ulp more:
+ *                            |x_device - x_numpy| <= 2^-52 * (8 * |d[i]| * noise_a * t * t * |g| + 3 * |x|)
+ *                        (the third |x| covers |d[i]| * |m| against |x| and every second-order term).  Derived, not measured.
+ *   visible [S,64]       per object: the emitted pixels whose part it owns.
+ *   vis_box [S,64,4]     per object: umin, vmin, umax, vmax over ALL valid pixels (stride 1) whose part it owns; W, H, -1, -1 for none.
+ *   workspace            T3D_SCENE_WORKSPACE_BYTES(S, H, W) bytes, 8-byte aligned; its content means nothing before or after the call.
+ * T3D_ERR_ARG: a NULL struct, input, output (point_pixel excepted) or host array, reserved != 0, a workspace that is NULL, misaligned or
+ * too small, points_capacity too small, a room that does not strictly contain the origin (a NaN bound included), p_drop or noise_a
+ * negative or NaN, max_range not above 0, min_cos2 outside [0, 1].  T3D_ERR_SHAPE: n_scenes outside [1, 65535], H or W < 1,
+ * H * W > 2^24, stride < 1, part_offsets_host not starting at 0 or decreasing, more than T3D_SCENE_MAX_PARTS parts or than
+ * T3D_SCENE_MAX_OBJECTS objects (or fewer than 0) in a scene.  Nothing is launched then.  The *_host arrays are host memory holding what
+ * the device arrays of the same name hold (they are read for these refusals and the grid alone). */
+#define T3D_SCENE_MAX_PARTS 512
+#define T3D_SCENE_MAX_OBJECTS 64
+#define T3D_SCENE_BLOCK_PIXELS 1024      /* consecutive pixels (row-major) of one scene per workgroup */
+#define T3D_SCENE_HIT_ROOM (-1)
+#define T3D_SCENE_HIT_INVALID (-2)
+#define T3D_SCENE_ROOM_COLOUR 200.0
+#define T3D_SCENE_SHADES {0.70, 0.80, 0.60, 0.90, 0.50, 1.00}      /* faces -x +x -y +y -z +z */
+#define T3D_SCENE_BLOCKS(H, W) (((uint64_t)(H) * (uint64_t)(W) + T3D_SCENE_BLOCK_PIXELS - 1u) / T3D_SCENE_BLOCK_PIXELS)
+/* per workgroup an int64 offset and an int32 count (rounded up to 8 bytes together) */
+#define T3D_SCENE_WORKSPACE_BYTES(S, H, W) ((uint64_t)(S) * T3D_SCENE_BLOCKS(H, W) * 16u)
+typedef struct {
+  double centre[3];
+  double half[3];
+  double cos_r, sin_r;
+  double colour[3];
+  int32_t owner;
+  int32_t reserved;                    /* 0 */
+} t3d_scene_part;
+
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_scene_raycast_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n_scenes; int H; int W; int stride;
+  uint32_t seed;
+  int reserved;                        /* 0 */
+  const double* rtilt;                 /* [S,9] */
+  const double* K;                     /* [S,9] */
+  const int32_t* scene_id;             /* [S] */
+  const double* room;                  /* [S,6] */
+  const int32_t* part_offsets;         /* [S+1] */
+  const t3d_scene_part* parts;         /* [part_offsets[S]] (may be NULL when that is 0) */
+  const double* room_host;             /* [S,6] host */
+  const int32_t* part_offsets_host;    /* [S+1] host */
+  const int32_t* n_objects_host;       /* [S] host */
+  double noise_a; double p_drop; double max_range; double min_cos2;
+  void* workspace;
+  uint64_t workspace_bytes;
+  int64_t points_capacity;             /* rows of `points` (and of point_pixel) */
+  int32_t* hit;                        /* [S,H,W] out */
+  uint8_t* image;                      /* [S,H,W,3] out */
+  double* points;                      /* [points_capacity,6] out */
+  int32_t* point_pixel;                /* [points_capacity] out, or NULL */
+  int64_t* scene_offsets;              /* [S+1] out */
+  int32_t* visible;                    /* [S,64] out */
+  int32_t* vis_box;                    /* [S,64,4] out */
+} t3d_scene_raycast_args;
+#define T3D_V2_SIZE_scene_raycast_args 216
+int t3d_scene_raycast(const t3d_scene_raycast_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -585,6 +585,37 @@ def rescore_fit_workspace_bytes(n):
     return (128 + rescore_slices(n) * 368) * 8
 
 
+# t3d.h T3D_SCENE_*
+SCENE_MAX_PARTS, SCENE_MAX_OBJECTS, SCENE_BLOCK_PIXELS = 512, 64, 1024
+SCENE_HIT_ROOM, SCENE_HIT_INVALID = -1, -2
+SCENE_ROOM_COLOUR = 200.0
+SCENE_SHADES = (0.70, 0.80, 0.60, 0.90, 0.50, 1.00)      # faces -x +x -y +y -z +z
+
+
+class ScenePart(C.Structure):
+    _fields_ = [('centre', C.c_double * 3), ('half', C.c_double * 3), ('cos_r', C.c_double), ('sin_r', C.c_double),
+                ('colour', C.c_double * 3), ('owner', C.c_int32), ('reserved', C.c_int32)]
+
+
+class SceneRaycastArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n_scenes', i32), ('H', i32), ('W', i32), ('stride', i32), ('seed', C.c_uint32),
+                ('reserved', i32), ('rtilt', D), ('K', D), ('scene_id', I), ('room', D), ('part_offsets', I), ('parts', C.POINTER(ScenePart)),
+                ('room_host', D), ('part_offsets_host', I), ('n_objects_host', I), ('noise_a', C.c_double), ('p_drop', C.c_double),
+                ('max_range', C.c_double), ('min_cos2', C.c_double), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64),
+                ('points_capacity', C.c_int64), ('hit', I), ('image', U8), ('points', D), ('point_pixel', I), ('scene_offsets', L),
+                ('visible', I), ('vis_box', I)]
+
+
+def scene_blocks(H, W):
+    """t3d.h T3D_SCENE_BLOCKS"""
+    return (H * W + SCENE_BLOCK_PIXELS - 1) // SCENE_BLOCK_PIXELS
+
+
+def scene_workspace_bytes(S, H, W):
+    """t3d.h T3D_SCENE_WORKSPACE_BYTES"""
+    return S * scene_blocks(H, W) * 16
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -688,6 +719,7 @@ ENTRY_POINTS = {
     't3d_rescore_features': [C.POINTER(RescoreFeaturesArgs), VP],
     't3d_rescore_fit': [C.POINTER(RescoreFitArgs), VP],
     't3d_rescore_apply': [C.POINTER(RescoreApplyArgs), VP],
+    't3d_scene_raycast': [C.POINTER(SceneRaycastArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],

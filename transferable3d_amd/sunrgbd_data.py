@@ -269,14 +269,16 @@ def _job_draws(draws, key):
 
 
 def extract_roi_seg(dataset_dir, idx_list, split='training', augmentX=1, perturb_box2d=False, type_whitelist=TYPE_WHITELIST,
-                    num_points=NUM_POINTS, seed=0, rt=None, draws=None, batch_scenes=16, workers=8, timings=None):
+                    num_points=NUM_POINTS, seed=0, rt=None, draws=None, batch_scenes=16, workers=8, timings=None, dataset=None):
     """sunrgbd_data.extract_roi_seg (sunrgbd_data.py:130-195) on the device.  idx_list: scene ids, or the path of an index file.
     Returns the reference's 13 lists: [id, box2d, box3d, image crop, points, label, type, heading, box3d size, Rtilt, K,
-    frustum angle, img_dims]."""
+    frustum angle, img_dims].  dataset: an object with sunrgbd_object's four getters (synth_scenes.SceneSet.dataset(): scenes held in
+    memory) in place of the files under dataset_dir."""
     if isinstance(idx_list, str):
         idx_list = [int(line.rstrip()) for line in open(idx_list)]
     ex = FrustumExtractor(_runtime(rt), num_points, seed)
-    dataset = sunrgbd_object(dataset_dir, split)
+    if dataset is None:
+        dataset = sunrgbd_object(dataset_dir, split)
 
     def load(idx):
         calib = dataset.get_calibration(idx)
@@ -312,13 +314,15 @@ def extract_roi_seg(dataset_dir, idx_list, split='training', augmentX=1, perturb
 
 
 def extract_roi_seg_from_rgb_detection(det_folder, dataset_dir, split='training', valid_id_list=None, type_whitelist=TYPE_WHITELIST,
-                                       seed=0, rt=None, draws=None, num_points=NUM_POINTS, batch_scenes=16, workers=8, timings=None):
+                                       seed=0, rt=None, draws=None, num_points=NUM_POINTS, batch_scenes=16, workers=8, timings=None,
+                                       dataset=None):
     """sunrgbd_data.extract_roi_seg_from_rgb_detection (sunrgbd_data.py:242-326) on the device.  Returns the reference's 7 lists:
-    [id, box2d, image crop, points, type, frustum angle, prob]."""
+    [id, box2d, image crop, points, type, frustum angle, prob].  dataset: as for extract_roi_seg."""
     det_id, det_type, det_box2d, det_prob = read_det_folder(det_folder)
     valid = None if valid_id_list is None else set(valid_id_list)
     ex = FrustumExtractor(_runtime(rt), num_points, seed)
-    dataset = sunrgbd_object(dataset_dir, split)
+    if dataset is None:
+        dataset = sunrgbd_object(dataset_dir, split)
     ordinal = collections.Counter()
     per_scene = collections.OrderedDict()         # scene id -> [(det index, ordinal)], scenes in order of their first detection
     for d, idx in enumerate(det_id):
