@@ -2375,6 +2375,108 @@ typedef struct {
 #define T3D_V2_SIZE_scene_raycast_args 216
 int t3d_scene_raycast(const t3d_scene_raycast_args* args, t3d_stream_t stream);
 
+/* ---- The floor of a scene and how a detection stands on it (csrc/floor.hip; transferable3d_amd/floor.py, detect --floor) ----
+ * t3d_scene_floor estimates, per scene of a batch, the floor plane Z = a X + b Y + c from the scene's depth points (upright depth
+ * coordinates: X right, Y forward, Z up, the camera at the origin) where the extraction left them.  Everything is fp64, every product
+ * and sum is an operation of its own (nothing is contracted), the histogram is summed by integer atomics and no floating-point atomic
+ * exists: a scene's bytes are a function of its own points and the options, never of S or its place in the batch.
+ *
+ *   points [sum n_s, ld]   row-major, ld >= 3, columns 0..2 = X Y Z;  scene s is rows scene_offsets[s] .. scene_offsets[s+1]-1 (a negative
+ *                          offset is taken as 0, an end before the start as the start; the offsets live on the device, so the caller
+ *                          answers for their not exceeding the rows of `points`).
+ *   A point counts         iff x, y and z are finite;  n_finite is their number.
+ *   hist [S, n_bins]       t = (z - z_lo) * inv_bin;  a counting point is binned iff t >= 0 && t < n_bins, into (int)floor(t).
+ *   c3[b]                  for 0 <= b < n_bins: hist[b-1] + hist[b] + hist[b+1], bins outside the histogram counting 0;  for every other
+ *                          b: 0 (so bin 0 competes with c3[-1] = 0, not with the window hist[0] alone).
+ *   The floor bin          the smallest b with (double)c3[b] >= min_share * (double)n_finite, c3[b] >= min_inliers, c3[b] > c3[j] for
+ *                          j in [b-2, b) and c3[b] >= c3[j] for j in (b, b+2] (c3 outside the histogram: 0).  None: flag
+ *                          T3D_FLOOR_NONE, the plane row is zeros, counts = (n_finite, 0, -1, T3D_FLOOR_NONE).
+ *   z0                     z_lo + ((double)b + 0.5) * bin.  The inliers are the counting points with |z - z0| <= band;  n1 is their
+ *                          number.  n1 == 0 (a band narrower than the bins): T3D_FLOOR_NONE as above, but counts[2] = b.
+ *   Level pass             Sx, Sy, Sz over the inliers;  mx = Sx / (double)n1, my, mz alike.
+ *   Moment pass            dx = x - mx, dy = y - my, dz = z - mz;  Sxx, Sxy, Syy, Sxz, Syz, Szz of the products dx * dx, ...
+ *   Order of every sum     chunk k of a scene is its points 4096 k .. 4096 k + 4095.  In a chunk, lane t < 256 starts from 0.0 and adds
+ *                          the terms of its inliers t, t + 256, ... in ascending order;  the lanes are combined by the halving tree
+ *                          v[t] = v[t] + v[t+s] for t < s, s = 128 ... 1.  Workgroup j < T3D_SCENE_FLOOR_BLOCKS of the scene starts from
+ *                          0.0 and adds v[0] of the chunks j, j + T3D_SCENE_FLOOR_BLOCKS, ... in ascending order (none: it stays 0.0);  the
+ *                          sum is 0.0 plus the workgroups' sums in ascending j.  tests/fake_floor.py replicates it.
+ *   Fit                    det = Sxx * Syy - Sxy * Sxy;  a = (Sxz * Syy - Syz * Sxy) / det;  b = (Syz * Sxx - Sxz * Sxy) / det.  Accepted
+ *                          iff a and b are finite, a * a + b * b <= max_slope2, Sxx >= ((double)n1 * min_spread) * min_spread and Syy
+ *                          alike, det >= min_det_ratio * (Sxx * Syy).  Otherwise a = b = 0 and flag T3D_FLOOR_LEVEL (a floor seen as a
+ *                          strip, a wrongly tilted peak).  c = mz - (a * mx + b * my);  r = Szz - (a * Sxz + b * Syz);
+ *                          msr = (r > 0 ? r : 0) / (double)n1 (the host takes the square root).
+ *   plane [S, 8]           a, b, c, mx, my, mz, msr, z0.      counts [S, 4]   n_finite, n1, the floor bin or -1, flags.
+ *   workspace              T3D_SCENE_FLOOR_WORKSPACE_BYTES(S) bytes, 8-byte aligned; its content means nothing before or after.
+ * T3D_ERR_ARG: a NULL struct or pointer, S < 0, reserved != 0, n_bins < 1, bin or inv_bin not finite or not above 0, z_hi <= z_lo (or a
+ * NaN), min_share outside [0, 1], band, max_slope2, min_spread or min_det_ratio negative or NaN, min_inliers < 0, a workspace that is
+ * misaligned or too small.  T3D_ERR_SHAPE: n_bins > T3D_SCENE_FLOOR_MAX_BINS, ld < 3, S > 65535.  S == 0: T3D_OK without a launch.  Nothing is
+ * launched after a refusal.  One clearing of hist and counts and five launches, no host synchronisation. */
+#define T3D_SCENE_FLOOR_MAX_BINS 1024
+#define T3D_SCENE_FLOOR_CHUNK 4096       /* consecutive points of a scene per step of a workgroup */
+#define T3D_SCENE_FLOOR_BLOCKS 64        /* workgroups per scene */
+#define T3D_SCENE_FLOOR_WORKSPACE_BYTES(S) ((uint64_t)(S) * T3D_SCENE_FLOOR_BLOCKS * 80u)
+#define T3D_FLOOR_NONE 1
+#define T3D_FLOOR_LEVEL 2
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_scene_floor_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n_scenes; int ld; int n_bins;
+  const double* points;                /* [sum n_s, ld] */
+  const int64_t* scene_offsets;        /* [S+1] */
+  double z_lo; double z_hi; double bin; double inv_bin; double min_share;
+  int min_inliers;
+  int reserved;                        /* 0 */
+  double band; double max_slope2; double min_spread; double min_det_ratio;
+  void* workspace;
+  uint64_t workspace_bytes;
+  double* plane;                       /* [S,8] out */
+  int32_t* counts;                     /* [S,4] out */
+  int32_t* hist;                       /* [S,n_bins] out */
+} t3d_scene_floor_args;
+#define T3D_V2_SIZE_scene_floor_args 152
+int t3d_scene_floor(const t3d_scene_floor_args* args, t3d_stream_t stream);
+
+/* t3d_detect_floor: how far the bottom of every decoded box lies from its scene's floor, and on request the box standing on it.  One
+ * thread per detection, fp64 on the widened fp32 entries, nothing contracted; inputs are never written, equal inputs give equal bytes.
+ *
+ *   label [n,7]        h, w, l, tx, ty, tz, ry (t3d_detect_decode): ty is the bottom of the box, y points down.  The upright camera's
+ *                      (x, y, z) is the depth frame's (X, -Z, Y).
+ *   yf                 -((a * tx + b * tz) + c) of the plane row scene_index[i] names;  gap = yf - ty: positive, the box floats above the
+ *                      floor; negative, it sinks into it.
+ *   flags              T3D_DETECT_FLOOR_NO_FLOOR: scene_index outside [0, n_scenes) or the scene's T3D_FLOOR_NONE; NOT_FINITE: a label entry
+ *                      that is not finite.  Either: gap is the NaN 0x7FF8000000000000 and no other flag is set.  Otherwise TOO_FAR:
+ *                      |gap| > max_snap;  INVERTED (mode 2 only): h' below is not above 0;  SNAPPED: mode != 0 and no other flag.
+ *   mode 0             measure.  label_out / corners_out may be NULL; where given they receive copies.
+ *   mode 1 (shift)     a snapped row: ty' = (float)yf, h' = h.
+ *   mode 2 (stretch)   a snapped row: ty' = (float)yf, h' = (float)(yf - ((double)ty - (double)h)): the top face stays.
+ *   label_out          label with h', ty' in a snapped row;  corners_out [n,8,3]: corners with, in a snapped row, the y of corner k
+ *                      rebuilt in fp32 as the decode does, (k < 4 ? h' : -h') / 2 + (ty' - h' / 2); x and z are copied.  A row that is
+ *                      not snapped is a copy of its input, byte for byte.
+ * T3D_ERR_ARG: a NULL struct, label, corners, scene_index, gap or flags, a NULL plane or counts where n_scenes > 0, n < 0, n_scenes < 0,
+ * reserved != 0, a mode outside 0..2, a NULL label_out or corners_out in mode 1 or 2, max_snap negative or NaN.  n == 0: T3D_OK without
+ * a launch. */
+#define T3D_DETECT_FLOOR_NO_FLOOR 1
+#define T3D_DETECT_FLOOR_NOT_FINITE 2
+#define T3D_DETECT_FLOOR_TOO_FAR 4
+#define T3D_DETECT_FLOOR_INVERTED 8
+#define T3D_DETECT_FLOOR_SNAPPED 16
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_floor_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_scenes; int mode;
+  const float* label;                  /* [n,7] */
+  const float* corners;                /* [n,8,3] */
+  const int32_t* scene_index;          /* [n]: the row of plane / counts, -1 for none */
+  const double* plane;                 /* [n_scenes,8] what t3d_scene_floor wrote */
+  const int32_t* counts;               /* [n_scenes,4] what t3d_scene_floor wrote */
+  double max_snap;
+  int reserved;                        /* 0 */
+  double* gap;                         /* [n] out */
+  int32_t* flags;                      /* [n] out */
+  float* label_out;                    /* [n,7] out, or NULL (mode 0) */
+  float* corners_out;                  /* [n,8,3] out, or NULL (mode 0) */
+} t3d_detect_floor_args;
+#define T3D_V2_SIZE_detect_floor_args 104
+int t3d_detect_floor(const t3d_detect_floor_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -616,6 +616,31 @@ def scene_workspace_bytes(S, H, W):
     return S * scene_blocks(H, W) * 16
 
 
+# t3d.h T3D_SCENE_FLOOR_* / T3D_FLOOR_* / T3D_DETECT_FLOOR_*
+SCENE_FLOOR_MAX_BINS, SCENE_FLOOR_CHUNK, SCENE_FLOOR_BLOCKS = 1024, 4096, 64
+FLOOR_NONE, FLOOR_LEVEL = 1, 2
+DETECT_FLOOR_NO_FLOOR, DETECT_FLOOR_NOT_FINITE, DETECT_FLOOR_TOO_FAR, DETECT_FLOOR_INVERTED, DETECT_FLOOR_SNAPPED = 1, 2, 4, 8, 16
+
+
+class SceneFloorArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n_scenes', i32), ('ld', i32), ('n_bins', i32), ('points', D), ('scene_offsets', L),
+                ('z_lo', C.c_double), ('z_hi', C.c_double), ('bin', C.c_double), ('inv_bin', C.c_double), ('min_share', C.c_double),
+                ('min_inliers', i32), ('reserved', i32), ('band', C.c_double), ('max_slope2', C.c_double), ('min_spread', C.c_double),
+                ('min_det_ratio', C.c_double), ('workspace', C.c_void_p), ('workspace_bytes', C.c_uint64), ('plane', D), ('counts', I),
+                ('hist', I)]
+
+
+def scene_floor_workspace_bytes(S):
+    """t3d.h T3D_SCENE_FLOOR_WORKSPACE_BYTES"""
+    return S * SCENE_FLOOR_BLOCKS * 80
+
+
+class DetectFloorArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_scenes', i32), ('mode', i32), ('label', F), ('corners', F), ('scene_index', I),
+                ('plane', D), ('counts', I), ('max_snap', C.c_double), ('reserved', i32), ('gap', D), ('flags', I), ('label_out', F),
+                ('corners_out', F)]
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -720,6 +745,8 @@ ENTRY_POINTS = {
     't3d_rescore_fit': [C.POINTER(RescoreFitArgs), VP],
     't3d_rescore_apply': [C.POINTER(RescoreApplyArgs), VP],
     't3d_scene_raycast': [C.POINTER(SceneRaycastArgs), VP],
+    't3d_scene_floor': [C.POINTER(SceneFloorArgs), VP],
+    't3d_detect_floor': [C.POINTER(DetectFloorArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],

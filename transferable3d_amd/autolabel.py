@@ -4,7 +4,8 @@
     python -m transferable3d_amd.autolabel --dataset_dir D --idx_path I --classes table sofa dresser night_stand bookshelf \
         --model_path M [test_semisup's model flags] --out_dir OUT [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] \
         [--keep_other_classes] [--link_inputs] [--score_against_labels] [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]] \
-        [--rescore MODEL.json [--min_rescore P]]
+        [--rescore MODEL.json [--min_rescore P]] [--floor] [--snap_floor {shift,stretch} [--snap_floor_max M]] [--max_floor_gap G] \
+        [--floor_json FILE] [--floor_bin B] [--floor_range LO HI] [--floor_min_share F] [--floor_band D] [--floor_max_tilt DEG]
 
 Of every object of --classes in D/training/label_dimension/*.txt only the class and the 2-D box are used.  detect.Detector runs on that
 box (with prob 1); t3d_detect_consistency (consistency.py) measures the 3-D box it predicts against the 2-D box and the segmented points,
@@ -28,6 +29,10 @@ labels gives every box one confidence from its measures, and --min_rescore rejec
 place of three cut-offs picked by hand (they still combine).  Every object is offered with prob 1, so a model's logit_prob column is
 constant here.  --score_against_labels reports the boxes that test alone accepts and rejects as well.
 
+--floor, --snap_floor, --max_floor_gap and the estimator's flags: detect's floor stage (floor.py).  The label line is written from the
+snapped box, --max_floor_gap rejects a box that floats above or sinks into its scene's floor by more than G, and
+--score_against_labels reports the boxes that test alone accepts and rejects as well.
+
 A label line, from a decoded label row (h, w, l, tx, ty, tz, ry) (`label_line`): the 2-D box as x, y, w, h; the centroid (tx, tz,
 -(ty - h/2)) in upright depth coordinates; the half sizes (w/2, l/2, h/2); the basis (cos ry, -sin ry, sin ry, cos ry); the orientation
 (cos ry, -sin ry).  sunrgbd_data.SUNObject3d + compute_box_3d read such a line back as the decode's corner set, to the six decimals of %f.
@@ -42,7 +47,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, ensemble as EN, rescore as RS, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
 
 LINE = '%s %d %d %d %d %f %f %f %f %f %f %f %f %f %f %f %f'
 IOU_HIT = 0.25
@@ -67,20 +72,27 @@ def label_corners(obj):
 EXTRA_TESTS = (('min_view_iou', 'view_iou'), ('min_rescore', 'rescore_prob'))
 
 
-def new_counts(thresholds, min_view_iou=None, min_rescore=None):
+def floor_ok(r, max_floor_gap):
+    """Whether --max_floor_gap alone accepts the record: its floor is unknown (the gap is NaN) or |floor_gap| does not exceed it."""
+    return not abs(r['floor_gap']) > max_floor_gap
+
+
+def new_counts(thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None):
     c = collections.OrderedDict(offered=0, too_few_points=0, accepted=0, rejected=0)
     c['rejected_by'] = collections.OrderedDict((name, 0) for name, t in zip(CS.THRESHOLDS, thresholds) if t is not None)
     for (flag, _), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
         if t is not None:
             c['rejected_by'][flag] = 0
+    if max_floor_gap is not None:
+        c['rejected_by']['max_floor_gap'] = 0
     return c
 
 
-def count(records, classes, thresholds, min_view_iou=None, min_rescore=None):
+def count(records, classes, thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None):
     """records: [{'class', 'detected' (False: its frustum held too few points), 'accepted', 'reproj_iou', 'mask_in_box', 'seg_box_iou'}] ->
     {class: offered, too_few_points, accepted, rejected, rejected_by {threshold: n}} (a box may fail several tests).  min_view_iou: the
-    records carry 'view_iou' and the boxes below it are counted too; min_rescore: the same for 'rescore_prob'."""
-    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou, min_rescore)) for c in classes)
+    records carry 'view_iou' and the boxes below it are counted too; min_rescore: the same for 'rescore_prob'; max_floor_gap: the same for the boxes whose |'floor_gap'| exceeds it."""
+    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou, min_rescore, max_floor_gap)) for c in classes)
     for r in records:
         c = out[r['class']]
         c['offered'] += 1
@@ -94,13 +106,15 @@ def count(records, classes, thresholds, min_view_iou=None, min_rescore=None):
         for (flag, measure), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
             if t is not None and not r[measure] >= t:
                 c['rejected_by'][flag] += 1
+        if max_floor_gap is not None and not floor_ok(r, max_floor_gap):
+            c['rejected_by']['max_floor_gap'] += 1
     return out
 
 
-def score(records, classes, rt, min_view_iou=None, min_rescore=None):
+def score(records, classes, rt, min_view_iou=None, min_rescore=None, max_floor_gap=None):
     """--score_against_labels: per class, for the accepted and the rejected boxes, how many, their mean 3-D IoU with the label's own box
     and the share at IoU >= 0.25.  min_view_iou: also under 'min_view_iou' for the boxes that test alone accepts and rejects; min_rescore: the
-    same under 'min_rescore'."""
+    same under 'min_rescore'; max_floor_gap: the same under 'max_floor_gap'."""
     from transferable3d_amd.eval_det import box3d_iou_batch
     rows = [r for r in records if r['detected']]
     iou = box3d_iou_batch(np.stack([r['corners'] for r in rows]), np.stack([r['label_corners'] for r in rows]), rt)[0] if rows else []
@@ -116,11 +130,15 @@ def score(records, classes, rt, min_view_iou=None, min_rescore=None):
                 out[c][flag] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
                                                       and bool(r[measure] >= t) == (kind == 'accepted')]))
                                 for kind in ('accepted', 'rejected')}
+        if max_floor_gap is not None:
+            out[c]['max_floor_gap'] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
+                                                             and floor_ok(r, max_floor_gap) == (kind == 'accepted')]))
+                                       for kind in ('accepted', 'rejected')}
     return out
 
 
 def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, link_inputs=False, score_against_labels=False, log=print,
-        batch_scenes=16, workers=8):
+        batch_scenes=16, workers=8, floor_json=None):
     """The command (module text) with a detect.Detector built by the caller (its thresholds decide).  ids: scene ids, or the path of an
     index file.  -> the dict written to OUT/autolabel.json, plus '_records': one entry per offered object (not written)."""
     from transferable3d_amd.detect import consistency_fields, scene_batches, view_fields
@@ -146,6 +164,8 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
             dets.append([(o.classname, o.box2d, 1.0) for _, o in take])
             offered.append((idx, take))
         parts.append(detector.extract(scenes, dets, batch))
+    if floor_json:
+        FL.write_json(floor_json, detector.floor_json_rows(parts))
     meta, d = detector.decode_all(parts)
     # the detections come back in the order they were offered, without those whose frustum held too few points
     records, i = [], 0
@@ -162,6 +182,8 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
                     r.update(view_fields(d, i))
                 if d.rescore_prob is not None:
                     r['rescore_prob'] = float(d.rescore_prob[i])
+                if d.floor_gap is not None:
+                    r.update(floor_gap=float(d.floor_gap[i]), floor_flags=int(d.floor_flags[i]))
                 if score_against_labels:
                     r['label_corners'] = label_corners(o)
                 i += 1
@@ -170,14 +192,18 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
     thresholds = detector.thresholds if detector.consistency else (None, None, None)
     min_view_iou = getattr(detector, 'min_view_iou', None)
     min_rescore = getattr(detector, 'min_rescore', None)
-    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou, min_rescore),
+    floor = getattr(detector, 'floor', None)
+    max_floor_gap = floor.max_floor_gap if floor is not None and floor.on else None
+    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou, min_rescore, max_floor_gap),
                                       thresholds=dict(zip(CS.THRESHOLDS, thresholds)), scenes=len(ids))
     if getattr(detector, 'tta', None) is not None:
         summary['tta'] = dict(views=detector.tta, flip=detector.tta_flip, vote_iou=detector.tta_vote_iou, min_view_iou=min_view_iou)
     if getattr(detector, 'rescore', None) is not None:
         summary['rescore'] = dict(features=detector.rescore.features, min_rescore=min_rescore)
+    if floor is not None and floor.on:
+        summary['floor'] = dict(snap=floor.snap, snap_max=floor.snap_max, max_floor_gap=max_floor_gap)
     if score_against_labels:
-        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou, min_rescore)
+        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou, min_rescore, max_floor_gap)
     written = write_labels(out_dir, ids, lines, records, classes, keep_other_classes)
     summary['scenes_written'] = len(written)
     if link_inputs:
@@ -190,7 +216,7 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
             ''.join(' (%s: %d)' % kv for kv in n['rejected_by'].items())))
         if score_against_labels:
             by = summary['score_against_labels'][c]
-            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag, _ in EXTRA_TESTS for k, v in by.get(flag, {}).items()]:
+            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag in [f for f, _ in EXTRA_TESTS] + ['max_floor_gap'] for k, v in by.get(flag, {}).items()]:
                 if v['n']:
                     log('  %s %d: mean 3-D IoU with the label %.3f, at IoU >= %g %.1f %%' % (kind, v['n'], v['mean_iou3d'], IOU_HIT,
                                                                                             100.0 * v['share_iou_ge_0.25']))
@@ -243,6 +269,8 @@ def parser():
     p.add_argument('--score_against_labels', action='store_true', help='report the 3-D IoU of accepted and rejected boxes with the 3-D boxes of the label lines')
     EN.add_arguments(p)
     RS.add_arguments(p)
+    FL.add_arguments(p)
+    p.add_argument('--floor_json', default=None, help='write one row per scene with its floor plane, the share of its points on it, their rms and the flags here')
     return p
 
 
@@ -255,6 +283,8 @@ def parse(argv=None):
         EN.check_options(args.tta, args.tta_flip, args.tta_vote_iou, args.min_view_iou)
         if RS.check_min_rescore(args.min_rescore) is not None and args.rescore is None:
             raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
+        if args.floor_json and not FL.check_options(**{k: getattr(args, k) for k in FL.FLAGS}).on:
+            raise ValueError('--floor_json writes the floor planes: it needs --floor, --snap_floor or --max_floor_gap')
     except ValueError as e:
         p.error(str(e))
     return args, TS.build_flags(list(rest))
@@ -267,9 +297,10 @@ def main(argv=None, rt=None, log=print):
         FLAGS.SUNRGBD_SEMI_TEST_CLS = list(args.classes)
     det = Detector(FLAGS, rt=rt, log=log, consistency=True, min_reproj_iou=args.thresholds[0], min_mask_in_box=args.thresholds[1],
                    min_seg_box_iou=args.thresholds[2], tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou,
-                   min_view_iou=args.min_view_iou, rescore=args.rescore, min_rescore=args.min_rescore)
+                   min_view_iou=args.min_view_iou, rescore=args.rescore, min_rescore=args.min_rescore,
+                   **{k: getattr(args, k) for k in FL.FLAGS})
     return run(det, args.dataset_dir, args.idx_path, args.classes, args.out_dir, keep_other_classes=args.keep_other_classes,
-               link_inputs=args.link_inputs, score_against_labels=args.score_against_labels, log=log)
+               link_inputs=args.link_inputs, score_against_labels=args.score_against_labels, log=log, floor_json=args.floor_json)
 
 
 if __name__ == '__main__':

@@ -97,9 +97,10 @@ def accept_of(reproj_iou, mask_in_box, seg_box_iou, thresholds):
 
 
 def log_line(accept, below, thresholds, extra=()):
-    """extra: (measure, threshold, how many lie below it) of further tests that reject where these do (ensemble.py: view_iou)."""
+    """extra: (measure, threshold, how many lie below it) of further tests that reject where these do (ensemble.py: view_iou), or the
+    finished text of one that rejects otherwise (floor.py: |floor_gap| above its threshold)."""
     parts = ['%s < %g: %d' % (m, t, below[name]) for name, m, t in zip(THRESHOLDS, MEASURES, thresholds) if t is not None]
-    parts += ['%s < %g: %d' % e for e in extra]
+    parts += [e if isinstance(e, str) else '%s < %g: %d' % e for e in extra]
     return 'consistency: kept %d of %d (%s)' % (int(np.sum(accept)), len(accept), ', '.join(parts) if parts else 'no threshold')
 
 

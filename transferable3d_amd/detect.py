@@ -15,6 +15,8 @@
         [--rescore MODEL.json [--min_rescore P]]
         [--rescore_fit MODEL.json [--rescore_classes C ..] [--rescore_target {overlap,tp}] [--rescore_lambda L] [--rescore_holdout H]
                        [--rescore_features NAME ..]]
+        [--floor] [--snap_floor {shift,stretch} [--snap_floor_max M]] [--max_floor_gap G] [--floor_json FILE]
+        [--floor_bin B] [--floor_range LO HI] [--floor_min_share F] [--floor_band D] [--floor_max_tilt DEG]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -96,6 +98,21 @@ last column of the result files, --official_eval, --diagnose and --bootstrap use
 evaluated on the device, the images are split by --seed, and the held-out part reports the AP by prob against the AP by rescore_prob.
 It does not go with --rescore, --sweep, a suppression or a threshold.  Without these flags every output is what it was, byte for byte.
 
+--floor: the one measure that looks at the whole scene (floor.py).  All evaluated classes stand on the floor, and a frustum seldom shows
+the floor under its object: the bottom of a box and its height are guesses of the size head.  Behind every extraction launch
+t3d_scene_floor fits the floor plane of each scene to the depth points the launch left on the device -- the lowest peak of a height
+histogram (--floor_bin, --floor_range) that holds --floor_min_share of the points, then a plane through the points within --floor_band
+of it, taken as level where it would tilt by more than --floor_max_tilt or the floor shows as a strip.  Behind the ensemble of the views
+and in front of the rescoring, t3d_detect_floor measures floor_gap, the distance from the bottom of every box down to that plane
+(positive: the box floats, negative: it sinks); records, legends and --consistency_json rows gain floor_gap and floor_flags.
+--snap_floor shift moves a box onto the floor, --snap_floor stretch moves its bottom face there and keeps its top; a box further than
+--snap_floor_max (default 0.3 m) from the floor is left alone.  The suppression, the records, the result files and --vis_dir then work
+on the snapped boxes; the consistency measures stay those of the box as decoded.  --max_floor_gap G rejects a detection whose
+|floor_gap| -- measured before any snapping -- exceeds G, where the --min_* thresholds reject; a scene without a floor snaps and rejects
+nothing.  --floor_json FILE takes one row per scene: its plane, the share of its points on it, their rms distance from it and the
+flags.  The floor flags do not go with --sweep or --rescore_fit.  Measured: the synthetic recipe (README).  Not measured: real SUN-RGBD.
+Without these flags every output is what it was, byte for byte.
+
 Where things live: the stages behind the decode (views, consistency, the accept rule, NMS, box voting) and their order belong to
 semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
 boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
@@ -114,7 +131,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, nms as NMS, render as RD, rescore as RS, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
+from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, floor as FL, nms as NMS, render as RD, rescore as RS, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -271,12 +288,13 @@ FIELD_GROUPS = {
     'soft': ('soft_prob', soft_fields),
     'views': ('view_iou', view_fields),
     'consistency': ('reproj_iou', consistency_fields),
+    'floor': ('floor_gap', lambda d, i, as_lists=False: {'floor_gap': float(d.floor_gap[i]), 'floor_flags': int(d.floor_flags[i])}),
 }
-RECORD_GROUPS = ('votes', 'rescore', 'soft', 'views', 'consistency')       # the records of `Detector.detect` and the legends of --vis_dir
-ROW_GROUPS = ('consistency', 'rescore', 'soft', 'views')                   # the rows of --consistency_json
+RECORD_GROUPS = ('votes', 'rescore', 'soft', 'views', 'consistency', 'floor')     # the records of `Detector.detect` and the legends of --vis_dir
+ROW_GROUPS = ('consistency', 'rescore', 'soft', 'views', 'floor')              # the rows of --consistency_json
 # the options of the stages as `Detector` takes them, under the names of the flags (the module docstring describes them)
 STAGE_KEYWORDS = ('nms_iou', 'nms_metric', 'nms_score', 'nms_fuse', 'nms_fuse_iou', 'soft_nms', 'soft_nms_sigma', 'soft_nms_min_prob', 'consistency',
-                  'min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou', 'tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou', 'rescore', 'min_rescore')
+                  'min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou', 'tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou', 'rescore', 'min_rescore') + FL.FLAGS
 
 
 def fields_of(d, i, groups, as_lists=False):
@@ -297,7 +315,8 @@ class Detector:
                  num_points=SD.NUM_POINTS, nms_iou=None, nms_metric=None, nms_score=None, log=None, consistency=False,
                  min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, tta=None, tta_flip=False,
                  tta_vote_iou=None, min_view_iou=None, soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, rescore=None, min_rescore=None,
-                 **keywords):
+                 floor=False, snap_floor=None, snap_floor_max=None, max_floor_gap=None, floor_bin=None, floor_range=None, floor_min_share=None,
+                 floor_band=None, floor_max_tilt=None, **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.  log: a
@@ -307,7 +326,8 @@ class Detector:
         rescore: a rescore.Model or the path of one.  They are checked here, before a model is built, and kept under their names:
         nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou and soft_nms (its nms.SoftOptions) as `suppression` (nms.Suppression)
         holds them -- with soft_nms, nms_iou is None -- thresholds, consistency, tta, tta_flip, tta_vote_iou, min_view_iou, rescore (the
-        Model), min_rescore."""
+        Model), min_rescore, and `floor` (floor.Floor: on, snap, snap_max, max_floor_gap and the estimator's FloorOptions)."""
+        self.floor = FL.check_options(floor, snap_floor, snap_floor_max, max_floor_gap, floor_bin, floor_range, floor_min_share, floor_band, floor_max_tilt)
         self.min_rescore = RS.check_min_rescore(min_rescore)
         if self.min_rescore is not None and rescore is None:
             raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
@@ -331,12 +351,14 @@ class Detector:
         self.sess, self.ops = TS.get_model(FLAGS, self.B, FLAGS.num_point, FLAGS.NUM_CHANNELS, rt=rt, state_dict=sd)
         self.rt = self.ops['graph'].rt
         self.extractor = SD.FrustumExtractor(self.rt, num_points, FLAGS.seed)
+        self.floor_estimator = FL.DeviceFloor(self.rt, self.floor.options) if self.floor.on else None
         self.whitelist = list(type_whitelist)
         self.classes = list(FLAGS.SUNRGBD_SEMI_TEST_CLS) or None
 
     def extract(self, scenes, detections, scene_ids=None, vis=None):
         """One t3d_frustum_extract launch over `scenes`; -> a part for `decode` (device tensors + what the host knows of the kept jobs).
-        vis (Vis): the scenes it will draw keep their points on the device."""
+        vis (Vis): the scenes it will draw keep their points on the device.  With the floor stage, t3d_scene_floor follows the launch on
+        the points it left there: part['floor'] = the planes and counts of the part's scenes on the device, the counts on the host, the ids."""
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
         jobs, meta = [], []
         for s, dets in enumerate(detections):
@@ -346,16 +368,19 @@ class Detector:
                 jobs.append({'scene': s, 'box2d': np.asarray(box2d, np.float64), 'box3d': None, 'key': (scene_ids[s], o, 0), 'choice': None})
                 meta.append(Detection(s, scene_ids[s], name, np.asarray(box2d, np.float64), float(prob)))
         want_scene = vis is not None and vis.taken < vis.max
-        out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene)
+        out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene or self.floor.on)
         calib = [CS.calib_row(sc['Rtilt'], sc['K'], sc.get('image_wh')) for sc in scenes] if self.consistency else []
         if out is None:
             return dict(out=None, keep=[], counts=[], meta=[], n_scenes=len(scenes), calib=calib)
         counts = out['count'].cpu().numpy()                          # the one copy back of this launch
         keep = np.nonzero(counts >= MIN_POINTS)[0]
         part = dict(out=out, keep=keep, counts=counts[keep], meta=[meta[j] for j in keep], n_scenes=len(scenes), calib=calib)
+        if self.floor.on:
+            plane, floor_counts, floor_counts_host = self.floor_estimator.estimate(*self.extractor.last_scene)
+            part['floor'] = dict(plane=plane, counts=floor_counts, counts_host=floor_counts_host, ids=scene_ids)
         if want_scene:
             vis.take(self.rt, part, scenes, scene_ids, self.extractor.last_scene)
-            self.extractor.last_scene = None
+        self.extractor.last_scene = None          # (the points go unless Vis took what it draws)
         return part
 
     def decode(self, parts):
@@ -379,7 +404,7 @@ class Detector:
         classes = [type2class[m.name] for m in meta]
         ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live], classes)
         source = DeviceEvalSource(self.ops['graph'], dataset=ds, seed=FLAGS.seed)
-        nms = con = views = rescore = None
+        nms = con = views = rescore = floor = None
         if self.rescore is not None:
             rescore = RS.RescoreRequest(self.rescore, [m.prob for m in meta], self.min_rescore)
         if self.suppression.on:
@@ -390,11 +415,13 @@ class Detector:
                 index += [len(rows) + m.scene for m in p['meta']]
                 rows += list(p.get('calib', []))
             con = SI.ConsistencyRequest([m.box2d for m in meta], rows, index, *self.thresholds)
+        if self.floor.on:
+            floor = FL.FloorRequest(*self.floor_rows(parts), snap=self.floor.snap, snap_max=self.floor.snap_max, max_floor_gap=self.floor.max_floor_gap)
         if self.tta is not None:
             views = EN.EnsembleRequest(EN.views_of(self.tta, self.tta_flip, FLAGS.seed), self.nms_metric, self.tta_vote_iou, self.min_view_iou)
         res = SI.inference(self.sess, self.ops, None, None, self.B, prefix=FLAGS.pred_prefix, use_boxpc_fit_prob=FLAGS.use_boxpc_fit_prob,
                            source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False, nms=nms, consistency=con,
-                           views=views, rescore=rescore)
+                           views=views, rescore=rescore, floor=floor)
         self.stages = res.device
         d = res.decoded[slice(0, ds.F)]
         if self.log:
@@ -402,6 +429,31 @@ class Detector:
         if d.accept is not None and not d.accept.all():          # a rejected detection is dropped wherever a suppressed one is
             d.keep = d.accept.copy() if d.keep is None else d.keep & d.accept
         return meta, d
+
+    def floor_rows(self, parts):
+        """The planes [S, 8] and counts [S, 4] of the parts' scenes on the device, one row per scene of every part in order (a part without
+        a frustum was not estimated: its scenes have no floor), and per detection the row of its scene -- indexed exactly as the
+        calibration rows of the consistency request."""
+        import torch
+        planes, counts, index, n_rows = [], [], [], 0
+        for p in parts:
+            index += [n_rows + m.scene for m in p['meta']]
+            n_rows += p['n_scenes']
+            if p.get('floor') is not None:
+                planes.append(p['floor']['plane'])
+                counts.append(p['floor']['counts'])
+            else:
+                planes.append(torch.zeros(p['n_scenes'], 8, dtype=torch.float64, device=self.rt.device))
+                counts.append(torch.tensor([[0, 0, -1, FL.NONE]] * p['n_scenes'], dtype=torch.int32, device=self.rt.device).view(-1, 4))
+        return torch.cat(planes), torch.cat(counts), index
+
+    def floor_json_rows(self, parts):
+        """--floor_json: one row per estimated scene of `parts` (floor.scene_rows)."""
+        rows = []
+        for p in parts:
+            if p.get('floor') is not None:
+                rows += FL.scene_rows(p['floor']['ids'], p['floor']['plane'].cpu().numpy(), p['floor']['counts_host'])
+        return rows
 
     def detect(self, scenes, detections, scene_ids=None, batch_scenes=16, vis_dir=None, vis_max=50, vis_gt=False, vis_suppressed=False):
         """scenes: [{'points' (n, C) fp64 upright depth, 'Rtilt', 'K'}] (FrustumExtractor.run); detections[s]: [(class name, box2d
@@ -415,8 +467,8 @@ class Detector:
         A stage that ran adds its fields to the records (FIELD_GROUPS, in the order of RECORD_GROUPS; the module docstring says what they
         mean): nms_fuse 'votes', the number of suppressed boxes that voted (0: the box is what the decode wrote); rescore
         'rescore_prob'; soft_nms 'soft_prob' and 'decays'; tta 'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view'; consistency
-        'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou' and 'flags'.  'prob' stays the 2-D detector's.  'label' and
-        'corners' are the box after every stage that ran: what t3d_detect_ensemble made of the views, and nms_fuse of that; 'score'
+        'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou' and 'flags'; floor 'floor_gap' and 'floor_flags'.  'prob' stays the 2-D detector's.  'label' and
+        'corners' are the box after every stage that ran: what t3d_detect_ensemble made of the views, snap_floor of that, and nms_fuse of that; 'score'
         and the consistency measures stay those of view 0's unfused box.  A detection that a threshold rejected, or whose confidence
         Soft-NMS took below soft_nms_min_prob, has no entry.  With consistency a scene may carry 'image_wh' = (W, H), to which the
         reprojected rectangle is then clipped (without it: no clipping)."""
@@ -468,6 +520,8 @@ class Detector:
             raise ValueError('the views of tta are not swept: the detector has tta')
         if self.rescore is not None:
             raise ValueError('a sweep starts from the plain run: the detector has a rescoring model')
+        if self.floor.on:
+            raise ValueError('a sweep starts from the plain run: the detector has the floor stage')
         if grid.consistency and not self.consistency:
             raise ValueError('the grid sweeps a min_* threshold: the detector needs consistency=True')
         meta, d = self.decode_all(parts)
@@ -549,6 +603,8 @@ def parser():
     BS.add_arguments(p)                       # with --official_eval or --sweep: intervals behind the APs (bootstrap.py)
     RS.add_arguments(p)
     RS.add_fit_arguments(p)
+    FL.add_arguments(p)
+    p.add_argument('--floor_json', default=None, help='write one row per scene with its floor plane, the share of its points on it, their rms and the flags here')
     return p
 
 
@@ -564,6 +620,7 @@ def sweep_options(args):
     single += ['soft_nms'] if args.soft_nms is not None else []      # (the scores differ per configuration: ranks cannot be shared)
     single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
     single += [f for f in ('rescore', 'min_rescore', 'rescore_fit') if getattr(args, f) is not None]
+    single += [f for f in FL.FLAGS + ('floor_json',) if getattr(args, f) not in (None, False)]
     if single:
         raise ValueError('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
     if args.vis_dir or args.consistency_json:
@@ -621,8 +678,12 @@ def main(argv=None, rt=None, log=print):
         if fit is not None:
             other = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'official_eval') if getattr(args, f)]
             other += [f for f in ('nms_fuse_iou', 'soft_nms', 'min_view_iou', 'vis_dir', 'consistency_json') if getattr(args, f) is not None]
+            other += [f for f in FL.FLAGS + ('floor_json',) if getattr(args, f) not in (None, False)]
             if other:
                 raise ValueError('--rescore_fit starts from the plain run, as --sweep does: it does not go with %s' % ' '.join('--' + f for f in other))
+        floor = FL.check_options(**{k: getattr(args, k) for k in FL.FLAGS})
+        if args.floor_json and not floor.on:
+            raise ValueError('--floor_json writes the floor planes: it needs --floor, --snap_floor or --max_floor_gap')
         if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
             raise ValueError('--vis_gt / --vis_suppressed need --vis_dir')
         consistency = args.consistency or any(getattr(args, t) is not None for t in CS.THRESHOLDS) or (grid is not None and grid.consistency)
@@ -658,6 +719,10 @@ def main(argv=None, rt=None, log=print):
             result.write_json(args.sweep_json)
             log('sweep of %d configurations written to %s' % (len(grid), args.sweep_json))
         return result
+    if args.floor_json:
+        rows = det.floor_json_rows(parts)
+        FL.write_json(args.floor_json, rows)
+        log('floor planes of %d scenes written to %s' % (len(rows), args.floor_json))
     meta, d = det.decode_all(parts)
     if args.consistency_json:                                    # the two reports that need every row, then the rows go
         write_consistency_json(args.consistency_json, meta, d)

@@ -20,8 +20,8 @@ detection whose confidence falls below --soft_nms_min_prob is absent like a supp
 
 What runs behind the decode, and in which order, is written down in one place: `DeviceStages`.  `inference` builds one from its requests
 (nms, consistency, views); per batch it decodes every view and then measures the consistency of view 0, after the last batch it runs
-the ensemble of the views, the rescoring, the accept rule, the suppression and the box voting, and fetches everything as one
-`Decoded`.  It holds the boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.
+the ensemble of the views, the floor stage, the rescoring, the accept rule, the suppression and the box voting, and fetches everything
+as one `Decoded`.  It holds the boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.
 `DeviceDecode` is the buffers of t3d_detect_decode alone; `report` writes a run's log lines and `kept` drops the rows that were not
 kept, for every caller.
 """
@@ -37,7 +37,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transferable3d_amd import abi, nms as NMS, test_semisup as TS       # noqa: E402
 from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
-from transferable3d_amd import consistency as CS, ensemble as EN, rescore as RS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS      # noqa: E402
 from transferable3d_amd.consistency import ConsistencyRequest, DeviceConsistency      # noqa: E402
 from transferable3d_amd.constants import type2class                     # noqa: E402
 
@@ -118,11 +118,15 @@ class Decoded:
     whose confidence fell below the floor and suppressed_by names the box whose decay took it there; None without.
     With a rescoring model (RescoreRequest, rescore.py) rescore_prob [n] is the confidence t3d_rescore_apply gave every detection from
     its measures; the suppression stages then rank by it where they rank by 'prob' (and soft_prob is what Soft-NMS left of it); None
-    without."""
+    without.
+    With a floor request (floor.FloorRequest) floor_gap [n] is how far the floor of the detection's scene lies below the bottom of its
+    box (positive: the box floats; negative: it sinks; NaN: no floor is known) and floor_flags [n] the bits t3d_detect_floor set, both
+    measured on the box the stage read: the ensemble's where views ran.  Where the request snaps, label and corners hold what the stage
+    wrote (and a fusion's raw_label / raw_corners with them) and unsnapped_label / unsnapped_corners what it read; None without."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
     OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept',
                 'raw_label', 'raw_corners', 'n_votes', 'view_label', 'view_score', 'view_iou', 'view_min_iou', 'anchor_view', 'n_views_voted',
-                'soft_prob', 'n_decays', 'rescore_prob')
+                'soft_prob', 'n_decays', 'rescore_prob', 'floor_gap', 'floor_flags', 'unsnapped_label', 'unsnapped_corners')
     VIEW_MAJOR = ('view_label', 'view_score')              # [V, n, ...]: the detection is the second axis
 
     def __init__(self, **fields):
@@ -203,17 +207,20 @@ class DeviceDecode:
 class DeviceStages:
     """The stages behind t3d_detect_decode of one `inference(decode='device')` run over `n` frustums, the first `total` of them real, and
     the one place that says in which order they run.  Per batch (`launch`): the decode of every view, then -- behind view 0's -- the
-    consistency measures.  After the last batch (`finish`): the ensemble of the views, the rescoring, the accept rows, the suppression,
-    the box voting, and the one fetch of everything as a Decoded.
+    consistency measures.  After the last batch (`finish`): the ensemble of the views, the floor stage, the rescoring, the accept rows, the
+    suppression, the box voting, and the one fetch of everything as a Decoded.
 
     label [n, 7], corners [n, 24]: the boxes on the device as the stages so far left them -- a stage that rewrites boxes (the ensemble,
-    the box voting) reads them and puts its output in their place, so neither a later stage nor a caller asks which stage ran; score [n]:
+    the floor stage where it snaps, the box voting) reads them and puts its output in their place, so neither a later stage nor a caller asks which stage ran; score [n]:
     where view 0's decode wrote it.  accept [n] bool (None: nothing was asked that could reject): the detections that miss no threshold
-    of the consistency request and do not lie below views.min_view_iou or rescore.min_rescore; below: how many of the real detections
+    of the consistency request, do not lie below views.min_view_iou or rescore.min_rescore and whose |floor_gap| does not exceed
+    floor.max_floor_gap; below: how many of the real detections
     lie below each of these thresholds (`report`).  rescore_out (rescore.DeviceRescore, None without a request): its out32 [n] is the
     rescored confidence on the device, which `nms` ranks by in the place of the request's `prob`."""
 
-    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None, rescore=None):
+    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None, rescore=None, floor=None):
+        if floor is not None and len(floor) != total:
+            raise ValueError('%d detections in the floor request, %d decoded' % (len(floor), total))
         if nms is not None and len(nms.image_ids) != total:
             raise ValueError('%d image ids for %d detections' % (len(nms.image_ids), total))
         if consistency is not None and len(consistency) != total:
@@ -228,6 +235,7 @@ class DeviceStages:
                 raise ValueError('the rescoring model reads the consistency measures: it needs a consistency request')
         self.rt, self.n, self.total, self.nms_request, self.views = rt, n, total, nms, views
         self.rescore_request, self.rescore_out = rescore, None
+        self.floor_request, self.floor_out, self.floor_in, self.floor_host = floor, None, None, None
         self.decodes = [DeviceDecode(rt, n, num_point, want_seg=want_seg and v == 0) for v in range(1 if views is None else len(views))]
         self.consistency = None if consistency is None else DeviceConsistency(rt, n, num_point, consistency)
         self.rot_angle = None if views is None else rt.zeros(n)      # every batch's angles: the ensemble mirrors back with them
@@ -250,6 +258,8 @@ class DeviceStages:
         """After the last batch -> (Decoded, masks [n, N] uint8 or None)."""
         if self.views is not None:
             self.ensemble()
+        if self.floor_request is not None:
+            self.floor()
         if self.rescore_request is not None:
             self.rescore()
         self.accept_rows()
@@ -264,6 +274,15 @@ class DeviceStages:
         out = self.ensemble_out.run([d.sec['label'] for d in self.decodes], [torch.exp(d.sec['score'].view(-1)) for d in self.decodes],
                                     self.corners, req.flip_mask, self.rot_angle, req.vote_threshold, req.metric)
         self.label, self.corners = out[0], out[1]
+
+    def floor(self):
+        """t3d_detect_floor on the current boxes: the gap between every box's bottom and its scene's floor and, where the request snaps,
+        the boxes standing on it in the place of the ones it read (`floor_in`)."""
+        self.floor_out = FL.DeviceFloorStage(self.rt)
+        out = self.floor_out.run(self.label, self.corners, self.floor_request, self.n)
+        if out is not None:
+            self.floor_in = (self.label, self.corners)
+            self.label, self.corners = out
 
     def rescore(self):
         """t3d_rescore_features on the buffers the stages so far wrote -- the 2-D confidences, view 0's decoded score, the consistency
@@ -280,7 +299,8 @@ class DeviceStages:
 
     def accept_rows(self):
         """The one accept rule: a detection is rejected where it misses a threshold of the consistency request, its view_iou lies below
-        views.min_view_iou or its rescored confidence below rescore.min_rescore.  Copies the consistency outputs, the agreement and the
+        views.min_view_iou, its rescored confidence below rescore.min_rescore, or its floor is known and |floor_gap|, measured before any
+        snapping, exceeds floor.max_floor_gap.  Copies the consistency outputs, the agreement and the
         rescored confidence back -- the small copies in front of the group building."""
         total, masks = self.total, []
         if self.consistency is not None:
@@ -296,6 +316,12 @@ class DeviceStages:
             self.below['rescore_prob'] = int((~ok[:total]).sum())
             ok[total:] = True                                     # (the rows that pad a last batch are no detections)
             masks.append(ok)
+        if self.floor_out is not None:
+            self.floor_host = (self.floor_out.gap[:self.n].cpu().numpy(), self.floor_out.flags[:self.n].cpu().numpy().astype(np.int64))
+            if self.floor_request.max_floor_gap is not None:
+                bad = FL.rejected(*self.floor_host, self.floor_request.max_floor_gap)
+                self.below['floor_gap'] = int(bad[:total].sum())
+                masks.append(~bad)
         if masks:
             self.accept = np.logical_and.reduce(masks)
 
@@ -342,6 +368,11 @@ class DeviceStages:
             d.label, d.corners = host(e.label), host(e.corners).reshape(n, 8, 3)
             d.view_iou, d.view_min_iou = host(e.agreement), host(e.min_iou)
             d.anchor_view, d.n_views_voted = host(e.anchor, np.int64), host(e.n_votes, np.int64)
+        if self.floor_out is not None:
+            d.floor_gap, d.floor_flags = self.floor_host
+            if self.floor_in is not None:
+                d.unsnapped_label, d.unsnapped_corners = d.label, d.corners
+                d.label, d.corners = host(self.floor_out.label_out), host(self.floor_out.corners_out).reshape(n, 8, 3)
         if self.fuse_out is not None:
             d.raw_label, d.raw_corners = d.label, d.corners
             d.label, d.corners = host(self.label), host(self.corners).reshape(n, 8, 3)
@@ -374,7 +405,7 @@ def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
 
 
 def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
-              decode='host', want_seg=True, nms=None, consistency=None, views=None, rescore=None):
+              decode='host', want_seg=True, nms=None, consistency=None, views=None, rescore=None, floor=None):
     """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
     padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
@@ -392,6 +423,9 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     rescore (rescore.RescoreRequest, decode='device' only): behind the ensemble, t3d_rescore_features and t3d_rescore_apply give every
     detection one confidence from its measures (`.decoded.rescore_prob`); a detection below rescore.min_rescore is rejected like one below
     a consistency threshold, and an nms request that ranks by 'prob' ranks by the rescored confidence.
+    floor (floor.FloorRequest, decode='device' only): behind the ensemble, t3d_detect_floor measures every box against the floor plane of
+    its scene (`.decoded.floor_gap` / `.floor_flags`), stands it on the floor where the request snaps, and a detection whose |floor_gap|
+    exceeds floor.max_floor_gap is rejected like one below a consistency threshold.
     The stages and their order are DeviceStages'; this function loads and runs the graph and says when a view of a batch is ready."""
     if decode == 'host' and nms is not None:
         raise ValueError("nms runs on the device-decoded boxes: decode='device'")
@@ -399,6 +433,8 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
         raise ValueError("the consistency measures are taken on the device-decoded boxes: decode='device'")
     if decode == 'host' and rescore is not None:
         raise ValueError("the rescoring reads the device-decoded records: decode='device'")
+    if decode == 'host' and floor is not None:
+        raise ValueError("the floor stage reads the device-decoded boxes: decode='device'")
     if views is not None and (decode != 'device' or source is None):
         raise ValueError("views are further draws of a device-resident source: decode='device' and a source")
     if decode == 'host':
@@ -415,7 +451,8 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     total = source.ds.F if source is not None else n                 # the frustums past it pad the last batch
     rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
     xyz = sess.g.inputs.pc if consistency is not None else None      # [B * N, ld] where the network read the batch
-    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views, rescore=rescore)
+    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views, rescore=rescore,
+                          floor=floor)
     sources = [source] + ([] if views is None else [source.view(seed, flip) for seed, flip in views.views[1:]])
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
@@ -456,15 +493,19 @@ def write_detection_results(result_dir, test_classes, predictions, class_names):
 def report(log, stages, d):
     """What a run says of its stages, one line each through `log` and in their order: `consistency:` (how many detections the accept rule
     kept, how many lie below each threshold), `tta:` (the views) and `nms ...` (how many of the accepted detections were kept and, with
-    a fusion, how many kept boxes changed, from how many votes).  stages: the run's DeviceStages; d: the records of its real detections."""
+    a fusion, how many kept boxes changed, from how many votes); `floor:` (floor.log_line) follows `tta:`.  stages: the run's DeviceStages; d: the records of its real detections."""
     if d.accept is not None:
         con = stages.consistency
         extra = [('view_iou', stages.views.min_view_iou, stages.below['view_iou'])] if 'view_iou' in stages.below else []
         if 'rescore_prob' in stages.below:
             extra.append(('rescore_prob', stages.rescore_request.min_rescore, stages.below['rescore_prob']))
+        if 'floor_gap' in stages.below:
+            extra.append('|floor_gap| > %g: %d' % (stages.floor_request.max_floor_gap, stages.below['floor_gap']))
         log(CS.log_line(d.accept, stages.below, con.thresholds if con is not None else (None, None, None), extra))
     if stages.views is not None:
         log(EN.log_line(stages.views, d))
+    if stages.floor_request is not None:
+        log(FL.log_line(stages.floor_request, d.floor_gap, d.floor_flags))
     req = stages.nms_request
     if req is not None:
         kept, offered = (d.keep, len(d)) if d.accept is None else (d.keep & d.accept, int(d.accept.sum()))
