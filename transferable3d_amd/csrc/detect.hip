@@ -8,6 +8,7 @@
 //                    corner each.
 // No atomics, nothing depends on the grid: a frustum's outputs are a function of its own inputs only.
 #include "common.h"
+#include "detbox_dev.h"
 
 // the host code this replaces is NumPy, elementwise: no fused multiply-adds, so that the same inputs round the same way whatever the
 // surrounding code looks like to the optimiser
@@ -119,14 +120,8 @@ __global__ __launch_bounds__(DD_THREADS) void k_detect_decode(const t3d_detect_d
     o = p.label + (size_t)b * 7;
     o[0] = h; o[1] = w; o[2] = l; o[3] = tx; o[4] = ty; o[5] = tz; o[6] = ry;
   }
-  if (lane < 8) {        // get_3d_box((l, w, h), ry, (tx, ty - h/2, tz)): x (l,l,-l,-l,..)/2, y (h x4, -h x4)/2, z (w,-w,-w,w,..)/2
-    const float x = ((lane & 2) ? -l : l) / 2.0f, y = (lane < 4 ? h : -h) / 2.0f, z = (((lane + 1) & 2) ? -w : w) / 2.0f;
-    const float cr = cosf(ry), sn = sinf(ry);
-    float* o = p.corners + ((size_t)b * 8 + lane) * 3;
-    o[0] = (cr * x + sn * z) + tx;
-    o[1] = y + (ty - h / 2.0f);
-    o[2] = (-sn * x + cr * z) + tz;
-  }
+  if (lane < 8)          // get_3d_box((l, w, h), ry, (tx, ty - h/2, tz))
+    detbox_corner(h, w, l, cosf(ry), sinf(ry), tx, ty - h / 2.0f, tz, lane, p.corners + ((size_t)b * 8 + lane) * 3);
 }
 
 }  // namespace

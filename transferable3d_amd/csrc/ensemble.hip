@@ -11,7 +11,7 @@
 // Every loop over views runs to the compile-time maximum under a `v < V` guard, so that the view labels and the IoUs are indexed
 // statically and stay in registers.  No atomics, no LDS, no dependence on the grid: a detection's outputs are a function of its own rows.
 #include "common.h"
-#include "boxgeom_dev.h"
+#include "detbox_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -20,23 +20,11 @@ namespace {
 constexpr int ENS_THREADS = 256;
 constexpr int ENS_MAXV = T3D_DETECT_ENSEMBLE_MAX_VIEWS;
 
-__device__ __forceinline__ bool ens_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }      // false for a NaN
-
-__device__ __forceinline__ double ens_weight(float w) {
-  const double x = (double)w;
-  return (ens_finite(x) && x >= 0.0) ? x : 0.0;
-}
-
-__device__ __forceinline__ double ens_wrap(double x) {
-  const double PI = 3.14159265358979323846, TWO_PI = 2.0 * PI;
-  return x - TWO_PI * ceil((x - PI) / TWO_PI);
-}
-
 struct EnsLabel { float h, w, l, tx, ty, tz, ry; };
 
 __device__ __forceinline__ bool ens_label_ok(const EnsLabel& b) {
-  return ens_finite((double)b.h) && ens_finite((double)b.w) && ens_finite((double)b.l) && ens_finite((double)b.tx) &&
-         ens_finite((double)b.ty) && ens_finite((double)b.tz) && ens_finite((double)b.ry);
+  return detbox_finite((double)b.h) && detbox_finite((double)b.w) && detbox_finite((double)b.l) && detbox_finite((double)b.tx) &&
+         detbox_finite((double)b.ty) && detbox_finite((double)b.tz) && detbox_finite((double)b.ry);
 }
 
 // The view label of t3d.h: row i of `label`, mirrored back where the view was assembled mirrored (c, s: cos and sin of rot_angle[i]).
@@ -49,21 +37,14 @@ __device__ __forceinline__ EnsLabel ens_view_label(const float* label, size_t i,
     const double xc = tx * c - tz * s, zc = tx * s + tz * c;
     b.tx = (float)(-xc * c + zc * s);
     b.tz = (float)(xc * s + zc * c);
-    b.ry = (float)ens_wrap((PI - (double)b.ry) + 2.0 * a);
+    b.ry = (float)detbox_wrap((PI - (double)b.ry) + 2.0 * a);
   }
   return b;
 }
 
-// k_detect_decode's corners of a label whose centre is (tx, yc, tz)
+// detbox_corners of a label whose centre is (tx, yc, tz)
 __device__ __forceinline__ void ens_corners(const EnsLabel& b, float tx, float yc, float tz, float* k) {
-  const float cr = cosf(b.ry), sn = sinf(b.ry);
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const float x = ((c & 2) ? -b.l : b.l) / 2.0f, y = (c < 4 ? b.h : -b.h) / 2.0f, z = (((c + 1) & 2) ? -b.w : b.w) / 2.0f;
-    k[c * 3 + 0] = (cr * x + sn * z) + tx;
-    k[c * 3 + 1] = y + yc;
-    k[c * 3 + 2] = (-sn * x + cr * z) + tz;
-  }
+  detbox_corners(b.h, b.w, b.l, b.ry, tx, yc, tz, k);
 }
 
 __global__ __launch_bounds__(ENS_THREADS) void k_ensemble_pairs(const t3d_detect_ensemble_args a, float* iou_out, int P) {
@@ -86,9 +67,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ensemble_pairs(const t3d_detect
     float k1[24], k2[24];
     ens_corners(bu, 0.f, 0.f, 0.f, k1);
     ens_corners(bv, bv.tx - bu.tx, (bv.ty - bv.h / 2.0f) - (bu.ty - bu.h / 2.0f), bv.tz - bu.tz, k2);
-    float iou2d;
-    const float iou3d = boxgeom::box3d_iou_corners(k1, k2, &iou2d);
-    iou = a.metric == T3D_NMS_IOU2D ? iou2d : iou3d;
+    iou = iou_by_metric(k1, k2, a.metric);
     iou = iou == iou ? iou : 0.f;                                 // (a NaN counts as 0)
   }
   iou_out[t] = iou;
@@ -180,7 +159,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ensemble(const t3d_detect_ensem
   double w_anchor = 0.0;
 #pragma unroll
   for (int v = 0; v < ENS_MAXV; ++v)                              // (weight[] lives in the kernel arguments: a static index)
-    if (v == anchor) w_anchor = ens_weight(a.weight[v][i]);
+    if (v == anchor) w_anchor = detbox_weight(a.weight[v][i]);
   double W = w_anchor, sx = w_anchor * (double)A.tx, sy = w_anchor * ((double)A.ty - h_a / 2.0), sz = w_anchor * (double)A.tz;
   double sl = w_anchor * (double)A.l, sw = w_anchor * (double)A.w, sh = w_anchor * h_a, sd = 0.0;
   int votes = 0;
@@ -194,12 +173,12 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ensemble(const t3d_detect_ensem
       int kq = 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const double wr = ens_wrap(d + (double)k * HALF_PI);
+        const double wr = detbox_wrap(d + (double)k * HALF_PI);
         if (k == 0 || fabs(wr) < fabs(delta)) { delta = wr; kq = k; }
       }
       const double h_v = L[v].h;
       const double l_v = (kq & 1) ? L[v].w : L[v].l, w_v = (kq & 1) ? L[v].l : L[v].w;      // (l and w exchanged for an odd quarter turn)
-      const double wv = ens_weight(a.weight[v][i]) * (double)ia[v];
+      const double wv = detbox_weight(a.weight[v][i]) * (double)ia[v];
       W = W + wv;
       sx = sx + wv * (double)L[v].tx;
       sy = sy + wv * ((double)L[v].ty - h_v / 2.0);
@@ -211,7 +190,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ensemble(const t3d_detect_ensem
     }
   }
   a.n_votes[i] = votes;
-  const bool fused = votes > 0 && W > 0.0 && ens_finite(W);
+  const bool fused = votes > 0 && W > 0.0 && detbox_finite(W);
   if (!fused && anchor <= 0) {                                    // view 0, or no valid view: byte copies
     const float* l0 = a.label[0] + i * 7;
 #pragma unroll

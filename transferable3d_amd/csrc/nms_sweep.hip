@@ -1,25 +1,21 @@
 // The greedy suppression of nms.hip for many configurations at once (t3d.h t3d_detect_nms_sweep): a configuration is one of K thresholds
 // (or none) and a subset of the boxes ("listed"), and its answer is what t3d_detect_nms answers on the groups restricted to that subset.
 // Neither the order of a group nor the IoU of a pair depends on the configuration -- the order of a subset is the induced order -- so
-// both are computed once, by nms.hip's own code:
-//   k_nms_order     (nms_dev.h) the rank of every box in its group, once;
-//   k_sweep_pairs   k_nms_pairs with K thresholds: (sorted position s of g, word w) computes each IoU(box at s, box at 64 w + c) once, by
-//                   the same call in the same argument order, and sets bit c of K words, mask[(first(g) + s) W + w][k] = IoU > thresholds[k];
+// both are computed once, by the kernels nms.hip launches (nms_pairs_dev.h):
+//   k_nms_order     the rank of every box in its group, once;
+//   k_nms_pairs     <4> or <16>, with K thresholds: (sorted position s of g, word w) computes each IoU(box at s, box at 64 w + c) once and
+//                   sets bit c of K words, mask[(first(g) + s) W + w][k] = IoU > thresholds[k];
 //   k_sweep_clear   keep[m, 0 .. n) = 0 and n_kept[m] = 0 for every configuration m (8 bytes per thread where the row allows it);
 //   k_sweep_walk    k_nms_sweep per (configuration, group): blockIdx.y / .z carry the configuration, the lanes of a group start with
 //                   the unlisted boxes of their words already "removed" (so those are never kept and suppress nothing), walk the ranks
 //                   with the bit rows of the configuration's threshold, and write a 1 for every box left.  A configuration without a
 //                   threshold skips the walk.  The ones are counted per wave and added to n_kept[m] by one integer atomic.
 // The work per configuration is spread over ceil(n_groups / groups per workgroup) workgroups, as the single suppression's is.
-#include "common.h"
-#include "boxgeom_dev.h"
-#include "nms_dev.h"
+#include "nms_pairs_dev.h"
 
 namespace {
 
 constexpr int SW_Y = 32768;      // configurations along gridDim.y; gridDim.z carries the rest (a grid's y and z end at 65535)
-
-struct SwThresholds { float t[T3D_NMS_SWEEP_MAX_THRESHOLDS]; };
 
 __device__ __forceinline__ int sw_config() { return blockIdx.z * SW_Y + blockIdx.y; }
 
@@ -38,42 +34,6 @@ __global__ __launch_bounds__(NMS_THREADS) void k_sweep_clear(const t3d_detect_nm
   }
 }
 
-template <int KMAX>      // the thresholds a thread keeps bit words for: >= K
-__global__ __launch_bounds__(NMS_THREADS) void k_sweep_pairs(const t3d_detect_nms_args a, const int32_t* order, unsigned long long* mask,
-                                                              int W, int K, const SwThresholds th) {
-  const int p = blockIdx.x * NMS_THREADS + threadIdx.x, w = blockIdx.y;
-  if (p >= a.n) return;
-  const NmsGroup g = nms_group_of(a, p);
-  if (g.size < 0) return;
-  const int s = p - g.first;                    // this row's sorted position
-  const int c0 = max(s + 1, 64 * w), c1 = min(g.size, 64 * w + 64);
-  if (64 * w + 63 < s || 64 * w >= g.size) return;       // wholly below the diagonal, or past the group: never read
-  unsigned long long bits[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) bits[k] = 0;
-  const int row = order[p];
-  if (nms_box_ok(a, row)) {
-    float k1[24];
-#pragma unroll
-    for (int i = 0; i < 24; ++i) k1[i] = a.corners[(size_t)row * 24 + i];
-    for (int c = c0; c < c1; ++c) {
-      const int col = order[g.first + c];
-      if (!nms_box_ok(a, col)) continue;
-      float iou2d;
-      const float iou3d = boxgeom::box3d_iou_corners(k1, a.corners + (size_t)col * 24, &iou2d);
-      const float iou = a.metric == T3D_NMS_IOU2D ? iou2d : iou3d;
-      const unsigned long long bit = 1ull << (c - 64 * w);
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K && iou > th.t[k]) bits[k] |= bit;      // a NaN compares false
-    }
-  }
-  unsigned long long* out = mask + ((size_t)p * W + w) * K;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) out[k] = bits[k];
-}
-
 template <int LPG>      // lanes per group: a power of two, >= W
 __global__ __launch_bounds__(NMS_THREADS) void k_sweep_walk(const t3d_detect_nms_args a, const t3d_detect_nms_sweep_args s,
                                                              const int32_t* order, const unsigned long long* mask, int W) {
@@ -83,14 +43,11 @@ __global__ __launch_bounds__(NMS_THREADS) void k_sweep_walk(const t3d_detect_nms
   const int ct = s.config_threshold[m], K = s.n_thresholds;
   if (ct < -1 || ct >= K) return;                // not a configuration: its row stays 0
   const int gi = blockIdx.x * GPB + threadIdx.x / LPG, w = threadIdx.x % LPG;
-  int first = 0, size = 0;
-  if (gi < a.n_groups) {
-    const int f = a.group_offsets[gi], e = a.group_offsets[gi + 1];
-    if (f >= 0 && e >= f && e <= a.n && e - f <= a.max_group) { first = f; size = e - f; }
-  }
+  const NmsGroup g = nms_group_at(a, gi);       // (a group that breaks the contract is not visited)
+  const int first = g.first, size = max(g.size, 0);
   const bool has_word = 64 * w < size;           // (implies w < W)
   const int nc = has_word ? min(64, size - 64 * w) : 0;
-  const unsigned long long cols = nc >= 64 ? ~0ull : (1ull << nc) - 1ull;
+  const unsigned long long cols = nms_cols(nc);
   // the boxes of this lane's word that take part in configuration m
   unsigned long long in = 0;
   const uint8_t* listed = s.listed ? s.listed + (size_t)m * s.listed_stride : nullptr;
@@ -100,9 +57,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_sweep_walk(const t3d_detect_nms
   }
   unsigned long long removed = cols & ~in;       // a box that is not listed is never kept, and its row is never taken
   if (ct >= 0) {                                  // (the same for every lane of the workgroup)
-    int steps = size;                            // the groups of a wave walk in lockstep: the shuffles below need every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o, 64));
+    const int steps = nms_wave_steps(size);
     for (int st = 0; st < steps; ++st) {
       const int sw = st >> 6;
       const unsigned long long owner = LPG == 1 ? removed : __shfl(removed, sw, LPG);
@@ -128,13 +83,11 @@ __global__ __launch_bounds__(NMS_THREADS) void k_sweep_walk(const t3d_detect_nms
 
 extern "C" int t3d_detect_nms_sweep(const t3d_detect_nms_sweep_args* s, t3d_stream_t stream) {
   T3D_ABI_TAKE(detect_nms_sweep_args, s);
-  if (!s) return T3D_ERR_ARG;
-  if (s->n < 0 || s->n_groups < 0 || s->max_group < 0) return T3D_ERR_ARG;
-  if (s->metric != T3D_NMS_IOU3D && s->metric != T3D_NMS_IOU2D) return T3D_ERR_ARG;
-  if (s->max_group > T3D_DETECT_NMS_MAX_GROUP) return T3D_ERR_SHAPE;
+  bool empty;
+  if (const int refused = nms_lists_gate(s, true, &empty)) return refused;
   if (s->M < 1 || s->M > T3D_SWEEP_MAX_CONFIGS) return T3D_ERR_SHAPE;
   if (s->n_thresholds < 1 || s->n_thresholds > T3D_NMS_SWEEP_MAX_THRESHOLDS) return T3D_ERR_SHAPE;
-  SwThresholds th;
+  NmsThresholds th;
   for (int k = 0; k < T3D_NMS_SWEEP_MAX_THRESHOLDS; ++k) {
     th.t[k] = k < s->n_thresholds ? s->thresholds[k] : 0.f;
     if (th.t[k] != th.t[k]) return T3D_ERR_ARG;
@@ -143,7 +96,6 @@ extern "C" int t3d_detect_nms_sweep(const t3d_detect_nms_sweep_args* s, t3d_stre
   if (s->keep && s->keep_stride < s->n) return T3D_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int my = s->M < SW_Y ? s->M : SW_Y, mz = (s->M + SW_Y - 1) / SW_Y;
-  const bool empty = s->n == 0 || s->n_groups == 0 || s->max_group == 0;
   if (!empty) {
     if (!s->corners || !s->score || !s->group_offsets || !s->members || !s->config_threshold || !s->keep || !s->workspace) return T3D_ERR_ARG;
     if (s->listed && s->listed_stride < s->n) return T3D_ERR_ARG;
@@ -158,8 +110,8 @@ extern "C" int t3d_detect_nms_sweep(const t3d_detect_nms_sweep_args* s, t3d_stre
   T3D_CHECK_LAUNCH();
   if (empty) return T3D_OK;
   const int W = (s->max_group + 63) / 64, K = s->n_thresholds;
-  int32_t* order = static_cast<int32_t*>(s->workspace);
-  unsigned long long* mask = reinterpret_cast<unsigned long long*>(static_cast<char*>(s->workspace) + ((uint64_t)s->n + 1) / 2 * 8);
+  unsigned long long* mask;
+  int32_t* order = nms_carve(s->workspace, s->n, &mask);
   t3d_detect_nms_args a;      // what nms.hip's kernels read of a call: the boxes, the scores and the lists
   memset(&a, 0, sizeof(a));
   a.struct_size = (uint32_t)sizeof(a);
@@ -169,18 +121,12 @@ extern "C" int t3d_detect_nms_sweep(const t3d_detect_nms_sweep_args* s, t3d_stre
   const int blocks = (s->n + NMS_THREADS - 1) / NMS_THREADS;
   T3D_LAUNCH(k_nms_order, dim3(blocks), dim3(NMS_THREADS), 0, st, a, order);
   T3D_CHECK_LAUNCH();
-  if (K <= 4) T3D_LAUNCH(k_sweep_pairs<4>, dim3(blocks, W), dim3(NMS_THREADS), 0, st, a, order, mask, W, K, th);
-  else T3D_LAUNCH(k_sweep_pairs<T3D_NMS_SWEEP_MAX_THRESHOLDS>, dim3(blocks, W), dim3(NMS_THREADS), 0, st, a, order, mask, W, K, th);
+  if (K <= 4) T3D_LAUNCH(k_nms_pairs<4>, dim3(blocks, W), dim3(NMS_THREADS), 0, st, a, order, mask, W, K, th);
+  else T3D_LAUNCH(k_nms_pairs<T3D_NMS_SWEEP_MAX_THRESHOLDS>, dim3(blocks, W), dim3(NMS_THREADS), 0, st, a, order, mask, W, K, th);
   T3D_CHECK_LAUNCH();
-#define SW_WALK(LPG)                                                                                                                  \
-  T3D_LAUNCH(k_sweep_walk<LPG>, dim3((s->n_groups + NMS_THREADS / LPG - 1) / (NMS_THREADS / LPG), my, mz), dim3(NMS_THREADS), 0, st, a, *s, \
-             order, mask, W)
-  if (W <= 1) SW_WALK(1);
-  else if (W <= 2) SW_WALK(2);
-  else if (W <= 4) SW_WALK(4);
-  else if (W <= 8) SW_WALK(8);
-  else SW_WALK(16);
-#undef SW_WALK
+  nms_for_lanes<16>(W, s->n_groups, [&](auto lpg, int group_blocks) {
+    T3D_LAUNCH(k_sweep_walk<decltype(lpg)::value>, dim3(group_blocks, my, mz), dim3(NMS_THREADS), 0, st, a, *s, order, mask, W);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }

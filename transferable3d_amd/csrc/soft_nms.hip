@@ -17,9 +17,7 @@
 // where boxes are pruned -- except the pairs whose centres lie too far apart to touch: their IoU is 0 and the polygon clipping is skipped
 // (in a group of 1024 boxes of 256 objects nearly all of them).
 // No workspace, no LDS, no atomics, no dependence on the grid: a group's outputs are a function of its own boxes.
-#include "common.h"
-#include "boxgeom_dev.h"
-#define NMS_DEV_NO_ORDER
+#include "detbox_dev.h"
 #include "nms_dev.h"
 
 namespace {
@@ -56,9 +54,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_soft_nms(const t3d_detect_soft_
       a.suppressed_by[box] = -1;
     }
   }
-  int steps = size;                              // the groups of a wave walk in lockstep: the shuffles below need every lane
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o, 64));
+  const int steps = nms_wave_steps(size);
   for (int st = 0; st < steps; ++st) {           // (a selection takes one live box out of its group: `steps` selections empty every group)
     if (!__any(live != 0)) break;                // the same answer in every lane of the wave
     float bs = -1.f;
@@ -105,11 +101,10 @@ __global__ __launch_bounds__(NMS_THREADS) void k_soft_nms(const t3d_detect_soft_
           // too far apart to touch, with room for the rounding of both sides: IoU 0, which decays nothing under either method
           // (a NaN on either side compares false and goes on to the IoU)
           if (sqrtf(gx * gx + gy * gy + gz * gz) > (h1 + h2) * 1.0001f + 1e-6f) continue;
-          float k2s[24], iou2d;
+          float k2s[24];
 #pragma unroll
           for (int i = 0; i < 8; ++i) { k2s[3 * i] = k2[3 * i] - ox; k2s[3 * i + 1] = k2[3 * i + 1]; k2s[3 * i + 2] = k2[3 * i + 2] - oz; }
-          const float iou3d = boxgeom::box3d_iou_corners(k1, k2s, &iou2d);
-          const float iou = a.metric == T3D_NMS_IOU2D ? iou2d : iou3d;
+          const float iou = iou_by_metric(k1, k2s, a.metric);
           float factor = 1.f;
           bool decay = false;
           if (a.method == T3D_SOFT_NMS_GAUSSIAN) {
@@ -134,34 +129,28 @@ __global__ __launch_bounds__(NMS_THREADS) void k_soft_nms(const t3d_detect_soft_
   }
 }
 
+bool soft_options_ok(const t3d_detect_soft_nms_args& a) {
+  if (a.method != T3D_SOFT_NMS_GAUSSIAN && a.method != T3D_SOFT_NMS_LINEAR) return false;
+  if (a.method == T3D_SOFT_NMS_GAUSSIAN && !(a.sigma > 0.f && a.sigma < __builtin_inff())) return false;
+  return a.min_score >= 0.f;      // (false for a NaN)
+}
+
 }  // namespace
 
 extern "C" int t3d_detect_soft_nms(const t3d_detect_soft_nms_args* a, t3d_stream_t stream) {
   T3D_ABI_TAKE(detect_soft_nms_args, a);
-  if (!a) return T3D_ERR_ARG;
-  if (a->n < 0 || a->n_groups < 0 || a->max_group < 0) return T3D_ERR_ARG;
-  if (a->metric != T3D_NMS_IOU3D && a->metric != T3D_NMS_IOU2D) return T3D_ERR_ARG;
-  if (a->method != T3D_SOFT_NMS_GAUSSIAN && a->method != T3D_SOFT_NMS_LINEAR) return T3D_ERR_ARG;
-  if (a->method == T3D_SOFT_NMS_GAUSSIAN && !(a->sigma > 0.f && a->sigma < __builtin_inff())) return T3D_ERR_ARG;
-  if (!(a->min_score >= 0.f)) return T3D_ERR_ARG;
-  if (a->max_group > T3D_DETECT_NMS_MAX_GROUP) return T3D_ERR_SHAPE;
-  if (a->n == 0 || a->n_groups == 0 || a->max_group == 0) return T3D_OK;
+  bool empty;
+  if (const int refused = nms_lists_gate(a, a && soft_options_ok(*a), &empty)) return refused;
+  if (empty) return T3D_OK;
   if (!a->corners || !a->score || !a->group_offsets || !a->members || !a->score_out || !a->keep || !a->suppressed_by || !a->n_decays)
     return T3D_ERR_ARG;
   const uint64_t need = T3D_DETECT_SOFT_NMS_WORKSPACE_BYTES(a->n, a->max_group);
   if (a->workspace_bytes < need || (need > 0 && (!a->workspace || (reinterpret_cast<uintptr_t>(a->workspace) & 7u)))) return T3D_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define SOFT_NMS(LPG) \
-  T3D_LAUNCH(k_soft_nms<LPG>, dim3((a->n_groups + NMS_THREADS / LPG - 1) / (NMS_THREADS / LPG)), dim3(NMS_THREADS), 0, st, *a)
-  const int lanes = (a->max_group + SOFT_OWN - 1) / SOFT_OWN;      // a lane of a small group owns up to SOFT_OWN boxes
-  if (lanes <= 1) SOFT_NMS(1);
-  else if (lanes <= 2) SOFT_NMS(2);
-  else if (lanes <= 4) SOFT_NMS(4);
-  else if (lanes <= 8) SOFT_NMS(8);
-  else if (lanes <= 16) SOFT_NMS(16);
-  else if (lanes <= 32) SOFT_NMS(32);
-  else SOFT_NMS(64);
-#undef SOFT_NMS
+  // a lane of a small group owns up to SOFT_OWN boxes
+  nms_for_lanes<64>((a->max_group + SOFT_OWN - 1) / SOFT_OWN, a->n_groups, [&](auto lpg, int group_blocks) {
+    T3D_LAUNCH(k_soft_nms<decltype(lpg)::value>, dim3(group_blocks), dim3(NMS_THREADS), 0, st, *a);
+  });
   T3D_CHECK_LAUNCH();
   return T3D_OK;
 }

@@ -172,6 +172,15 @@ def _lists(rt, group_offsets, members, n):
     return n_groups, max_group, d_go, d_mem
 
 
+def _boxes_and_lists(rt, corners, score, group_offsets, members):
+    """What the three suppressions take alike: corners [n, 8, 3] / [n, 24] and score [n], fp32 and contiguous on the runtime's device,
+    and the lists of groups_of -> (n, and what _lists answers)."""
+    n = int(score.numel())
+    assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
+    assert corners.dtype == torch.float32 and score.dtype == torch.float32
+    return (n,) + _lists(rt, group_offsets, members, n)
+
+
 class DeviceNms:
     """Workspace and outputs of t3d_detect_nms; `run` launches on device tensors.  The buffers grow as needed and are reused (abi.grown)."""
 
@@ -186,10 +195,7 @@ class DeviceNms:
         next run.  fill: (keep, suppressed_by, rank) values the outputs hold before the launch (what a box in no group keeps; default
         1, -1, -1: an unlisted box is a kept one)."""
         rt = self.rt
-        n = int(score.numel())
-        assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
-        assert corners.dtype == torch.float32 and score.dtype == torch.float32
-        n_groups, max_group, d_go, d_mem = _lists(rt, group_offsets, members, n)
+        n, n_groups, max_group, d_go, d_mem = _boxes_and_lists(rt, corners, score, group_offsets, members)
         fk, fs, fr = (1, -1, -1) if fill is None else fill
         self.keep = abi.grown(self.keep, n, torch.uint8, rt.device)
         self.suppressed_by, self.rank = (abi.grown(t, n, torch.int32, rt.device) for t in (self.suppressed_by, self.rank))
@@ -226,14 +232,11 @@ class DeviceSoftNms:
         the next run.  fill: (score_out, keep, suppressed_by, n_decays) values the outputs hold before the launch (what a box in no
         group keeps; default: its input score, 1, -1, 0: an unlisted box is a kept one that nothing decayed)."""
         rt = self.rt
-        n = int(score.numel())
-        assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
-        assert corners.dtype == torch.float32 and score.dtype == torch.float32
         if method not in SOFT_METHODS:
             raise ValueError('method is one of %s, got %r' % (SOFT_METHODS, method))
         if method == 'linear' and threshold is None:
             raise ValueError("method 'linear' needs a threshold")
-        n_groups, max_group, d_go, d_mem = _lists(rt, group_offsets, members, n)
+        n, n_groups, max_group, d_go, d_mem = _boxes_and_lists(rt, corners, score, group_offsets, members)
         self.score_out, self.keep = abi.grown(self.score_out, n, torch.float32, rt.device), abi.grown(self.keep, n, torch.uint8, rt.device)
         self.suppressed_by, self.n_decays = (abi.grown(t, n, torch.int32, rt.device) for t in (self.suppressed_by, self.n_decays))
         out, keep, sup, dec = self.score_out[:n], self.keep[:n], self.suppressed_by[:n], self.n_decays[:n]
@@ -317,10 +320,7 @@ class DeviceNmsSweep:
         -> (keep uint8 [M, n] -- a view of rows `stride` bytes apart, row m what DeviceNms.run answers for configuration m with the
         unlisted boxes left out of the groups and 0 for a box that is in no group or not listed -- and n_kept int32 [M])."""
         rt = self.rt
-        n = int(score.numel())
-        assert corners.numel() == n * 24 and corners.is_contiguous() and score.is_contiguous()
-        assert corners.dtype == torch.float32 and score.dtype == torch.float32
-        n_groups, max_group, d_go, d_mem = _lists(rt, group_offsets, members, n)
+        n, n_groups, max_group, d_go, d_mem = _boxes_and_lists(rt, corners, score, group_offsets, members)
         thresholds = [float(t) for t in thresholds]
         K = len(thresholds)
         if not 1 <= K <= abi.NMS_SWEEP_MAX_THRESHOLDS:
