@@ -861,6 +861,9 @@ int t3d_box_head_iou(const t3d_box_head_iou_args* args, t3d_stream_t stream);
  * angle2class over 12 bins, size -> (class, size - mean size of the class), one-hot class.
  * Draws: `choice` [B,N] and `aug` [B,3] = (flip, randn, u) when given (parity tests), else generated from
  * (seed, hyper[0] = step, b, n) -- so the whole input pipeline can sit inside the captured step.
+ * Every frustum a launch can sample holds at least one point (offsets[f+1] > offsets[f]): of a frustum without points the
+ * generated draw is row offsets[f], which is the next frustum's, or behind `points` and `seg` for the last one; a given
+ * `choice` holds values in [0, count).  Neither is checked on the device (dataset.DeviceFrustumSet refuses such a set).
  * ALTERNATE_BATCH (train_semisup_adv.py:538-565, sample_pure_from_2D_cls / _3D_cls 589-596): see sample2. */
 typedef struct {
   const float* points;         /* [total, C_src] all frustums, concatenated; xyz in columns 0..2 */

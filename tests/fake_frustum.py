@@ -49,7 +49,12 @@ class FakeFrustumLib(FakeLib):
             p = _struct(a)
         except AbiSizeError:
             return abi.ERR_ABI
-        if p.n_scenes <= 0 or p.num_points <= 0 or p.num_points > 4096 or p.C < 3 or p.C_src < p.C:
+        need = ('points', 'scene_offsets', 'rtilt', 'K', 'scene_jobs', 'box2d', 'job_key', 'mask_offsets', 'masks', 'seg_prefix',
+                'box2d_out', 'frustum_angle', 'n_in_box', 'count', 'index', 'out_points')
+        if not all(getattr(p, k) for k in need) or (p.box3d and not p.label):
+            return -1
+        if p.n_scenes <= 0 or p.n_scenes > 65535 or p.n_jobs < 0 or p.max_scene_points < 0 or p.num_points <= 0 or p.num_points > 4096 \
+                or p.C < 3 or p.C_src < p.C:
             return -2
         S, J, NP, Cs, Cc = p.n_scenes, p.n_jobs, p.num_points, p.C_src, p.C
         if J == 0:

@@ -6,7 +6,7 @@ usually masked or never stored; a stray store lands in allocator slack.  `guarde
 ONE flat allocation of its own:
 
   input   the valid elements hold the caller's values; the front band, the back band and, with a leading dimension `ld` wider than
-          the valid columns, every row's padding hold NaN (integer operands: INT32_MIN, an index no kernel accepts).  A result that
+          the valid columns, every row's padding hold NaN (integer operands: the type's minimum, an index no kernel accepts).  A result that
           used one of them is NaN (or wildly out of range) where the fp64 reference is finite: `assert_clean`.  The checker asserts
           that the launch changed nothing in the whole allocation.
   output  the interior, the row padding and both bands are pre-filled with one sentinel bit pattern (a NaN with a payload no
@@ -20,11 +20,15 @@ import torch
 
 G = 256
 INT_BAND = -2 ** 31
+INT64_BAND = -2 ** 63
 SENTINEL = object()          # fill=SENTINEL: an output operand
 
-# quiet NaNs with a payload (a kernel that produces a NaN produces the canonical one, 0x7FC00000 / 0x7FC0), and an unlikely index
+# quiet NaNs with a payload (a kernel that produces a NaN produces the canonical one, 0x7FC00000 / 0x7FC0 / 0x7FF8000000000000), and
+# an unlikely index.  torch.int64 also stands for a uint64 operand (a scratch of bit masks): the caller passes its address as uint64.
 _SENT_BITS = {torch.float32: (torch.int32, 0xFFC5A3E1 - (1 << 32)), torch.bfloat16: (torch.int16, 0xFFD5 - (1 << 16)),
-              torch.int32: (torch.int32, -0x7FFFFFFF)}
+              torch.float64: (torch.int64, 0xFFF8C5A3E1B2D497 - (1 << 64)), torch.int32: (torch.int32, -0x7FFFFFFF),
+              torch.int64: (torch.int64, -0x7FFFFFFFC5A3E1B3)}
+_IN_FILL = {torch.int32: INT_BAND, torch.int64: INT64_BAND}          # every other type: NaN
 
 
 def roundup4(k):
@@ -36,13 +40,16 @@ def _bits(t):
 
 
 class Check:
-    """What `guarded` returns next to the view.  check() / check(written=True) after the launch; `.valid` is the view of the valid
-    elements ([rows, width] at column `col0` of the [rows, ld] interior), `.buf` the whole flat allocation."""
+    """What `guarded` returns next to the view.  check() / check(written=True) after the launch (written=None: an output that the
+    launch must leave untouched, interior included); `.valid` is the view of the valid elements ([rows, width] at column `col0` of the
+    [rows, ld] interior), `.buf` the whole flat allocation, `.ptr` the interior's address (the view's data_ptr(), also for an operand
+    of no elements, whose view has none)."""
 
     def __init__(self, name, buf, view, valid, front, n_int, is_out, pad_mask):
         self.name, self.buf, self.view, self.valid = name, buf, view, valid
         self._front, self._n, self._out, self._pad = front, n_int, is_out, pad_mask
         self._before = None if is_out else buf.clone()
+        self.ptr = buf.data_ptr() + front * buf.element_size()
 
     def __call__(self, written=False):
         name, b = self.name, _bits(self.buf)
@@ -63,6 +70,9 @@ class Check:
         if self._pad is not None:
             bad = ((inner != sent) & self._pad).nonzero().flatten()
             assert bad.numel() == 0, '%s: %d store(s) into the row PADDING (interior offsets %s)' % (name, bad.numel(), bad[:8].tolist())
+        if written is None:
+            assert bool((inner == sent).all()), '%s: %d element(s) written by a launch that must not touch it (first interior offsets %s)' % (
+                name, int((inner != sent).sum()), (inner != sent).nonzero().flatten()[:8].tolist())
         if written:
             un = inner == sent
             if self._pad is not None:
@@ -97,7 +107,7 @@ def guarded(shape, dtype, device, ld=None, front=G, back=G, fill=SENTINEL, col0=
     if is_out:
         _bits(buf).fill_(_SENT_BITS[dtype][1])
     else:
-        buf.fill_(INT_BAND if dtype == torch.int32 else float('nan'))
+        buf.fill_(_IN_FILL.get(dtype, float('nan')))
     inner = buf[front:front + n]
     pad = None
     if strided:

@@ -1,8 +1,10 @@
 """Device-side batch assembly (t3d_batch_assemble): the NumPy specification against the oracle's restatement of the
-reference's get_classes3D / get_batch on identical draws, and the statistics of the generated draws."""
+reference's get_classes3D / get_batch on identical draws, the statistics of the generated draws, and (below) the kernel-level
+cases that tests/test_dataset_gpu.py runs on the device."""
 import ctypes as C
 
 import numpy as np
+import pytest
 import torch
 
 from fake_t3d import FakeLib
@@ -43,7 +45,10 @@ def check_against_oracle(rt, flags=(True, True, True)):
     flip, rn, hu = (r.uniform(size=B) > 0.5), r.normal(size=B), r.uniform(size=B)
     kw = dict(rotate_to_center=flags[0], random_flip=flags[1], random_shift=flags[2])
     got, _ = assemble(rt, host, B, N, Cc, sample=sample, choice=choice, aug=np.stack([flip, rn, hu], 1), **kw)
-    ref = D.get_batch(host, sample, choice, flip, rn, hu, Cc, **kw)
+    compare_with_oracle(got, D.get_batch(host, sample, choice, flip, rn, hu, Cc, **kw))
+
+
+def compare_with_oracle(got, ref):
     assert np.abs(got['pc'] - ref['pc']).max() < 2e-5
     assert np.array_equal(got['y_seg'], ref['y_seg'])
     assert np.abs(got['y_center'] - ref['y_center']).max() < 2e-5
@@ -361,3 +366,177 @@ def test_epoch_is_one_pass_and_replicas_walk_disjoint_slices():
     for epoch in range(2):
         assert not (seen[0][epoch] & seen[1][epoch])           # replicas see disjoint frustums
         assert len(seen[0][epoch] | seen[1][epoch]) == 48      # 50 frustums, 2 dropped with the incomplete batch
+
+
+# ---- t3d_batch_assemble at kernel level: a direct call on guarded operands (tests/guard_bands.py), at the shapes the data-set wrapper
+# and the comfortable frustums of the checks above never reach ----
+
+EDGE_COUNTS = (1, 5, 64, 65, 1)              # the 1-point frustum is the set's first and its last; 64 / 65: a wave and one more
+LAYOUTS = ((6, 3, 4), (6, 4, 4), (6, 6, 8), (4, 4, 0))          # (C_src, C, ld_pc)
+
+
+def edge_set(C_src, counts=EDGE_COUNTS, seed=0, heading=None):
+    """A tiny ragged set of fp32-exact values; channel 3 (where there is one) holds the point's row in `points`, so that a copied
+    channel names the row a draw took."""
+    r = np.random.RandomState(seed)
+    F, total = len(counts), int(np.sum(counts))
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    pts = (r.normal(size=(total, C_src)) * 0.5 + np.array([0, 0, 3] + [0] * (C_src - 3))).astype(np.float32)
+    if C_src > 3:
+        pts[:, 3] = np.arange(total)
+    return dict(points=pts, seg=r.randint(0, 2, total).astype(np.int32), offsets=np.concatenate([[0], np.cumsum(counts)]).astype(np.int64),
+                frustum_angle=f32(r.uniform(-0.6, 0.6, F) - np.pi / 2), box_center=f32(r.normal(size=(F, 3)) * 0.2 + [0, 0.2, 3]),
+                heading=f32(r.uniform(-np.pi, np.pi, F) if heading is None else heading), size=f32(r.uniform(0.5, 2, (F, 3))),
+                cls=r.randint(0, 10, F).astype(np.int32))
+
+
+def assemble_direct(lib, dev, host, B, N, Cc, ld_pc=0, sample=None, sample_len=0, choice=None, aug=None, step=0, seed=7,
+                    rotate_to_center=True, random_flip=True, random_shift=True):
+    """One t3d_batch_assemble call with every operand in guard bands: a NaN / INT_BAND row stands right behind the last frustum of
+    `points` / `seg`.  Checks that the inputs are unchanged, that nothing is stored outside the outputs, that every output element
+    (the pad columns of pc included: zeros) is written and that pc is finite; returns the outputs."""
+    from guard_bands import guarded
+    from transferable3d_amd import abi
+    from transferable3d_amd.abi import fptr, iptr
+    F32, I32 = torch.float32, torch.int32
+    F = len(host['cls'])
+    ins = dict(points=(host['points'], F32), seg=(host['seg'], I32), offsets=(host['offsets'], torch.int64),
+               frustum_angle=(host['frustum_angle'], F32), box_center=(host['box_center'], F32), heading=(host['heading'], F32),
+               size=(host['size'], F32), cls=(host['cls'], I32), sample=(np.asarray(sample), I32),
+               hyper=(np.array([step, 0, 0, 0], np.float32), F32))
+    if choice is not None:
+        ins['choice'] = (np.asarray(choice), I32)
+    if aug is not None:
+        ins['aug'] = (np.asarray(aug), F32)
+    ld = ld_pc or Cc
+    outs = dict(pc=((B * N, ld), F32), y_seg=((B, N), I32), y_center=((B, 3), F32), y_orient_cls=((B,), I32), y_orient_reg=((B,), F32),
+                y_dims_cls=((B,), I32), y_dims_reg=((B, 3), F32), one_hot=((B, 10), F32), rot_angle=((B,), F32), is_data_2D=((B,), I32))
+    t, chk = {}, {}
+    for k, (a, dt) in ins.items():
+        t[k], chk[k] = guarded(np.shape(a), dt, dev, fill=torch.as_tensor(np.ascontiguousarray(a)), name=k)
+    for k, (shape, dt) in outs.items():
+        t[k], chk[k] = guarded(shape, dt, dev, name=k)
+    a = abi.BatchAssembleArgs()
+    for k in t:
+        ptr = abi.C.cast(abi.C.c_void_p(t[k].data_ptr()), abi.C.POINTER(abi.C.c_int64)) if k == 'offsets' else \
+            (fptr if t[k].dtype == F32 else iptr)(t[k])
+        setattr(a, k, ptr)
+    a.sample_len, a.C_src, a.C, a.B, a.N, a.ld_pc, a.seed = sample_len, host['points'].shape[1], Cc, B, N, ld_pc, seed
+    a.rotate_to_center, a.random_flip, a.random_shift = int(rotate_to_center), int(random_flip), int(random_shift)
+    assert lib.t3d_batch_assemble(C.byref(a), _stream(isinstance(lib, FakeLib))) == 0
+    if torch.device(dev).type == 'cuda':
+        torch.cuda.synchronize()
+    for k, ck in chk.items():
+        ck(written=True) if k in outs else ck()
+    num = {k: t[k].cpu().numpy().copy() for k in outs}
+    pc = num['pc'].reshape(B, N, ld)
+    assert np.isfinite(pc).all() and not pc[:, :, Cc:].any()                # no band row was drawn; the pad columns are zeros
+    num['pc'], num['one_hot_vec'] = pc[:, :, :Cc], num.pop('one_hot')
+    return num
+
+
+def check_small_frustums(lib, dev):
+    """Frustums of 1, 5, 64 and 65 points, every slot sampling each of them, in every row layout.  Generated draws: 0 <= ch < cnt,
+    read off the copied channel that names the source row (and, for another library than the specification, the specification's
+    draws); given draws that hold 0 and cnt - 1: the oracle restatement."""
+    F, N = len(EDGE_COUNTS), 300                                            # two workgroups per slot
+    for C_src, Cc, ld in LAYOUTS:
+        host = edge_set(C_src, seed=C_src + Cc)
+        off, cnt = host['offsets'], np.asarray(EDGE_COUNTS)
+        for roll in range(F):
+            sample = np.roll(np.arange(F), roll)
+            kw = dict(ld_pc=ld, sample=sample, step=roll, seed=11)
+            gen = assemble_direct(lib, dev, host, F, N, Cc, **kw)
+            if Cc > 3:
+                row = gen['pc'][:, :, 3].astype(np.int64)
+                ch = row - off[sample][:, None]
+                assert (gen['pc'][:, :, 3] == row).all() and (ch >= 0).all() and (ch < cnt[sample][:, None]).all()
+                assert np.array_equal(gen['y_seg'], host['seg'][row])
+                for b in range(F):
+                    if cnt[sample[b]] <= 5:
+                        assert set(ch[b].tolist()) == set(range(cnt[sample[b]]))          # every point of a tiny frustum is drawn
+            assert np.array_equal(gen['y_dims_cls'], host['cls'][sample]) and not gen['is_data_2D'].any()
+            if not isinstance(lib, FakeLib):                                # the tolerances of test_generated_batch_equals_the_specification
+                c = assemble_direct(FakeLib(), 'cpu', host, F, N, Cc, **kw)
+                assert np.array_equal(c['y_seg'], gen['y_seg']) and np.array_equal(c['pc'][:, :, 3:], gen['pc'][:, :, 3:])
+                assert np.abs(c['pc'] - gen['pc']).max() < 1e-4 and np.abs(c['y_center'] - gen['y_center']).max() < 1e-4
+                assert np.array_equal(c['y_orient_cls'], gen['y_orient_cls']) and np.abs(c['y_orient_reg'] - gen['y_orient_reg']).max() < 1e-5
+            r = np.random.RandomState(roll)
+            choice = np.stack([r.randint(0, n, size=N) for n in cnt[sample]])
+            choice[:, 0], choice[:, 1], choice[:, N - 1] = cnt[sample] - 1, 0, cnt[sample] - 1
+            flip, rn, hu = (r.uniform(size=F) > 0.5), r.normal(size=F), r.uniform(size=F)
+            got = assemble_direct(lib, dev, host, F, N, Cc, ld_pc=ld, sample=sample, choice=choice, aug=np.stack([flip, rn, hu], 1))
+            compare_with_oracle(got, D.get_batch(host, sample, choice, flip, rn, hu, Cc))
+
+
+def check_heading_bin_edges(lib, dev):
+    """Headings exactly on the 12 bin edges, one fp32 step either side of them and further off, negative headings, and each of them
+    flipped (pi - h), in one batch against the oracle restatement with the tolerances of check_against_oracle: class * bin + residual
+    gives the angle back whichever bin fp32 chooses at an edge, the residual stays within half a bin, and the bins agree for
+    at least 0.8 of the batch -- 36 of its 180 headings lie within an fp32 step of an edge, the others at least 1e-3 away."""
+    per = 2 * np.pi / 12
+    edges = np.float32(np.arange(12) * per - per / 2)
+    near = np.concatenate([edges, np.nextafter(edges, np.float32(-9)), np.nextafter(edges, np.float32(9))])
+    off = np.concatenate([s * (edges.astype(np.float64) + d) for s in (1, -1) for d in (1e-3, -1e-3, 0.1, -0.1, 0.2, -0.2)])
+    heading = np.concatenate([near.astype(np.float64), off])
+    B = len(heading)
+    assert B == 180 and (heading < 0).sum() > 60
+    host = edge_set(4, counts=(3,) * B, seed=3, heading=heading)
+    choice = np.random.RandomState(0).randint(0, 3, size=(B, 4))
+    for flipped in (False, True):
+        flip = np.full(B, flipped)
+        got = assemble_direct(lib, dev, host, B, 4, 4, sample=np.arange(B), choice=choice, aug=np.stack([flip, 0.0 * flip, 0.0 * flip], 1),
+                              rotate_to_center=False, random_shift=False)
+        ref = D.get_batch(host, np.arange(B), choice, flip, np.zeros(B), np.zeros(B), 4, rotate_to_center=False, random_shift=False)
+        compare_with_oracle(got, ref)
+        assert np.array_equal(got['y_orient_cls'][36:], ref['y_orient_cls'][36:])          # 1e-3 and more from an edge: fp32 resolves it
+        assert set(got['y_orient_cls'].tolist()) == set(range(12))
+
+
+def check_batch_of_one_and_wrapping_walk(lib, dev):
+    """B = 1, and a permutation walk shorter than the batch: slot b of step s takes sample[(s * B + b) mod sample_len], the same
+    bytes as naming those frustums slot by slot (the generated draws follow seed, step, slot and point, not the frustum)."""
+    host = edge_set(6, seed=5)
+    one = assemble_direct(lib, dev, host, 1, 70, 6, ld_pc=8, sample=[3], step=4)
+    assert int(one['y_dims_cls'][0]) == host['cls'][3] and one['one_hot_vec'][0].argmax() == host['cls'][3]
+    row = one['pc'][0, :, 3]
+    assert (row >= host['offsets'][3]).all() and (row < host['offsets'][4]).all()
+    perm, B, step = np.array([4, 0, 2], np.int32), 4, 2
+    walk = assemble_direct(lib, dev, host, B, 70, 6, ld_pc=8, sample=perm, sample_len=3, step=step)
+    named = perm[(step * B + np.arange(B)) % 3]
+    assert named.tolist() == [2, 4, 0, 2]                                   # wraps inside the batch
+    same = assemble_direct(lib, dev, host, B, 70, 6, ld_pc=8, sample=named, step=step)
+    assert np.array_equal(walk['y_dims_cls'], host['cls'][named])
+    for k in walk:
+        assert walk[k].tobytes() == same[k].tobytes(), k
+
+
+def test_small_frustums_in_every_row_layout():
+    check_small_frustums(FakeLib(), 'cpu')
+
+
+def test_headings_on_the_bin_edges():
+    check_heading_bin_edges(FakeLib(), 'cpu')
+
+
+def test_batch_of_one_and_a_walk_that_wraps_inside_the_batch():
+    check_batch_of_one_and_wrapping_walk(FakeLib(), 'cpu')
+
+
+def test_a_set_with_an_empty_frustum_is_refused():
+    """t3d_batch_assemble would read the row behind an empty frustum (t3d.h); the set refuses it, wherever it stands, and no kernel
+    is launched on one anywhere."""
+    rt = Runtime(device='cpu', lib=FakeLib())
+    for where, counts in ((0, (0, 5, 7)), (1, (5, 0, 7)), (2, (5, 7, 0)), (1, (4, 0, 0))):
+        host = edge_set(4, counts=counts)
+        with pytest.raises(ValueError, match='frustum %d of 3 holds no points' % where):
+            DeviceFrustumSet(rt, **host)
+        r = np.random.RandomState(0)
+        lists = [r.normal(size=(n, 4)) for n in counts], [np.zeros(n) for n in counts]
+        with pytest.raises(ValueError, match='frustum %d of 3 holds no points' % where):
+            DeviceFrustumSet.from_lists(rt, lists[0], lists[1], host['frustum_angle'], host['box_center'], host['heading'], host['size'], host['cls'])
+    out = {'out_points': torch.zeros(3, 8, 4, dtype=torch.float64), 'frustum_angle': torch.zeros(3, dtype=torch.float64)}
+    with pytest.raises(ValueError, match='frustum 1 of 2 holds no points'):
+        DeviceFrustumSet.from_device(rt, out, [0, 2], [5, 0], [1, 2])
+    assert DeviceFrustumSet.from_device(rt, out, [0, 2], [5, 1], [1, 2]).offsets.tolist() == [0, 5, 6]
+    assert DeviceFrustumSet(rt, **edge_set(4, counts=(1, 1))).F == 2

@@ -1,5 +1,7 @@
 """GPU: t3d_batch_assemble against the oracle restatement (explicit draws), against the NumPy specification (generated
-draws: same hash generator), and the statistics of the generated draws."""
+draws: same hash generator), and the statistics of the generated draws; at kernel level (a direct call on guarded operands,
+test_dataset_cpu.assemble_direct): frustums of 1 .. 65 points in every row layout, headings on the bin edges, B = 1 and a walk that
+wraps inside the batch.  The kernels that feed it: tests/test_kernels_frustum_gpu.py."""
 import numpy as np
 import pytest
 
@@ -64,3 +66,18 @@ def test_boxpc_perturb_generated_draws_equal_the_specification(hip_lib):
 def test_equal_samples_per_class_sampler(hip_lib):
     from test_dataset_cpu import check_equal_class_sampler
     check_equal_class_sampler(Runtime(lib=hip_lib))
+
+
+def test_small_frustums_in_every_row_layout(hip_lib):
+    from test_dataset_cpu import check_small_frustums
+    check_small_frustums(hip_lib, 'cuda')
+
+
+def test_headings_on_the_bin_edges(hip_lib):
+    from test_dataset_cpu import check_heading_bin_edges
+    check_heading_bin_edges(hip_lib, 'cuda')
+
+
+def test_batch_of_one_and_a_walk_that_wraps_inside_the_batch(hip_lib):
+    from test_dataset_cpu import check_batch_of_one_and_wrapping_walk
+    check_batch_of_one_and_wrapping_walk(hip_lib, 'cuda')

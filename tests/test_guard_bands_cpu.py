@@ -4,7 +4,7 @@ consumed a band value -- each naming the operand -- and passes a clean op."""
 import pytest
 import torch
 
-from guard_bands import G, INT_BAND, assert_clean, guarded, roundup4
+from guard_bands import G, INT64_BAND, INT_BAND, assert_clean, guarded, roundup4
 
 DTYPES = [torch.float32, torch.bfloat16]
 
@@ -94,6 +94,64 @@ def test_integer_bands_and_modified_input():
     oc.buf[-1] = 5
     with pytest.raises(AssertionError, match='pamax: 1 store.s. AFTER the operand, nearest %d element' % G):
         oc()
+
+
+def test_fp64_operands_have_a_payload_sentinel_and_nan_bands():
+    """the frustum ABI's fp64 operands: the same five failures, and a canonical NaN stored by the op is a store, not the sentinel"""
+    x = torch.randn(5, 6, dtype=torch.float64)
+    xv, xc = guarded((5, 6), torch.float64, 'cpu', fill=x, name='points')
+    assert xv.dtype == torch.float64 and torch.isnan(xc.buf[:G]).all() and torch.isnan(xc.buf[-G:]).all() and torch.equal(xv, x)
+    yv, yc = guarded((5, 6), torch.float64, 'cpu', name='out_points')
+    assert torch.isnan(yc.buf).all() and (yc.buf.view(torch.int64) != torch.tensor(float('nan'), dtype=torch.float64).view(torch.int64)).all()
+    with pytest.raises(AssertionError, match='out_points: 30 element.s. never written'):
+        yc(written=True)
+    yc(written=None)
+    yv.copy_(2 * x)
+    yv[4, 5] = float('nan')
+    xc()
+    yc(written=True)
+    with pytest.raises(AssertionError, match='out_points: 30 element.s. written by a launch that must not touch it'):
+        yc(written=None)
+    with pytest.raises(AssertionError, match='out_points: 1 non-finite'):
+        assert_clean('out_points', yv, 2 * x)
+    for at, where in ((G - 1, 'BEFORE'), (G + 30, 'AFTER')):
+        keep = yc.buf[at].clone()
+        yc.buf[at] = 0.0
+        with pytest.raises(AssertionError, match='out_points: 1 store.s. %s the operand, nearest 1 element' % where):
+            yc()
+        yc.buf[at] = keep                   # the payload survives a copy
+        yc()
+    xv[0, 0] += 1
+    with pytest.raises(AssertionError, match='points: the launch changed an INPUT'):
+        xc()
+
+
+def test_int64_operands_and_a_uint64_scratch_through_an_int64_view():
+    off = torch.tensor([0, 3, 3, 1 << 40], dtype=torch.int64)
+    ov, oc = guarded((4,), torch.int64, 'cpu', fill=off, name='scene_offsets')
+    assert (oc.buf[:G] == INT64_BAND).all() and (oc.buf[-G:] == INT64_BAND).all() and torch.equal(ov, off)
+    oc()
+    ov[3] -= 1
+    with pytest.raises(AssertionError, match='scene_offsets: the launch changed an INPUT'):
+        oc()
+    mv, mc = guarded((7,), torch.int64, 'cpu', name='masks')          # uint64 bit masks: every pattern but the sentinel is a value
+    mc(written=None)
+    mv[:6] = torch.tensor([0, -1, 1, INT64_BAND, 2 ** 63 - 1, 5], dtype=torch.int64)        # 0, ~0, 1, 1 << 63, ...
+    mc()
+    with pytest.raises(AssertionError, match='masks: 1 element.s. never written'):
+        mc(written=True)
+    mc.buf[G + 7] = 0
+    with pytest.raises(AssertionError, match='masks: 1 store.s. AFTER the operand, nearest 1 element'):
+        mc()
+
+
+def test_an_empty_operand_is_two_bands():
+    ev, ec = guarded((0, 4), torch.float64, 'cpu', name='box2d_out')
+    assert ev.shape == (0, 4) and ec.buf.numel() == 2 * G
+    ec(written=True)
+    ec.buf[G] = 1.0
+    with pytest.raises(AssertionError, match='box2d_out: 1 store.s. AFTER the operand, nearest 1 element'):
+        ec()
 
 
 def test_scale_table_holds_exactly_roundup4_floats():

@@ -1,6 +1,7 @@
 """GPU: frustum extraction through libt3d.so (t3d_frustum_extract) -- the golden comparison of tests/test_sunrgbd_extract_cpu.py on the
 reference's own draws, the generated draws (distinct, in range, independent of the batch, keyed by seed and augmentation index, uniform
-inclusion), a full-size scene against tests/ref_frustum.py, and the ABI size check."""
+inclusion), a full-size scene against tests/ref_frustum.py, and the ABI size check.  The entry point itself at its edges (ragged batches,
+the cut at num_points, hash ties, exact boundaries, guard bands): tests/test_kernels_frustum_gpu.py."""
 import ctypes as C
 
 import numpy as np

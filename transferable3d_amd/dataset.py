@@ -18,11 +18,22 @@ from .abi import fptr, iptr
 from .constants import MEAN_DIMS_ARR, NUM_CLASS, type2class
 
 
+def _refuse_empty_frustums(counts):
+    """t3d_batch_assemble draws a frustum's points with replacement; of a frustum without points it would read the next frustum's
+    first row (behind the last frustum: the row behind the arrays).  The reference fails there too (np.random.choice over an empty
+    range, roi_semi_dataset.py:303), so a set never holds one."""
+    empty = np.nonzero(np.asarray(counts) < 1)[0]
+    if len(empty):
+        raise ValueError('frustum %d of %d holds no points: every frustum of a DeviceFrustumSet needs at least one' % (empty[0], len(counts)))
+
+
 class DeviceFrustumSet:
     def __init__(self, rt, points, seg, offsets, frustum_angle, box_center, heading, size, cls):
         """points [total, C_src] fp32, seg [total] int32, offsets [F+1] int64 (ragged rows of frustum f:
-        offsets[f]..offsets[f+1]), per-frustum frustum_angle [F], box_center [F,3], heading [F], size [F,3] (l,w,h), cls [F]."""
+        offsets[f]..offsets[f+1], at least one each), per-frustum frustum_angle [F], box_center [F,3], heading [F], size [F,3] (l,w,h),
+        cls [F]."""
         dev = rt.device
+        _refuse_empty_frustums(np.diff(np.asarray(torch.as_tensor(offsets).cpu(), np.int64)))
         up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(dev)
         self.rt = rt
         self.points, self.seg, self.offsets = up(points, torch.float32), up(seg, torch.int32), up(offsets, torch.int64)
@@ -119,6 +130,7 @@ class DeviceFrustumSet:
             raise ValueError('no frustum is kept: a DeviceFrustumSet cannot be empty')
         if len(cls_ids) != len(counts):
             raise ValueError('%d class ids for %d kept frustums' % (len(cls_ids), len(counts)))
+        _refuse_empty_frustums(counts)
         up = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(dt).to(dev)
         ds = cls.__new__(cls)
         ds.rt, ds.F = rt, len(counts)
