@@ -2480,6 +2480,138 @@ typedef struct {
 #define T3D_V2_SIZE_detect_floor_args 104
 int t3d_detect_floor(const t3d_detect_floor_args* args, t3d_stream_t stream);
 
+/* ---- The free space of a scene and how a detection stands in it (csrc/range.hip; transferable3d_amd/visibility.py, detect
+ *      --visibility) ----
+ * Every pixel of a depth image says that the space between the camera and its return is empty.  t3d_scene_range keeps that of each
+ * scene of an extraction launch as a range map -- per cell of `cell` x `cell` pixels the smallest camera depth of the points that
+ * project into it, as an fp32 -- from the scene's depth points (upright depth coordinates) where the extraction left them.  The map
+ * holds fp32 values that are not negative, whose bit patterns order as unsigned integers: it is a minimum by integer atomics, and a
+ * scene's bytes are a function of its own points, its calibration row and `cell`, never of S, of its place in the batch or of the
+ * order of anything.  Everything is fp64, every product and sum an operation of its own (nothing is contracted).
+ *
+ *   points, scene_offsets  as t3d_scene_floor reads them.
+ *   Scene s                its calibration is row calib_index[s] of `calib` (the 20 doubles t3d_detect_consistency reads: Rtilt (9), K
+ *                          (9), image W, H; W and H are not read here);  its grid is gw = grid_dims[s][0] by gh = grid_dims[s][1] cells,
+ *                          row-major (cell (cx, cy) at grid_offsets[s] + cy * gw + cx of `range`).  The caller chooses gw = ceil(W / cell)
+ *                          and gh alike.  GW = (double)gw * (double)cell, GH alike.
+ *   Scene flags            T3D_RANGE_NO_CALIB: calib_index[s] outside [0, n_calib).  T3D_RANGE_BAD_GRID: gw < 1, gh < 1, gw * gh >
+ *                          T3D_RANGE_MAX_CELLS, grid_offsets[s] < 0 or grid_offsets[s] + gw * gh > n_cells.  With either no point of the
+ *                          scene is binned and no cell of `range` is written for it.
+ *   A point counts         iff x, y and z are finite;  n_finite is their number (whatever the flags).
+ *   Projection             the paragraph "Projection" of t3d_detect_consistency with d = (x, y, z), the point:  t_i = (R[0][i]*d0 +
+ *                          R[1][i]*d1) + R[2][i]*d2;  cam = (t0, -t2, t1);  w_i = (K[i][0]*cam0 + K[i][1]*cam1) + K[i][2]*cam2;  u = w0/w2,
+ *                          v = w1/w2;  depth = cam2.
+ *   A point is binned      iff it counts, depth > 0, the bit pattern of (float)depth lies below T3D_RANGE_EMPTY (the depth does not
+ *                          round to infinity), u and v are finite, 0 <= u < GW and 0 <= v < GH.  cx = (int)floor(u / (double)cell),
+ *                          taken as gw - 1 where the quotient rounds up to gw;  cy alike.  The cell becomes the smaller of what it
+ *                          holds and the bit pattern of (float)depth.
+ *   range [n_cells]        uint32;  every cell is T3D_RANGE_EMPTY (the bits of +infinity) before the points are binned, cells that belong
+ *                          to no scene included.
+ *   counts [S, 4]          n_finite, the points binned, the cells that hold a depth, the scene flags.
+ * T3D_ERR_ARG: a NULL struct or pointer (`range` may be NULL where n_cells == 0), S < 0, cell < 1, n_calib < 0, n_cells < 0,
+ * reserved != 0.  T3D_ERR_SHAPE: ld < 3, S > 65535, n_cells > 2^31 - 1.  S == 0: T3D_OK without a launch.  Nothing is launched after a
+ * refusal.  Two launches (the fill, the points), no host synchronisation; the offsets and the grids live on the device, so the
+ * caller answers for the rows of `points` as for t3d_scene_floor -- a grid that does not fit `range` is refused by its flag. */
+#define T3D_RANGE_EMPTY 0x7F800000u
+#define T3D_RANGE_BLOCKS 64              /* workgroups per scene */
+#define T3D_RANGE_MAX_CELLS (1 << 24)    /* cells of one scene's grid */
+#define T3D_RANGE_NO_CALIB 1
+#define T3D_RANGE_BAD_GRID 2
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_scene_range_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n_scenes; int ld; int cell; int n_calib;
+  const double* points;                /* [sum n_s, ld] */
+  const int64_t* scene_offsets;        /* [S+1] */
+  const double* calib;                 /* [n_calib,20] */
+  const int32_t* calib_index;          /* [S] */
+  const int32_t* grid_dims;            /* [S,2]: gw, gh */
+  const int64_t* grid_offsets;         /* [S+1] */
+  int64_t n_cells;                     /* cells of `range` */
+  int reserved;                        /* 0 */
+  uint32_t* range;                     /* [n_cells] out */
+  int32_t* counts;                     /* [S,4] out */
+} t3d_scene_range_args;
+#define T3D_V2_SIZE_scene_range_args 104
+int t3d_scene_range(const t3d_scene_range_args* args, t3d_stream_t stream);
+
+/* t3d_detect_visibility: every decoded box against the range map of its scene.  A box pulled towards the camera has the surface behind
+ * it seen THROUGH it, a box pushed away has every return IN FRONT of it, a box in mid-air is seen through entirely.  One workgroup of
+ * 256 threads per detection; fp64 on the widened fp32 entries, nothing contracted, each product and sum in the order written; the
+ * counts are integers, so no order of lanes matters; inputs are never written, equal inputs give equal bytes.
+ *
+ *   label [n,7], corners [n,8,3]   as t3d_detect_decode wrote them (upright camera coordinates; tx = label[3], tz = label[5]).
+ *   Scene                  s = scene_index[i] names row s of `calib` (20 doubles as above), of grid_dims and of grid_offsets.  Flag
+ *                          T3D_VIS_NO_SCENE: s outside [0, n_scenes) or a grid that t3d_scene_range would flag T3D_RANGE_BAD_GRID.
+ *                          T3D_VIS_NOT_FINITE: an entry of the label or the corners that is not finite.  With either nothing is
+ *                          measured: the profile and the measures are 0, choice is (K - 1) / 2, the row is copied.
+ *   Candidate k < K        offsets[k] is a relative depth offset: K odd, 1 <= K <= T3D_VIS_MAX_OFFSETS, ascending, all above -1,
+ *                          offsets[(K-1)/2] == 0.  Corner c of candidate k is (X, Y, Z) = ((double)x_c + offsets[k] * (double)tx,
+ *                          (double)y_c, (double)z_c + offsets[k] * (double)tz): a slide along the horizontal viewing ray by a fraction
+ *                          of the distance -- no square root, every decision stays in + - * /.  mid = (K - 1) / 2 is the box itself.
+ *   Rectangle              the eight corners are projected as "Projection" of t3d_detect_consistency states (d = (X, Z, -Y)).  A
+ *                          candidate is MEASURED iff every corner has depth > 0 and finite u and v; one that is not has a profile of
+ *                          zeros and cannot be chosen.  xmin = u of corner 0, then for corners 0..7 in order xmin = u < xmin ? u : xmin;
+ *                          xmax, ymin, ymax likewise.  No cell where xmax < 0, xmin >= GW, ymax < 0 or ymin >= GH.  Otherwise the cells
+ *                          cx0 .. cx1 by cy0 .. cy1:  cx0 = xmin < 0 ? 0 : (int)floor(xmin / (double)cell) (gw - 1 where the quotient
+ *                          rounds up to gw),  cx1 = xmax >= GW ? gw - 1 : (int)floor(xmax / (double)cell);  cy0, cy1 alike.
+ *   Ray of cell (cx, cy)   pu = ((double)cx + 0.5) * (double)cell, pv alike;  as t3d_scene_raycast inverts the projection:
+ *                          rx = (pu - K[0][2]) / K[0][0];  ry = (pv - K[1][2]) / K[1][1];  q = (rx, 1, -ry);
+ *                          d_i = (R[i][0]*q0 + R[i][1]*q1) + R[i][2]*q2;  in upright camera coordinates g = (d0, -d2, d1).  The point t * g
+ *                          has camera depth t.
+ *   Intersection           with the parallelepiped at corner 0 (K0) with the edges e to corners 1, 3 and 4, in this order.  Per edge:
+ *                          a = (g0*e0 + g1*e1) + g2*e2;  b = (K0x*e0 + K0y*e1) + K0z*e2;  dd = (e0*e0 + e1*e1) + e2*e2.
+ *                          a == 0: a miss unless 0 <= -b && -b <= dd, no constraint otherwise.  Else r0 = b / a, r1 = (dd + b) / a,
+ *                          lo = r0 < r1 ? r0 : r1, hi = r0 < r1 ? r1 : r0;  t_in = lo > t_in ? lo : t_in (from 0);  t_out = hi < t_out ?
+ *                          hi : t_out (from +infinity).  A hit iff no edge misses and t_in < t_out.
+ *   Category of a hit      t_out - t_in < min_chord: GRAZE.  Otherwise a RAY; with z the cell's depth widened: UNKNOWN where the cell is
+ *                          T3D_RANGE_EMPTY, else FRONT where z < t_in - margin, else THROUGH where z > t_out + margin, else INSIDE.
+ *   profile [n,K,6]        rays, unknown, front, inside, through, graze of every candidate (rays = unknown + front + inside + through).
+ *   measures [n,3]         of candidate mid:  see_through = (double)through / (double)(through + inside);  occluded = (double)front /
+ *                          (double)rays;  support = (double)inside / (double)rays;  0 where the denominator is 0.
+ *   flags                  also T3D_VIS_BEHIND: candidate mid is not measured (the measures are 0);  where none of these three is set,
+ *                          T3D_VIS_NO_RAYS: rays of mid == 0;  T3D_VIS_NO_EVIDENCE: through + inside of mid == 0.
+ *   choice [n]             score_k = inside_k - through_k.  Over the measured candidates the largest score; among equal scores the
+ *                          smaller |k - mid|, then the lower k.  mid where mid is not measured.
+ *   mode 0                 measure.  label_out / corners_out may be NULL; where given they receive copies.
+ *   mode 1 (snap)          the box moves iff none of NO_SCENE, NOT_FINITE, BEHIND is set, choice != mid and score_choice - score_mid >=
+ *                          min_gain: flag T3D_VIS_SNAPPED.  label_out of a moved row: tx' = (float)((double)tx + offsets[choice] *
+ *                          (double)tx), tz' alike with tz;  corners_out: every x' = (float)((double)x + offsets[choice] * (double)tx),
+ *                          every z' alike with tz;  everything else, and every row that did not move, is a copy byte for byte.
+ * T3D_ERR_ARG: a NULL struct, label, corners, scene_index, profile, measures, choice or flags, a NULL calib, grid_dims or grid_offsets
+ * where n_scenes > 0, a NULL range where n_cells > 0, n < 0, n_scenes < 0, n_cells < 0, reserved != 0, a mode outside 0..1, a NULL
+ * label_out or corners_out in mode 1, cell < 1, min_gain < 0, margin or min_chord negative, NaN or infinite, offsets that are not
+ * ascending, not above -1 or not 0 at mid.  T3D_ERR_SHAPE: K even or outside [1, T3D_VIS_MAX_OFFSETS].  n == 0: T3D_OK without a launch. */
+#define T3D_VIS_MAX_OFFSETS 17
+#define T3D_VIS_NO_SCENE 1
+#define T3D_VIS_NOT_FINITE 2
+#define T3D_VIS_BEHIND 4
+#define T3D_VIS_NO_RAYS 8
+#define T3D_VIS_NO_EVIDENCE 16
+#define T3D_VIS_SNAPPED 32
+typedef struct {
+  uint32_t struct_size;    /* = sizeof(t3d_detect_visibility_args) of the caller's header (see T3D_ABI_VERSION) */
+  int n; int n_scenes; int mode; int K; int cell; int min_gain;
+  int reserved;                        /* 0 */
+  const float* label;                  /* [n,7] */
+  const float* corners;                /* [n,8,3] */
+  const int32_t* scene_index;          /* [n]: the scene's row, -1 for none */
+  const double* calib;                 /* [n_scenes,20] */
+  const int32_t* grid_dims;            /* [n_scenes,2] */
+  const int64_t* grid_offsets;         /* [n_scenes+1] */
+  const uint32_t* range;               /* [n_cells] what t3d_scene_range wrote */
+  int64_t n_cells;
+  double margin; double min_chord;
+  double offsets[T3D_VIS_MAX_OFFSETS]; /* the first K are read */
+  int32_t* profile;                    /* [n,K,6] out */
+  double* measures;                    /* [n,3] out */
+  int32_t* choice;                     /* [n] out */
+  int32_t* flags;                      /* [n] out */
+  float* label_out;                    /* [n,7] out, or NULL (mode 0) */
+  float* corners_out;                  /* [n,8,3] out, or NULL (mode 0) */
+} t3d_detect_visibility_args;
+#define T3D_V2_SIZE_detect_visibility_args 296
+int t3d_detect_visibility(const t3d_detect_visibility_args* args, t3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@
 split: 3-D labels for bed chair toilet desk bathtub, 2-D labels only for table sofa dresser night_stand bookshelf) from
 --frustum_file, then run `detect --official_eval --diagnose` on the validation scenes and the simulated 2-D detections: once plain and
 once each with --nms_iou 0.25, --nms_iou 0.25 --nms_fuse, --soft_nms gaussian and --tta 4; then three runs with --diagnose_parts, which
-splits `loc` into xy, z, centre, size and heading: plain, --snap_floor shift and --snap_floor stretch.
+splits `loc` into xy, z, centre, size and heading: plain, --snap_floor shift, --snap_floor stretch, --visibility (which measures and
+must leave every AP as the plain row has it) and --max_see_through 0.5.
 
 Every step is a fresh child process under its own `timeout -k 10`; the tool stops at the first non-zero status and retries nothing.  The
 sizes are chosen so that the whole run takes minutes and are written into the record.  Writes profiles/synth_recipe.json (`--out`): the
@@ -26,7 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLASSES = ['bed', 'table', 'sofa', 'chair', 'toilet', 'desk', 'dresser', 'night_stand', 'bookshelf', 'bathtub']
 RUNS = [('plain', []), ('nms', ['--nms_iou', '0.25']), ('nms_fuse', ['--nms_iou', '0.25', '--nms_fuse']), ('soft_nms', ['--soft_nms', 'gaussian']),
         ('tta4', ['--tta', '4']), ('parts', ['--diagnose_parts']), ('floor_shift', ['--snap_floor', 'shift', '--diagnose_parts']),
-        ('floor_stretch', ['--snap_floor', 'stretch', '--diagnose_parts'])]
+        ('floor_stretch', ['--snap_floor', 'stretch', '--diagnose_parts']), ('visibility', ['--visibility', '--diagnose_parts']),
+        ('max_see_through', ['--max_see_through', '0.5', '--diagnose_parts'])]
 
 
 def step(name, seconds, argv, log_path, steps):
@@ -88,9 +90,10 @@ def main():
                           'predictions': {c: doc['classes'][c]['predictions'] for c in CLASSES}}
             if 'mean_dAP_parts' in doc:
                 runs[name]['mean_dAP_parts'] = doc['mean_dAP_parts']
-            floor_line = [l.strip() for l in open(os.path.join(work, 'detect_%s.log' % name)) if l.startswith('floor:')]
-            if floor_line:
-                runs[name]['floor'] = floor_line[-1]
+            for stage in ('floor', 'visibility'):
+                line = [l.strip() for l in open(os.path.join(work, 'detect_%s.log' % name)) if l.startswith(stage + ':')]
+                if line:
+                    runs[name][stage] = line[-1]
     except SystemExit as e:          # the record says how far the run came
         failure = str(e)
     train_log = os.path.join(work, 'train_a.log')

@@ -641,6 +641,29 @@ class DetectFloorArgs(Sized):
                 ('corners_out', F)]
 
 
+# t3d.h T3D_RANGE_* / T3D_VIS_*
+RANGE_EMPTY, RANGE_BLOCKS, RANGE_MAX_CELLS = 0x7F800000, 64, 1 << 24
+RANGE_NO_CALIB, RANGE_BAD_GRID = 1, 2
+VIS_MAX_OFFSETS = 17
+VIS_NO_SCENE, VIS_NOT_FINITE, VIS_BEHIND, VIS_NO_RAYS, VIS_NO_EVIDENCE, VIS_SNAPPED = 1, 2, 4, 8, 16, 32
+VIS_PROFILE = ('rays', 'unknown', 'front', 'inside', 'through', 'graze')          # the columns of a profile row
+U32 = C.POINTER(C.c_uint32)
+
+
+class SceneRangeArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n_scenes', i32), ('ld', i32), ('cell', i32), ('n_calib', i32), ('points', D), ('scene_offsets', L),
+                ('calib', D), ('calib_index', I), ('grid_dims', I), ('grid_offsets', L), ('n_cells', C.c_int64), ('reserved', i32), ('range', U32),
+                ('counts', I)]
+
+
+class DetectVisibilityArgs(Sized):
+    _fields_ = [('struct_size', C.c_uint32), ('n', i32), ('n_scenes', i32), ('mode', i32), ('K', i32), ('cell', i32), ('min_gain', i32),
+                ('reserved', i32), ('label', F), ('corners', F), ('scene_index', I), ('calib', D), ('grid_dims', I), ('grid_offsets', L),
+                ('range', U32), ('n_cells', C.c_int64), ('margin', C.c_double), ('min_chord', C.c_double),
+                ('offsets', C.c_double * VIS_MAX_OFFSETS), ('profile', I), ('measures', D), ('choice', I), ('flags', I), ('label_out', F),
+                ('corners_out', F)]
+
+
 VP = C.c_void_p
 # name -> argtypes.  Struct entry points take (const args*, stream).
 
@@ -747,6 +770,8 @@ ENTRY_POINTS = {
     't3d_scene_raycast': [C.POINTER(SceneRaycastArgs), VP],
     't3d_scene_floor': [C.POINTER(SceneFloorArgs), VP],
     't3d_detect_floor': [C.POINTER(DetectFloorArgs), VP],
+    't3d_scene_range': [C.POINTER(SceneRangeArgs), VP],
+    't3d_detect_visibility': [C.POINTER(DetectVisibilityArgs), VP],
     't3d_detect_decode': [C.POINTER(DetectDecodeArgs), VP],
     't3d_detect_nms': [C.POINTER(DetectNmsArgs), VP],
     't3d_render': [C.POINTER(RenderArgs), VP],

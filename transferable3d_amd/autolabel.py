@@ -5,7 +5,9 @@
         --model_path M [test_semisup's model flags] --out_dir OUT [--min_reproj_iou T] [--min_mask_in_box F] [--min_seg_box_iou F] \
         [--keep_other_classes] [--link_inputs] [--score_against_labels] [--tta K [--tta_flip] [--tta_vote_iou V] [--min_view_iou A]] \
         [--rescore MODEL.json [--min_rescore P]] [--floor] [--snap_floor {shift,stretch} [--snap_floor_max M]] [--max_floor_gap G] \
-        [--floor_json FILE] [--floor_bin B] [--floor_range LO HI] [--floor_min_share F] [--floor_band D] [--floor_max_tilt DEG]
+        [--floor_json FILE] [--floor_bin B] [--floor_range LO HI] [--floor_min_share F] [--floor_band D] [--floor_max_tilt DEG] \
+        [--visibility] [--visibility_cell PX] [--visibility_margin M] [--visibility_min_chord M] [--max_see_through F \
+        [--visibility_min_rays N]]
 
 Of every object of --classes in D/training/label_dimension/*.txt only the class and the 2-D box are used.  detect.Detector runs on that
 box (with prob 1); t3d_detect_consistency (consistency.py) measures the 3-D box it predicts against the 2-D box and the segmented points,
@@ -33,6 +35,10 @@ constant here.  --score_against_labels reports the boxes that test alone accepts
 snapped box, --max_floor_gap rejects a box that floats above or sinks into its scene's floor by more than G, and
 --score_against_labels reports the boxes that test alone accepts and rejects as well.
 
+--visibility, --max_see_through and their flags: detect's visibility stage (visibility.py).  --max_see_through rejects a box through
+which the scene behind it is seen (on at least --visibility_min_rays rays), and --score_against_labels reports the boxes that test
+alone accepts and rejects as well.
+
 A label line, from a decoded label row (h, w, l, tx, ty, tz, ry) (`label_line`): the 2-D box as x, y, w, h; the centroid (tx, tz,
 -(ty - h/2)) in upright depth coordinates; the half sizes (w/2, l/2, h/2); the basis (cos ry, -sin ry, sin ry, cos ry); the orientation
 (cos ry, -sin ry).  sunrgbd_data.SUNObject3d + compute_box_3d read such a line back as the decode's corner set, to the six decimals of %f.
@@ -47,7 +53,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, sunrgbd_data as SD, test_semisup as TS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, sunrgbd_data as SD, test_semisup as TS, visibility as VS      # noqa: E402
 
 LINE = '%s %d %d %d %d %f %f %f %f %f %f %f %f %f %f %f %f'
 IOU_HIT = 0.25
@@ -77,7 +83,13 @@ def floor_ok(r, max_floor_gap):
     return not abs(r['floor_gap']) > max_floor_gap
 
 
-def new_counts(thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None):
+def see_through_ok(r, max_see_through, min_rays):
+    """Whether --max_see_through alone accepts the record: it was not measured, through + inside ('visibility_evidence') lies below
+    min_rays, or see_through does not exceed it."""
+    return bool(r['visibility_flags'] & VS.UNMEASURED) or r['visibility_evidence'] < min_rays or not r['see_through'] > max_see_through
+
+
+def new_counts(thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None, max_see_through=None):
     c = collections.OrderedDict(offered=0, too_few_points=0, accepted=0, rejected=0)
     c['rejected_by'] = collections.OrderedDict((name, 0) for name, t in zip(CS.THRESHOLDS, thresholds) if t is not None)
     for (flag, _), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
@@ -85,14 +97,17 @@ def new_counts(thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=No
             c['rejected_by'][flag] = 0
     if max_floor_gap is not None:
         c['rejected_by']['max_floor_gap'] = 0
+    if max_see_through is not None:
+        c['rejected_by']['max_see_through'] = 0
     return c
 
 
-def count(records, classes, thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None):
+def count(records, classes, thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None, max_see_through=None, min_rays=0):
     """records: [{'class', 'detected' (False: its frustum held too few points), 'accepted', 'reproj_iou', 'mask_in_box', 'seg_box_iou'}] ->
     {class: offered, too_few_points, accepted, rejected, rejected_by {threshold: n}} (a box may fail several tests).  min_view_iou: the
-    records carry 'view_iou' and the boxes below it are counted too; min_rescore: the same for 'rescore_prob'; max_floor_gap: the same for the boxes whose |'floor_gap'| exceeds it."""
-    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou, min_rescore, max_floor_gap)) for c in classes)
+    records carry 'view_iou' and the boxes below it are counted too; min_rescore: the same for 'rescore_prob'; max_floor_gap: the same for the boxes whose |'floor_gap'| exceeds it;
+    max_see_through (with min_rays): the same for the boxes `see_through_ok` does not accept."""
+    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou, min_rescore, max_floor_gap, max_see_through)) for c in classes)
     for r in records:
         c = out[r['class']]
         c['offered'] += 1
@@ -108,13 +123,15 @@ def count(records, classes, thresholds, min_view_iou=None, min_rescore=None, max
                 c['rejected_by'][flag] += 1
         if max_floor_gap is not None and not floor_ok(r, max_floor_gap):
             c['rejected_by']['max_floor_gap'] += 1
+        if max_see_through is not None and not see_through_ok(r, max_see_through, min_rays):
+            c['rejected_by']['max_see_through'] += 1
     return out
 
 
-def score(records, classes, rt, min_view_iou=None, min_rescore=None, max_floor_gap=None):
+def score(records, classes, rt, min_view_iou=None, min_rescore=None, max_floor_gap=None, max_see_through=None, min_rays=0):
     """--score_against_labels: per class, for the accepted and the rejected boxes, how many, their mean 3-D IoU with the label's own box
     and the share at IoU >= 0.25.  min_view_iou: also under 'min_view_iou' for the boxes that test alone accepts and rejects; min_rescore: the
-    same under 'min_rescore'; max_floor_gap: the same under 'max_floor_gap'."""
+    same under 'min_rescore'; max_floor_gap: the same under 'max_floor_gap'; max_see_through (with min_rays): the same under 'max_see_through'."""
     from transferable3d_amd.eval_det import box3d_iou_batch
     rows = [r for r in records if r['detected']]
     iou = box3d_iou_batch(np.stack([r['corners'] for r in rows]), np.stack([r['label_corners'] for r in rows]), rt)[0] if rows else []
@@ -134,6 +151,10 @@ def score(records, classes, rt, min_view_iou=None, min_rescore=None, max_floor_g
             out[c]['max_floor_gap'] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
                                                              and floor_ok(r, max_floor_gap) == (kind == 'accepted')]))
                                        for kind in ('accepted', 'rejected')}
+        if max_see_through is not None:
+            out[c]['max_see_through'] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
+                                                               and see_through_ok(r, max_see_through, min_rays) == (kind == 'accepted')]))
+                                         for kind in ('accepted', 'rejected')}
     return out
 
 
@@ -141,7 +162,7 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
         batch_scenes=16, workers=8, floor_json=None):
     """The command (module text) with a detect.Detector built by the caller (its thresholds decide).  ids: scene ids, or the path of an
     index file.  -> the dict written to OUT/autolabel.json, plus '_records': one entry per offered object (not written)."""
-    from transferable3d_amd.detect import consistency_fields, scene_batches, view_fields
+    from transferable3d_amd.detect import consistency_fields, scene_batches, view_fields, visibility_fields
     if isinstance(ids, str):
         ids = [int(line.rstrip()) for line in open(ids) if line.strip()]
     classes = list(classes)
@@ -155,7 +176,8 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
         with open(dataset._path('label_dimension', idx, 'txt')) as fh:
             lines[idx] = [line.rstrip() for line in fh if line.strip()]
 
-    image_wh = (lambda path: CS.image_size(path) if os.path.exists(path) else None) if detector.consistency else None
+    visibility = getattr(detector, 'visibility', None)
+    image_wh = (lambda path: CS.image_size(path) if os.path.exists(path) else None) if detector.consistency or (visibility is not None and visibility.on) else None
     parts, offered = [], []
     for batch, scenes in scene_batches(dataset, ids, batch_scenes, workers, image_wh=image_wh, also=read_lines):
         dets = []
@@ -184,6 +206,8 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
                     r['rescore_prob'] = float(d.rescore_prob[i])
                 if d.floor_gap is not None:
                     r.update(floor_gap=float(d.floor_gap[i]), floor_flags=int(d.floor_flags[i]))
+                if d.see_through is not None:
+                    r.update(visibility_fields(d, i), visibility_evidence=int(d.visibility_profile[i][VS.THROUGH] + d.visibility_profile[i][VS.INSIDE]))
                 if score_against_labels:
                     r['label_corners'] = label_corners(o)
                 i += 1
@@ -194,7 +218,9 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
     min_rescore = getattr(detector, 'min_rescore', None)
     floor = getattr(detector, 'floor', None)
     max_floor_gap = floor.max_floor_gap if floor is not None and floor.on else None
-    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou, min_rescore, max_floor_gap),
+    max_see_through = visibility.max_see_through if visibility is not None and visibility.on else None
+    min_rays = visibility.options.min_rays if visibility is not None else 0
+    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou, min_rescore, max_floor_gap, max_see_through, min_rays),
                                       thresholds=dict(zip(CS.THRESHOLDS, thresholds)), scenes=len(ids))
     if getattr(detector, 'tta', None) is not None:
         summary['tta'] = dict(views=detector.tta, flip=detector.tta_flip, vote_iou=detector.tta_vote_iou, min_view_iou=min_view_iou)
@@ -202,8 +228,11 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
         summary['rescore'] = dict(features=detector.rescore.features, min_rescore=min_rescore)
     if floor is not None and floor.on:
         summary['floor'] = dict(snap=floor.snap, snap_max=floor.snap_max, max_floor_gap=max_floor_gap)
+    if visibility is not None and visibility.on:
+        o = visibility.options
+        summary['visibility'] = dict(cell=o.cell, margin=o.margin, min_chord=o.min_chord, max_see_through=max_see_through, min_rays=o.min_rays)
     if score_against_labels:
-        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou, min_rescore, max_floor_gap)
+        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou, min_rescore, max_floor_gap, max_see_through, min_rays)
     written = write_labels(out_dir, ids, lines, records, classes, keep_other_classes)
     summary['scenes_written'] = len(written)
     if link_inputs:
@@ -216,7 +245,7 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
             ''.join(' (%s: %d)' % kv for kv in n['rejected_by'].items())))
         if score_against_labels:
             by = summary['score_against_labels'][c]
-            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag in [f for f, _ in EXTRA_TESTS] + ['max_floor_gap'] for k, v in by.get(flag, {}).items()]:
+            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag in [f for f, _ in EXTRA_TESTS] + ['max_floor_gap', 'max_see_through'] for k, v in by.get(flag, {}).items()]:
                 if v['n']:
                     log('  %s %d: mean 3-D IoU with the label %.3f, at IoU >= %g %.1f %%' % (kind, v['n'], v['mean_iou3d'], IOU_HIT,
                                                                                             100.0 * v['share_iou_ge_0.25']))
@@ -271,6 +300,7 @@ def parser():
     RS.add_arguments(p)
     FL.add_arguments(p)
     p.add_argument('--floor_json', default=None, help='write one row per scene with its floor plane, the share of its points on it, their rms and the flags here')
+    VS.add_arguments(p)
     return p
 
 
@@ -285,6 +315,7 @@ def parse(argv=None):
             raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
         if args.floor_json and not FL.check_options(**{k: getattr(args, k) for k in FL.FLAGS}).on:
             raise ValueError('--floor_json writes the floor planes: it needs --floor, --snap_floor or --max_floor_gap')
+        VS.check_options(**{k: getattr(args, k) for k in VS.FLAGS})
     except ValueError as e:
         p.error(str(e))
     return args, TS.build_flags(list(rest))
@@ -298,7 +329,7 @@ def main(argv=None, rt=None, log=print):
     det = Detector(FLAGS, rt=rt, log=log, consistency=True, min_reproj_iou=args.thresholds[0], min_mask_in_box=args.thresholds[1],
                    min_seg_box_iou=args.thresholds[2], tta=args.tta, tta_flip=args.tta_flip, tta_vote_iou=args.tta_vote_iou,
                    min_view_iou=args.min_view_iou, rescore=args.rescore, min_rescore=args.min_rescore,
-                   **{k: getattr(args, k) for k in FL.FLAGS})
+                   **{k: getattr(args, k) for k in FL.FLAGS + VS.FLAGS})
     return run(det, args.dataset_dir, args.idx_path, args.classes, args.out_dir, keep_other_classes=args.keep_other_classes,
                link_inputs=args.link_inputs, score_against_labels=args.score_against_labels, log=log, floor_json=args.floor_json)
 

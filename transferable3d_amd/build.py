@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB_PATH = os.path.join(HERE, 'libt3d.so')
-SOURCES = ['pointmlp.hip', 'pointmlp_x3.hip', 'bn_optim.hip', 'fc.hip', 'heads.hip', 'boxpc.hip', 'poolbwd.hip', 'data.hip', 'frustum.hip', 'sunrgbd_eval.hip', 'sunrgbd_diagnose.hip', 'sunrgbd_locparts.hip', 'sunrgbd_sweep.hip', 'sunrgbd_bootstrap.hip', 'detect.hip', 'nms.hip', 'nms_sweep.hip', 'soft_nms.hip', 'fuse.hip', 'ensemble.hip', 'render.hip', 'consistency.hip', 'rescore.hip', 'scene_synth.hip', 'floor.hip', 'weak.hip', 'pair.hip', 'version.hip']
+SOURCES = ['pointmlp.hip', 'pointmlp_x3.hip', 'bn_optim.hip', 'fc.hip', 'heads.hip', 'boxpc.hip', 'poolbwd.hip', 'data.hip', 'frustum.hip', 'sunrgbd_eval.hip', 'sunrgbd_diagnose.hip', 'sunrgbd_locparts.hip', 'sunrgbd_sweep.hip', 'sunrgbd_bootstrap.hip', 'detect.hip', 'nms.hip', 'nms_sweep.hip', 'soft_nms.hip', 'fuse.hip', 'ensemble.hip', 'render.hip', 'consistency.hip', 'rescore.hip', 'scene_synth.hip', 'floor.hip', 'range.hip', 'weak.hip', 'pair.hip', 'version.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 # per-source flags (none at present: -fno-slp-vectorize on the x3 unit made every rider kernel spill two registers)
 EXTRA_FLAGS = {}

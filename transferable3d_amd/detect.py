@@ -17,6 +17,8 @@
                        [--rescore_features NAME ..]]
         [--floor] [--snap_floor {shift,stretch} [--snap_floor_max M]] [--max_floor_gap G] [--floor_json FILE]
         [--floor_bin B] [--floor_range LO HI] [--floor_min_share F] [--floor_band D] [--floor_max_tilt DEG]
+        [--visibility] [--visibility_cell PX] [--visibility_margin M] [--visibility_min_chord M]
+        [--max_see_through F [--visibility_min_rays N]]
 
 What `sunrgbd_data --option rgb_detection` followed by `semisup_infer --from_rgb_detection --device_decode` computes, with the frustum
 points staying where t3d_frustum_extract wrote them: extraction -> DeviceFrustumSet.from_device -> DeviceEvalSource -> the network ->
@@ -113,6 +115,20 @@ nothing.  --floor_json FILE takes one row per scene: its plane, the share of its
 flags.  The floor flags do not go with --sweep or --rescore_fit.  Measured: the synthetic recipe (README).  Not measured: real SUN-RGBD.
 Without these flags every output is what it was, byte for byte.
 
+--visibility: the free space of the scene (visibility.py).  Every pixel of a depth image says that the space between the camera and its
+return is empty: a box pulled towards the camera has the wall behind it visible through it, a box pushed away has every return in front
+of it, a background box in mid-air is seen through entirely.  Behind every extraction launch t3d_scene_range keeps, per cell of
+--visibility_cell pixels (default 4), the nearest return of the points the launch left on the device -- a few KB per scene, which stay
+when the points go.  Behind the floor stage and in front of the rescoring, t3d_detect_visibility casts a ray through every cell a box
+covers and asks where the cell's return lies: in front of the box, inside it (within --visibility_margin, default 0.05 m) or behind it;
+a ray that crosses less than --visibility_min_chord (default 0.1 m) of the box counts nowhere.  Records, legends and --consistency_json
+rows gain see_through = through / (through + inside), occluded = front / rays, support = inside / rays and visibility_flags.
+--max_see_through F rejects a detection whose see_through exceeds F on at least --visibility_min_rays (default 16) rays, where the
+--min_* thresholds reject.  The stage moves no box: the kernel's slide along the viewing ray (t3d.h, mode 1) is offered by no flag,
+because on clean label boxes it brought back fewer than half of the displaced ones (README).  Every default is an option, not a tuned
+value.  The flags do not go with --sweep or --rescore_fit.  Measured: the synthetic recipe (README).  Not
+measured: real SUN-RGBD.  Without these flags every output is what it was, byte for byte.
+
 Where things live: the stages behind the decode (views, consistency, the accept rule, NMS, box voting) and their order belong to
 semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
 boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
@@ -131,7 +147,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, floor as FL, nms as NMS, render as RD, rescore as RS, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS      # noqa: E402
+from transferable3d_amd import bootstrap as BS, consistency as CS, ensemble as EN, floor as FL, nms as NMS, render as RD, rescore as RS, semisup_infer as SI, sunrgbd_data as SD, sweep as SW, test_semisup as TS, visibility as VS      # noqa: E402
 from transferable3d_amd.constants import type2class                        # noqa: E402
 from transferable3d_amd.dataset import DeviceEvalSource, DeviceFrustumSet   # noqa: E402
 from transferable3d_amd.tf_checkpoint import load_state                    # noqa: E402
@@ -280,6 +296,12 @@ def view_fields(d, i, as_lists=False):
             'anchor_view': int(d.anchor_view[i])}
 
 
+def visibility_fields(d, i, as_lists=False):
+    """What a record (or a legend / JSON entry) says of how detection i stands in the free space of its scene (detect --visibility)."""
+    return {'see_through': float(d.see_through[i]), 'occluded': float(d.occluded[i]), 'support': float(d.support[i]),
+            'visibility_flags': int(d.visibility_flags[i])}
+
+
 # The optional fields of a detection, one group per stage that adds some: the Decoded attribute that says the stage ran, and the fields
 # it contributes to a record (as_lists: to a legend entry or a JSON row).  A writer names the groups it carries, in its own order.
 FIELD_GROUPS = {
@@ -289,12 +311,13 @@ FIELD_GROUPS = {
     'views': ('view_iou', view_fields),
     'consistency': ('reproj_iou', consistency_fields),
     'floor': ('floor_gap', lambda d, i, as_lists=False: {'floor_gap': float(d.floor_gap[i]), 'floor_flags': int(d.floor_flags[i])}),
+    'visibility': ('see_through', visibility_fields),
 }
-RECORD_GROUPS = ('votes', 'rescore', 'soft', 'views', 'consistency', 'floor')     # the records of `Detector.detect` and the legends of --vis_dir
-ROW_GROUPS = ('consistency', 'rescore', 'soft', 'views', 'floor')              # the rows of --consistency_json
+RECORD_GROUPS = ('votes', 'rescore', 'soft', 'views', 'consistency', 'visibility', 'floor')     # the records of `Detector.detect` and the legends of --vis_dir
+ROW_GROUPS = ('consistency', 'rescore', 'soft', 'views', 'visibility', 'floor')              # the rows of --consistency_json
 # the options of the stages as `Detector` takes them, under the names of the flags (the module docstring describes them)
 STAGE_KEYWORDS = ('nms_iou', 'nms_metric', 'nms_score', 'nms_fuse', 'nms_fuse_iou', 'soft_nms', 'soft_nms_sigma', 'soft_nms_min_prob', 'consistency',
-                  'min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou', 'tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou', 'rescore', 'min_rescore') + FL.FLAGS
+                  'min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou', 'tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou', 'rescore', 'min_rescore') + FL.FLAGS + VS.FLAGS
 
 
 def fields_of(d, i, groups, as_lists=False):
@@ -316,7 +339,8 @@ class Detector:
                  min_reproj_iou=None, min_mask_in_box=None, min_seg_box_iou=None, nms_fuse=False, nms_fuse_iou=None, tta=None, tta_flip=False,
                  tta_vote_iou=None, min_view_iou=None, soft_nms=None, soft_nms_sigma=None, soft_nms_min_prob=None, rescore=None, min_rescore=None,
                  floor=False, snap_floor=None, snap_floor_max=None, max_floor_gap=None, floor_bin=None, floor_range=None, floor_min_share=None,
-                 floor_band=None, floor_max_tilt=None, **keywords):
+                 floor_band=None, floor_max_tilt=None, visibility=False, visibility_cell=None, visibility_margin=None, visibility_min_chord=None,
+                 max_see_through=None, visibility_min_rays=None, **keywords):
         """FLAGS: test_semisup.build_flags(...), or keyword arguments of the same names.  model_path / boxpc_model_path: state dicts
         (.npz) or TensorFlow checkpoint prefixes (default: FLAGS'; neither: the graph's initial weights).  num_points: the cap of a
         frustum's points at extraction (the frustum files': 2048); the network draws FLAGS.num_point of them per batch.  log: a
@@ -326,8 +350,10 @@ class Detector:
         rescore: a rescore.Model or the path of one.  They are checked here, before a model is built, and kept under their names:
         nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou and soft_nms (its nms.SoftOptions) as `suppression` (nms.Suppression)
         holds them -- with soft_nms, nms_iou is None -- thresholds, consistency, tta, tta_flip, tta_vote_iou, min_view_iou, rescore (the
-        Model), min_rescore, and `floor` (floor.Floor: on, snap, snap_max, max_floor_gap and the estimator's FloorOptions)."""
+        Model), min_rescore, `floor` (floor.Floor: on, snap, snap_max, max_floor_gap and the estimator's FloorOptions) and `visibility`
+        (visibility.Visibility: on, max_see_through and the kernels' VisibilityOptions)."""
         self.floor = FL.check_options(floor, snap_floor, snap_floor_max, max_floor_gap, floor_bin, floor_range, floor_min_share, floor_band, floor_max_tilt)
+        self.visibility = VS.check_options(visibility, visibility_cell, visibility_margin, visibility_min_chord, max_see_through, visibility_min_rays)
         self.min_rescore = RS.check_min_rescore(min_rescore)
         if self.min_rescore is not None and rescore is None:
             raise ValueError('--min_rescore rejects by the rescored confidence: it needs --rescore')
@@ -352,13 +378,16 @@ class Detector:
         self.rt = self.ops['graph'].rt
         self.extractor = SD.FrustumExtractor(self.rt, num_points, FLAGS.seed)
         self.floor_estimator = FL.DeviceFloor(self.rt, self.floor.options) if self.floor.on else None
+        self.range_builder = VS.DeviceRange(self.rt, self.visibility.options) if self.visibility.on else None
         self.whitelist = list(type_whitelist)
         self.classes = list(FLAGS.SUNRGBD_SEMI_TEST_CLS) or None
 
     def extract(self, scenes, detections, scene_ids=None, vis=None):
         """One t3d_frustum_extract launch over `scenes`; -> a part for `decode` (device tensors + what the host knows of the kept jobs).
         vis (Vis): the scenes it will draw keep their points on the device.  With the floor stage, t3d_scene_floor follows the launch on
-        the points it left there: part['floor'] = the planes and counts of the part's scenes on the device, the counts on the host, the ids."""
+        the points it left there: part['floor'] = the planes and counts of the part's scenes on the device, the counts on the host, the ids.
+        With the visibility stage, t3d_scene_range follows it alike: part['range'] = the range maps of the part's scenes on the device and,
+        on the host, their grids, calibration rows and counts (visibility.DeviceRange.build)."""
         scene_ids = list(range(len(scenes))) if scene_ids is None else list(scene_ids)
         jobs, meta = [], []
         for s, dets in enumerate(detections):
@@ -368,7 +397,7 @@ class Detector:
                 jobs.append({'scene': s, 'box2d': np.asarray(box2d, np.float64), 'box3d': None, 'key': (scene_ids[s], o, 0), 'choice': None})
                 meta.append(Detection(s, scene_ids[s], name, np.asarray(box2d, np.float64), float(prob)))
         want_scene = vis is not None and vis.taken < vis.max
-        out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene or self.floor.on)
+        out = self.extractor.run(scenes, jobs, on_device=True, keep_scene=want_scene or self.floor.on or self.visibility.on)
         calib = [CS.calib_row(sc['Rtilt'], sc['K'], sc.get('image_wh')) for sc in scenes] if self.consistency else []
         if out is None:
             return dict(out=None, keep=[], counts=[], meta=[], n_scenes=len(scenes), calib=calib)
@@ -378,6 +407,8 @@ class Detector:
         if self.floor.on:
             plane, floor_counts, floor_counts_host = self.floor_estimator.estimate(*self.extractor.last_scene)
             part['floor'] = dict(plane=plane, counts=floor_counts, counts_host=floor_counts_host, ids=scene_ids)
+        if self.visibility.on:
+            part['range'] = self.range_builder.build(*self.extractor.last_scene, scenes)
         if want_scene:
             vis.take(self.rt, part, scenes, scene_ids, self.extractor.last_scene)
         self.extractor.last_scene = None          # (the points go unless Vis took what it draws)
@@ -404,7 +435,10 @@ class Detector:
         classes = [type2class[m.name] for m in meta]
         ds = DeviceFrustumSet.from_device(self.rt, [p['out'] for p in live], [p['keep'] for p in live], [p['counts'] for p in live], classes)
         source = DeviceEvalSource(self.ops['graph'], dataset=ds, seed=FLAGS.seed)
-        nms = con = views = rescore = floor = None
+        nms = con = views = rescore = floor = visibility = None
+        if self.visibility.on:
+            visibility = VS.VisibilityRequest(*self.visibility_rows(parts), options=self.visibility.options,
+                                              max_see_through=self.visibility.max_see_through)
         if self.rescore is not None:
             rescore = RS.RescoreRequest(self.rescore, [m.prob for m in meta], self.min_rescore)
         if self.suppression.on:
@@ -421,7 +455,7 @@ class Detector:
             views = EN.EnsembleRequest(EN.views_of(self.tta, self.tta_flip, FLAGS.seed), self.nms_metric, self.tta_vote_iou, self.min_view_iou)
         res = SI.inference(self.sess, self.ops, None, None, self.B, prefix=FLAGS.pred_prefix, use_boxpc_fit_prob=FLAGS.use_boxpc_fit_prob,
                            source=source, n_batches=(ds.F + self.B - 1) // self.B, decode='device', want_seg=False, nms=nms, consistency=con,
-                           views=views, rescore=rescore, floor=floor)
+                           views=views, rescore=rescore, floor=floor, visibility=visibility)
         self.stages = res.device
         d = res.decoded[slice(0, ds.F)]
         if self.log:
@@ -447,6 +481,27 @@ class Detector:
                 counts.append(torch.tensor([[0, 0, -1, FL.NONE]] * p['n_scenes'], dtype=torch.int32, device=self.rt.device).view(-1, 4))
         return torch.cat(planes), torch.cat(counts), index
 
+    def visibility_rows(self, parts):
+        """The calibration rows [S, 20], grids (dims [S, 2], offsets [S + 1]) and range maps (one int32 tensor on the device) of the parts'
+        scenes, one row per scene of every part in order (a part without a frustum built no map: its scenes have a grid of no cells and
+        so no scene), and per detection the row of its scene -- indexed exactly as the planes of the floor request."""
+        import torch
+        calib, dims, maps, index, n_rows = [], [], [], [], 0
+        for p in parts:
+            index += [n_rows + m.scene for m in p['meta']]
+            n_rows += p['n_scenes']
+            if p.get('range') is not None:
+                calib.append(p['range']['calib'])
+                dims.append(p['range']['dims'])
+                maps.append(p['range']['range'])
+            else:
+                calib.append(np.zeros((p['n_scenes'], 20)))
+                dims.append(np.zeros((p['n_scenes'], 2), np.int32))
+        dims = np.concatenate(dims).reshape(-1, 2)
+        offsets = np.concatenate([[0], np.cumsum(dims[:, 0].astype(np.int64) * dims[:, 1])]).astype(np.int64)
+        range_ = torch.cat(maps) if maps else torch.zeros(0, dtype=torch.int32, device=self.rt.device)
+        return np.concatenate(calib).reshape(-1, 20), dims, offsets, range_, index
+
     def floor_json_rows(self, parts):
         """--floor_json: one row per estimated scene of `parts` (floor.scene_rows)."""
         rows = []
@@ -467,7 +522,8 @@ class Detector:
         A stage that ran adds its fields to the records (FIELD_GROUPS, in the order of RECORD_GROUPS; the module docstring says what they
         mean): nms_fuse 'votes', the number of suppressed boxes that voted (0: the box is what the decode wrote); rescore
         'rescore_prob'; soft_nms 'soft_prob' and 'decays'; tta 'view_iou', 'view_min_iou', 'views_voted' and 'anchor_view'; consistency
-        'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou' and 'flags'; floor 'floor_gap' and 'floor_flags'.  'prob' stays the 2-D detector's.  'label' and
+        'reproj_iou', 'reproj_rect' (4,), 'mask_in_box', 'seg_box_iou' and 'flags'; visibility 'see_through', 'occluded', 'support' and 'visibility_flags'; floor 'floor_gap' and
+        'floor_flags'.  'prob' stays the 2-D detector's.  'label' and
         'corners' are the box after every stage that ran: what t3d_detect_ensemble made of the views, snap_floor of that, and nms_fuse of that; 'score'
         and the consistency measures stay those of view 0's unfused box.  A detection that a threshold rejected, or whose confidence
         Soft-NMS took below soft_nms_min_prob, has no entry.  With consistency a scene may carry 'image_wh' = (W, H), to which the
@@ -522,6 +578,8 @@ class Detector:
             raise ValueError('a sweep starts from the plain run: the detector has a rescoring model')
         if self.floor.on:
             raise ValueError('a sweep starts from the plain run: the detector has the floor stage')
+        if self.visibility.on:
+            raise ValueError('a sweep starts from the plain run: the detector has the visibility stage')
         if grid.consistency and not self.consistency:
             raise ValueError('the grid sweeps a min_* threshold: the detector needs consistency=True')
         meta, d = self.decode_all(parts)
@@ -605,6 +663,7 @@ def parser():
     RS.add_fit_arguments(p)
     FL.add_arguments(p)
     p.add_argument('--floor_json', default=None, help='write one row per scene with its floor plane, the share of its points on it, their rms and the flags here')
+    VS.add_arguments(p)
     return p
 
 
@@ -620,7 +679,7 @@ def sweep_options(args):
     single += ['soft_nms'] if args.soft_nms is not None else []      # (the scores differ per configuration: ranks cannot be shared)
     single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
     single += [f for f in ('rescore', 'min_rescore', 'rescore_fit') if getattr(args, f) is not None]
-    single += [f for f in FL.FLAGS + ('floor_json',) if getattr(args, f) not in (None, False)]
+    single += [f for f in FL.FLAGS + ('floor_json',) + VS.FLAGS if getattr(args, f) not in (None, False)]
     if single:
         raise ValueError('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
     if args.vis_dir or args.consistency_json:
@@ -678,12 +737,13 @@ def main(argv=None, rt=None, log=print):
         if fit is not None:
             other = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'official_eval') if getattr(args, f)]
             other += [f for f in ('nms_fuse_iou', 'soft_nms', 'min_view_iou', 'vis_dir', 'consistency_json') if getattr(args, f) is not None]
-            other += [f for f in FL.FLAGS + ('floor_json',) if getattr(args, f) not in (None, False)]
+            other += [f for f in FL.FLAGS + ('floor_json',) + VS.FLAGS if getattr(args, f) not in (None, False)]
             if other:
                 raise ValueError('--rescore_fit starts from the plain run, as --sweep does: it does not go with %s' % ' '.join('--' + f for f in other))
         floor = FL.check_options(**{k: getattr(args, k) for k in FL.FLAGS})
         if args.floor_json and not floor.on:
             raise ValueError('--floor_json writes the floor planes: it needs --floor, --snap_floor or --max_floor_gap')
+        visibility = VS.check_options(**{k: getattr(args, k) for k in VS.FLAGS})
         if (args.vis_gt or args.vis_suppressed) and not args.vis_dir:
             raise ValueError('--vis_gt / --vis_suppressed need --vis_dir')
         consistency = args.consistency or any(getattr(args, t) is not None for t in CS.THRESHOLDS) or (grid is not None and grid.consistency)
@@ -707,7 +767,7 @@ def main(argv=None, rt=None, log=print):
     dataset = SD.sunrgbd_object(args.dataset_dir, 'training')
     pictures = None if vis is None else (lambda idx: scene_pictures(dataset, idx, args.vis_gt, args.type_whitelist) if vis.taken < vis.max else {})
     parts = [det.extract(scenes, [per_scene[idx] for idx in batch], batch, vis=vis)
-             for batch, scenes in scene_batches(dataset, ids, image_wh=CS.image_size if consistency else None, pictures=pictures)]
+             for batch, scenes in scene_batches(dataset, ids, image_wh=CS.image_size if consistency or visibility.on else None, pictures=pictures)]
     if fit is not None:
         return RS.fit_parts(det, parts, args.dataset_dir, args.idx_path, args.test_on, seed=FLAGS.seed, log=log, **fit)
     if grid is not None:

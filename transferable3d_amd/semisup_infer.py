@@ -37,7 +37,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from transferable3d_amd import abi, nms as NMS, test_semisup as TS       # noqa: E402
 from transferable3d_amd.abi import fptr, iptr                            # noqa: E402
-from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, visibility as VS      # noqa: E402
 from transferable3d_amd.consistency import ConsistencyRequest, DeviceConsistency      # noqa: E402
 from transferable3d_amd.constants import type2class                     # noqa: E402
 
@@ -122,11 +122,15 @@ class Decoded:
     With a floor request (floor.FloorRequest) floor_gap [n] is how far the floor of the detection's scene lies below the bottom of its
     box (positive: the box floats; negative: it sinks; NaN: no floor is known) and floor_flags [n] the bits t3d_detect_floor set, both
     measured on the box the stage read: the ensemble's where views ran.  Where the request snaps, label and corners hold what the stage
-    wrote (and a fusion's raw_label / raw_corners with them) and unsnapped_label / unsnapped_corners what it read; None without."""
+    wrote (and a fusion's raw_label / raw_corners with them) and unsnapped_label / unsnapped_corners what it read; None without.
+    With a visibility request (visibility.VisibilityRequest) see_through, occluded and support [n] are what t3d_detect_visibility
+    measured of the box the stage read (the floor stage's where it snapped), visibility_flags [n] the bits it set and visibility_profile
+    [n, 6] the counts behind them (abi.VIS_PROFILE: rays, unknown, front, inside, through, graze); None without."""
     FIELDS = ('score', 'mask_count', 'heading_cls', 'size_cls', 'center', 'heading_res', 'size_res', 'label', 'corners')
     OPTIONAL = ('keep', 'suppressed_by', 'reproj_rect', 'reproj_iou', 'n_mask', 'n_box', 'n_both', 'flags', 'mask_in_box', 'seg_box_iou', 'accept',
                 'raw_label', 'raw_corners', 'n_votes', 'view_label', 'view_score', 'view_iou', 'view_min_iou', 'anchor_view', 'n_views_voted',
-                'soft_prob', 'n_decays', 'rescore_prob', 'floor_gap', 'floor_flags', 'unsnapped_label', 'unsnapped_corners')
+                'soft_prob', 'n_decays', 'rescore_prob', 'floor_gap', 'floor_flags', 'unsnapped_label', 'unsnapped_corners', 'see_through', 'occluded',
+                'support', 'visibility_flags', 'visibility_profile')
     VIEW_MAJOR = ('view_label', 'view_score')              # [V, n, ...]: the detection is the second axis
 
     def __init__(self, **fields):
@@ -207,20 +211,22 @@ class DeviceDecode:
 class DeviceStages:
     """The stages behind t3d_detect_decode of one `inference(decode='device')` run over `n` frustums, the first `total` of them real, and
     the one place that says in which order they run.  Per batch (`launch`): the decode of every view, then -- behind view 0's -- the
-    consistency measures.  After the last batch (`finish`): the ensemble of the views, the floor stage, the rescoring, the accept rows, the
+    consistency measures.  After the last batch (`finish`): the ensemble of the views, the floor stage, the visibility stage, the rescoring, the accept rows, the
     suppression, the box voting, and the one fetch of everything as a Decoded.
 
     label [n, 7], corners [n, 24]: the boxes on the device as the stages so far left them -- a stage that rewrites boxes (the ensemble,
     the floor stage where it snaps, the box voting) reads them and puts its output in their place, so neither a later stage nor a caller asks which stage ran; score [n]:
     where view 0's decode wrote it.  accept [n] bool (None: nothing was asked that could reject): the detections that miss no threshold
     of the consistency request, do not lie below views.min_view_iou or rescore.min_rescore and whose |floor_gap| does not exceed
-    floor.max_floor_gap; below: how many of the real detections
+    floor.max_floor_gap and whose see_through does not exceed visibility.max_see_through; below: how many of the real detections
     lie below each of these thresholds (`report`).  rescore_out (rescore.DeviceRescore, None without a request): its out32 [n] is the
     rescored confidence on the device, which `nms` ranks by in the place of the request's `prob`."""
 
-    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None, rescore=None, floor=None):
+    def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None, rescore=None, floor=None, visibility=None):
         if floor is not None and len(floor) != total:
             raise ValueError('%d detections in the floor request, %d decoded' % (len(floor), total))
+        if visibility is not None and len(visibility) != total:
+            raise ValueError('%d detections in the visibility request, %d decoded' % (len(visibility), total))
         if nms is not None and len(nms.image_ids) != total:
             raise ValueError('%d image ids for %d detections' % (len(nms.image_ids), total))
         if consistency is not None and len(consistency) != total:
@@ -236,6 +242,7 @@ class DeviceStages:
         self.rt, self.n, self.total, self.nms_request, self.views = rt, n, total, nms, views
         self.rescore_request, self.rescore_out = rescore, None
         self.floor_request, self.floor_out, self.floor_in, self.floor_host = floor, None, None, None
+        self.visibility_request, self.visibility_out, self.visibility_host = visibility, None, None
         self.decodes = [DeviceDecode(rt, n, num_point, want_seg=want_seg and v == 0) for v in range(1 if views is None else len(views))]
         self.consistency = None if consistency is None else DeviceConsistency(rt, n, num_point, consistency)
         self.rot_angle = None if views is None else rt.zeros(n)      # every batch's angles: the ensemble mirrors back with them
@@ -260,6 +267,8 @@ class DeviceStages:
             self.ensemble()
         if self.floor_request is not None:
             self.floor()
+        if self.visibility_request is not None:
+            self.visibility()
         if self.rescore_request is not None:
             self.rescore()
         self.accept_rows()
@@ -284,6 +293,11 @@ class DeviceStages:
             self.floor_in = (self.label, self.corners)
             self.label, self.corners = out
 
+    def visibility(self):
+        """t3d_detect_visibility on the current boxes: every box against the range map of its scene.  It moves no box."""
+        self.visibility_out = VS.DeviceVisibilityStage(self.rt)
+        self.visibility_out.run(self.label, self.corners, self.visibility_request, self.n)
+
     def rescore(self):
         """t3d_rescore_features on the buffers the stages so far wrote -- the 2-D confidences, view 0's decoded score, the consistency
         kernel's rectangle and counts, the ensemble's agreement -- and t3d_rescore_apply of the request's model over the real rows."""
@@ -300,7 +314,8 @@ class DeviceStages:
     def accept_rows(self):
         """The one accept rule: a detection is rejected where it misses a threshold of the consistency request, its view_iou lies below
         views.min_view_iou, its rescored confidence below rescore.min_rescore, or its floor is known and |floor_gap|, measured before any
-        snapping, exceeds floor.max_floor_gap.  Copies the consistency outputs, the agreement and the
+        snapping, exceeds floor.max_floor_gap, or it was measured on visibility.options.min_rays rays and its see_through exceeds
+        visibility.max_see_through.  Copies the consistency outputs, the agreement and the
         rescored confidence back -- the small copies in front of the group building."""
         total, masks = self.total, []
         if self.consistency is not None:
@@ -321,6 +336,13 @@ class DeviceStages:
             if self.floor_request.max_floor_gap is not None:
                 bad = FL.rejected(*self.floor_host, self.floor_request.max_floor_gap)
                 self.below['floor_gap'] = int(bad[:total].sum())
+                masks.append(~bad)
+        if self.visibility_out is not None:
+            req = self.visibility_request
+            h = self.visibility_host = self.visibility_out.fetch(self.n)
+            if req.max_see_through is not None:
+                bad = VS.rejected(h['measures'], h['profile'], h['flags'], req.max_see_through, req.options.min_rays)
+                self.below['see_through'] = int(bad[:total].sum())
                 masks.append(~bad)
         if masks:
             self.accept = np.logical_and.reduce(masks)
@@ -373,6 +395,10 @@ class DeviceStages:
             if self.floor_in is not None:
                 d.unsnapped_label, d.unsnapped_corners = d.label, d.corners
                 d.label, d.corners = host(self.floor_out.label_out), host(self.floor_out.corners_out).reshape(n, 8, 3)
+        if self.visibility_out is not None:
+            h = self.visibility_host
+            d.see_through, d.occluded, d.support = (h['measures'][:, k].copy() for k in range(3))
+            d.visibility_flags, d.visibility_profile = h['flags'], h['profile']
         if self.fuse_out is not None:
             d.raw_label, d.raw_corners = d.label, d.corners
             d.label, d.corners = host(self.label), host(self.corners).reshape(n, 8, 3)
@@ -405,7 +431,7 @@ def decode_sources(ops, prefix, use_boxpc_fit_prob=False):
 
 
 def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_prob=False, source=None, n_batches=None, oracle_mask=None,
-              decode='host', want_seg=True, nms=None, consistency=None, views=None, rescore=None, floor=None):
+              decode='host', want_seg=True, nms=None, consistency=None, views=None, rescore=None, floor=None, visibility=None):
     """test_semisup.inference with `decode`: 'host' is that function; 'device' runs t3d_detect_decode behind every batch's graph and
     returns the same 7-tuple (InferenceResult; the records as `.decoded`; the mask entry is None unless `want_seg`).  The rows of a
     padded last batch are zeros.  nms (NmsRequest, decode='device' only): t3d_detect_nms runs on the decoded corners before anything is
@@ -426,6 +452,9 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     floor (floor.FloorRequest, decode='device' only): behind the ensemble, t3d_detect_floor measures every box against the floor plane of
     its scene (`.decoded.floor_gap` / `.floor_flags`), stands it on the floor where the request snaps, and a detection whose |floor_gap|
     exceeds floor.max_floor_gap is rejected like one below a consistency threshold.
+    visibility (visibility.VisibilityRequest, decode='device' only): behind the floor stage, t3d_detect_visibility holds every box against
+    the range map of its scene (`.decoded.see_through` / `.occluded` / `.support` / `.visibility_flags`), and a detection whose
+    see_through exceeds visibility.max_see_through on enough rays is rejected like one below a consistency threshold.
     The stages and their order are DeviceStages'; this function loads and runs the graph and says when a view of a batch is ready."""
     if decode == 'host' and nms is not None:
         raise ValueError("nms runs on the device-decoded boxes: decode='device'")
@@ -435,6 +464,8 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
         raise ValueError("the rescoring reads the device-decoded records: decode='device'")
     if decode == 'host' and floor is not None:
         raise ValueError("the floor stage reads the device-decoded boxes: decode='device'")
+    if decode == 'host' and visibility is not None:
+        raise ValueError("the visibility stage reads the device-decoded boxes: decode='device'")
     if views is not None and (decode != 'device' or source is None):
         raise ValueError("views are further draws of a device-resident source: decode='device' and a source")
     if decode == 'host':
@@ -452,7 +483,7 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
     xyz = sess.g.inputs.pc if consistency is not None else None      # [B * N, ld] where the network read the batch
     stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views, rescore=rescore,
-                          floor=floor)
+                          floor=floor, visibility=visibility)
     sources = [source] + ([] if views is None else [source.view(seed, flip) for seed, flip in views.views[1:]])
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
@@ -493,7 +524,7 @@ def write_detection_results(result_dir, test_classes, predictions, class_names):
 def report(log, stages, d):
     """What a run says of its stages, one line each through `log` and in their order: `consistency:` (how many detections the accept rule
     kept, how many lie below each threshold), `tta:` (the views) and `nms ...` (how many of the accepted detections were kept and, with
-    a fusion, how many kept boxes changed, from how many votes); `floor:` (floor.log_line) follows `tta:`.  stages: the run's DeviceStages; d: the records of its real detections."""
+    a fusion, how many kept boxes changed, from how many votes); `floor:` (floor.log_line) follows `tta:` and `visibility:` (visibility.log_line) follows that.  stages: the run's DeviceStages; d: the records of its real detections."""
     if d.accept is not None:
         con = stages.consistency
         extra = [('view_iou', stages.views.min_view_iou, stages.below['view_iou'])] if 'view_iou' in stages.below else []
@@ -501,11 +532,16 @@ def report(log, stages, d):
             extra.append(('rescore_prob', stages.rescore_request.min_rescore, stages.below['rescore_prob']))
         if 'floor_gap' in stages.below:
             extra.append('|floor_gap| > %g: %d' % (stages.floor_request.max_floor_gap, stages.below['floor_gap']))
+        if 'see_through' in stages.below:
+            extra.append('see_through > %g: %d' % (stages.visibility_request.max_see_through, stages.below['see_through']))
         log(CS.log_line(d.accept, stages.below, con.thresholds if con is not None else (None, None, None), extra))
     if stages.views is not None:
         log(EN.log_line(stages.views, d))
     if stages.floor_request is not None:
         log(FL.log_line(stages.floor_request, d.floor_gap, d.floor_flags))
+    if stages.visibility_request is not None:
+        host = dict(measures=np.stack([d.see_through, d.occluded, d.support], 1), profile=d.visibility_profile, flags=d.visibility_flags)
+        log(VS.log_line(stages.visibility_request, host))
     req = stages.nms_request
     if req is not None:
         kept, offered = (d.keep, len(d)) if d.accept is None else (d.keep & d.accept, int(d.accept.sum()))
