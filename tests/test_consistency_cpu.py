@@ -129,7 +129,7 @@ def test_autolabel_counts_on_injected_records():
                                                                             **dict(zip(CS.MEASURES, v)))
     records = [rec('table', accepted=True), rec('table', v=(0.1, 0.9, 0.9)), rec('table', v=(0.1, 0.2, 0.9)), rec('table', detected=False),
                rec('sofa', accepted=True), rec('sofa', v=(0.9, 0.9, float('nan')))]
-    got = AL.count(records, ['table', 'sofa', 'desk'], (0.5, 0.5, None))
+    got = AL.count(records, ['table', 'sofa', 'desk'], SI.active_tests(CS.ConsistencyRequest(np.zeros((0, 4)), np.zeros((0, 20)), [], 0.5, 0.5, None)))
     assert dict(got['table']) == {'offered': 4, 'too_few_points': 1, 'accepted': 1, 'rejected': 2,
                                   'rejected_by': {'min_reproj_iou': 2, 'min_mask_in_box': 1}}
     assert got['sofa']['accepted'] == 1 and got['sofa']['rejected'] == 1 and got['desk']['offered'] == 0

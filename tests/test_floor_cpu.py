@@ -132,9 +132,10 @@ def test_autolabel_takes_the_flags(capsys):
     with pytest.raises(SystemExit):
         AL.parse(base + ['--floor_json', 'f.json'] + DC.MODEL_FLAGS)
     assert 'needs --floor' in capsys.readouterr().err
-    records = [dict({'class': 'chair', 'detected': True, 'accepted': g <= 0.2}, floor_gap=g) for g in (0.1, -0.3, float('nan'), 0.25)]
-    c = AL.count(records, ['chair'], (None, None, None), max_floor_gap=0.2)['chair']
-    assert c['rejected_by'] == {'max_floor_gap': 2} and AL.floor_ok(records[2], 0.2)
+    records = [dict({'class': 'chair', 'detected': True, 'accepted': g <= 0.2}, floor_gap=g, floor_flags=0) for g in (0.1, -0.3, float('nan'), 0.25)]
+    tests = SI.active_tests(FL.check_options(max_floor_gap=0.2))
+    c = AL.count(records, ['chair'], tests)['chair']
+    assert c['rejected_by'] == {'max_floor_gap': 2} and AL.rejected_by(tests, records)['max_floor_gap'].tolist() == [False, True, False, True]
 
 
 def test_semisup_infer_and_evaluate_do_not_take_the_flags(capsys):

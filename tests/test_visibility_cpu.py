@@ -150,8 +150,9 @@ def test_autolabel_takes_the_flags(capsys):
     assert 'needs --max_see_through' in capsys.readouterr().err
     rec = lambda see, n, fl=0: {'class': 'chair', 'detected': True, 'accepted': True, 'see_through': see, 'visibility_evidence': n, 'visibility_flags': fl}
     records = [rec(0.9, 20), rec(0.9, 7), rec(0.4, 20), rec(1.0, 0, abi.VIS_NO_SCENE), rec(0.51, 8)]
-    c = AL.count(records, ['chair'], (None, None, None), max_see_through=0.5, min_rays=8)['chair']
-    assert c['rejected_by'] == {'max_see_through': 2} and AL.see_through_ok(records[1], 0.5, 8) and AL.see_through_ok(records[3], 0.5, 8)
+    tests = SI.active_tests(VS.check_options(max_see_through=0.5, visibility_min_rays=8))
+    c = AL.count(records, ['chair'], tests)['chair']
+    assert c['rejected_by'] == {'max_see_through': 2} and AL.rejected_by(tests, records)['max_see_through'].tolist() == [True, False, False, False, True]
 
 
 def test_semisup_infer_and_evaluate_do_not_take_the_flags(capsys):

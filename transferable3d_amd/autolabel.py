@@ -53,7 +53,7 @@ import numpy as np
 
 if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, sunrgbd_data as SD, test_semisup as TS, visibility as VS      # noqa: E402
+from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, semisup_infer as SI, sunrgbd_data as SD, test_semisup as TS, visibility as VS      # noqa: E402
 
 LINE = '%s %d %d %d %d %f %f %f %f %f %f %f %f %f %f %f %f'
 IOU_HIT = 0.25
@@ -74,87 +74,52 @@ def label_corners(obj):
     return get_3d_box((2.0 * obj.l, 2.0 * obj.w, 2.0 * obj.h), obj.heading_angle, (obj.centroid[0], -obj.centroid[2], obj.centroid[1]))
 
 
-# the tests beside the consistency thresholds: (flag, the record's measure)
-EXTRA_TESTS = (('min_view_iou', 'view_iou'), ('min_rescore', 'rescore_prob'))
+def rejected_by(tests, rows):
+    """{flag: [len(rows)] bool} of the active tests (semisup_infer.active_tests), in their order: which of the records `rows` each
+    test alone rejects -- the predicates of semisup_infer.TESTS on arrays made of the records' fields."""
+    return collections.OrderedDict((t.flag, t.rejected(*(np.array([r[k] for r in rows]) for k in t.fields), limit, **parameters))
+                                   for t, limit, parameters in tests)
 
 
-def floor_ok(r, max_floor_gap):
-    """Whether --max_floor_gap alone accepts the record: its floor is unknown (the gap is NaN) or |floor_gap| does not exceed it."""
-    return not abs(r['floor_gap']) > max_floor_gap
-
-
-def see_through_ok(r, max_see_through, min_rays):
-    """Whether --max_see_through alone accepts the record: it was not measured, through + inside ('visibility_evidence') lies below
-    min_rays, or see_through does not exceed it."""
-    return bool(r['visibility_flags'] & VS.UNMEASURED) or r['visibility_evidence'] < min_rays or not r['see_through'] > max_see_through
-
-
-def new_counts(thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None, max_see_through=None):
+def new_counts(tests):
     c = collections.OrderedDict(offered=0, too_few_points=0, accepted=0, rejected=0)
-    c['rejected_by'] = collections.OrderedDict((name, 0) for name, t in zip(CS.THRESHOLDS, thresholds) if t is not None)
-    for (flag, _), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
-        if t is not None:
-            c['rejected_by'][flag] = 0
-    if max_floor_gap is not None:
-        c['rejected_by']['max_floor_gap'] = 0
-    if max_see_through is not None:
-        c['rejected_by']['max_see_through'] = 0
+    c['rejected_by'] = collections.OrderedDict((t.flag, 0) for t, _, _ in tests)
     return c
 
 
-def count(records, classes, thresholds, min_view_iou=None, min_rescore=None, max_floor_gap=None, max_see_through=None, min_rays=0):
-    """records: [{'class', 'detected' (False: its frustum held too few points), 'accepted', 'reproj_iou', 'mask_in_box', 'seg_box_iou'}] ->
-    {class: offered, too_few_points, accepted, rejected, rejected_by {threshold: n}} (a box may fail several tests).  min_view_iou: the
-    records carry 'view_iou' and the boxes below it are counted too; min_rescore: the same for 'rescore_prob'; max_floor_gap: the same for the boxes whose |'floor_gap'| exceeds it;
-    max_see_through (with min_rays): the same for the boxes `see_through_ok` does not accept."""
-    out = collections.OrderedDict((c, new_counts(thresholds, min_view_iou, min_rescore, max_floor_gap, max_see_through)) for c in classes)
+def count(records, classes, tests):
+    """records: [{'class', 'detected' (False: its frustum held too few points), 'accepted', and the fields the tests read}]; tests: the
+    active tests (semisup_infer.active_tests) -> {class: offered, too_few_points, accepted, rejected, rejected_by {flag: n}} (a box may
+    fail several tests)."""
+    out = collections.OrderedDict((c, new_counts(tests)) for c in classes)
+    rows = [r for r in records if r['detected']]
     for r in records:
-        c = out[r['class']]
-        c['offered'] += 1
-        if not r['detected']:
-            c['too_few_points'] += 1
-            continue
-        c['accepted' if r['accepted'] else 'rejected'] += 1
-        for name, measure, t in zip(CS.THRESHOLDS, CS.MEASURES, thresholds):
-            if t is not None and not r[measure] >= t:
-                c['rejected_by'][name] += 1
-        for (flag, measure), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
-            if t is not None and not r[measure] >= t:
-                c['rejected_by'][flag] += 1
-        if max_floor_gap is not None and not floor_ok(r, max_floor_gap):
-            c['rejected_by']['max_floor_gap'] += 1
-        if max_see_through is not None and not see_through_ok(r, max_see_through, min_rays):
-            c['rejected_by']['max_see_through'] += 1
+        out[r['class']]['offered'] += 1
+        out[r['class']]['too_few_points'] += not r['detected']
+    for r in rows:
+        out[r['class']]['accepted' if r['accepted'] else 'rejected'] += 1
+    for flag, bad in rejected_by(tests, rows).items():
+        for r in np.array(rows, object)[bad]:
+            out[r['class']]['rejected_by'][flag] += 1
     return out
 
 
-def score(records, classes, rt, min_view_iou=None, min_rescore=None, max_floor_gap=None, max_see_through=None, min_rays=0):
+def score(records, classes, rt, tests):
     """--score_against_labels: per class, for the accepted and the rejected boxes, how many, their mean 3-D IoU with the label's own box
-    and the share at IoU >= 0.25.  min_view_iou: also under 'min_view_iou' for the boxes that test alone accepts and rejects; min_rescore: the
-    same under 'min_rescore'; max_floor_gap: the same under 'max_floor_gap'; max_see_through (with min_rays): the same under 'max_see_through'."""
+    and the share at IoU >= 0.25; and the same under its flag for the boxes each of the active tests (semisup_infer.active_tests)
+    beside the consistency thresholds alone accepts and rejects."""
     from transferable3d_amd.eval_det import box3d_iou_batch
     rows = [r for r in records if r['detected']]
-    iou = box3d_iou_batch(np.stack([r['corners'] for r in rows]), np.stack([r['label_corners'] for r in rows]), rt)[0] if rows else []
-    out = collections.OrderedDict()
+    iou = np.asarray(box3d_iou_batch(np.stack([r['corners'] for r in rows]), np.stack([r['label_corners'] for r in rows]), rt)[0] if rows else [], np.float64)
+    names = np.array([r['class'] for r in rows], object)
+    kinds = collections.OrderedDict(accepted=np.array([r['accepted'] for r in rows], bool))
+    kinds.update((flag, ~bad) for flag, bad in rejected_by([t for t in tests if t[0] not in CS.TESTS], rows).items())
     stats = lambda v: {'n': len(v), 'mean_iou3d': float(v.mean()) if len(v) else None,
                        'share_iou_ge_0.25': float((v >= IOU_HIT).mean()) if len(v) else None}
+    out = collections.OrderedDict()
     for c in classes:
-        out[c] = {}
-        for kind in ('accepted', 'rejected'):
-            out[c][kind] = stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c and r['accepted'] == (kind == 'accepted')]))
-        for (flag, measure), t in zip(EXTRA_TESTS, (min_view_iou, min_rescore)):
-            if t is not None:
-                out[c][flag] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
-                                                      and bool(r[measure] >= t) == (kind == 'accepted')]))
-                                for kind in ('accepted', 'rejected')}
-        if max_floor_gap is not None:
-            out[c]['max_floor_gap'] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
-                                                             and floor_ok(r, max_floor_gap) == (kind == 'accepted')]))
-                                       for kind in ('accepted', 'rejected')}
-        if max_see_through is not None:
-            out[c]['max_see_through'] = {kind: stats(np.array([float(i) for r, i in zip(rows, iou) if r['class'] == c
-                                                               and see_through_ok(r, max_see_through, min_rays) == (kind == 'accepted')]))
-                                         for kind in ('accepted', 'rejected')}
+        by = {key: {kind: stats(iou[(names == c) & (ok == (kind == 'accepted'))]) for kind in ('accepted', 'rejected')} for key, ok in kinds.items()}
+        out[c] = dict(by.pop('accepted'), **by)          # 'accepted' and 'rejected' of the run itself, then of each test under its flag
     return out
 
 
@@ -176,8 +141,8 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
         with open(dataset._path('label_dimension', idx, 'txt')) as fh:
             lines[idx] = [line.rstrip() for line in fh if line.strip()]
 
-    visibility = getattr(detector, 'visibility', None)
-    image_wh = (lambda path: CS.image_size(path) if os.path.exists(path) else None) if detector.consistency or (visibility is not None and visibility.on) else None
+    floor, visibility = detector.floor, detector.visibility
+    image_wh = (lambda path: CS.image_size(path) if os.path.exists(path) else None) if detector.consistency or visibility.on else None
     parts, offered = [], []
     for batch, scenes in scene_batches(dataset, ids, batch_scenes, workers, image_wh=image_wh, also=read_lines):
         dets = []
@@ -207,32 +172,25 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
                 if d.floor_gap is not None:
                     r.update(floor_gap=float(d.floor_gap[i]), floor_flags=int(d.floor_flags[i]))
                 if d.see_through is not None:
-                    r.update(visibility_fields(d, i), visibility_evidence=int(d.visibility_profile[i][VS.THROUGH] + d.visibility_profile[i][VS.INSIDE]))
+                    r.update(visibility_fields(d, i), visibility_evidence=int(VS.evidence(d.visibility_profile[i])))
                 if score_against_labels:
                     r['label_corners'] = label_corners(o)
                 i += 1
             records.append(r)
     assert i == len(meta), 'a detection matches no offered object'
-    thresholds = detector.thresholds if detector.consistency else (None, None, None)
-    min_view_iou = getattr(detector, 'min_view_iou', None)
-    min_rescore = getattr(detector, 'min_rescore', None)
-    floor = getattr(detector, 'floor', None)
-    max_floor_gap = floor.max_floor_gap if floor is not None and floor.on else None
-    max_see_through = visibility.max_see_through if visibility is not None and visibility.on else None
-    min_rays = visibility.options.min_rays if visibility is not None else 0
-    summary = collections.OrderedDict(classes=count(records, classes, thresholds, min_view_iou, min_rescore, max_floor_gap, max_see_through, min_rays),
-                                      thresholds=dict(zip(CS.THRESHOLDS, thresholds)), scenes=len(ids))
-    if getattr(detector, 'tta', None) is not None:
-        summary['tta'] = dict(views=detector.tta, flip=detector.tta_flip, vote_iou=detector.tta_vote_iou, min_view_iou=min_view_iou)
-    if getattr(detector, 'rescore', None) is not None:
-        summary['rescore'] = dict(features=detector.rescore.features, min_rescore=min_rescore)
-    if floor is not None and floor.on:
-        summary['floor'] = dict(snap=floor.snap, snap_max=floor.snap_max, max_floor_gap=max_floor_gap)
-    if visibility is not None and visibility.on:
+    tests = SI.active_tests(detector, floor, visibility)
+    summary = collections.OrderedDict(classes=count(records, classes, tests), thresholds=dict(zip(CS.THRESHOLDS, detector.thresholds)), scenes=len(ids))
+    if detector.tta is not None:
+        summary['tta'] = dict(views=detector.tta, flip=detector.tta_flip, vote_iou=detector.tta_vote_iou, min_view_iou=detector.min_view_iou)
+    if detector.rescore is not None:
+        summary['rescore'] = dict(features=detector.rescore.features, min_rescore=detector.min_rescore)
+    if floor.on:
+        summary['floor'] = dict(snap=floor.snap, snap_max=floor.snap_max, max_floor_gap=floor.max_floor_gap)
+    if visibility.on:
         o = visibility.options
-        summary['visibility'] = dict(cell=o.cell, margin=o.margin, min_chord=o.min_chord, max_see_through=max_see_through, min_rays=o.min_rays)
+        summary['visibility'] = dict(cell=o.cell, margin=o.margin, min_chord=o.min_chord, max_see_through=visibility.max_see_through, min_rays=o.min_rays)
     if score_against_labels:
-        summary['score_against_labels'] = score(records, classes, detector.rt, min_view_iou, min_rescore, max_floor_gap, max_see_through, min_rays)
+        summary['score_against_labels'] = score(records, classes, detector.rt, tests)
     written = write_labels(out_dir, ids, lines, records, classes, keep_other_classes)
     summary['scenes_written'] = len(written)
     if link_inputs:
@@ -245,7 +203,7 @@ def run(detector, dataset_dir, ids, classes, out_dir, keep_other_classes=False, 
             ''.join(' (%s: %d)' % kv for kv in n['rejected_by'].items())))
         if score_against_labels:
             by = summary['score_against_labels'][c]
-            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag in [f for f, _ in EXTRA_TESTS] + ['max_floor_gap', 'max_see_through'] for k, v in by.get(flag, {}).items()]:
+            for kind, v in [(k, by[k]) for k in ('accepted', 'rejected')] + [('%s by --%s' % (k, flag), v) for flag in list(by)[2:] for k, v in by[flag].items()]:
                 if v['n']:
                     log('  %s %d: mean 3-D IoU with the label %.3f, at IoU >= %g %.1f %%' % (kind, v['n'], v['mean_iou3d'], IOU_HIT,
                                                                                             100.0 * v['share_iou_ge_0.25']))

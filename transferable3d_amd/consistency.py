@@ -9,9 +9,11 @@ finished detections, behind t3d_detect_decode and on the buffers it wrote:
     mask_in_box   n_both / n_mask: the share of the segmented points that lie inside the 3-D box
     seg_box_iou   n_both / (n_mask + n_box - n_both): IoU of the segmented points with the frustum's points inside the box
 
-The last two are computed here, on the host, from the kernel's integer counts.  Nothing runs this unless it is asked for (detect
+The last two are computed here, on the host, from the kernel's integer counts.  `Test` is the form in which this module and the later
+stages (ensemble, rescore, floor, visibility) each state the tests that reject a detection by their measure; `log_line` prints them.  Nothing runs this unless it is asked for (detect
 --consistency / --min_*, autolabel).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -23,6 +25,20 @@ from .abi import dptr, fptr, iptr
 BAD_PROJECTION, EMPTY_MASK, NO_CALIB = abi.CONSISTENCY_BAD_PROJECTION, abi.CONSISTENCY_EMPTY_MASK, abi.CONSISTENCY_NO_CALIB
 THRESHOLDS = ('min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou')
 MEASURES = ('reproj_iou', 'mask_in_box', 'seg_box_iou')
+
+# A test that can reject a detection, stated once beside the stage that takes its measure: the flag that carries its limit; the fields
+# it reads (attributes of semisup_infer.Decoded and keys of autolabel's records; visibility_evidence is a record's name for through +
+# inside of Decoded.visibility_profile); its fragment of the `consistency:` line; rejected(*fields, limit, **parameters) -> [n] bool; and
+# the parameters it takes besides the limit, attributes of the options its stage was given.  semisup_infer.TESTS names them all, in order.
+Test = collections.namedtuple('Test', 'flag fields fragment rejected parameters')
+
+
+def lies_below(values, limit):
+    """[n] bool: the value lies below the limit.  A NaN fails the `>=`, so it lies below every limit."""
+    return ~(np.asarray(values) >= limit)
+
+
+TESTS = tuple(Test(flag, (measure,), measure + ' < %g', lies_below, ()) for flag, measure in zip(THRESHOLDS, MEASURES))
 
 
 def calib_row(Rtilt, K, image_wh=None):
@@ -79,6 +95,7 @@ class ConsistencyRequest:
         if len(self.calib_index) != len(self.box2d):
             raise ValueError('%d 2-D boxes, %d calibration indices' % (len(self.box2d), len(self.calib_index)))
         self.thresholds = check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
+        self.min_reproj_iou, self.min_mask_in_box, self.min_seg_box_iou = self.thresholds
 
     def __len__(self):
         return len(self.box2d)
@@ -87,20 +104,19 @@ class ConsistencyRequest:
 def accept_of(reproj_iou, mask_in_box, seg_box_iou, thresholds):
     """-> (accept [n] bool, {threshold name: how many detections lie below it}).  A detection below any threshold given is rejected."""
     accept = np.ones(len(reproj_iou), bool)
-    below = {}
-    for name, v, t in zip(THRESHOLDS, (reproj_iou, mask_in_box, seg_box_iou), thresholds):
+    counts = {}
+    for test, v, t in zip(TESTS, (reproj_iou, mask_in_box, seg_box_iou), thresholds):
         if t is not None:
-            bad = ~(np.asarray(v) >= t)
-            below[name] = int(bad.sum())
+            bad = test.rejected(v, t)
+            counts[test.flag] = int(bad.sum())
             accept &= ~bad
-    return accept, below
+    return accept, counts
 
 
-def log_line(accept, below, thresholds, extra=()):
-    """extra: (measure, threshold, how many lie below it) of further tests that reject where these do (ensemble.py: view_iou), or the
-    finished text of one that rejects otherwise (floor.py: |floor_gap| above its threshold)."""
-    parts = ['%s < %g: %d' % (m, t, below[name]) for name, m, t in zip(THRESHOLDS, MEASURES, thresholds) if t is not None]
-    parts += [e if isinstance(e, str) else '%s < %g: %d' % e for e in extra]
+def log_line(accept, below, thresholds, tests=TESTS):
+    """The `consistency:` line: how many of `accept` are True and, per test with a limit (`thresholds` runs beside `tests`), its
+    fragment with below[its flag], the number of detections it rejects."""
+    parts = [(t.fragment + ': %d') % (limit, below[t.flag]) for t, limit in zip(tests, thresholds) if limit is not None]
     return 'consistency: kept %d of %d (%s)' % (int(np.sum(accept)), len(accept), ', '.join(parts) if parts else 'no threshold')
 
 

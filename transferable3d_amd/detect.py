@@ -131,8 +131,8 @@ measured: real SUN-RGBD.  Without these flags every output is what it was, byte 
 
 Where things live: the stages behind the decode (views, consistency, the accept rule, NMS, box voting) and their order belong to
 semisup_infer.DeviceStages, which `Detector.decode_all` reaches through `inference` and keeps as `Detector.stages` -- its `corners` are the
-boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  semisup_infer.report writes the
-`consistency:` / `tta:` / `nms` lines, semisup_infer.kept drops the rows that were not kept.  Here: what the host knows of a detection
+boxes on the device after every stage that ran, which `Vis.write` draws and `sweep_parts` suppresses.  What rejects a detection is
+semisup_infer.TESTS, one entry beside each stage's measure.  semisup_infer.report writes the `consistency:` / `tta:` / `nms` lines, semisup_infer.kept drops the rows that were not kept.  Here: what the host knows of a detection
 (`Detection`), the extraction, the requests, the records and reports with the fields every stage adds to them (`FIELD_GROUPS`), and
 `main`, which checks its own flags, lets `Detector` check the rest (`STAGE_KEYWORDS`), and turns either's ValueError into an argument
 error in one place, before a model is built.
@@ -316,8 +316,20 @@ FIELD_GROUPS = {
 RECORD_GROUPS = ('votes', 'rescore', 'soft', 'views', 'consistency', 'visibility', 'floor')     # the records of `Detector.detect` and the legends of --vis_dir
 ROW_GROUPS = ('consistency', 'rescore', 'soft', 'views', 'visibility', 'floor')              # the rows of --consistency_json
 # the options of the stages as `Detector` takes them, under the names of the flags (the module docstring describes them)
+SCENE_FLAGS = FL.FLAGS + ('floor_json',) + VS.FLAGS          # the flags of the stages that look at the whole scene: not for --sweep or --rescore_fit
 STAGE_KEYWORDS = ('nms_iou', 'nms_metric', 'nms_score', 'nms_fuse', 'nms_fuse_iou', 'soft_nms', 'soft_nms_sigma', 'soft_nms_min_prob', 'consistency',
                   'min_reproj_iou', 'min_mask_in_box', 'min_seg_box_iou', 'tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou', 'rescore', 'min_rescore') + FL.FLAGS + VS.FLAGS
+
+
+def scene_rows(parts):
+    """-> (per detection of `parts`, in order, the row of its scene among the scenes of all parts; the number of those rows).  A part's
+    meta names its scenes by their position in the part; every part has one row per scene, with or without a frustum.  The consistency,
+    floor and visibility requests all index their per-scene tables by it."""
+    index, n_rows = [], 0
+    for p in parts:
+        index += [n_rows + m.scene for m in p['meta']]
+        n_rows += p['n_scenes']
+    return index, n_rows
 
 
 def fields_of(d, i, groups, as_lists=False):
@@ -362,6 +374,7 @@ class Detector:
         self.suppression = NMS.suppression(soft_nms, soft_nms_sigma, soft_nms_min_prob, nms_iou, nms_metric, nms_score, nms_fuse, nms_fuse_iou)
         self.nms_iou, self.nms_metric, self.nms_score, self.nms_fuse, self.nms_fuse_iou, self.soft_nms = self.suppression
         self.thresholds = CS.check_thresholds(min_reproj_iou, min_mask_in_box, min_seg_box_iou)
+        self.min_reproj_iou, self.min_mask_in_box, self.min_seg_box_iou = self.thresholds
         self.consistency = bool(consistency) or any(t is not None for t in self.thresholds) or self.rescore is not None
         if self.rescore is not None and 'view_iou' in self.rescore.features and self.tta is None:
             raise ValueError('the rescoring model reads view_iou, the agreement of the augmented views: it needs --tta')
@@ -444,11 +457,7 @@ class Detector:
         if self.suppression.on:
             nms = SI.NmsRequest.of(self.suppression, [m.image for m in meta], classes, [m.prob for m in meta])
         if self.consistency:
-            rows, index = [], []
-            for p in parts:                              # a part's meta names its scenes by their position in the part
-                index += [len(rows) + m.scene for m in p['meta']]
-                rows += list(p.get('calib', []))
-            con = SI.ConsistencyRequest([m.box2d for m in meta], rows, index, *self.thresholds)
+            con = SI.ConsistencyRequest([m.box2d for m in meta], [row for p in parts for row in p.get('calib', [])], scene_rows(parts)[0], *self.thresholds)
         if self.floor.on:
             floor = FL.FloorRequest(*self.floor_rows(parts), snap=self.floor.snap, snap_max=self.floor.snap_max, max_floor_gap=self.floor.max_floor_gap)
         if self.tta is not None:
@@ -465,31 +474,26 @@ class Detector:
         return meta, d
 
     def floor_rows(self, parts):
-        """The planes [S, 8] and counts [S, 4] of the parts' scenes on the device, one row per scene of every part in order (a part without
-        a frustum was not estimated: its scenes have no floor), and per detection the row of its scene -- indexed exactly as the
-        calibration rows of the consistency request."""
+        """The planes [S, 8] and counts [S, 4] of the parts' scenes on the device (a part without a frustum was not estimated: its scenes
+        have no floor) and per detection the row of its scene (`scene_rows`)."""
         import torch
-        planes, counts, index, n_rows = [], [], [], 0
+        planes, counts = [], []
         for p in parts:
-            index += [n_rows + m.scene for m in p['meta']]
-            n_rows += p['n_scenes']
             if p.get('floor') is not None:
                 planes.append(p['floor']['plane'])
                 counts.append(p['floor']['counts'])
             else:
                 planes.append(torch.zeros(p['n_scenes'], 8, dtype=torch.float64, device=self.rt.device))
                 counts.append(torch.tensor([[0, 0, -1, FL.NONE]] * p['n_scenes'], dtype=torch.int32, device=self.rt.device).view(-1, 4))
-        return torch.cat(planes), torch.cat(counts), index
+        return torch.cat(planes), torch.cat(counts), scene_rows(parts)[0]
 
     def visibility_rows(self, parts):
         """The calibration rows [S, 20], grids (dims [S, 2], offsets [S + 1]) and range maps (one int32 tensor on the device) of the parts'
-        scenes, one row per scene of every part in order (a part without a frustum built no map: its scenes have a grid of no cells and
-        so no scene), and per detection the row of its scene -- indexed exactly as the planes of the floor request."""
+        scenes (a part without a frustum built no map: its scenes have a grid of no cells and so no scene) and per detection the row of
+        its scene (`scene_rows`)."""
         import torch
-        calib, dims, maps, index, n_rows = [], [], [], [], 0
+        calib, dims, maps = [], [], []
         for p in parts:
-            index += [n_rows + m.scene for m in p['meta']]
-            n_rows += p['n_scenes']
             if p.get('range') is not None:
                 calib.append(p['range']['calib'])
                 dims.append(p['range']['dims'])
@@ -500,7 +504,7 @@ class Detector:
         dims = np.concatenate(dims).reshape(-1, 2)
         offsets = np.concatenate([[0], np.cumsum(dims[:, 0].astype(np.int64) * dims[:, 1])]).astype(np.int64)
         range_ = torch.cat(maps) if maps else torch.zeros(0, dtype=torch.int32, device=self.rt.device)
-        return np.concatenate(calib).reshape(-1, 20), dims, offsets, range_, index
+        return np.concatenate(calib).reshape(-1, 20), dims, offsets, range_, scene_rows(parts)[0]
 
     def floor_json_rows(self, parts):
         """--floor_json: one row per estimated scene of `parts` (floor.scene_rows)."""
@@ -679,7 +683,7 @@ def sweep_options(args):
     single += ['soft_nms'] if args.soft_nms is not None else []      # (the scores differ per configuration: ranks cannot be shared)
     single += [f for f in EN.FLAGS if getattr(args, f) not in (None, False)]
     single += [f for f in ('rescore', 'min_rescore', 'rescore_fit') if getattr(args, f) is not None]
-    single += [f for f in FL.FLAGS + ('floor_json',) + VS.FLAGS if getattr(args, f) not in (None, False)]
+    single += [f for f in SCENE_FLAGS if getattr(args, f) not in (None, False)]
     if single:
         raise ValueError('--sweep starts from the plain run and chooses the thresholds itself: it does not go with %s' % ' '.join('--' + f for f in single))
     if args.vis_dir or args.consistency_json:
@@ -737,7 +741,7 @@ def main(argv=None, rt=None, log=print):
         if fit is not None:
             other = [f for f in SW.FLAGS if getattr(args, f) is not None] + [f for f in ('nms_fuse', 'official_eval') if getattr(args, f)]
             other += [f for f in ('nms_fuse_iou', 'soft_nms', 'min_view_iou', 'vis_dir', 'consistency_json') if getattr(args, f) is not None]
-            other += [f for f in FL.FLAGS + ('floor_json',) + VS.FLAGS if getattr(args, f) not in (None, False)]
+            other += [f for f in SCENE_FLAGS if getattr(args, f) not in (None, False)]
             if other:
                 raise ValueError('--rescore_fit starts from the plain run, as --sweep does: it does not go with %s' % ' '.join('--' + f for f in other))
         floor = FL.check_options(**{k: getattr(args, k) for k in FL.FLAGS})

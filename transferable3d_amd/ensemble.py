@@ -15,9 +15,11 @@ import torch
 
 from . import abi
 from .abi import fptr, iptr
+from .consistency import Test, lies_below
 
 MAX_VIEWS = abi.DETECT_ENSEMBLE_MAX_VIEWS
 FLAGS = ('tta', 'tta_flip', 'tta_vote_iou', 'min_view_iou')
+TEST = Test('min_view_iou', ('view_iou',), 'view_iou < %g', lies_below, ())       # the stage's rejecting test (consistency.Test)
 
 
 def check_options(tta=None, tta_flip=False, tta_vote_iou=None, min_view_iou=None):

@@ -16,6 +16,7 @@ import torch
 
 from . import abi
 from .abi import dptr, fptr, iptr
+from .consistency import Test
 
 NONE, LEVEL = abi.FLOOR_NONE, abi.FLOOR_LEVEL
 NO_FLOOR, NOT_FINITE, TOO_FAR, INVERTED, SNAPPED = (abi.DETECT_FLOOR_NO_FLOOR, abi.DETECT_FLOOR_NOT_FINITE, abi.DETECT_FLOOR_TOO_FAR,
@@ -197,9 +198,12 @@ class DeviceFloorStage:
 
 
 def rejected(gap, flags, max_floor_gap):
-    """[n] bool: the floor is known and |gap| > max_floor_gap (the gap measured before any snapping)."""
+    """[n] bool: the floor is known and |gap| > max_floor_gap (the gap measured before any snapping; a NaN exceeds nothing)."""
     with np.errstate(invalid='ignore'):
-        return ((np.asarray(flags) & UNKNOWN) == 0) & (np.abs(gap) > max_floor_gap)
+        return ((np.asarray(flags, np.int64) & UNKNOWN) == 0) & (np.abs(gap) > max_floor_gap)
+
+
+TEST = Test('max_floor_gap', ('floor_gap', 'floor_flags'), '|floor_gap| > %g', rejected, ())       # the stage's rejecting test (consistency.Test)
 
 
 def log_line(request, gap, flags):

@@ -19,7 +19,9 @@ import torch
 
 from . import abi
 from .abi import dptr, fptr, iptr
+from .consistency import Test, lies_below
 
+TEST = Test('min_rescore', ('rescore_prob',), 'rescore_prob < %g', lies_below, ())       # the stage's rejecting test (consistency.Test)
 FEATURES = abi.RESCORE_FEATURES
 DEFAULT_FEATURES = FEATURES[:6]                    # view_iou exists only under --tta
 TARGETS = ('overlap', 'tp')

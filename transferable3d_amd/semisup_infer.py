@@ -20,8 +20,8 @@ detection whose confidence falls below --soft_nms_min_prob is absent like a supp
 
 What runs behind the decode, and in which order, is written down in one place: `DeviceStages`.  `inference` builds one from its requests
 (nms, consistency, views); per batch it decodes every view and then measures the consistency of view 0, after the last batch it runs
-the ensemble of the views, the floor stage, the rescoring, the accept rule, the suppression and the box voting, and fetches everything
-as one `Decoded`.  It holds the boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.
+the ensemble of the views, the floor stage, the visibility stage, the rescoring, the accept rule (one loop over the run's tests of `TESTS`),
+the suppression and the box voting, and fetches everything as one `Decoded`.  It holds the boxes on the device as the stages so far left them, so nothing behind it asks which stage ran.
 `DeviceDecode` is the buffers of t3d_detect_decode alone; `report` writes a run's log lines and `kept` drops the rows that were not
 kept, for every caller.
 """
@@ -40,6 +40,25 @@ from transferable3d_amd.abi import fptr, iptr                            # noqa:
 from transferable3d_amd import consistency as CS, ensemble as EN, floor as FL, rescore as RS, visibility as VS      # noqa: E402
 from transferable3d_amd.consistency import ConsistencyRequest, DeviceConsistency      # noqa: E402
 from transferable3d_amd.constants import type2class                     # noqa: E402
+
+# Every test that can reject a detection (consistency.Test, each stated beside the stage that takes its measure), in the order the
+# `consistency:` line prints them.  DeviceStages.accept_rows, `report` and autolabel's counts all run over this tuple.
+TESTS = CS.TESTS + (EN.TEST, RS.TEST, FL.TEST, VS.TEST)
+# the stages that need the device-decoded boxes: the keyword of `inference`, what it refuses them with under decode='host', and how
+# DeviceStages names a request whose length is not the number of detections
+REQUESTS = (('nms', "nms runs on the device-decoded boxes: decode='device'", None),
+            ('consistency', "the consistency measures are taken on the device-decoded boxes: decode='device'", '%d detections in the consistency request, %d decoded'),
+            ('rescore', "the rescoring reads the device-decoded records: decode='device'", '%d confidences in the rescore request, %d decoded'),
+            ('floor', "the floor stage reads the device-decoded boxes: decode='device'", '%d detections in the floor request, %d decoded'),
+            ('visibility', "the visibility stage reads the device-decoded boxes: decode='device'", '%d detections in the visibility request, %d decoded'))
+
+
+def active_tests(*holders):
+    """[(test, limit, parameters)] of the tests of TESTS that are on: one of `holders` -- the requests of a run, or a Detector and its
+    checked floor and visibility options; None counts for nothing -- carries a limit under the flag's name, and the test's parameters
+    are attributes of that holder's `options`."""
+    return [(t, getattr(h, t.flag), {k: getattr(h.options, k) for k in t.parameters})
+            for t in TESTS for h in holders if getattr(h, t.flag, None) is not None]
 
 
 def build_flags(argv=None):
@@ -102,8 +121,9 @@ class Decoded:
     answered, or None where no suppression was asked for.  A sliced Decoded carries its rows' values; suppressed_by keeps naming rows of
     the unsliced run.
     reproj_rect [n,4], reproj_iou, n_mask, n_box, n_both, flags, mask_in_box, seg_box_iou are what t3d_detect_consistency measured
-    (consistency.py) and accept [n] bool whether the detection misses none of the request's thresholds; None where no consistency
-    request was made.
+    (consistency.py); None where no consistency request was made.  accept [n] bool: whether none of the run's tests (TESTS) rejects
+    the detection -- True for the rows that pad a last batch, which are no detections -- or None where the run measured no
+    consistency and had no test with a limit.
     With a fusion (NmsRequest(fuse=True)) label and corners hold what t3d_detect_fuse wrote -- for a kept box with voters the fused
     geometry, for every other box what the decode wrote -- raw_label / raw_corners what the decode wrote, and n_votes [n] the number of
     voters of a kept box (-1: suppressed; 0: nothing to fuse, or listed in no group); None without.  center, heading_cls, heading_res,
@@ -216,24 +236,19 @@ class DeviceStages:
 
     label [n, 7], corners [n, 24]: the boxes on the device as the stages so far left them -- a stage that rewrites boxes (the ensemble,
     the floor stage where it snaps, the box voting) reads them and puts its output in their place, so neither a later stage nor a caller asks which stage ran; score [n]:
-    where view 0's decode wrote it.  accept [n] bool (None: nothing was asked that could reject): the detections that miss no threshold
-    of the consistency request, do not lie below views.min_view_iou or rescore.min_rescore and whose |floor_gap| does not exceed
-    floor.max_floor_gap and whose see_through does not exceed visibility.max_see_through; below: how many of the real detections
-    lie below each of these thresholds (`report`).  rescore_out (rescore.DeviceRescore, None without a request): its out32 [n] is the
+    where view 0's decode wrote it.  tests: the tests of TESTS for which a request carries a limit (`active_tests`); accept [n] bool
+    (None: nothing was asked that could reject): the detections none of them rejects; below: per flag of `tests`, how many of the real
+    detections its test rejects (`report`).  rescore_out (rescore.DeviceRescore, None without a request): its out32 [n] is the
     rescored confidence on the device, which `nms` ranks by in the place of the request's `prob`."""
 
     def __init__(self, rt, n, total, num_point, want_seg=False, nms=None, consistency=None, views=None, rescore=None, floor=None, visibility=None):
-        if floor is not None and len(floor) != total:
-            raise ValueError('%d detections in the floor request, %d decoded' % (len(floor), total))
-        if visibility is not None and len(visibility) != total:
-            raise ValueError('%d detections in the visibility request, %d decoded' % (len(visibility), total))
         if nms is not None and len(nms.image_ids) != total:
             raise ValueError('%d image ids for %d detections' % (len(nms.image_ids), total))
-        if consistency is not None and len(consistency) != total:
-            raise ValueError('%d detections in the consistency request, %d decoded' % (len(consistency), total))
+        requests = dict(consistency=consistency, rescore=rescore, floor=floor, visibility=visibility)
+        for name, _, message in REQUESTS:
+            if requests.get(name) is not None and len(requests[name]) != total:
+                raise ValueError(message % (len(requests[name]), total))
         if rescore is not None:
-            if len(rescore) != total:
-                raise ValueError('%d confidences in the rescore request, %d decoded' % (len(rescore), total))
             names = rescore.model.features
             if 'view_iou' in names and views is None:
                 raise ValueError('the rescoring model reads view_iou, the agreement of the augmented views: it needs --tta')
@@ -248,6 +263,7 @@ class DeviceStages:
         self.rot_angle = None if views is None else rt.zeros(n)      # every batch's angles: the ensemble mirrors back with them
         sec = self.decodes[0].sec
         self.label, self.corners, self.score = sec['label'], sec['corners'], sec['score'].view(-1)
+        self.tests = active_tests(consistency, views, rescore, floor, visibility)
         self.accept, self.below = None, {}
         self.measures = self.ensemble_out = self.nms_out = self.fuse_out = None
 
@@ -312,40 +328,31 @@ class DeviceStages:
         out.apply(n_valid=total)
 
     def accept_rows(self):
-        """The one accept rule: a detection is rejected where it misses a threshold of the consistency request, its view_iou lies below
-        views.min_view_iou, its rescored confidence below rescore.min_rescore, or its floor is known and |floor_gap|, measured before any
-        snapping, exceeds floor.max_floor_gap, or it was measured on visibility.options.min_rays rays and its see_through exceeds
-        visibility.max_see_through.  Copies the consistency outputs, the agreement and the
-        rescored confidence back -- the small copies in front of the group building."""
-        total, masks = self.total, []
+        """The one accept rule: a detection is rejected where one of the run's tests (`tests`, of TESTS) rejects it; `below` counts,
+        per flag, the real detections it rejects.  The rows that pad a last batch are no detections: every test accepts them.  Copies
+        the consistency outputs, the agreement, the rescored confidence and the floor and visibility measures back -- the small copies
+        in front of the group building."""
+        total, host = self.total, {}
         if self.consistency is not None:
-            m = self.measures = self.consistency.fetch()
-            masks.append(m['accept'])
-            # (the counts fetch returns take in the zero rows that pad a last batch; the report counts the real detections)
-            self.below = CS.accept_of(*(m[k][:total] for k in CS.MEASURES), self.consistency.thresholds)[1]
+            self.measures = self.consistency.fetch()
+            host.update(self.measures)
         if self.views is not None and self.views.min_view_iou is not None:
-            masks.append(self.ensemble_out.agreement[:self.n].cpu().numpy().astype(np.float64) >= self.views.min_view_iou)
-            self.below['view_iou'] = int((~masks[-1][:total]).sum())
+            host['view_iou'] = self.ensemble_out.agreement[:self.n].cpu().numpy().astype(np.float64)
         if self.rescore_request is not None and self.rescore_request.min_rescore is not None:
-            ok = self.rescore_out.out[:self.n].cpu().numpy() >= self.rescore_request.min_rescore
-            self.below['rescore_prob'] = int((~ok[:total]).sum())
-            ok[total:] = True                                     # (the rows that pad a last batch are no detections)
-            masks.append(ok)
+            host['rescore_prob'] = self.rescore_out.out[:self.n].cpu().numpy()
         if self.floor_out is not None:
             self.floor_host = (self.floor_out.gap[:self.n].cpu().numpy(), self.floor_out.flags[:self.n].cpu().numpy().astype(np.int64))
-            if self.floor_request.max_floor_gap is not None:
-                bad = FL.rejected(*self.floor_host, self.floor_request.max_floor_gap)
-                self.below['floor_gap'] = int(bad[:total].sum())
-                masks.append(~bad)
+            host['floor_gap'], host['floor_flags'] = self.floor_host
         if self.visibility_out is not None:
-            req = self.visibility_request
             h = self.visibility_host = self.visibility_out.fetch(self.n)
-            if req.max_see_through is not None:
-                bad = VS.rejected(h['measures'], h['profile'], h['flags'], req.max_see_through, req.options.min_rays)
-                self.below['see_through'] = int(bad[:total].sum())
-                masks.append(~bad)
-        if masks:
-            self.accept = np.logical_and.reduce(masks)
+            host.update(see_through=h['measures'][:, 0], visibility_evidence=VS.evidence(h['profile']), visibility_flags=h['flags'])
+        if not self.tests and self.consistency is None:
+            return
+        self.accept = np.ones(self.n, bool)
+        for test, limit, parameters in self.tests:
+            bad = test.rejected(*(host[k][:total] for k in test.fields), limit, **parameters)
+            self.below[test.flag] = int(bad.sum())
+            self.accept[:total] &= ~bad
 
     def nms(self):
         """t3d_detect_nms over the real rows, on the current corners.  A rejected detection is listed in no group, so it suppresses
@@ -456,16 +463,10 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     the range map of its scene (`.decoded.see_through` / `.occluded` / `.support` / `.visibility_flags`), and a detection whose
     see_through exceeds visibility.max_see_through on enough rays is rejected like one below a consistency threshold.
     The stages and their order are DeviceStages'; this function loads and runs the graph and says when a view of a batch is ready."""
-    if decode == 'host' and nms is not None:
-        raise ValueError("nms runs on the device-decoded boxes: decode='device'")
-    if decode == 'host' and consistency is not None:
-        raise ValueError("the consistency measures are taken on the device-decoded boxes: decode='device'")
-    if decode == 'host' and rescore is not None:
-        raise ValueError("the rescoring reads the device-decoded records: decode='device'")
-    if decode == 'host' and floor is not None:
-        raise ValueError("the floor stage reads the device-decoded boxes: decode='device'")
-    if decode == 'host' and visibility is not None:
-        raise ValueError("the visibility stage reads the device-decoded boxes: decode='device'")
+    requests = dict(nms=nms, consistency=consistency, rescore=rescore, floor=floor, visibility=visibility)
+    for name, message, _ in REQUESTS:
+        if decode == 'host' and requests[name] is not None:
+            raise ValueError(message)
     if views is not None and (decode != 'device' or source is None):
         raise ValueError("views are further draws of a device-resident source: decode='device' and a source")
     if decode == 'host':
@@ -482,8 +483,7 @@ def inference(sess, ops, pc, one_hot_vec, batch_size, prefix='', use_boxpc_fit_p
     total = source.ds.F if source is not None else n                 # the frustums past it pad the last batch
     rot = sess.g.inputs.rot_frust if source is not None else None    # written by t3d_batch_assemble; fed frustums are in their centre view
     xyz = sess.g.inputs.pc if consistency is not None else None      # [B * N, ld] where the network read the batch
-    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, nms=nms, consistency=consistency, views=views, rescore=rescore,
-                          floor=floor, visibility=visibility)
+    stages = DeviceStages(sess.g.rt, n, total, npts, want_seg=want_seg, views=views, **requests)
     sources = [source] + ([] if views is None else [source.view(seed, flip) for seed, flip in views.views[1:]])
     for i in range(n // batch_size):
         sl = slice(i * batch_size, (i + 1) * batch_size)
@@ -526,15 +526,7 @@ def report(log, stages, d):
     kept, how many lie below each threshold), `tta:` (the views) and `nms ...` (how many of the accepted detections were kept and, with
     a fusion, how many kept boxes changed, from how many votes); `floor:` (floor.log_line) follows `tta:` and `visibility:` (visibility.log_line) follows that.  stages: the run's DeviceStages; d: the records of its real detections."""
     if d.accept is not None:
-        con = stages.consistency
-        extra = [('view_iou', stages.views.min_view_iou, stages.below['view_iou'])] if 'view_iou' in stages.below else []
-        if 'rescore_prob' in stages.below:
-            extra.append(('rescore_prob', stages.rescore_request.min_rescore, stages.below['rescore_prob']))
-        if 'floor_gap' in stages.below:
-            extra.append('|floor_gap| > %g: %d' % (stages.floor_request.max_floor_gap, stages.below['floor_gap']))
-        if 'see_through' in stages.below:
-            extra.append('see_through > %g: %d' % (stages.visibility_request.max_see_through, stages.below['see_through']))
-        log(CS.log_line(d.accept, stages.below, con.thresholds if con is not None else (None, None, None), extra))
+        log(CS.log_line(d.accept, stages.below, [limit for _, limit, _ in stages.tests], [test for test, _, _ in stages.tests]))
     if stages.views is not None:
         log(EN.log_line(stages.views, d))
     if stages.floor_request is not None:

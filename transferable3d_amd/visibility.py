@@ -22,7 +22,7 @@ import torch
 
 from . import abi
 from .abi import dptr, fptr, iptr
-from .consistency import calib_row
+from .consistency import Test, calib_row
 
 NO_SCENE, NOT_FINITE, BEHIND, NO_RAYS, NO_EVIDENCE = abi.VIS_NO_SCENE, abi.VIS_NOT_FINITE, abi.VIS_BEHIND, abi.VIS_NO_RAYS, abi.VIS_NO_EVIDENCE
 UNMEASURED = NO_SCENE | NOT_FINITE | BEHIND        # such a detection is not rejected
@@ -207,10 +207,18 @@ class DeviceVisibilityStage:
                     flags=self.flags[:n].cpu().numpy().astype(np.int64))
 
 
-def rejected(measures, profile, flags, max_see_through, min_rays):
-    """[n] bool: the detection was measured, through + inside >= min_rays and see_through > max_see_through.  profile [n, 6]."""
-    mid = np.asarray(profile)
-    return ((np.asarray(flags) & UNMEASURED) == 0) & (mid[:, THROUGH] + mid[:, INSIDE] >= min_rays) & (np.asarray(measures)[:, 0] > max_see_through)
+def evidence(profile):
+    """through + inside of profile [..., 6]: the rays that say whether a box is seen through ('visibility_evidence' in autolabel's records)."""
+    return np.asarray(profile)[..., THROUGH] + np.asarray(profile)[..., INSIDE]
+
+
+def rejected(see_through, evidence, flags, max_see_through, min_rays):
+    """[n] bool: the detection was measured, evidence (through + inside) >= min_rays and see_through > max_see_through."""
+    return ((np.asarray(flags, np.int64) & UNMEASURED) == 0) & (np.asarray(evidence) >= min_rays) & (np.asarray(see_through) > max_see_through)
+
+
+# the stage's rejecting test (consistency.Test); min_rays is VisibilityOptions.min_rays
+TEST = Test('max_see_through', ('see_through', 'visibility_evidence', 'visibility_flags'), 'see_through > %g', rejected, ('min_rays',))
 
 
 def log_line(request, host, n_scenes=None):
@@ -221,5 +229,5 @@ def log_line(request, host, n_scenes=None):
     line = 'visibility: %d scenes, median see_through %.2f' % (len(request.calib) if n_scenes is None else n_scenes,
                                                                float(np.median(see)) if len(see) else float('nan'))
     if request.max_see_through is not None:
-        line += ', rejected %d' % int(rejected(host['measures'], host['profile'], flags, request.max_see_through, request.options.min_rays).sum())
+        line += ', rejected %d' % int(rejected(host['measures'][:, 0], evidence(host['profile']), flags, request.max_see_through, request.options.min_rays).sum())
     return line
